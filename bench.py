@@ -4,7 +4,9 @@ A "step" is one transition of EVERY env of the batch (4096 envs x 5 humans per G
 ORCA robot, in-kernel auto-reset): `--steps K` executes exactly K such batched steps per rank after W warm-up
 steps, in fused launches of at most `--chunk` steps each.  value = total env transitions of all ranks / wall time.
 
-    python bench.py                                        # 1 GPU
+    python bench.py                                        # 1 GPU: the headline only
+    python bench.py --full                                 # + everything measured beside it (see below)
+    python bench.py --dump-outputs DIR                     # + what the timed steps computed, as DIR/<name>.npy
     python bench.py --gpus N [--steps K --warmup W]        # N GPUs: re-executes itself as N ranks (127.0.0.1 rendezvous)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # the same under an external launcher (RANK/WORLD_SIZE set)
@@ -22,9 +24,12 @@ explorer.py:74-90 (the reference computes them after its episode loop), i.e. the
 their all-gather (RCCL), and the summary kernel — is the shard boundary: timed separately as `boundary_ms` AT EVERY WORLD SIZE,
 1 included (and `value_incl_boundary` charges it to these K steps).  The JSON line also carries
 `roofline` (algorithmic bytes of the dominant kernel over its HIP-event duration), `issue_roofline` (the bound that
-actually limits this kernel, only when the committed PMC profile is of the same launch shape) and, at N=1, `cpu_baseline`
-(the CPU oracle timed on this host's cores on a bounded sample of the same workload; + the unmodified reference Python
-loop as timed in the build container) and `secondary` (BASELINE configs[2] and configs[3] measured in the same run).
+actually limits this kernel, only when the committed PMC profile is of the same launch shape).  A plain run stops there.
+`--full` adds what takes measurements of its own: `value_r3_definition` (a second engine), `fill_ms`, `value_samples` and, at
+N=1, `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample of the same workload; + the unmodified
+reference Python loop as timed in the build container) and `secondary` (BASELINE configs[2] and configs[3] measured in the
+same run).  `--dump-outputs DIR` writes the arrays the K timed steps left (env states, episode records and counters, the
+boundary's summary) after the run; with the same arguments the inputs are the same seeded episodes from run to run.
 
 Two environment switches exist so that the N > 1 code path can be EXECUTED on a one-GPU box (tests/test_bench_multirank.py):
 CROWDNAV_AMD_BENCH_BACKEND=gloo (torch.distributed backend of the ranks; RCCL refuses two ranks on one device, gloo moves
@@ -209,11 +214,11 @@ def sarl_flop(B, H, om):
     return 2 * (81 * H * (62050 + (7200 if om else 0)) + 81 * 33500) * B
 
 
-def measure_sarl(B, H, om, steps, warm, preroll, world, rank, local_rank, comm=None):
+def measure_sarl(B, H, om, steps, warm, preroll, world, rank, local_rank, comm=None, outputs=None):
     """BASELINE configs[2]: B envs x H humans, SARL value-network rollout (random-init weights), greedy phase.
     A step = cn_sarl_select (81 lookaheads + value network per env) + cn_rollout_step (transition, bookkeeping, seeded
     auto-reset).  HIP events bracket every cn_sarl_select (the MFMA roofline is the value network's flops over THAT time)
-    and every whole step."""
+    and every whole step.  outputs: a dict that receives what the last timed step computed (host tensors)."""
     import numpy as np
     import torch
     import crowdnav_amd
@@ -251,6 +256,10 @@ def measure_sarl(B, H, om, steps, warm, preroll, world, rank, local_rank, comm=N
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     comm.barrier()
+    if outputs is not None:
+        state, gtime = eng.get_state()
+        outputs.update({k: v.cpu() for k, v in ro.bufs.items()}, best=sel['best'].cpu(), action=sel['action'].cpu(),
+                       state=state.cpu(), global_time=gtime.cpu())
     transitions = int(ro.transitions.item()) - before
     per_rank = comm.all_gather({'rank': rank, 'transitions': transitions, 'seconds': elapsed})
     tot = sum(r['transitions'] for r in per_rank)  # real per-rank counts over the slowest rank's time
@@ -293,10 +302,13 @@ def measure_sarl(B, H, om, steps, warm, preroll, world, rank, local_rank, comm=N
 
 
 def bench_sarl(args, world, rank, local_rank, comm):
-    out = measure_sarl(args.envs, args.humans, args.workload == 'om-sarl', min(args.steps, 200), min(args.warmup, 20),
-                       min(args.preroll, 60), world, rank, local_rank, comm)
+    outputs = {} if args.dump_outputs else None
+    out = measure_sarl(args.envs, args.humans, args.workload == 'om-sarl', args.steps, min(args.warmup, 20),
+                       min(args.preroll, 60), world, rank, local_rank, comm, outputs=outputs)
     if os.environ.get('CROWDNAV_AMD_BENCH_SHARE_GPU') == '1':
         out['config']['shared_gpu'] = True
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs, args.envs, '' if world == 1 else 'rank%d_' % rank)
     if rank == 0:
         print(json.dumps(out), flush=True)
 
@@ -642,10 +654,11 @@ def measure_fill_seconds(eng, depth):
     return max(0.0, med(with_fill) - med(without)) / 1e3
 
 
-def measure_orca(args, world, rank, local_rank, comm, inkernel, backend, fill_probe=True, repeats=0):
+def measure_orca(args, world, rank, local_rank, comm, inkernel, backend, fill_probe=True, repeats=0, outputs=None):
     """One measurement of the ORCA workload on a fresh engine: preroll, warm-up, the K timed steps, the shard boundary.
     inkernel: round 3's arrangement (every launch leaves the job-wide counter, the explorer.py:74-90 sums and the record
-    blocks itself) instead of ABI v6's (per-env counters, statistics once at the boundary)."""
+    blocks itself) instead of ABI v6's (per-env counters, statistics once at the boundary).  outputs: a dict that receives
+    what the K timed steps and the boundary computed (host tensors), before anything else runs on the engine."""
     import torch
     import torch.distributed as dist
     import crowdnav_amd
@@ -774,6 +787,9 @@ def measure_orca(args, world, rank, local_rank, comm, inkernel, backend, fill_pr
     now_t, now_e = snapshot()
     own_episodes = int((now_e - snap_e).sum().item())
     transitions = int((now_t - snap_t).sum().item())
+    if outputs is not None:
+        state, gtime = eng.get_state()
+        outputs.update({k: v.cpu() for k, v in bufs.items()}, state=state.cpu(), global_time=gtime.cpu(), summary=summary.cpu())
     # VERDICT r5 weak #4d: `value` is ONE sample of a region that can be as short as 120 us.  `repeats` further repetitions of
     # the same (warm-up + K timed steps) pattern on the same engine, each with the same fences, so that the line shows the spread
     # (value stays the first sample, as defined): short regions only — a default 8000-step run is its own average
@@ -955,6 +971,32 @@ def config5_schedule_estimate():
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir, rows, prefix=''):
+    """--dump-outputs: every array of `outputs` as out_dir/<prefix><name>.npy, float32 kept, everything else as float64 (exact
+    for the flags, counters and outcome codes).  When they exceed 64 MB in all, the arrays whose first axis is the env axis
+    (`rows` long) keep the same fixed, seeded sample of envs, whose indices are written as env_index.npy."""
+    import numpy as np
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.numpy() if hasattr(v, 'numpy') else np.asarray(v)
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    per_env = {k for k, a in arrs.items() if a.ndim and a.shape[0] == rows}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        fixed = sum(a.nbytes for k, a in arrs.items() if k not in per_env) + 4096 * (len(arrs) + 1)  # (+ the .npy headers)
+        row_bytes = sum(arrs[k].nbytes // rows for k in per_env) + 8  # (+ its entry of env_index)
+        keep = max(1, min(rows, (DUMP_LIMIT_BYTES - fixed) // row_bytes))
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrs = {k: a[idx] if k in per_env else a for k, a in arrs.items()}
+        arrs['env_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, prefix + k + '.npy'), np.ascontiguousarray(a))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-execute this script as N ranks, one per GPU, rendezvous on
     127.0.0.1 (what torch.distributed.run would set up).  Rank 0's JSON line goes to our stdout."""
@@ -1019,6 +1061,13 @@ def main():
                     help='skip the configs[2] / configs[3] measurements that follow the headline at N=1')
     ap.add_argument('--workload', choices=['orca', 'sarl', 'om-sarl'], default='orca',
                     help="orca = BASELINE configs[1] (the headline metric); sarl / om-sarl = configs[2]")
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline as well: value_r3_definition, the fill probe, value_samples and, at N=1, '
+                         'cpu_baseline and secondary (each still subject to its --no-* / --repeats option); without it a run '
+                         'measures the K timed steps and the shard boundary only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed (state and episode bookkeeping after the last timed step, the '
+                         'boundary\'s summary) as DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded sample of envs beyond)')
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.preroll < 0 or args.chunk < 1 or args.records < 1:
         raise SystemExit('--gpus/--steps/--chunk/--records must be >= 1, --warmup/--preroll >= 0')
@@ -1061,14 +1110,18 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    # CROWDNAV_AMD_BENCH_INKERNEL_STATS=1: round 3's arrangement for the HEADLINE (A/B runs); the default line measures both
+    # CROWDNAV_AMD_BENCH_INKERNEL_STATS=1: round 3's arrangement for the HEADLINE (A/B runs); the --full line measures both
     inkernel = os.environ.get('CROWDNAV_AMD_BENCH_INKERNEL_STATS') == '1'
-    m = measure_orca(args, world, rank, local_rank, comm, inkernel, backend, repeats=args.repeats)
+    outputs = {} if args.dump_outputs else None
+    m = measure_orca(args, world, rank, local_rank, comm, inkernel, backend, fill_probe=args.full,
+                     repeats=args.repeats if args.full else 0, outputs=outputs)
     # `value` changed definition in round 4 (the job-wide statistics left the timed launches).  The same K
     # steps in round 3's arrangement — every launch leaves the job-wide transition counter, the explorer.py:74-90 sums and the
     # record blocks behind itself — are measured right after, on a fresh engine, and reported beside it
-    m3 = None if (inkernel or args.no_r3_definition) else measure_orca(args, world, rank, local_rank, comm, True, backend,
-                                                                         fill_probe=False)
+    m3 = None if (not args.full or inkernel or args.no_r3_definition) else measure_orca(args, world, rank, local_rank, comm, True,
+                                                                                          backend, fill_probe=False)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs, B, '' if world == 1 else 'rank%d_' % rank)
 
     elapsed, boundary, total, episodes = m['elapsed'], m['boundary'], m['total'], m['episodes']
     events = m['events']
@@ -1122,7 +1175,7 @@ def main():
                                     % (m['ring_depth'], fills, launches),
                    'fills_in_timed_region': fills,
                    'scenario_cache': (H > 8 and args.seed_mod <= 4096 and os.environ.get('CROWDNAV_AMD_SCENARIO_CACHE', '1') != '0'),
-                   'preroll_steps': args.preroll,
+                   'preroll_steps': args.preroll, 'full': args.full,
                    'parallelism': 'env-axis shards x%d, no collective on the step path; the job-wide statistics (record blocks, '
                                   'their all-gather on several GPUs, summary kernel) once when a run ends (boundary_ms)' % world,
                    'backend': backend if world > 1 else None, 'shared_gpu': share_gpu},
@@ -1161,9 +1214,9 @@ def main():
         'mean_recorded_return': s[6] / max(s[1], 1.0),
         'recorded_success_rate': s[2] / max(s[1], 1.0),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(B, H)
-    if rank == 0 and world == 1 and not args.no_secondary and (B, H) == (4096, 5):
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and (B, H) == (4096, 5):
         out['secondary'] = secondary(B, local_rank)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -18,7 +18,7 @@ REPO=$GRAFT_REPO_ROOT; TAG=${CN_TAG:-r06}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $
 line() { timeout 20 python scripts/bench_line.py "$1"; }
 bench() { # name, [VAR=val ...] -- args
   name=$1; shift; envs=(); while [ "$1" != "--" ] && [ $# -gt 0 ]; do envs+=("$1"); shift; done; shift
-  ( [ ${#envs[@]} -gt 0 ] && export "${envs[@]}"; timeout 400 python bench.py "$@" > $OUT/$name.log 2>&1 < /dev/null )
+  ( [ ${#envs[@]} -gt 0 ] && export "${envs[@]}"; timeout 400 python bench.py --full "$@" > $OUT/$name.log 2>&1 < /dev/null )
   echo -n "$name: "; line $OUT/$name.log; }
 prof() { name=$1; shift; ( cd /tmp; timeout 400 rocprofv3 "$@" > $OUT/$name.log 2>&1 < /dev/null ); echo "$name rc=$?"; }
 
@@ -74,11 +74,11 @@ sarl)
     ( export CROWDNAV_AMD_LIB=$lib; timeout 200 python scripts/sarl_bench.py ${CN_SARL_ARGS} ) 2>&1 | grep -v amdgpu.ids | tail -n 6 | sed "s/^/$n: /" | tee -a $OUT/sarl_bench.txt
   done ;;
 trace)
-  prof trace_default --kernel-trace --stats --output-format csv -d $OUT/trace_default -o trace -- python $REPO/bench.py --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe
-  prof trace_driver --kernel-trace --stats --output-format csv -d $OUT/trace_driver -o trace -- python $REPO/bench.py --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe --steps 20 --warmup 5
+  prof trace_default --kernel-trace --stats --output-format csv -d $OUT/trace_default -o trace -- python $REPO/bench.py --full --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe
+  prof trace_driver --kernel-trace --stats --output-format csv -d $OUT/trace_driver -o trace -- python $REPO/bench.py --full --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe --steps 20 --warmup 5
   prof trace_sarl --kernel-trace --stats --output-format csv -d $OUT/trace_sarl -o trace -- python $REPO/scripts/sarl_bench.py
   prof trace_om_sarl --kernel-trace --stats --output-format csv -d $OUT/trace_om_sarl -o trace -- python $REPO/scripts/sarl_bench.py --om 1
-  prof trace_h20 --kernel-trace --stats --output-format csv -d $OUT/trace_h20 -o trace -- python $REPO/bench.py --no-cpu-baseline --no-r3-definition --no-fill-probe --humans 20 --circle-radius 12 --steps 2997 --warmup 999 --chunk 999
+  prof trace_h20 --kernel-trace --stats --output-format csv -d $OUT/trace_h20 -o trace -- python $REPO/bench.py --full --no-cpu-baseline --no-r3-definition --no-fill-probe --humans 20 --circle-radius 12 --steps 2997 --warmup 999 --chunk 999
   for t in default driver sarl om_sarl h20; do python scripts/prof_summary.py $OUT/trace_$t | head -8; done ;;
 pmc)
   SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY"
@@ -86,10 +86,10 @@ pmc)
   SQ3="SQ_INSTS SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_INSTS_SENDMSG SQ_INST_CYCLES_SALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
   MF="SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
   declare -A CMD
-  CMD[default]="$REPO/bench.py --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe"
-  CMD[driver]="$REPO/bench.py --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe --steps 20 --warmup 5"
+  CMD[default]="$REPO/bench.py --full --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe"
+  CMD[driver]="$REPO/bench.py --full --no-cpu-baseline --no-secondary --no-r3-definition --no-fill-probe --steps 20 --warmup 5"
   # (h20 counters: the dynamic schedule is ONE dispatch per call: 4096 envs x 999 steps, the shape of stage benchh20)
-  CMD[h20]="$REPO/bench.py --no-cpu-baseline --no-r3-definition --no-fill-probe --humans 20 --circle-radius 12 --steps 2997 --warmup 999 --chunk 999"
+  CMD[h20]="$REPO/bench.py --full --no-cpu-baseline --no-r3-definition --no-fill-probe --humans 20 --circle-radius 12 --steps 2997 --warmup 999 --chunk 999"
   for shape in ${CN_PMC_SHAPES:-default driver h20}; do
     prof pmc_${shape}_fetch --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_${shape}_fetch -o p -- python ${CMD[$shape]}
     prof pmc_${shape}_write --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_${shape}_write -o p -- python ${CMD[$shape]}

@@ -5,6 +5,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -199,3 +201,66 @@ def test_fill_probe_classifies_calls_by_the_engines_launch_counters(monkeypatch)
     assert abs(bench.measure_fill_seconds(Eng(), 48) - 80e-6) < 1e-9
     monkeypatch.setenv('CROWDNAV_AMD_RING_DEPTH', '5')
     assert bench.ring_depth() == 5
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_envs_beyond_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: integer and byte arrays become float64 (exactly), float32 stays; over the size limit every per-env array
+    keeps the same seeded sample of envs (env_index.npy), the rest is written whole, and the files fit the limit."""
+    import numpy as np
+    import torch
+    import bench
+    B = 1000
+    outputs = {'state': torch.rand(B, 6, 8, dtype=torch.float64), 'ep_outcome': torch.randint(0, 4, (B, 1), dtype=torch.uint8),
+               'env_transitions': torch.arange(B, dtype=torch.int64), 'orca_vel': torch.rand(B, 6, 2),
+               'summary': torch.arange(8, dtype=torch.float64)}
+    whole = tmp_path / 'whole'
+    bench.dump_outputs(outputs, str(whole), B)
+    assert sorted(os.listdir(str(whole))) == sorted(k + '.npy' for k in outputs)
+    for k, v in outputs.items():
+        a = np.load(str(whole / (k + '.npy')))
+        assert a.dtype == (np.float32 if v.dtype == torch.float32 else np.float64)
+        assert np.array_equal(a, v.numpy().astype(a.dtype))
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 200000)
+    runs = []
+    for name in ('s1', 's2'):
+        bench.dump_outputs(outputs, str(tmp_path / name), B)
+        runs.append({f[:-4]: np.load(str(tmp_path / name / f)) for f in os.listdir(str(tmp_path / name))})
+        assert sum(os.path.getsize(str(tmp_path / name / f)) for f in os.listdir(str(tmp_path / name))) <= 200000
+    a, b = runs
+    idx = a['env_index'].astype(np.int64)
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0) and np.array_equal(idx, b['env_index'])
+    assert np.array_equal(a['state'], outputs['state'].numpy()[idx]) and np.array_equal(a['env_transitions'], idx.astype(np.float64))
+    assert np.array_equal(a['summary'], np.arange(8.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline only (none of what --full measures), K steps timed;
+    --dump-outputs writes what those steps left, identical from run to run (same seeded episodes)."""
+    import subprocess
+    import numpy as np
+    lines, dumps = [], []
+    for name in ('a', 'b'):
+        out = tmp_path / name
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '30', '--warmup', '5',
+                            '--dump-outputs', str(out)], capture_output=True, text=True, timeout=280)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = [json.loads(l) for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(line) == 1
+        lines.append(line[0])
+        dumps.append({f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    d, a = lines[0], dumps[0]
+    assert d['steps'] == 30 and d['warmup'] == 5 and d['config']['full'] is False
+    assert d['ms_per_step'] == pytest.approx(d['ranks'][0]['seconds'] * 1e3 / 30, rel=1e-12)
+    assert d['value'] == pytest.approx(d['ranks'][0]['transitions'] / d['ranks'][0]['seconds'], rel=1e-12)
+    assert 'cpu_baseline' not in d and 'secondary' not in d
+    assert d['value_r3_definition'] is None and d['value_samples'] is None and d['fill_ms'] is None
+    B, A = 4096, 6
+    assert a['state'].shape == (B, A, 8) and a['state'].dtype == np.float64 and a['global_time'].shape == (B,)
+    assert a['ep_count'].shape == (B,) and a['summary'].tolist() == d['summary']
+    # the per-env counters hold the pre-roll, the warm-up and the timed steps (less any paused env-steps)
+    assert d['ranks'][0]['transitions'] <= a['env_transitions'].sum() <= B * (200 + 5 + 30)
+    assert d['episodes_finished'] <= a['ep_count'].sum()
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert sorted(a) == sorted(dumps[1]) and all(np.array_equal(a[k], dumps[1][k]) for k in a)

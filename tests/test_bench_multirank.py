@@ -46,7 +46,7 @@ SHARED = dict(CROWDNAV_AMD_BENCH_BACKEND='gloo', CROWDNAV_AMD_BENCH_SHARE_GPU='1
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_two_ranks_sharing_one_gpu_orca():
-    flags = ['--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-secondary']
+    flags = ['--full', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-secondary']
     two = _run(['--gpus', '2'] + flags, **SHARED)
     assert two['n_gpus'] == 2 and two['scaling'] == 'weak' and two['steps'] == 20 and two['warmup'] == 5
     assert two['config']['backend'] == 'gloo' and two['config']['shared_gpu'] is True
