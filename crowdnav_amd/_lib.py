@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CROWDNAV_AMD_LIB: another build of the same library (kernel A/B experiments, scripts/gpu_ab.sh); default in-tree
 LIB_PATH = os.environ.get('CROWDNAV_AMD_LIB') or os.path.join(HERE, 'lib', 'libcrowdnav_amd.so')
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 CN_OK, CN_ERR_INVALID, CN_ERR_UNSUPPORTED, CN_ERR_HIP, CN_ERR_NO_DEVICE = 0, -1, -2, -3, -4
 INFO_NAMES = ('Nothing', 'Danger', 'ReachGoal', 'Collision', 'Timeout')
@@ -103,6 +103,7 @@ SYMBOLS = {
     'cn_sarl_configure': (C.c_int, [_P, C.POINTER(CnSarlConfig), _P]),
     'cn_sarl_set_weights': (C.c_int, [_P, C.POINTER(_P)]),
     'cn_sarl_select': (C.c_int, [_P, _P, _P, _P]),
+    'cn_sarl_select_attention': (C.c_int, [_P, _P, _P, _P, _P]),
     'cn_sarl_explore': (C.c_int, [_P, C.c_double, _P, _P, _P, _P]),
     'cn_sarl_transform': (C.c_int, [_P, _P, C.c_int64, C.c_int]),
     'cn_sarl_sample_step': (C.c_int, [_P, C.c_double, _P, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),

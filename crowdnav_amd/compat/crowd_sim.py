@@ -265,8 +265,9 @@ class CrowdSim(_Base):
         v = self._eng.orca().cpu().numpy()[0, 0]
         return float(v[0]), float(v[1])
 
-    def sarl_action(self, policy):
-        """Greedy SARL decision for the current device state: (best index | -1 stop | -2 invalid, 81 values)."""
+    def sarl_action(self, policy, want_attention=False):
+        """Greedy SARL decision for the current device state: (best index | -1 stop | -2 invalid, 81 values); with
+        want_attention also the attention weights of the last action's lookahead state over the env's humans."""
         eng = self._eng
         if self._rule == 'mixed' and eng.H != 5:
             raise NotImplementedError('value networks under the mixed rule need the 5 human slots the rule can draw')
@@ -280,7 +281,10 @@ class CrowdSim(_Base):
         if getattr(eng, '_sarl_weights_stamp', None) != stamp:
             eng.sarl_set_weights(policy.model.state_dict())
             eng._sarl_weights_stamp = stamp
-        out = eng.sarl_select()
+        out = eng.sarl_select(want_attention=want_attention)
+        if want_attention:  # env 0's row of action n_actions - 1, H floats (absent humans of a `mixed` episode trimmed)
+            att = out['attention'][0, -1, :len(self.humans)].cpu().numpy()
+            return int(out['best'].cpu()[0]), out['values'].cpu().numpy()[0].tolist(), att
         return int(out['best'].cpu()[0]), out['values'].cpu().numpy()[0].tolist()
 
     def render(self, mode='human', output_file=None):

@@ -41,14 +41,26 @@ class ValueNetwork(nn.Module):
         self.cell_num = cell_num
         self.mlp3 = mlp(mlp2_dims[-1] + self_state_dim, mlp3_dims)
         self._attention_row = None
+        self._cn_decision_row = None  # (weights epoch, weights) of the last device decision (SARL.predict)
 
     @property
     def attention_weights(self):
         """Attention weights of batch element 0 of the last forward (sarl.py:54), fetched from the device on demand —
-        a host copy inside forward() would cost one device sync per SGD step and forbid graph capture."""
+        a host copy inside forward() would cost one device sync per SGD step and forbid graph capture.  After a device
+        decision: the weights of its last action's lookahead state, which is the reference's last forward, until a torch
+        forward runs again — eagerly (forward() drops the decision's row) or as a replayed SGD step (the Trainer bumps
+        _cn_weights_epoch; the replay rewrites the captured _attention_row in place, so that tensor is never replaced here)."""
+        dec = self._cn_decision_row
+        if dec is not None and dec[0] == getattr(self, '_cn_weights_epoch', 0):
+            return dec[1]
         return None if self._attention_row is None else self._attention_row.cpu().numpy()
 
+    def set_decision_attention(self, weights):
+        """The weights a device decision left (what the reference's last forward of MultiHumanRL.predict stores)."""
+        self._cn_decision_row = (getattr(self, '_cn_weights_epoch', 0), weights)
+
     def forward(self, state):
+        self._cn_decision_row = None
         n, h, d = state.shape
         self_state = state[:, 0, :self.self_state_dim]
         hidden = self.mlp1(state.reshape(-1, d))
@@ -176,9 +188,15 @@ class SARL(Policy):
         if self.phase == 'train' and probability < self.epsilon:
             action = self.action_space[np.random.choice(len(self.action_space))]
         else:
-            best, values = env.sarl_action(self)
+            # sarl.ValueNetwork keeps the attention weights of its last forward (sarl.py:54): the reference's last one is the
+            # lookahead state of the LAST action (multi_human_rl.py:35-51), so that row comes back with the values
+            attention = isinstance(self.model, ValueNetwork)
+            got = env.sarl_action(self, want_attention=attention)
+            best, values = got[0], got[1]
             if best < 0:
                 raise ValueError('Value network is not well trained. ')
+            if attention:
+                self.model.set_decision_attention(got[2])
             self.action_values = values
             action = self.action_space[best]
         if self.phase == 'train':

@@ -517,7 +517,9 @@ static bool sarl_om_direct(const cn_sarl* s) {
     return s->reg_mlp && (s->reg_xks == cn::kRegSarlPre || s->reg_xks == cn::kRegChunkAPre) && s->net.in_dim == 61;
 }
 
-int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) {
+// cn_sarl_select and cn_sarl_select_attention: att == nullptr launches exactly cn_sarl_select's kernels; otherwise every SARL
+// route takes its ATT instantiation, which also writes the softmax weights it holds, float [B][n_actions][H]
+static int sarl_select(cn_engine* e, double* values, int32_t* best, double* action, float* att) {
     int rc = bind(e);
     if (rc) return rc;
     cn_sarl* s = e->sarl;
@@ -536,10 +538,12 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
                                e->S.vel, e->S.rv, s->orca_vel, s->next_obs, s->om);
         cn::SarlDecide D0{};
         D0.in_dim = s->net.in_dim;
-        const auto narrow_kernel = s->cfg.model == CN_MODEL_LSTM_RL ? cn::sarl_narrow_kernel<true> : cn::sarl_narrow_kernel<false>;
+        const auto narrow_kernel = s->cfg.model == CN_MODEL_LSTM_RL ? cn::sarl_narrow_kernel<true>
+                                   : att                            ? cn::sarl_narrow_kernel<false, true>
+                                                                    : cn::sarl_narrow_kernel<false>;
         hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)s->narrow_tiles), dim3(cn::kNarrowThreads), s->narrow_lds,
                            e->stream, s->ref, C, e->S.pos, e->S.vel, e->S.goal, e->S.rv, e->S.theta, s->actions, s->orca_vel,
-                           s->next_obs, s->V, D0, C.with_om ? (const float*)s->om : (const float*)nullptr);
+                           s->next_obs, s->V, D0, C.with_om ? (const float*)s->om : (const float*)nullptr, att);
         e->launch_counts[CN_COUNT_SARL_NARROW] += 1;
         hipLaunchKernelGGL(cn::sarl_select_kernel, dim3((C.B + 3) / 4), dim3(256), 0, e->stream, C, e->S.pos, e->S.vel,
                            e->S.goal, e->S.rv, e->S.gtime, e->S.theta, s->actions, s->reward, s->V, values, best, action);
@@ -566,6 +570,9 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
         else if (s->cfg.model == CN_MODEL_LSTM_RL)                                                                   \
             hipLaunchKernelGGL(cn::lstm_mlp_kernel<HH>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng,   \
                                s->hcount);                                                                          \
+        else if (att)                                                                                                \
+            hipLaunchKernelGGL((cn::sarl_mlp_pipe_kernel<HH, true>), pgrid, block, s->lds_bytes, e->stream, s->ref, s->X, \
+                               s->V, ng, (int)s->n_tiles, s->hcount, att);                                           \
         else                                                                                                         \
             hipLaunchKernelGGL(cn::sarl_mlp_pipe_kernel<HH>, pgrid, block, s->lds_bytes, e->stream, s->ref, s->X, s->V, \
                                ng, (int)s->n_tiles, s->hcount);                                                      \
@@ -589,15 +596,21 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
         if (s->n_chunks) {
             const dim3 cgrid(wgs < (unsigned)s->n_cus ? wgs : (unsigned)s->n_cus);
 #define CN_SARL_CHUNK(NT, PRE)                                                                                               \
-    hipLaunchKernelGGL((cn::sarl_reg_chunk_kernel<NT, PRE>), cgrid, rblock, 0, e->stream, s->reg_stream, s->reg_stream3, s->reg_stream2, \
-                       s->X, s->V, s->reg_scratch, ng, (int)s->n_tiles, H, s->n_chunks, s->net.ks_x, s->hcount, om_direct, C.n_actions)
+    if (att)                                                                                                                 \
+        hipLaunchKernelGGL((cn::sarl_reg_chunk_kernel<NT, PRE, true>), cgrid, rblock, 0, e->stream, s->reg_stream, s->reg_stream3, \
+                           s->reg_stream2, s->X, s->V, s->reg_scratch, ng, (int)s->n_tiles, H, s->n_chunks, s->net.ks_x, s->hcount, \
+                           om_direct, C.n_actions, att);                                                                     \
+    else                                                                                                                     \
+        hipLaunchKernelGGL((cn::sarl_reg_chunk_kernel<NT, PRE>), cgrid, rblock, 0, e->stream, s->reg_stream, s->reg_stream3, \
+                           s->reg_stream2, s->X, s->V, s->reg_scratch, ng, (int)s->n_tiles, H, s->n_chunks, s->net.ks_x, s->hcount, \
+                           om_direct, C.n_actions)
             const bool pre = s->reg_xks == cn::kRegChunkAPre;
             if (s->chunk_nt == 3) {
-                if (pre) CN_SARL_CHUNK(3, true);
-                else CN_SARL_CHUNK(3, false);
+                if (pre) { CN_SARL_CHUNK(3, true); }
+                else { CN_SARL_CHUNK(3, false); }
             } else {
-                if (pre) CN_SARL_CHUNK(4, true);
-                else CN_SARL_CHUNK(4, false);
+                if (pre) { CN_SARL_CHUNK(4, true); }
+                else { CN_SARL_CHUNK(4, false); }
             }
 #undef CN_SARL_CHUNK
         } else if (cn::reg_is_lstm_mlp1(s->reg_xks)) {
@@ -623,8 +636,10 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
 #define CN_SARL_REG_NT(NT)                                                                        \
     case NT:                                                                                      \
         if (reg_cadrl) CN_SARL_REG(cn::cadrl_reg_kernel<NT>, H, s->cadrl_chunks);                 \
-        else if (s->reg_xks == 4) CN_SARL_REG((cn::sarl_reg_kernel<4, NT>), om_direct, C.n_actions); \
-        else CN_SARL_REG((cn::sarl_reg_kernel<4, NT, true>), om_direct, C.n_actions);             \
+        else if (att && s->reg_xks == 4) CN_SARL_REG((cn::sarl_reg_kernel<4, NT, false, true>), om_direct, C.n_actions, att); \
+        else if (att) CN_SARL_REG((cn::sarl_reg_kernel<4, NT, true, true>), om_direct, C.n_actions, att);                 \
+        else if (s->reg_xks == 4) CN_SARL_REG((cn::sarl_reg_kernel<4, NT>), om_direct, C.n_actions);                       \
+        else CN_SARL_REG((cn::sarl_reg_kernel<4, NT, true>), om_direct, C.n_actions);                                       \
         break;
         switch (NTK) {
             CN_SARL_REG_NT(1)
@@ -640,6 +655,9 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
                            s->V, ng);
     } else if (s->chunked && s->cfg.model == CN_MODEL_LSTM_RL) {
         hipLaunchKernelGGL(cn::lstm_mlp_anyh_kernel, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
+    } else if (s->chunked && att) {
+        hipLaunchKernelGGL((cn::sarl_mlp_chunked_kernel<cn::kSarlChunk, true>), grid, block, s->lds_bytes, e->stream, s->net, s->X,
+                           s->V, ng, att);
     } else if (s->chunked) {
         hipLaunchKernelGGL(cn::sarl_mlp_chunked_kernel<cn::kSarlChunk>, grid, block, s->lds_bytes, e->stream, s->net, s->X,
                            s->V, ng);
@@ -653,6 +671,22 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) 
                        e->S.rv, e->S.gtime, e->S.theta, s->actions, s->reward, s->V, values, best, action);
     CN_HIP(hipGetLastError());
     return CN_OK;
+}
+
+int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action) {
+    return sarl_select(e, values, best, action, nullptr);
+}
+
+int cn_sarl_select_attention(cn_engine* e, double* values, int32_t* best, double* action, float* attention) {
+    if (attention) {
+        int rc = bind(e);
+        if (rc) return rc;
+        const cn_sarl* s = e->sarl;
+        if (!s) return fail(CN_ERR_INVALID, "cn_sarl_select_attention: configure and set weights first");
+        if (s->cfg.model != CN_MODEL_SARL)
+            return fail(CN_ERR_UNSUPPORTED, "cn_sarl_select_attention: only sarl.ValueNetwork has attention weights");
+    }
+    return sarl_select(e, values, best, action, attention);
 }
 
 int cn_sarl_explore(cn_engine* e, double epsilon, const uint8_t* mask, int32_t* best, double* action,
@@ -728,7 +762,7 @@ int cn_sarl_sample_step(cn_engine* e, double epsilon, uint8_t* alive, int32_t* b
         const auto narrow_kernel = s->cfg.model == CN_MODEL_LSTM_RL ? cn::sarl_narrow_kernel<true> : cn::sarl_narrow_kernel<false>;
         hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)s->narrow_tiles + (unsigned)D.side_wg), dim3(cn::kNarrowThreads), s->narrow_lds,
                            e->stream, s->ref, C, e->S.pos, e->S.vel, e->S.goal, e->S.rv, e->S.theta, s->actions, s->orca_vel,
-                           s->next_obs, s->V, D, C.with_om ? (const float*)s->om : (const float*)nullptr);
+                           s->next_obs, s->V, D, C.with_om ? (const float*)s->om : (const float*)nullptr, (float*)nullptr);
         e->launch_counts[CN_COUNT_SARL_NARROW] += 1;
         CN_HIP(hipGetLastError());
         if (fused) {
@@ -778,7 +812,8 @@ int cn_sarl_values(cn_engine* e, const float* states, int64_t n, float* out) {
     const unsigned tiles = (unsigned)((n + GT - 1) / GT);
     const auto narrow_kernel = s->cfg.model == CN_MODEL_LSTM_RL ? cn::sarl_narrow_kernel<true> : cn::sarl_narrow_kernel<false>;
     hipLaunchKernelGGL(narrow_kernel, dim3(tiles), dim3(cn::kNarrowThreads), s->narrow_lds, e->stream, s->ref, C, e->S.pos, e->S.vel,
-                       e->S.goal, e->S.rv, e->S.theta, s->actions, s->orca_vel, s->next_obs, out, D, (const float*)nullptr);
+                       e->S.goal, e->S.rv, e->S.theta, s->actions, s->orca_vel, s->next_obs, out, D, (const float*)nullptr,
+                       (float*)nullptr);
     e->launch_counts[CN_COUNT_SARL_NARROW] += 1;
     CN_HIP(hipGetLastError());
     return CN_OK;

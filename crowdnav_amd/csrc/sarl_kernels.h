@@ -928,9 +928,10 @@ __device__ __forceinline__ void value_head_on_one_wave(const PackedLinear& P, co
     if (slice == 0 && row < groups_per_tile && G < (size_t)n_groups) V[G] = v;
 }
 
-template <int H>
+// ATT (compile time; cn_sarl_select_attention): the softmax threads also write their group's weights, att [n_groups][H].
+template <int H, bool ATT = false>
 __global__ __launch_bounds__(kSarlThreads) void sarl_mlp_pipe_kernel(SarlNetRef net, const float* X, float* V, int n_groups,
-                                                                     int n_tiles, const int* hcount) {
+                                                                     int n_tiles, const int* hcount, [[maybe_unused]] float* att = nullptr) {
     extern __shared__ float lds[];
     float* bufA = lds;                            // [H][ks_a][64]  wide hidden layers
     float* bufB = bufA + H * net.ks_a * 64;       // [H][ks_b][64]  X staging, then mlp1 output (h2), then attention.2
@@ -1015,6 +1016,12 @@ __global__ __launch_bounds__(kSarlThreads) void sarl_mlp_pipe_kernel(SarlNetRef 
             }
 #pragma unroll
             for (int h = 0; h < H; ++h) sbuf[h * n->ks_s * 64 + tid] = e[h] / total;
+            if constexpr (ATT) {
+                const size_t G = (size_t)tile * kSarlGroups + tid;
+                if (G < (size_t)n_groups)
+#pragma unroll
+                    for (int h = 0; h < H; ++h) att[G * H + h] = sbuf[h * n->ks_s * 64 + tid];
+            }
         }
         lds_barrier();
         // the joint state of this tile: self features, weighted feature sum (sarl.py:60), zero k padding
@@ -1060,9 +1067,11 @@ __host__ inline size_t sarl_mlp_pipe_extra_lds_bytes(const SarlNet& net) { retur
 //           exp(score) * feature accumulate per group in human order, the division by the total comes last
 //           (the reference divides first: w_h = e_h / total, then sums w_h f_h — same value to rounding)
 // then the value head.  Rows of a partial last chunk are computed on zero inputs and masked out of every sum.
-template <int HC>
+// ATT (compile time): thread g < 16 writes exp(score) of its group's humans into att [n_groups][H] chunk by chunk and divides
+// that row by the total after the last chunk.
+template <int HC, bool ATT = false>
 __global__ __launch_bounds__(kSarlThreads) void sarl_mlp_chunked_kernel(SarlNet net, const float* X, float* V,
-                                                                        int n_groups) {
+                                                                        int n_groups, [[maybe_unused]] float* att = nullptr) {
     extern __shared__ float lds[];
     const int H = net.H;
     float* bufA = lds;                            // [HC][ks_a][64]
@@ -1136,6 +1145,8 @@ __global__ __launch_bounds__(kSarlThreads) void sarl_mlp_chunked_kernel(SarlNet 
                 const float e = expf(sc) * (sc != 0.0f ? 1.0f : 0.0f);
                 sbuf[rt * net.ks_s * 64 + tid] = e;
                 total += e;
+                if constexpr (ATT)
+                    if (tile * kSarlGroups + tid < (size_t)n_groups) att[(tile * kSarlGroups + tid) * H + h0 + rt] = e;
             }
             den[tid] = total;
         }
@@ -1153,6 +1164,11 @@ __global__ __launch_bounds__(kSarlThreads) void sarl_mlp_chunked_kernel(SarlNet 
         const int g = i & 15, c = i >> 4, n = 6 + c;
         jbuf[(n >> 2) * 64 + (n & 3) * 16 + g] = wsum[(c >> 2) * 64 + (c & 3) * 16 + g] / den[g];
     }
+    if constexpr (ATT)  // the row this thread wrote above, normalised
+        if (tid < kSarlGroups && tile * kSarlGroups + tid < (size_t)n_groups) {
+            float* const row = att + (tile * kSarlGroups + tid) * H;
+            for (int h = 0; h < H; ++h) row[h] = row[h] / den[tid];
+        }
     __syncthreads();
     dense_mfma<1>(net.L[kL_mlp3_0], jbuf, net.ks_a, kbuf, net.ks_a, true, nullptr, wave, lane);
     __syncthreads();
@@ -1662,11 +1678,12 @@ __device__ CN_NARROW_CALL double narrow_reward(const SarlCfg& C, const double2* 
 // is computed up front with each wave holding its column tile of W_ih across the steps, the recurrent half with W_hh held in
 // registers across them; then the joint MLP on [self_state | h].  dense_mfma<1>'s arithmetic layer by layer and the gate
 // expressions of lstm_mlp_kernel: V is bit-identical to that kernel's.
-template <bool LSTM = false>
+// ATT (compile time; SARL, cn_sarl_select_attention): wave 0 also writes the weights of the tile's rows, att [n_groups][H].
+template <bool LSTM = false, bool ATT = false>
 __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef net, SarlCfg C, const double2* pos, const double2* vel,
                                                                      const double2* goal, const double2* rv, const double* theta,
                                                                      const double* actions, const float* orca_vel, double* next_obs,
-                                                                     float* V, SarlDecide D, const float* om) {
+                                                                     float* V, SarlDecide D, const float* om, [[maybe_unused]] float* att = nullptr) {
     extern __shared__ float lds[];
     float* xs = lds;                          // [ks_x][64]  X of the tile
     float* bufA = xs + net.ks_x * 64;         // [ks_a][64]  wide hidden layers
@@ -2029,6 +2046,8 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
             float total = 0.0f;
             for (int h = 0; h < H; ++h) total += __shfl(e, (g0 + h) & 15);  // (row 15 of 3 x 5 wraps: unused)
             if (lane < 16) wrow[lane] = e / total;
+            if constexpr (ATT)
+                if (wave == 0 && lane < rows && tile * GT + lane / H < (size_t)n_groups) att[tile * rows + lane] = wrow[lane];
         }
     }
     wave_lds_sync();

@@ -487,10 +487,12 @@ __device__ __forceinline__ void reg_dense1(WS& ws, In in, f32x4 (&out)[MT]) {
 // cycles each); from 2 humans on consecutive MFMAs alternate between accumulators.
 // PRE (XKS = 4): `om` is the term of sarl_om_term_kernel, [env][human][10 tiles][4 lane groups][4 registers] — mlp1.0's
 // accumulator for (row, output tile) in the lane's own order, one 16-byte load each, requested one output tile ahead.
-template <int XKS, int NT, bool PRE = false>
+// ATT (compile time; cn_sarl_select_attention): lanes 0..15 also write their group's softmax weights, att_out [n_groups][NT].
+template <int XKS, int NT, bool PRE = false, bool ATT = false>
 __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_kernel(const float* stream, const float* X, float* V, int n_groups,
                                                                   int n_tiles, int ks_x, const int* hcount,
-                                                                  const float* om = nullptr, int n_actions = 1) {
+                                                                  const float* om = nullptr, int n_actions = 1,
+                                                                  [[maybe_unused]] float* att_out = nullptr) {
     static_assert(NT >= 1 && NT <= kRegHumans, "the activations of at most 5 humans fit the register file");
     static_assert(!PRE || XKS == 4, "the hoisted occupancy-map term replaces k-steps 4..15");
     constexpr int KEY = PRE ? kRegSarlPre : XKS;
@@ -622,6 +624,12 @@ __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_kernel(const float* s
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) e[nt] = e[nt] / total;
+            if constexpr (ATT) {  // the weights as they stand (absent humans 0), from the lanes that own a group
+                const size_t G = (size_t)tile * kSarlGroups + lane;
+                if (lane < kSarlGroups && G < (size_t)n_groups)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) att_out[G * NT + nt] = e[nt];
+            }
             // weighted feature sum (sarl.py:60)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -1026,11 +1034,13 @@ __global__ __launch_bounds__(kRegWaves * 64) void lstm2_reg_kernel(const float* 
 //           (the reference divides first: w_h = e_h / total, then sums w_h f_h — same value to rounding);
 //   then    the value head.
 // PRE as in sarl_reg_kernel: mlp1.0 starts from the hoisted occupancy-map term instead of its bias.
-template <int NT, bool PRE>
+// ATT (compile time): the group's lanes 0..15 write exp(score) per human into att_out [n_groups][H] in pass 2 and divide that row
+// by the total once the last chunk is in.
+template <int NT, bool PRE, bool ATT = false>
 __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_chunk_kernel(const float* sa, const float* sb, const float* sg, const float* X,
                                                                         float* V, float* scratch, int n_groups, int n_tiles, int H,
                                                                         int n_chunks, int ks_x, const int* hcount, const float* term,
-                                                                        int n_actions) {
+                                                                        int n_actions, [[maybe_unused]] float* att_out = nullptr) {
     static_assert(NT == 3 || NT == 4, "two accumulator sets, mlp1's 17 tiles and three weight queues fit the register file up to 4 N tiles");
     constexpr int KA = PRE ? kRegChunkAPre : kRegChunkA, KB = kRegChunkB, KG = kRegChunkG;
     constexpr int QA = reg_total_quads(KA), QB = reg_total_quads(KB), QG = reg_total_quads(KG);
@@ -1171,6 +1181,8 @@ __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_chunk_kernel(const fl
                 const float s_ = sc[nt];
                 const float e = c * NT + nt < cnt ? expf(s_) * (s_ != 0.0f ? 1.0f : 0.0f) : 0.0f;
                 den += e;
+                if constexpr (ATT)
+                    if (lane < kSarlGroups && G < (long long)n_groups && c * NT + nt < H) att_out[(size_t)G * H + c * NT + nt] = e;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const f32x4 f = mypark[nt * 4 + t][lane];
@@ -1183,6 +1195,9 @@ __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_chunk_kernel(const fl
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) wf[t][i] = wf[t][i] / den;
+        if constexpr (ATT)  // the row this lane wrote above, normalised
+            if (lane < kSarlGroups && G < (long long)n_groups)
+                for (int h = 0; h < H; ++h) att_out[(size_t)G * H + h] = att_out[(size_t)G * H + h] / den;
         // ---- value head on joint = [self | weighted feature] (sarl.py:61-62)
         f32x4 j1[10], j2[7], j3[7], val[1];
         const float mix = lane < 32 ? wf[3][0] : self0;

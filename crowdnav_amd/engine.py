@@ -358,9 +358,10 @@ def _sarl_set_weights(self, state_dict):
     self._sarl_weights_keepalive = tensors
 
 
-def _sarl_select(self, want_values=True, best=None, action=None):
+def _sarl_select(self, want_values=True, best=None, action=None, want_attention=False):
     """Greedy SARL action of every env: dict(values [B,K] f64, best [B] i32, action [B,2] f64).  best / action: the caller's
-    device tensors to write into (e.g. row t of an action history) instead of fresh ones."""
+    device tensors to write into (e.g. row t of an action history) instead of fresh ones.  want_attention (SARL only): also
+    attention [B,K,H] f32, the softmax weights of every lookahead state (cn_sarl_select_attention; 0 for absent humans)."""
     K = self.sarl['n_actions']
     if best is None:
         best = self._new((self.B,), torch.int32)
@@ -368,7 +369,12 @@ def _sarl_select(self, want_values=True, best=None, action=None):
         action = self._new((self.B, 2), torch.float64)
     assert best.dtype == torch.int32 and best.is_contiguous() and action.dtype == torch.float64 and action.is_contiguous()
     out = dict(values=self._new((self.B, K), torch.float64) if want_values else None, best=best, action=action)
-    check(self._lib.cn_sarl_select(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action'])))
+    if want_attention:
+        out['attention'] = self._new((self.B, K, self.H), torch.float32)
+        check(self._lib.cn_sarl_select_attention(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action']),
+                                                 _ptr(out['attention'])))
+    else:
+        check(self._lib.cn_sarl_select(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action'])))
     return out
 
 

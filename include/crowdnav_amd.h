@@ -97,7 +97,8 @@ const char* cn_last_error(void);
 /* ABI version of this header (bumped on any change of a signature or of what a call does).  v10 (round 6): no new symbol —
  * cn_sarl_sample_step skips the envs outside `alive` on its two-launch route, takes CN_MODEL_LSTM_RL there and accepts `info` in
  * pinned host memory; cn_rollout / cn_rollout_step / the boundary calls refuse an io whose seed_base / seed_mod differ from
- * cn_rollout_begin's.  v11 (round 6): + cn_sarl_values. */
+ * cn_rollout_begin's.  v11 (round 6): + cn_sarl_values.  v12: + cn_sarl_select_attention. */
+#define CN_ABI_VERSION 12
 int cn_abi_version(void);
 
 /* replaces gym.make('CrowdSim-v0') + CrowdSim.configure + set_robot (crowd_sim.py:13-82): allocates the
@@ -312,6 +313,15 @@ int cn_sarl_set_weights(cn_engine* e, const float* const* params_host_array);
  *                  -2 = no finite value (the reference raises ValueError, :57-58)
  *   action  double [B][2] the chosen ActionXY */
 int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action);
+/* (ABI v12) cn_sarl_select plus the attention weights of every (env, action) group — what sarl.ValueNetwork.forward keeps
+ * of batch element 0 (sarl.py:52-54) and SARL.get_attention_weights returns (sarl.py:88-89), for every lookahead state:
+ *   attention  float32 [B][n_actions][num_humans]: exp(s_h) [s_h != 0] / sum over the humans present, humans in env order
+ *              as the network saw them; 0 for the absent humans of a `mixed` episode; a group whose scores are all exactly
+ *              zero gets the kernel's 0 / 0 (NaN), as the reference does.
+ * The weights are a by-product of the decision's own network kernel (no second pass): values / best / action are
+ * bit-identical to cn_sarl_select's on the same state, and attention == NULL IS cn_sarl_select.  CN_MODEL_SARL only:
+ * CN_MODEL_CADRL and CN_MODEL_LSTM_RL (no attention in the reference) return CN_ERR_UNSUPPORTED. */
+int cn_sarl_select_attention(cn_engine* e, double* values, int32_t* best, double* action, float* attention);
 /* replaces the epsilon-greedy branch of MultiHumanRL.predict in the train phase (multi_human_rl.py:28-31), applied to
  * the best/action a cn_sarl_select just produced: per env (mask == NULL or mask[b] != 0, and not already at its goal)
  *   probability = np.random.random(); if probability < epsilon: action_space[np.random.choice(n_actions)]
