@@ -18,7 +18,14 @@
 thread_local char cn_g_err[512] = "";
 
 // every agent's ORCA velocity on the engine's stream (cn_orca; the first kernel of cn_sarl_select in sarl_abi.hip)
-void cn_launch_orca(cn_engine* e, float* out_vel) { CN_LAUNCH_MAXL(e, orca_kernel, grid_envs(e), e->P, e->S, out_vel); }
+void cn_launch_orca(cn_engine* e, float* out_vel) {
+    pick_maxl(e, [&](auto maxl) {
+        pick_bool(e->P.kd, [&](auto kd) {
+            hipLaunchKernelGGL((cn::orca_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)), dim3(e->P.threads),
+                               e->smem, e->stream, e->P, e->S, out_vel);
+        });
+    });
+}
 
 extern "C" {
 
@@ -418,7 +425,10 @@ int cn_step(cn_engine* e, const double* action, int update, double* reward, uint
     if (!e->P.robot_orca && !action)
         return fail(CN_ERR_INVALID, "cn_step: action is required when robot_policy == CN_ROBOT_EXTERNAL");
     cn::StepIo io{action, reward, done, info, dmin, action_out, orca_vel, obs, update ? 1 : 0};
-    CN_LAUNCH_MAXL_UNI(e, step_kernel, grid_envs(e), e->P, e->S, io);
+    pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
+        hipLaunchKernelGGL((cn::step_kernel<decltype(maxl)::value, decltype(uni)::value, decltype(kd)::value>), dim3(grid_envs(e)),
+                           dim3(e->P.threads), e->smem, e->stream, e->P, e->S, io);
+    });
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -633,7 +643,11 @@ static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, 
                                (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, q, action);
         }
     } else {
-        CN_LAUNCH_ROLLOUT(e, grid_envs(e), e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
+        pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
+            hipLaunchKernelGGL((cn::rollout_kernel<decltype(maxl)::value, decltype(uni)::value, false, decltype(kd)::value>),
+                               dim3(grid_envs(e)), dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
+                               (const int*)e->S.ring_filled_in, R, n_steps, action);
+        });
     }
     if (e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] == kernels_before) e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
 }

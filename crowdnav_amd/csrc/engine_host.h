@@ -141,54 +141,31 @@ int dev_alloc(cn_engine* e, T** out, size_t n) {
 
 inline int grid_envs(const cn_engine* e) { return (e->P.B + e->P.E - 1) / e->P.E; }
 
-// launch a kernel template instantiated for the engine's half-plane capacity (and with / without the kd-tree bookkeeping of
-// simulators with more than 10 agents)
-#define CN_LAUNCH_MAXL(e, kernel, grid, ...)                                                                        \
-    do {                                                                                                            \
-        const dim3 g__(grid), b__((e)->P.threads);                                                                  \
-        if ((e)->maxl == 5 && !(e)->P.kd)                                                                           \
-            hipLaunchKernelGGL((cn::kernel<5, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__);               \
-        else if ((e)->maxl == 5)                                                                                    \
-            hipLaunchKernelGGL((cn::kernel<5, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__);                \
-        else if (!(e)->P.kd)                                                                                        \
-            hipLaunchKernelGGL((cn::kernel<10, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__);              \
-        else                                                                                                        \
-            hipLaunchKernelGGL((cn::kernel<10, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__);               \
-    } while (0)
-
-// ... and for the robot kinematics (the unicycle code only exists in the <.., true, ..> instantiations).  K: the kernel
-// template takes <MAXL, UNI, KD> (step_kernel) — rollout_kernel has HEADLINE in between, see CN_LAUNCH_ROLLOUT
-#define CN_LAUNCH_MAXL_UNI(e, kernel, grid, ...)                                                                    \
-    do {                                                                                                            \
-        const dim3 g__(grid), b__((e)->P.threads);                                                                  \
-        const int v__ = ((e)->maxl == 5 ? 0 : 4) | ((e)->P.robot_unicycle ? 2 : 0) | ((e)->P.kd ? 1 : 0);           \
-        switch (v__) {                                                                                              \
-            case 0: hipLaunchKernelGGL((cn::kernel<5, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            case 1: hipLaunchKernelGGL((cn::kernel<5, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;   \
-            case 2: hipLaunchKernelGGL((cn::kernel<5, true, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;   \
-            case 3: hipLaunchKernelGGL((cn::kernel<5, true, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;    \
-            case 4: hipLaunchKernelGGL((cn::kernel<10, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break; \
-            case 5: hipLaunchKernelGGL((cn::kernel<10, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            case 6: hipLaunchKernelGGL((cn::kernel<10, true, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            default: hipLaunchKernelGGL((cn::kernel<10, true, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-        }                                                                                                           \
-    } while (0)
-
-#define CN_LAUNCH_ROLLOUT(e, grid, ...)                                                                             \
-    do {                                                                                                            \
-        const dim3 g__(grid), b__((e)->P.threads);                                                                  \
-        const int v__ = ((e)->maxl == 5 ? 0 : 4) | ((e)->P.robot_unicycle ? 2 : 0) | ((e)->P.kd ? 1 : 0);           \
-        switch (v__) {                                                                                              \
-            case 0: hipLaunchKernelGGL((cn::rollout_kernel<5, false, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            case 1: hipLaunchKernelGGL((cn::rollout_kernel<5, false, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;   \
-            case 2: hipLaunchKernelGGL((cn::rollout_kernel<5, true, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;   \
-            case 3: hipLaunchKernelGGL((cn::rollout_kernel<5, true, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;    \
-            case 4: hipLaunchKernelGGL((cn::rollout_kernel<10, false, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break; \
-            case 5: hipLaunchKernelGGL((cn::rollout_kernel<10, false, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            case 6: hipLaunchKernelGGL((cn::rollout_kernel<10, true, false, false>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-            default: hipLaunchKernelGGL((cn::rollout_kernel<10, true, false, true>), g__, b__, (e)->smem, (e)->stream, __VA_ARGS__); break;  \
-        }                                                                                                           \
-    } while (0)
+// Run-time values as template arguments: f(std::integral_constant<int, V>{}) for the V of the list that equals v (false: none
+// does), f(std::true_type{}) or f(std::false_type{}).  A launch names its kernel as kernel<decltype(v)::value, ...>; every
+// combination of the listed values is instantiated.
+template <int... Vs, class F>
+inline bool pick_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F>
+inline void pick_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// ... the engine's half-plane capacity: 5, or 10 for everything else
+template <class F>
+inline void pick_maxl(const cn_engine* e, F&& f) {
+    if (!pick_int<5>(e->maxl, f)) f(std::integral_constant<int, 10>{});
+}
+// ... with the robot kinematics (the unicycle code only exists in the UNI instantiations) and the kd-tree bookkeeping of
+// simulators with more than 10 agents: step_kernel<MAXL, UNI, KD>, rollout_kernel<MAXL, UNI, HEADLINE, KD>
+template <class F>
+inline void pick_maxl_uni_kd(const cn_engine* e, F&& f) {
+    pick_maxl(e, [&](auto maxl) {
+        pick_bool(e->P.robot_unicycle, [&](auto uni) { pick_bool(e->P.kd, [&](auto kd) { f(maxl, uni, kd); }); });
+    });
+}
 
 [[maybe_unused]] int env_int(const char* name, int fallback) {
     const char* v = std::getenv(name);

@@ -478,11 +478,8 @@ __device__ __forceinline__ void reg_dense1(WS& ws, In in, f32x4 (&out)[MT]) {
 // X: the feature kernel's fragment order, X[((tile * 5 + h) * ks_x + ks) * 64 + lane] = feature 4 ks + (lane >> 4) of human h
 // of group lane & 15 — exactly the B operand of k-step ks.  V[group] out.  Persistent: wave w of the grid takes tiles
 // w, w + waves, ...; the next tile's X is requested while the value head of the current one runs.
-// om (XKS = 16 only; nullptr: everything comes from X): the occupancy maps [env][human][48] of the lookahead kernel.  They do
-// not depend on the action, so instead of 81 copies inside X (425 MB written by the feature kernel and read back here per
-// decision, 48 of every 61 floats) k-steps 4..15 are read from the maps themselves: lane l wants feature 4 ks + (l >> 4) of
-// group l & 15, i.e. map value 4 ks + (l >> 4) - 13 of the group's env — 16 consecutive groups are one or two envs, so the
-// loads of a k-step hit one or two cache lines.
+// XKS = k-steps of the input read from X: only 4 is instantiated (13 rotated features; the 48 occupancy-map features of the 61-wide
+// input do not depend on the action and come in through PRE, not as 81 copies inside X).
 // NT = humans of the crowd (N tiles per wave), 1..5.  With NT = 1 the MFMAs of a k-step chain are dependent (40 instead of 32
 // cycles each); from 2 humans on consecutive MFMAs alternate between accumulators.
 // PRE (XKS = 4): `om` is the term of sarl_om_term_kernel, [env][human][10 tiles][4 lane groups][4 registers] — mlp1.0's
@@ -494,7 +491,7 @@ __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_kernel(const float* s
                                                                   const float* om = nullptr, int n_actions = 1,
                                                                   [[maybe_unused]] float* att_out = nullptr) {
     static_assert(NT >= 1 && NT <= kRegHumans, "the activations of at most 5 humans fit the register file");
-    static_assert(!PRE || XKS == 4, "the hoisted occupancy-map term replaces k-steps 4..15");
+    static_assert(XKS == 4, "k-steps 4..15 of a 61-wide input are the hoisted occupancy-map term (PRE), never part of X");
     constexpr int KEY = PRE ? kRegSarlPre : XKS;
     constexpr int QT = reg_total_quads(KEY);
     const int lane = threadIdx.x & 63;
@@ -508,24 +505,12 @@ __global__ __launch_bounds__(kRegWaves * 64) void sarl_reg_kernel(const float* s
     const gfloat_p Xg = as_global(X) + lane;
     float x[NT][XKS];
     int cnt;
-    const bool om_direct = XKS == 16 && om != nullptr;
     const auto load_x = [&](int t) {
         const gfloat_p xt = Xg + (size_t)t * NT * ks_x * 64;
-        gfloat_p ob = as_global(om);
-        if (om_direct) {
-            const long long G = (long long)t * kSarlGroups + (lane & 15);
-            const int env = (int)((G < n_groups ? G : (long long)n_groups - 1) / n_actions);
-            ob += (size_t)env * NT * 48 + (lane >> 4);
-        }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int ks = 0; ks < XKS; ++ks) {
-                if (om_direct && ks >= 4)  // map value 4 ks + (lane >> 4) - 13; 61..63 do not exist (k-step 15, lanes 16..63)
-                    x[nt][ks] = (ks < 15 || lane < 16) ? ob[nt * 48 + 4 * ks - 13] : 0.0f;
-                else
-                    x[nt][ks] = xt[(nt * ks_x + ks) * 64];
-            }
+            for (int ks = 0; ks < XKS; ++ks) x[nt][ks] = xt[(nt * ks_x + ks) * 64];
     };
     load_x(wid < n_tiles ? wid : 0);
     cnt = hcount[(size_t)(wid < n_tiles ? wid : 0) * kSarlGroups + (lane & 15)];

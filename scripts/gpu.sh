@@ -11,7 +11,7 @@
 #   sarl                  cn_sarl_select timing (scripts/sarl_bench.py) for the in-tree library and build/exp/lib_ab_sarl*.so
 #   trace                 rocprofv3 --kernel-trace --stats of both bench shapes and the SARL decision
 #   pmc                   separate rocprofv3 --pmc passes: FETCH / WRITE / SQ for the fused kernel (both shapes), rollout_kernel<10>,
-#                         sarl_reg_kernel<4> and <16> (MFMA busy) -> ${TAG}_traffic.json
+#                         sarl_reg_kernel<4, 5> with and without PRE (MFMA busy) -> ${TAG}_traffic.json
 mkdir -p gpurun_out && cd /tmp && export TMPDIR=/tmp
 shopt -s nullglob
 REPO=$GRAFT_REPO_ROOT; TAG=${CN_TAG:-r06}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; cd $REPO

@@ -1,7 +1,9 @@
 """Per-kernel register / spill / LDS table of libcrowdnav_amd.so's code object, from hipcc's own resource report
 (-Rpass-analysis=kernel-resource-usage; cross-compiles without a GPU).
 
-    python scripts/kernel_resources.py [filter-regex] [-D...]      # extra -D flags go to hipcc
+    python scripts/kernel_resources.py [--tu env|sarl] [filter-regex] [-D...]      # extra -D flags go to hipcc
+
+--tu names the translation unit: env (default) = crowdnav_amd.hip, sarl = sarl_abi.hip (the value-network kernels).
 """
 import os
 import re
@@ -9,13 +11,14 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'crowdnav_amd', 'csrc', 'crowdnav_amd.hip')
+TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip'}
 
 
-def report(extra=()):
+def report(extra=(), tu='env'):
+    src = os.path.join(ROOT, 'crowdnav_amd', 'csrc', TUS[tu])
     cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-slp-vectorize',
-           '-fno-fast-math', '-Rpass-analysis=kernel-resource-usage', '-c', SRC, '-o', '/dev/null'] + list(extra)
-    err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, cwd=os.path.dirname(SRC)).stderr
+           '-fno-fast-math', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', '/dev/null'] + list(extra)
+    err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, cwd=os.path.dirname(src)).stderr
     rows, cur = [], None
     for line in err.splitlines():
         m = re.search(r'remark: +(.*?): (.*?) \[-Rpass', line)
@@ -36,10 +39,17 @@ def demangle(names):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith('-D')]
-    extra = [a for a in sys.argv[1:] if a.startswith('-D')]
+    argv, tu = sys.argv[1:], 'env'
+    if '--tu' in argv:
+        i = argv.index('--tu')
+        tu = argv[i + 1]
+        if tu not in TUS:
+            sys.exit('--tu takes one of: ' + ', '.join(TUS))
+        del argv[i:i + 2]
+    args = [a for a in argv if not a.startswith('-D')]
+    extra = [a for a in argv if a.startswith('-D')]
     pat = re.compile(args[0]) if args else None
-    rows = report(extra)
+    rows = report(extra, tu)
     if not rows:
         sys.exit('no kernel resource remarks: the compile failed (run the hipcc command by hand to see why)')
     names = demangle([r['name'] for r in rows])

@@ -215,18 +215,14 @@ def test_narrow_tile_lstm_rl_network_is_bit_identical_to_the_one_tile_kernel(hum
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('with_om', [False, True, 'maps inside the kernel'])
+@pytest.mark.parametrize('with_om', [False, True])
 def test_register_resident_and_lds_value_networks_agree(with_om, monkeypatch):
     """5 humans at the shipped widths run sarl_reg_kernel (activations in registers); CROWDNAV_AMD_SARL_REG=0 keeps the LDS
     pipe kernel on the same engine configuration.  Same inputs, same weights: both within 2e-5 of torch and within 1e-6 of
     each other (they add the bias at opposite ends of the same fma chain), including a last tile of padding groups.  With
-    occupancy maps the default hoists their half of mlp1.0 out of the action loop (sarl_om_term_kernel + sarl_reg_kernel<4, 5,
-    true>); CROWDNAV_AMD_SARL_OM_HOIST=0 keeps all 16 k-steps inside sarl_reg_kernel<16, 5>."""
+    occupancy maps their half of mlp1.0 is hoisted out of the action loop (sarl_om_term_kernel + sarl_reg_kernel<4, 5, true>)."""
     import crowdnav_amd
     from crowdnav_amd.compat.sarl import ValueNetwork, build_action_space
-    if with_om == 'maps inside the kernel':
-        monkeypatch.setenv('CROWDNAV_AMD_SARL_OM_HOIST', '0')
-        with_om = True
     torch.manual_seed(5)
     d = 61 if with_om else 13
     net = ValueNetwork(d, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
@@ -254,7 +250,7 @@ def test_register_resident_and_lds_value_networks_agree(with_om, monkeypatch):
 @pytest.mark.parametrize('humans', [1, 2, 3, 4])
 @pytest.mark.parametrize('with_om', [False, True])
 def test_register_resident_value_network_for_one_to_four_humans(humans, with_om, monkeypatch):
-    """sarl_reg_kernel<XKS, NT> for crowds of 1..4 humans (NT N tiles per wave; 3 / 2 waves per SIMD at 1 / 2 humans) against the
+    """sarl_reg_kernel<4, NT> for crowds of 1..4 humans (NT N tiles per wave; 3 / 2 waves per SIMD at 1 / 2 humans) against the
     torch module and the LDS kernel on the same engine configuration, with a ragged last tile and more tiles than resident
     waves at 3 and 4 humans."""
     import crowdnav_amd
