@@ -115,6 +115,12 @@ SYMBOLS = {
     'cn_rollout_summary': (C.c_int, [_P, C.POINTER(CnRolloutIo), _P]),
     'cn_launch_counts': (C.c_int, [_P, _P]),
     'cn_mt_random': (C.c_int, [_P, C.c_uint32, C.c_int, _P]),
+    # device SGD step (added after v12, no version bump)
+    'cn_trainer_create': (C.c_int, [C.POINTER(CnSarlConfig), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    'cn_trainer_destroy': (C.c_int, [_P]),
+    'cn_trainer_set_stream': (C.c_int, [_P, _P]),
+    'cn_train_step': (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _P, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P]),
+    'cn_trainer_steps': (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -1,6 +1,9 @@
 """Replay memory and SGD trainer on the reference's interfaces (crowd_nav/utils/memory.py:4-28,
 trainer.py:8-71).  They stay plain PyTorch (ROCm) exactly as BASELINE configs[4] asks: the rollouts come from the
-HIP engine, the optimizer from torch.  When the reference is importable its own classes can be used instead."""
+HIP engine, the optimizer from torch.  When the reference is importable its own classes can be used instead.
+Opt-in (CROWDNAV_AMD_SGD_KERNEL=1, default 0): a sarl.ValueNetwork on a GPU with a DeviceReplayMemory on the same device takes
+its SGD steps through cn_train_step instead — two HIP launches per batch on the same parameter tensors and on momentum buffers
+installed in the torch optimizer's state, so the two paths can follow each other within one run."""
 import logging
 import os
 
@@ -120,6 +123,11 @@ class Trainer(object):
         self.optimizer = None
         self._graph = None          # hipGraph of one full-batch SGD step (device memory on a GPU only)
         self._graph_failed = os.environ.get('CROWDNAV_AMD_SGD_GRAPH', '1') == '0'
+        self._kernel_on = os.environ.get('CROWDNAV_AMD_SGD_KERNEL', '0') == '1'  # device SGD step (cn_train_step), opt-in
+        self._kernel_off = False    # ... refused for this model / memory: today's path for the rest of the run
+        self._kstep = None          # crowdnav_amd.train.SarlTrainStep
+        self._kshape = None         # (H, D) of the memory the handle was made for
+        self._kopt = None           # the optimizer whose momentum buffers the handle is bound to
 
     def set_learning_rate(self, learning_rate):
         logging.info('Current learning rate: %f', learning_rate)
@@ -209,9 +217,89 @@ class Trainer(object):
         return (isinstance(self.memory, DeviceReplayMemory) and self.memory.device == torch.device(self.device)
                 and len(self.memory) > 0)
 
+    def _kernel_refused(self, why):
+        logging.warning('CROWDNAV_AMD_SGD_KERNEL=1: %s; the SGD steps stay on PyTorch', why)
+        self._kernel_off = True
+        return None
+
+    def _kernel(self):
+        """The device SGD step bound to this model, optimizer and memory, or None where today's path applies: switch off,
+        a CPU model, a list-backed memory (silently: nothing was asked of a GPU), or a model / size the library has no
+        step for (one log line, then today's path for the rest of the run)."""
+        if not self._kernel_on or self._kernel_off or not self._device_memory():
+            return None
+        states = self.memory.states
+        params = [p for g in self.optimizer.param_groups for p in g['params']]
+        if states is None or not states.is_cuda or not params or any(p.device != states.device for p in params):
+            return None
+        from .sarl import ValueNetwork
+        if not isinstance(self.model, ValueNetwork):
+            return self._kernel_refused('%s.%s has no device SGD step' % (type(self.model).__module__.rsplit('.', 1)[-1],
+                                                                                   type(self.model).__name__))
+        group = self.optimizer.param_groups[0]
+        if (len(self.optimizer.param_groups) != 1 or group.get('dampening', 0) or group.get('weight_decay', 0)
+                or group.get('nesterov', False) or group.get('maximize', False)):
+            return self._kernel_refused('the optimizer is not plain SGD with momentum')
+        shape = tuple(states.shape[1:])
+        if self._kstep is None or self._kshape != shape:
+            from .. import train as cn_train
+            from .._lib import CN_ERR_UNSUPPORTED, CrowdNavAmdError
+            try:
+                if states.dim() != 3:
+                    raise CrowdNavAmdError(CN_ERR_UNSUPPORTED, 'memory states of shape %s' % (tuple(states.shape),))
+                self._kstep = cn_train.SarlTrainStep(cn_train.module_net_config(self.model), shape[0], self.batch_size,
+                                                     states.device.index or 0)
+            except CrowdNavAmdError as exc:
+                if exc.status != CN_ERR_UNSUPPORTED:
+                    raise
+                return self._kernel_refused(str(exc))
+            self._kshape, self._kopt = shape, None
+        if self._kopt is not self.optimizer:  # a new optimizer starts from zero buffers, as torch's does
+            bufs = []
+            for p in params:
+                st = self.optimizer.state[p]
+                if st.get('momentum_buffer') is None:
+                    st['momentum_buffer'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                bufs.append(st['momentum_buffer'])
+            self._kstep.bind([p.data for p in params], bufs)
+            self._kopt = self.optimizer
+        return self._kstep
+
+    def _fit_kernel(self, kstep, index, total):
+        """One device SGD step on the ring rows `index` names; the batch's MSE is added to the float64 device scalar total."""
+        group = self.optimizer.param_groups[0]
+        kstep.step(self.memory.states, self.memory.values, index, int(index.numel()), group['lr'], group['momentum'], total)
+        self._bump()
+
+    def _draw_batches(self, count):
+        """Index sets of `count` batches, each the head of a fresh uniform permutation of the memory (trainer.py:57): the
+        batch_size largest of one i.i.d. uniform float64 key per row — a uniformly random ordered subset without duplicates,
+        since every ordering of distinct keys is equally likely.  Drawn a chunk of batches at a time (two kernels per
+        chunk instead of a sort per batch); the random stream differs from the torch path's randperm."""
+        size, k = len(self.memory), min(self.batch_size, len(self.memory))
+        chunk = max(1, min(count, (1 << 22) // size))
+        done = 0
+        while done < count:
+            c = min(chunk, count - done)
+            keys = torch.rand(c, size, dtype=torch.float64, device=self.memory.device)
+            for row in keys.topk(k, dim=1).indices:
+                yield row
+            done += c
+
     def optimize_epoch(self, num_epochs):
         if self.optimizer is None:
             raise ValueError('Learning rate is not set!')
+        kstep = self._kernel()
+        if kstep is not None:
+            average_epoch_loss = 0
+            for epoch in range(num_epochs):
+                total = torch.zeros((), dtype=torch.float64, device=self.memory.device)
+                perm = torch.randperm(self.memory.size, device=self.memory.device)
+                for start in range(0, self.memory.size, self.batch_size):
+                    self._fit_kernel(kstep, perm[start:start + self.batch_size], total)
+                average_epoch_loss = total.item() / len(self.memory)
+                logging.debug('Average loss in epoch %d: %.2E', epoch, average_epoch_loss)
+            return average_epoch_loss
         if self._device_memory():
             average_epoch_loss = 0
             for epoch in range(num_epochs):
@@ -232,6 +320,14 @@ class Trainer(object):
     def optimize_batch(self, num_batches):
         if self.optimizer is None:
             raise ValueError('Learning rate is not set!')
+        kstep = self._kernel()
+        if kstep is not None:
+            total = torch.zeros((), dtype=torch.float64, device=self.memory.device)
+            for index in self._draw_batches(num_batches):
+                self._fit_kernel(kstep, index, total)
+            average_loss = total.item() / num_batches
+            logging.debug('Average loss : %.2E', average_loss)
+            return average_loss
         if self._device_memory():
             total = torch.zeros((), device=self.memory.device)
             for _ in range(num_batches):  # a fresh permutation per batch, as trainer.py:57 does

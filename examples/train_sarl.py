@@ -172,6 +172,8 @@ def parser():
     ap.add_argument('--resume', action='store_true', help='continue from <output-dir>/rl_model.pth (train.py:106-111)')
     ap.add_argument('--seed', type=int, default=None, help='torch.manual_seed (weights, batch order); default: unseeded')
     ap.add_argument('--timing-json', default=None, help='write losses, final stats and per-phase wall-clock here')
+    ap.add_argument('--sgd-kernel', action='store_true',
+                    help='CROWDNAV_AMD_SGD_KERNEL=1 for this run: SGD steps through cn_train_step (needs --gpu, SARL)')
     for name, default in (('il-episodes', 3000), ('il-epochs', 50), ('train-episodes', 10000), ('train-batches', 100),
                           ('sample-episodes', 1), ('target-update-interval', 50), ('evaluation-interval', 1000),
                           ('checkpoint-interval', 1000), ('capacity', 100000), ('batch-size', 100),
@@ -185,6 +187,8 @@ def parser():
 
 if __name__ == '__main__':
     cli = parser().parse_args()
+    if cli.sgd_kernel:  # read by compat.Trainer when it is constructed
+        os.environ['CROWDNAV_AMD_SGD_KERNEL'] = '1'
     handlers = [logging.StreamHandler(sys.stdout)]
     if cli.output_dir:  # train.py:51-56: output.log next to the weights — what crowd_nav/utils/plot.py parses
         os.makedirs(cli.output_dir, exist_ok=True)
