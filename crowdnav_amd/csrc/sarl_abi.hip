@@ -3,6 +3,8 @@
 #define CN_SARL_TU  // step_kernels.h: the ORCA / step kernels and the engine types, not the rollout and scenario kernels
 #include "engine_host.h"
 #include "sarl_kernels.h"
+#include "sarl_lds_kernels.h"
+#include "sarl_narrow_kernel.h"
 #include "sarl_reg_kernel.h"
 #include "sarl_step_fused.h"
 
@@ -153,7 +155,6 @@ int sarl_size_network(cn_sarl* s, bool* lds_chunked) {
     if (lstm) {
         net.ks_a = ks_of(max2(max2(j0, j1), max2(j2, 6 + hid)));
         net.ks_b = net.ks_c = 0;
-        const size_t ks_g = (size_t)net.L[cn::kL_mlp1_0].ctiles * 4, ks_h = (size_t)cn::sarl_ks(hid);
         if (pairwise) {  // ping-pong buffers of ValueNetwork2.mlp1, all H row tiles: widths d0, d2 -> ks_b; d1, d3 -> ks_c
             const int* id = c->interaction_dims;
             net.ks_b = ks_of(max2(id[0], id[2]));
@@ -161,25 +162,19 @@ int sarl_size_network(cn_sarl* s, bool* lds_chunked) {
         }
         // more than kSarlMaxHumans humans: lstm_mlp_anyh_kernel stages one human's row tile per LSTM step (nothing sized by H)
         // (... and whenever H row tiles do not fit: ValueNetwork2's ping-pong buffers from 6 humans on)
-        const auto lds_for = [&](size_t row_tiles) {
-            return sizeof(float) * (64 * (row_tiles * (net.ks_x + net.ks_b + net.ks_c) + ks_g + ks_h + 2 * net.ks_a + net.ks_s) +
-                                    (size_t)hid * cn::kSarlGroups);
-        };
-        chunked = H > cn::kSarlMaxHumans || lds_for((size_t)H) > 160 * 1024;
-        s->lds_bytes = lds_for(chunked ? 1 : (size_t)H);
+        chunked = H > cn::kSarlMaxHumans || cn::lstm_lds_bytes(net, H, hid) > 160 * 1024;
+        s->lds_bytes = cn::lstm_lds_bytes(net, chunked ? 1 : H, hid);
     } else if (cadrl) {  // ping-pong between A (first / third hidden layer) and B (X staging, second hidden layer)
         net.ks_a = ks_of(max2(j0, j2));
         net.ks_b = max2(ks_of(j1), net.ks_x);
         net.ks_c = 0;
-        s->lds_bytes = sizeof(float) * 64 * (size_t)H * (net.ks_a + net.ks_b + net.ks_s);
         chunked = H > cn::kSarlMaxHumans;  // cadrl_mlp_chunked_kernel streams the humans in chunks of 5
-        if (chunked) s->lds_bytes = cn::cadrl_mlp_chunked_lds_bytes(net);
+        s->lds_bytes = cn::cadrl_lds_bytes(net, chunked ? cn::kSarlChunk : H, chunked);
     } else {
         // one tile's activations + the side chain's pong buffer (sarl_mlp_pipe_kernel) in LDS, or the humans stream through
         // in chunks (6+ humans at the shipped widths)
-        s->lds_bytes = cn::sarl_mlp_lds_bytes(net) + cn::sarl_mlp_pipe_extra_lds_bytes(net);
-        chunked = H > cn::kSarlMaxHumans || s->lds_bytes > 160 * 1024;
-        if (chunked) s->lds_bytes = cn::sarl_mlp_chunked_lds_bytes(net);
+        chunked = H > cn::kSarlMaxHumans || cn::sarl_pipe_lds_bytes(net, H) > 160 * 1024;
+        s->lds_bytes = chunked ? cn::sarl_chunked_lds_bytes(net) : cn::sarl_pipe_lds_bytes(net, H);
     }
     s->n_groups = (size_t)s->C.B * s->C.n_actions;
     s->n_tiles = (s->n_groups + cn::kSarlGroups - 1) / cn::kSarlGroups;
@@ -522,7 +517,7 @@ int launch_lds(cn_engine* e, float* att) {  // LdsTile, LdsChunked
     const int ng = (int)s->n_groups;
     const bool cadrl = is_cadrl(s->cfg), lstm = is_lstm(s->cfg), chunked = s->route == SarlRoute::LdsChunked;
     if (chunked && cadrl)
-        hipLaunchKernelGGL(cn::cadrl_mlp_chunked_kernel<cn::kSarlChunk5>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
+        hipLaunchKernelGGL(cn::cadrl_mlp_chunked_kernel<cn::kSarlChunk>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
     else if (chunked && lstm)
         hipLaunchKernelGGL(cn::lstm_mlp_anyh_kernel, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
     else if (chunked)
@@ -652,7 +647,7 @@ int cn_sarl_configure(cn_engine* e, const cn_sarl_config* c, const double* actio
                         "value networks under the mixed rule run the one-tile kernel (it masks an episode's absent humans), whose "
                         "tile — activations %zu B + the pipelined side buffer %zu B — must fit the 160 KiB of LDS; these layer "
                         "widths do not (narrower mlp1 / mlp3 layers do: the shipped 150-wide network needs 150.5 KiB)",
-                        cn::sarl_mlp_lds_bytes(s->net), cn::sarl_mlp_pipe_extra_lds_bytes(s->net));
+                        cn::sarl_pipe_lds_bytes(s->net, s->C.H) - sizeof(float) * 64 * (size_t)s->net.ks_a, sizeof(float) * 64 * (size_t)s->net.ks_a);
         return fail(CN_ERR_UNSUPPORTED,
                     "value networks under the mixed rule run the one-tile kernels (they mask an episode's absent humans): "
                     "num_humans must be 5 (the rule never draws more)");

@@ -1,7 +1,7 @@
 // sarl.ValueNetwork.forward (crowd_nav/policy/sarl.py:28-65) with the ACTIVATIONS IN REGISTERS: the shipped widths
 // (mlp1 150-100, mlp2 100-50, attention 100-100-1 with the global state, mlp3 150-100-100-1) and 5 humans.
 //
-// The LDS kernels (sarl_kernels.h) compute Y = X W^T with the activations as the MFMA A operand: a layer's output has to
+// The LDS kernels (sarl_lds_kernels.h) compute Y = X W^T with the activations as the MFMA A operand: a layer's output has to
 // travel through LDS to become the next layer's input, every layer ends in a workgroup barrier, and 7 column tiles on 16
 // waves leave the MFMA pipes 54 % busy.  Here a wave computes Y^T = W X^T for ITS OWN 16 (env, action) groups x 5 humans
 // (5 "N tiles" of 16 rows) through the whole network:
