@@ -1,9 +1,9 @@
 """Replay memory and SGD trainer on the reference's interfaces (crowd_nav/utils/memory.py:4-28,
 trainer.py:8-71).  They stay plain PyTorch (ROCm) exactly as BASELINE configs[4] asks: the rollouts come from the
 HIP engine, the optimizer from torch.  When the reference is importable its own classes can be used instead.
-Opt-in (CROWDNAV_AMD_SGD_KERNEL=1, default 0): a sarl.ValueNetwork on a GPU with a DeviceReplayMemory on the same device takes
-its SGD steps through cn_train_step instead — two HIP launches per batch on the same parameter tensors and on momentum buffers
-installed in the torch optimizer's state, so the two paths can follow each other within one run."""
+Opt-in (CROWDNAV_AMD_SGD_KERNEL=1, default 0): a sarl.ValueNetwork or an lstm_rl.ValueNetwork1 on a GPU with a DeviceReplayMemory
+on the same device takes its SGD steps through cn_train_step instead — two HIP launches per batch on the same parameter tensors
+and on momentum buffers installed in the torch optimizer's state, so the two paths can follow each other within one run."""
 import logging
 import os
 
@@ -125,7 +125,7 @@ class Trainer(object):
         self._graph_failed = os.environ.get('CROWDNAV_AMD_SGD_GRAPH', '1') == '0'
         self._kernel_on = os.environ.get('CROWDNAV_AMD_SGD_KERNEL', '0') == '1'  # device SGD step (cn_train_step), opt-in
         self._kernel_off = False    # ... refused for this model / memory: today's path for the rest of the run
-        self._kstep = None          # crowdnav_amd.train.SarlTrainStep
+        self._kstep = None          # crowdnav_amd.train.SarlTrainStep / LstmTrainStep
         self._kshape = None         # (H, D) of the memory the handle was made for
         self._kopt = None           # the optimizer whose momentum buffers the handle is bound to
 
@@ -232,8 +232,9 @@ class Trainer(object):
         params = [p for g in self.optimizer.param_groups for p in g['params']]
         if states is None or not states.is_cuda or not params or any(p.device != states.device for p in params):
             return None
+        from .lstm_rl import ValueNetwork1
         from .sarl import ValueNetwork
-        if not isinstance(self.model, ValueNetwork):
+        if not isinstance(self.model, (ValueNetwork, ValueNetwork1)):
             return self._kernel_refused('%s.%s has no device SGD step' % (type(self.model).__module__.rsplit('.', 1)[-1],
                                                                                    type(self.model).__name__))
         group = self.optimizer.param_groups[0]
@@ -247,8 +248,8 @@ class Trainer(object):
             try:
                 if states.dim() != 3:
                     raise CrowdNavAmdError(CN_ERR_UNSUPPORTED, 'memory states of shape %s' % (tuple(states.shape),))
-                self._kstep = cn_train.SarlTrainStep(cn_train.module_net_config(self.model), shape[0], self.batch_size,
-                                                     states.device.index or 0)
+                make = cn_train.LstmTrainStep if isinstance(self.model, ValueNetwork1) else cn_train.SarlTrainStep
+                self._kstep = make(cn_train.module_net_config(self.model), shape[0], self.batch_size, states.device.index or 0)
             except CrowdNavAmdError as exc:
                 if exc.status != CN_ERR_UNSUPPORTED:
                     raise

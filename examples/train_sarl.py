@@ -173,7 +173,8 @@ def parser():
     ap.add_argument('--seed', type=int, default=None, help='torch.manual_seed (weights, batch order); default: unseeded')
     ap.add_argument('--timing-json', default=None, help='write losses, final stats and per-phase wall-clock here')
     ap.add_argument('--sgd-kernel', action='store_true',
-                    help='CROWDNAV_AMD_SGD_KERNEL=1 for this run: SGD steps through cn_train_step (needs --gpu, SARL)')
+                    help='CROWDNAV_AMD_SGD_KERNEL=1 for this run: SGD steps through cn_train_step (needs --gpu; SARL, or '
+                         'LSTM-RL without the interaction module)')
     for name, default in (('il-episodes', 3000), ('il-epochs', 50), ('train-episodes', 10000), ('train-batches', 100),
                           ('sample-episodes', 1), ('target-update-interval', 50), ('evaluation-interval', 1000),
                           ('checkpoint-interval', 1000), ('capacity', 100000), ('batch-size', 100),

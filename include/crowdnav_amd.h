@@ -432,21 +432,27 @@ int cn_mt_random(cn_engine* e, uint32_t seed, int n, double* out);
  * Device SGD step (added after v12, no version bump: purely additive).  Replaces ONE iteration of Trainer.optimize_epoch /
  * optimize_batch (crowd_nav/utils/trainer.py:21-23, 56-66):
  *   optimizer.zero_grad(); loss = MSELoss()(model(x), y); loss.backward(); optimizer.step()
- * with optim.SGD(lr, momentum) — dampening 0, no weight decay, no Nesterov — for crowd_nav/policy/sarl.py:9-65 as two
- * launches, float32 throughout.  A trainer needs no environments and is therefore not a cn_engine; it keeps NO copy of the
+ * with optim.SGD(lr, momentum) — dampening 0, no weight decay, no Nesterov — for crowd_nav/policy/sarl.py:9-65 or
+ * crowd_nav/policy/lstm_rl.py:9-33 as two launches, float32 throughout.  A trainer needs no environments and is therefore not a cn_engine; it keeps NO copy of the
  * parameters: they and their momentum buffers are the caller's tensors, updated in place, so state_dict(), checkpoints,
  * update_target_model and cn_sarl_set_weights see them as after a framework step.
- * Built for CN_MODEL_SARL, with_global_state = 1, the shipped widths (mlp1 150,100 / mlp2 100,50 / attention 100,100,1 /
- * mlp3 150,100,100,1), input width 13 + (with_om ? cell_num^2 * om_channel_size : 0) <= 64, 1..8 humans, batches of
- * 1..128; anything else is CN_ERR_UNSUPPORTED (n_actions, gamma, cell_size and the other fields of net are not read).
+ * Built for two networks, the shipped widths only; anything else is CN_ERR_UNSUPPORTED with a message that names the field and
+ * the value (n_actions, gamma, cell_size and the other fields of net are not read):
+ *   CN_MODEL_SARL     with_global_state = 1, mlp1 150,100 / mlp2 100,50 / attention 100,100,1 / mlp3 150,100,100,1: 22 tensors.
+ *   CN_MODEL_LSTM_RL  lstm_rl.ValueNetwork1 under the convention of cn_sarl_config above: mlp1_dims = (hidden, 1) with hidden =
+ *                     50, mlp3_dims = the value head 150,100,100,1 (its input: 6 self-state columns + hidden), interaction_dims
+ *                     all zero (non-zero = lstm_rl.ValueNetwork2: refused): 12 tensors.  The humans are the LSTM's steps in the
+ *                     order of the rows; torch's gate order i, f, g, o.
+ * Both: input width 13 + (with_om ? cell_num^2 * om_channel_size : 0) <= 64, 1..8 humans, batches of 1..128.
  * cn_trainer_create validates and touches no device; the first cn_train_step probes it and allocates the scratch rows
  * (make that call outside a stream capture; every later one is two kernel launches and capturable). */
 typedef struct cn_trainer cn_trainer;
 int cn_trainer_create(const cn_sarl_config* net, int num_humans, int max_batch, int device, cn_trainer** out);
 int cn_trainer_destroy(cn_trainer* t);
 int cn_trainer_set_stream(cn_trainer* t, void* hip_stream);
-/* params_host_array / momentum_host_array: HOST arrays of 22 DEVICE pointers in state_dict order (as cn_sarl_set_weights
- * takes them), weights [out][in] row-major; a zero momentum buffer gives the framework's first step (buf = g).
+/* params_host_array / momentum_host_array: HOST arrays of 22 (CN_MODEL_SARL) or 12 (CN_MODEL_LSTM_RL: mlp.{0,2,4,6}.{weight,
+ * bias}, lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0) DEVICE pointers in state_dict order (as cn_sarl_set_weights
+ * takes them), every one non-NULL, weights [out][in] row-major; a zero momentum buffer gives the framework's first step (buf = g).
  * states float32 [rows][num_humans][D] and values float32 [rows] are read WHERE THEY LIE — a replay ring — through
  * index int64 [n] (device; NULL = rows 0..n-1); an index outside [0, rows) is clamped into it rather than read out of bounds.
  * Per parameter tensor: buf = momentum_factor * buf + g; p -= lr * buf, g summed over the batch rows in row order by one

@@ -1,0 +1,149 @@
+"""Shared by test_train_step_lstm_host.py / test_train_step_lstm.py: the LSTM-RL fixtures' replay memories at other crowd sizes,
+torch's SGD step on lstm_rl.ValueNetwork1 as the reference Trainer takes it, a numpy restatement of the formulas the device
+step is written from (torch's gate order i, f, g, o; back through time from dh_H = dJ[:, 6:]; 16-row partial sums for the weight
+gradients), and the project's rule for judging a float32 step against the float64 truth (tests/test_train_step.py)."""
+import os
+
+import numpy as np
+import torch
+
+from conftest import GOLDEN
+from sgd_step_reference import report  # noqa: F401  (the LSTM tables go to the same file, keys prefixed lstm/)
+
+FIXTURES = ('rl_lstm_rl.npz', 'rl_lstm_rl_om.npz')
+NAMES = ['mlp.%d.%s' % (i, w) for i in (0, 2, 4, 6) for w in ('weight', 'bias')] + \
+        ['lstm.weight_ih_l0', 'lstm.weight_hh_l0', 'lstm.bias_ih_l0', 'lstm.bias_hh_l0']
+HIDDEN = 50
+FACTOR, FLOOR = 8.0, 2.0 ** -20
+
+
+def load(fixture, H=5):
+    """(params {name: float32 array}, states [rows, H, D], values [rows]); H = 1, 3: the first humans; 8: rows 0-4 then 0-2."""
+    g = np.load(os.path.join(GOLDEN, fixture))
+    P = {k[6:]: g[k] for k in g.files if k.startswith('param_')}
+    assert list(P) == NAMES
+    S, V = g['memory_states'], g['memory_values']
+    S = np.concatenate([S, S[:, :H - 5]], 1) if H > 5 else S[:, :H]
+    return P, np.ascontiguousarray(S), np.ascontiguousarray(V)
+
+
+def network(P, dtype, device='cpu'):
+    from crowdnav_amd.compat.lstm_rl import ValueNetwork1
+    m = ValueNetwork1(P['lstm.weight_ih_l0'].shape[1], 6, [150, 100, 100, 1], HIDDEN).to(dtype)
+    m.load_state_dict({k: torch.from_numpy(v).to(dtype) for k, v in P.items()})
+    return m.to(device)
+
+
+def torch_steps(P, batches, lr, mom, dtype, device='cpu', buf0=None):
+    """The reference Trainer's step (trainer.py:56-66) on each (x, y) of batches.  Returns (params, buffers, last loss,
+    last gradients) as float64 numpy dicts.  ValueNetwork1.forward makes its h_0 / c_0 in torch's default dtype, so a float64
+    model runs under that default (put back afterwards)."""
+    default = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+        m = network(P, dtype, device)
+        opt = torch.optim.SGD(m.parameters(), lr=lr, momentum=mom)
+        if buf0 is not None:
+            for (k, p) in m.named_parameters():
+                opt.state[p]['momentum_buffer'] = torch.from_numpy(np.asarray(buf0[k])).to(dtype).to(device).clone()
+        crit = torch.nn.MSELoss()
+        for x, y in batches:
+            opt.zero_grad()
+            loss = crit(m(torch.from_numpy(x).to(dtype).to(device)), torch.from_numpy(y).to(dtype).to(device).reshape(-1, 1))
+            loss.backward()
+            opt.step()
+    finally:
+        torch.set_default_dtype(default)
+    out = lambda f: {k: f(p).detach().double().cpu().numpy() for k, p in m.named_parameters()}  # noqa: E731
+    return out(lambda p: p), out(lambda p: opt.state[p]['momentum_buffer']), float(loss.detach().double()), out(lambda p: p.grad)
+
+
+def manual_step(P, x, y, lr, mom, buf, dt):
+    """One step in dtype dt by the device step's formulas.  Returns (params, buffers, loss)."""
+    P = {k: v.astype(dt) for k, v in P.items()}
+    n, H, d = x.shape
+    x, y = x.astype(dt), y.astype(dt).reshape(-1, 1)
+    one = dt(1.0)
+    sig = lambda z: one / (one + np.exp(-z))  # noqa: E731
+    lin = lambda a, p: a @ P[p + '.weight'].T + P[p + '.bias']  # noqa: E731
+    Wih, Whh = P['lstm.weight_ih_l0'], P['lstm.weight_hh_l0']
+    gx = (x.reshape(-1, d) @ Wih.T + P['lstm.bias_ih_l0']).reshape(n, H, -1)  # the input half of every step's gates, up front
+    h, c, kept = np.zeros((n, HIDDEN), dt), np.zeros((n, HIDDEN), dt), []
+    for t in range(H):
+        z = gx[:, t] + (h @ Whh.T + P['lstm.bias_hh_l0'])
+        i, f, g, o = sig(z[:, :50]), sig(z[:, 50:100]), np.tanh(z[:, 100:150]), sig(z[:, 150:])
+        cn = f * c + i * g
+        kept.append((i, f, g, o, c, cn, h))
+        h, c = o * np.tanh(cn), cn
+    j = np.concatenate([x[:, 0, :6], h], 1)
+    d1 = lin(j, 'mlp.0'); q1 = np.maximum(d1, 0); d2 = lin(q1, 'mlp.2'); q2 = np.maximum(d2, 0)  # noqa: E702
+    d3 = lin(q2, 'mlp.4'); q3 = np.maximum(d3, 0); v = lin(q3, 'mlp.6')  # noqa: E702
+    loss = ((v - y) ** 2).mean(dtype=dt)
+    G = {}
+
+    def grad(dout, ain):  # the update kernel's sum: all rows in row order, here as 16-row partial sums
+        gw, gb = np.zeros((dout.shape[1], ain.shape[1]), dt), np.zeros(dout.shape[1], dt)
+        for r in range(0, len(dout), 16):
+            gw += dout[r:r + 16].T @ ain[r:r + 16]
+            gb += dout[r:r + 16].sum(0)
+        return gw, gb
+
+    def back(dout, ain, p):
+        G[p + '.weight'], G[p + '.bias'] = grad(dout, ain)
+        return dout @ P[p + '.weight']
+
+    t = back((dt(2.0) / dt(n) * (v - y)).astype(dt), q3, 'mlp.6') * (d3 > 0)
+    t = back(t, q2, 'mlp.4') * (d2 > 0)
+    t = back(t, q1, 'mlp.2') * (d1 > 0)
+    dh = back(t, j, 'mlp.0')[:, 6:]
+    dc = np.zeros((n, HIDDEN), dt)
+    dG, hp = np.zeros((n, H, 4 * HIDDEN), dt), np.zeros((n, H, HIDDEN), dt)
+    for t in range(H - 1, -1, -1):
+        i, f, g, o, cp, cn, hprev = kept[t]
+        tc = np.tanh(cn)
+        dc = dc + dh * o * (one - tc * tc)
+        do = dh * tc * (o * (one - o))
+        di = dc * g * (i * (one - i))
+        dg = dc * i * (one - g * g)
+        df = dc * cp * (f * (one - f))
+        dc = dc * f
+        dG[:, t] = np.concatenate([di, df, dg, do], 1)
+        hp[:, t] = hprev
+        dh = dG[:, t] @ Whh
+    G['lstm.weight_ih_l0'], G['lstm.bias_ih_l0'] = grad(dG.reshape(n * H, -1), x.reshape(n * H, d))
+    G['lstm.weight_hh_l0'], G['lstm.bias_hh_l0'] = grad(dG.reshape(n * H, -1), hp.reshape(n * H, -1))
+    newP, newB = {}, {}
+    for k in P:
+        newB[k] = (dt(mom) * buf[k].astype(dt) + G[k]).astype(dt)
+        newP[k] = (P[k] - dt(lr) * newB[k]).astype(dt)
+    return newP, newB, float(loss)
+
+
+# ---- the rule (tests/test_train_step.py): per tensor the error of the momentum buffer after the step,
+# max|buf - buf64| / max(max|buf64|, 1e-6 G), pooled over the cases of one (fixture, H); E_new <= max(8 E_torch, 2^-20)
+
+def zero_gradient(name, H):
+    """h_0 = 0, so at H = 1 nothing multiplies W_hh: its gradient is exactly zero and is judged absolutely."""
+    return H == 1 and name == 'lstm.weight_hh_l0'
+
+
+def errors(buf, buf64, grad64):
+    G = max(np.abs(g).max() for g in grad64.values())
+    return {k: np.abs(np.asarray(buf[k], np.float64) - buf64[k]).max() / max(np.abs(buf64[k]).max(), 1e-6 * G) for k in NAMES}, G
+
+
+def pool(into, new):
+    for k, v in new.items():
+        into[k] = max(into.get(k, 0.0), float(v))
+
+
+def check_pooled(E_torch, E_new, H, where):
+    table, bad = {}, []
+    for k in NAMES:
+        ratio = E_new[k] / E_torch[k] if E_torch[k] > 0 else float('inf')
+        judged = 'absolute' if zero_gradient(k, H) else 'ratio'
+        table[k] = dict(E_torch=E_torch[k], E_kernel=E_new[k], ratio=ratio, judged=judged)
+        print('%-28s %-20s E_torch %.3e  E_kernel %.3e  ratio %6.2f  %s' % (where, k, E_torch[k], E_new[k], ratio, judged))
+        if not zero_gradient(k, H) and not E_new[k] <= max(FACTOR * E_torch[k], FLOOR):
+            bad.append((k, E_torch[k], E_new[k]))
+    return table, bad
