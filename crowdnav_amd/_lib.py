@@ -65,6 +65,14 @@ class CnRolloutIo(C.Structure):
     ]
 
 
+class CnTraceOut(C.Structure):
+    """struct cn_trace_out (include/crowdnav_amd.h): device pointers; reward, info and dmin may be NULL."""
+    _fields_ = [
+        ('state8', C.c_void_p), ('episode', C.c_void_p), ('step', C.c_void_p),
+        ('reward', C.c_void_p), ('info', C.c_void_p), ('dmin', C.c_void_p),
+    ]
+
+
 class CnSarlConfig(C.Structure):
     """struct cn_sarl_config (include/crowdnav_amd.h)."""
     _fields_ = [
@@ -121,6 +129,8 @@ SYMBOLS = {
     'cn_trainer_set_stream': (C.c_int, [_P, _P]),
     'cn_train_step': (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _P, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P]),
     'cn_trainer_steps': (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    # per-step record of a batched ORCA rollout (added after v12, no version bump)
+    'cn_rollout_trace': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnTraceOut)]),
 }
 
 _lib = None

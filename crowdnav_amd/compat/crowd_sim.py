@@ -288,7 +288,9 @@ class CrowdSim(_Base):
         return int(out['best'].cpu()[0]), out['values'].cpu().numpy()[0].tolist()
 
     def render(self, mode='human', output_file=None):
-        raise NotImplementedError('rendering is outside the accelerated path; use the reference CrowdSim')
+        raise NotImplementedError('rendering is outside the accelerated path; use the reference CrowdSim (the states it would '
+                                  'draw: env.states here, Explorer.keep_trajectories / examples/dump_trajectories.py '
+                                  'for a whole batched phase)')
 
     def get_human_times(self):
         """crowd_sim.py:209-249: after the robot reached its goal, run ONE centralised rvo2 simulation of all agents

@@ -16,6 +16,7 @@ from ..engine import BatchedCrowdSim
 from .policy import is_device_orca
 from .sarl import SARL
 from ..sarl_rollout import SarlRollout
+from ..trace import episodes as trace_episodes
 from .types import Collision, Danger, ReachGoal, Timeout
 
 
@@ -25,6 +26,11 @@ def average(values):
 
 class Explorer(object):
     max_envs = 4096  # envs per batched launch
+    # Batched ORCA-robot runs (_run_batched) keep every episode's joint states when this is set: last_batch['trajectories'] is
+    # then a list in case order of float64 [steps, A, 8] arrays — the state before each transition, the reference's env.states
+    # without its last entry (engine.rollout_trace).  An attribute, not a parameter: run_k_episodes keeps the reference's
+    # signature.  Off: nothing is recorded, launched or allocated for it.
+    keep_trajectories = False
 
     def __init__(self, env, robot, device, memory=None, gamma=None, target_policy=None):
         self.env = env
@@ -237,8 +243,14 @@ class Explorer(object):
             # (no job-wide counter, no in-kernel statistics: the records are read once below, as explorer.py:50-90 does)
             bufs = eng.rollout_begin(seed_base=offset + start, seed_mod=size, episode_limit=k, record_capacity=per_env,
                                      per_env_transitions=True)
+            traces = []
             while True:
-                eng.rollout(max_steps)
+                if self.keep_trajectories:  # rows go to the host call by call: the device holds one call's trace at a time
+                    tr = eng.rollout_trace(max_steps)
+                    traces.append({n: v.cpu().numpy() for n, v in tr.items()})
+                    del tr
+                else:
+                    eng.rollout(max_steps)
                 if int(bufs['active'].sum().item()) == 0:
                     break
             rec = {n: bufs[n].cpu().numpy() for n in names}
@@ -254,6 +266,7 @@ class Explorer(object):
             while ro.any_active():
                 ro.run(8)
             rec = {n: ro.rec[m].cpu().numpy() for n, m in zip(names, ('outcome', 'steps', 'ret', 'time', 'danger', 'dsum'))}
+            traces = []
         env.case_counter[phase] = (start + k) % size
         # episode id c = b + j*B  ->  record [b, j]
         order = [(c % B, c // B) for c in range(k)]
@@ -262,6 +275,9 @@ class Explorer(object):
         returns = [float(rec['ep_return'][b, j]) for b, j in order]
         self.last_batch = dict(outcome=outcome, nav_time=times, discounted_return=returns,
                                steps=[int(rec['ep_steps'][b, j]) for b, j in order])
+        if traces:  # global episode id c of the rollout = case c of this call
+            per_episode = trace_episodes(traces)
+            self.last_batch['trajectories'] = [per_episode[c]['state8'] for c in range(k)]
         success_times = [t for o, t in zip(outcome, times) if o == _lib.REACH_GOAL]
         collision_times = [t for o, t in zip(outcome, times) if o == _lib.COLLISION]
         timeout_times = [t for o, t in zip(outcome, times) if o == _lib.TIMEOUT]

@@ -669,6 +669,38 @@ int cn_rollout(cn_engine* e, const cn_rollout_io* io, int n_steps) {
     return CN_OK;
 }
 
+// cn_rollout with the per-step rows of `out`: cn_rollout's host path, then ONE launch of rollout_trace_kernel — the generic
+// phase kernel's instantiation for the engine's half-plane capacity and kd bookkeeping — whatever the geometry.
+int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const cn_trace_out* out) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_rollout_trace: engine is NULL");
+    if (!out) return fail(CN_ERR_INVALID, "cn_rollout_trace: out is NULL");
+    if (!out->state8) return fail(CN_ERR_INVALID, "cn_rollout_trace: out->state8 is NULL");
+    if (!out->episode) return fail(CN_ERR_INVALID, "cn_rollout_trace: out->episode is NULL");
+    if (!out->step) return fail(CN_ERR_INVALID, "cn_rollout_trace: out->step is NULL");
+    if (!e->P.robot_orca)
+        return fail(CN_ERR_UNSUPPORTED, "cn_rollout_trace needs an on-device robot policy (robot_policy == CN_ROBOT_ORCA); with "
+                                        "CN_ROBOT_EXTERNAL use cn_rollout_step(action)");
+    int rc = bind(e);
+    if (rc) return rc;
+    if ((rc = check_io(e, io))) return rc;
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
+    if (n_steps == 0) return CN_OK;
+    if ((rc = upload_io(e, io))) return rc;
+    cn::RolloutView R{e->io_dev, e->discount, e->discount_len};
+    if ((rc = fill_ring_if_needed(e, R, n_steps))) return rc;
+    const cn_trace_out T = *out;
+    pick_maxl(e, [&](auto maxl) {
+        pick_bool(e->P.kd, [&](auto kd) {
+            hipLaunchKernelGGL((cn::rollout_trace_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)),
+                               dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
+                               (const int*)e->S.ring_filled_in, R, n_steps, T);
+        });
+    });
+    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
 int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action) {
     int rc = bind(e);
     if (rc) return rc;

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CnConfig, CnRolloutIo, check
+from ._lib import CnConfig, CnRolloutIo, CnTraceOut, check
 
 # shipped defaults of crowd_nav/configs/env.config + the hard-coded ORCA constants (orca.py:60-66)
 _DEFAULTS = dict(
@@ -226,6 +226,45 @@ class BatchedCrowdSim(object):
             raise RuntimeError('call rollout_begin() first')
         check(self._lib.cn_rollout(self._h, C.byref(self._rollout[0]), int(n_steps)))
         return self._rollout[1]
+
+    def rollout_trace(self, n_steps, rewards=False, out=None):
+        """rollout(n_steps) that also records every step (cn_rollout_trace): the same transitions, counters and records, plus a
+        dict of device tensors whose row [b, t] belongs to the t-th step of THIS call —
+            state8  float64 [B, n, A, 8]  the joint state BEFORE the transition (get_state()'s layout; env.states of the reference)
+            episode int32   [B, n]        ordinal j of env b's episode (global id env_offset + b + j * env_stride);
+                                          -1 where the env made no transition (retired, or waiting for a scenario)
+            step    int32   [B, n]        index of the transition inside its episode (0 = from the reset state)
+        and with rewards=True reward float64, info uint8, dmin float64 [B, n]: what step() returns for that transition.
+        Where episode is -1 the other arrays are not written (fresh tensors hold whatever torch.empty left there).  The state
+        after an episode's last transition is not recorded: the next row is the next episode's reset state.
+        Size: 64 * A + 8 bytes per env-step, plus 17 with rewards (4096 envs x 5 humans x 1000 steps: 1.6 GB) — trace in
+        chunks, or pass the previous call's dict as `out` to reuse it (validated; episode is refilled with -1).
+        One launch of the generic phase kernel whatever the geometry: slower than rollout(), which it may be mixed with freely.
+        crowdnav_amd.trace.episodes() splits the result into episodes on the host."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        n = int(n_steps)
+        if n < 0:
+            raise ValueError('n_steps must be >= 0')
+        spec = dict(state8=(torch.float64, (self.B, n, self.A, 8)), episode=(torch.int32, (self.B, n)),
+                    step=(torch.int32, (self.B, n)))
+        if rewards:
+            spec.update(reward=(torch.float64, (self.B, n)), info=(torch.uint8, (self.B, n)), dmin=(torch.float64, (self.B, n)))
+        if out is None:
+            out = {k: self._new(shape, dt) for k, (dt, shape) in spec.items()}
+        else:
+            for k, (dt, shape) in spec.items():
+                t = out.get(k)
+                if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape
+                        or not t.is_contiguous()):
+                    raise ValueError('rollout_trace: out[%r] must be a contiguous %s %s tensor on %s' % (k, dt, shape, self.device))
+            out = {k: out[k] for k in spec}
+        out['episode'].fill_(-1)
+        if n == 0:  # a no-op, as rollout(0) is (empty tensors have no address to hand over)
+            return out
+        tr =CnTraceOut(**{k: v.data_ptr() for k, v in out.items()})
+        check(self._lib.cn_rollout_trace(self._h, C.byref(self._rollout[0]), n, C.byref(tr)))
+        return out
 
     def rollout_step(self, action):
         """One bookkept transition of every running env with caller-supplied actions ([B, 2] float64 device tensor):

@@ -464,6 +464,31 @@ int cn_train_step(cn_trainer* t, float* const* params_host_array, float* const* 
 /* steps_host (HOST pointer): cn_train_step calls of this trainer that launched their kernels. */
 int cn_trainer_steps(const cn_trainer* t, int64_t* steps_host);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Per-step record of a batched ORCA rollout (added after v12, no version bump: purely additive).  The reference keeps
+ * env.states for every episode it runs (crowd_sim/envs/crowd_sim.py:246,393: the joint state is appended BEFORE the step);
+ * cn_rollout returns per-episode totals only.  cn_rollout_trace(e, io, n, out) changes the engine and io exactly as
+ * cn_rollout(e, io, n) does — same checks, same scenario-ring fill, same states, counters, records, transitions, summary /
+ * blocks; the two may be mixed freely on one rollout — and writes row [b][t] of `out` for the t-th step of THIS call:
+ *   - an env that makes a transition at step t: every non-NULL array's row;
+ *   - an env that is retired (episode_limit reached) or waiting for a scenario: episode[b][t] = -1, nothing else;
+ *   - the state AFTER an episode's last transition is not recorded: the next row is the next episode's reset state, step 0;
+ *   - humans absent under the `mixed` rule show as the parked placeholders cn_get_state shows.
+ * Always ONE launch of the generic phase kernel (counted under CN_COUNT_ROLLOUT_KERNELS, never under
+ * CN_COUNT_SCHEDULED_KERNELS): the fused small-crowd kernel and the 20-human shard kernel are not involved, so a traced call
+ * is slower than cn_rollout — this is the inspection path.  64 A + 8 bytes per env-step, 17 more with all optional arrays.
+ * NULL e / out / state8 / episode / step: CN_ERR_INVALID; CN_ROBOT_EXTERNAL: CN_ERR_UNSUPPORTED (use cn_rollout_step).
+ * Asynchronous on the engine's stream. */
+typedef struct cn_trace_out {      /* all DEVICE pointers */
+    double*  state8;   /* [B][n_steps][A][8]  required: the state before the transition, as cn_get_state lays it out */
+    int32_t* episode;  /* [B][n_steps]        required: ordinal j of the env's episode (global id env_offset + b + j * env_stride); -1 = no transition */
+    int32_t* step;     /* [B][n_steps]        required: index of the transition inside its episode (0 = from the reset state) */
+    double*  reward;   /* [B][n_steps]        optional (NULL = off): what cn_step returns for that transition */
+    uint8_t* info;     /* [B][n_steps]        optional: CN_NOTHING .. CN_TIMEOUT */
+    double*  dmin;     /* [B][n_steps]        optional */
+} cn_trace_out;
+int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const cn_trace_out* out);
+
 #ifdef __cplusplus
 }
 #endif
