@@ -20,6 +20,7 @@ CIRCLE_CROSSING, SQUARE_CROSSING, MIXED = 0, 1, 2
 HOLONOMIC, UNICYCLE = 0, 1
 RECORD_FIELDS, SUMMARY_FIELDS = 6, 8
 LAUNCH_COUNTERS = ('rollout_kernels', 'scheduled_kernels', 'ring_fills', 'async_fills', 'sarl_narrow', 'sarl_decide_steps')  # CN_COUNT_*
+ROLLOUT_ROUTES = ('generic', 'fused', 'fused_split', 'shard')  # CN_ROUTE_*
 FLAG_ASYNC_SCENARIO_FILL = 1
 
 
@@ -131,6 +132,8 @@ SYMBOLS = {
     'cn_trainer_steps': (C.c_int, [_P, C.POINTER(C.c_int64)]),
     # per-step record of a batched ORCA rollout (added after v12, no version bump)
     'cn_rollout_trace': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnTraceOut)]),
+    # which transition kernel cn_rollout would launch (added after v12, no version bump)
+    'cn_rollout_route': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -32,6 +32,11 @@ extern "C" {
 const char* cn_last_error(void) { return cn_g_err; }
 int cn_abi_version(void) { return CN_ABI_VERSION; }
 
+// BASELINE configs[1]: 5 humans + robot, 2 envs per workgroup — the geometry the fused kernels hold as compile-time constants
+static bool headline_geometry(const cn::Params& P) {
+    return P.A == 6 && P.NC == 5 && P.E == 2 && P.nA == 12 && P.pairs == 60 && P.threads == 64;
+}
+
 int cn_create(const cn_config* c, cn_engine** out) {
     if (!c || !out) return fail(CN_ERR_INVALID, "cn_create: NULL argument");
     *out = nullptr;
@@ -120,6 +125,17 @@ int cn_create(const cn_config* c, cn_engine** out) {
     }
     P.kdl = cn::kd_layout(P.nA, P.A, P.E);
     e->smem = cn::smem_bytes(P.nA, P.pairs, e->maxl, P.A, P.E);
+    e->use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
+    // 0: the one-wave fused kernel everywhere (A/B runs); 2: the two-wave kernel also for launches of several rounds (measurements)
+    e->fused_split = env_int("CROWDNAV_AMD_FUSED_SPLIT", 1);
+    e->split_slots = 0;
+    if (headline_geometry(P)) {  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
+        int per_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true>, 2 * cn::kWave, e->smem) == hipSuccess &&
+            hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
+            e->split_slots = per_cu * prop.multiProcessorCount;
+    }
     e->gen_wave = env_int("CROWDNAV_AMD_WAVE_SCENARIOS", c->num_humans > 8 ? 1 : 0) != 0;
     P.robot_visible = c->robot_visible ? 1 : 0;
     P.robot_orca = c->robot_policy == CN_ROBOT_ORCA;
@@ -563,29 +579,51 @@ static int fill_ring_if_needed(cn_engine* e, const cn::RolloutView& R, int n_ste
     return CN_OK;
 }
 
-// The transitions themselves: the four-barrier fused kernel (rollout_fused.h) for the small-crowd geometries it covers,
-// with BASELINE configs[1]'s geometry folded in as compile-time constants; the general phase kernel otherwise.
-static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
+// Which transition kernel a call runs: decided HERE, once (launch_rollout launches what this says; cn_rollout_route reports it).
+// The four-barrier fused kernel (rollout_fused.h) takes the small-crowd geometries it covers, with BASELINE configs[1]'s
+// geometry folded in as compile-time constants; that geometry's on-device rollout (no caller-supplied action) runs as the
+// two-wave kernel when all its workgroups are resident at once; the 20-human shard has its own kernel; the general phase
+// kernel takes everything else.
+static int rollout_route(const cn_engine* e, const double* action) {
     const cn::Params& P = e->P;
-    const uint64_t kernels_before = e->launch_counts[CN_COUNT_ROLLOUT_KERNELS];
-    static const bool use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
     static const bool use_geom20 = env_int("CROWDNAV_AMD_GEOM20", 1) != 0;  // the compile-time geometry of configs[3]'s shard
-    const bool headline = P.A == 6 && P.NC == 5 && P.E == 2 && P.nA == 12 && P.pairs == 60 && P.threads == 64;
     // (small crowds the fused kernel does not take — unicycle robot, asynchronous fill, several waves per workgroup — run the
     // generic rollout_kernel<5, ..>; its own compile-time-geometry instantiation for configs[1] went when the fused kernel
     // became the headline path)
     // (the fused kernel reads the launch-time fill level only: never with the asynchronous fill, whose slots are published
     // one by one — CROWDNAV_AMD_WAVE_SCENARIOS=1 can switch that on for a small crowd)
-    if (use_fused && !e->async_fill && e->maxl == 5 && !P.robot_unicycle && P.NC <= cn::kFusedMaxNC && P.pairs <= cn::kWave &&
+    if (e->use_fused && !e->async_fill && e->maxl == 5 && !P.robot_unicycle && P.NC <= cn::kFusedMaxNC && P.pairs <= cn::kWave &&
         P.nA * 5 <= cn::kWave && P.threads == cn::kWave) {
-        if (headline)
+#if defined(CN_PHASE_TIMING) || defined(CN_WAVE_TRACE)
+        (void)action;
+        return CN_ROUTE_FUSED;  // the probe builds instrument the one-wave kernel
+#else
+        const bool split = e->fused_split != 0 && headline_geometry(P) && P.robot_orca && action == nullptr &&
+                           (grid_envs(e) <= e->split_slots || e->fused_split == 2);
+        return split ? CN_ROUTE_FUSED_SPLIT : CN_ROUTE_FUSED;
+#endif
+    }
+    if (use_geom20 && e->maxl == 10 && !P.robot_unicycle && P.A == 21 && P.NC == 20 && P.E == 1 && P.threads == 64 &&
+        P.orca.max_neighbors == 10 && P.kd)
+        return CN_ROUTE_SHARD;
+    return CN_ROUTE_GENERIC;
+}
+
+static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
+    const cn::Params& P = e->P;
+    const uint64_t kernels_before = e->launch_counts[CN_COUNT_ROLLOUT_KERNELS];
+    const int route = rollout_route(e, action);
+    if (route == CN_ROUTE_FUSED_SPLIT) {
+        hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem, e->stream, e->P,
+                           (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
+    } else if (route == CN_ROUTE_FUSED) {
+        if (headline_geometry(P))
             hipLaunchKernelGGL((cn::rollout_fused_kernel<true>), dim3(grid_envs(e)), dim3(64), e->smem, e->stream, e->P,
                                (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
         else
             hipLaunchKernelGGL((cn::rollout_fused_kernel<false>), dim3(grid_envs(e)), dim3(64), e->smem, e->stream, e->P,
                                (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-    } else if (use_geom20 && e->maxl == 10 && !P.robot_unicycle && P.A == 21 && P.NC == 20 && P.E == 1 && P.threads == 64 &&
-               P.orca.max_neighbors == 10 && P.kd) {
+    } else if (route == CN_ROUTE_SHARD) {
         const size_t smem20 = cn::smem_bytes_compact(P.nA, P.pairs, P.A, P.E);
         // Three resident waves per SIMD (step_kernels.h: kGeom20Waves): 3072 one-wave workgroups fill the chip, so B = 4096 envs would run as
         // a full round plus a third of one.  A call of 3 q + r steps becomes one launch of r steps over all envs (if r > 0) and
@@ -712,6 +750,13 @@ int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action)
     if ((rc = fill_ring_if_needed(e, R, 1))) return rc;
     launch_rollout(e, R, 1, action);
     CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
+    if (!e || !route_host) return fail(CN_ERR_INVALID, "cn_rollout_route: NULL argument");
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
+    *route_host = rollout_route(e, nullptr);  // (no route depends on the call's length today; the shard's schedules are not routes)
     return CN_OK;
 }
 

@@ -79,6 +79,9 @@ struct cn_engine {
     size_t smem;       // dynamic LDS bytes per workgroup
     int sched_min, sched_slots, sched_reserve, dyn_visits;  // the 20-human shard kernel's schedules (launch_rollout): shortest call split, resident workgroups, slots left free beside the asynchronous fill
     bool sched_force, sched_dynamic;
+    bool use_fused;   // CROWDNAV_AMD_FUSED (rollout_route)
+    int fused_split;  // CROWDNAV_AMD_FUSED_SPLIT: 0 never, 1 launches of one round (default), 2 always
+    int split_slots;              // workgroups of the two-wave fused kernel the device holds at once (occupancy query, cn_create)
     bool scenario_cache;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
     uint64_t launch_counts[CN_LAUNCH_COUNTERS];  // cn_launch_counts: what the host enqueued since cn_create
     // Device memory comes from a few large slabs, not one hipMalloc per buffer: an engine has ~60 device buffers, most of them a

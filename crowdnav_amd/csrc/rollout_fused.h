@@ -16,6 +16,8 @@
 // the env's lanes; only the robot lane keeps the return / danger accumulators and writes records.
 // Launch conditions (cn_rollout / cn_rollout_step check them, everything else runs rollout_kernel): 5-half-plane
 // instantiation, NC <= 5, pairs <= 64, nA * 5 <= 64, 64 threads, holonomic robot.
+// SPLIT (further down): the headline geometry's cn_rollout as TWO waves per workgroup — the phases above, dealt to an ORCA
+// wave and an env wave that meet at two s_barrier per step.
 #pragma once
 #include "step_kernels.h"
 
@@ -76,17 +78,344 @@ __device__ __forceinline__ void preferred_velocity(const AgentRegs& r, float max
 // The one-pass fallback runs the four planar programs of an infeasible agent on four lanes (orca_device.h: lp3_inner_program /
 // lp3_outer_scan); the multi-pass form (more than six infeasible agents in a wave) keeps lp3_scan.
 
+// ---------------------------------------------------------------------------------------------- shared phase bodies
+// The one-wave kernel and the two-wave kernel (rollout_fused_split below) run the SAME phase bodies: what differs is which
+// wave runs them and what sits between them.
+
+// A pair lane's row: the kin slots of its agent's candidates (8 bits each).  A pair that does not exist (robot invisible to
+// the humans, env beyond the batch, fewer than 5 candidates) points at slot nA = (+inf, +inf): its squared distance is +inf
+// without a select, so the pair phase has no data-dependent control flow at all.
+struct PairRow {
+    int my_info, my_slot;
+    unsigned long long row_slots;
+};
+__device__ __forceinline__ PairRow pair_row_of(const Params& P, const Smem& s, int lane) {
+    PairRow pr{0, P.nA, 0ull};
+    if (lane < P.pairs) {
+        pr.my_info = s.pinfo[lane];
+        const int c = (pr.my_info >> 16) & 0xff;
+        for (int k = 0; k < kFusedMaxNC; ++k) {
+            int slot = P.nA;
+            if (k < P.NC) {
+                const int ik = s.pinfo[lane - c + k];
+                slot = ((ik >> 24) & 1) ? ((ik >> 8) & 0xff) : P.nA;
+            }
+            pr.row_slots |= (unsigned long long)slot << (8 * k);
+        }
+        pr.my_slot = (int)((pr.row_slots >> (8 * c)) & 0xffull);
+    }
+    return pr;
+}
+
+// pairs: candidate distances (Appendix A.2), stable rank = RVO2's sorted-insertion slot, half-plane (A.3).  Pair lanes only.
+// `mid` runs between the rank and the stores, in the same basic block (the one-wave kernel's preferred velocity).
+template <typename Mid>
+__device__ __forceinline__ void fused_pair_phase(const Params& P, const Smem& s, const PairRow& pr, float range_sq, Mid&& mid) {
+    const int my_info = pr.my_info, my_slot = pr.my_slot;
+    const unsigned long long row_slots = pr.row_slots;
+    const int q = my_info & 0xff, c = (my_info >> 16) & 0xff;
+    const int ol = (my_info >> 8) & 0xff;
+    const bool robot_sim = (my_info >> 25) & 1;
+    // every LDS request of the phase first, none of them behind a condition
+    const float4 me = s.kin[q];
+    const float4 other = s.kin[my_slot];
+    float4 ot[kFusedMaxNC];
+#pragma unroll
+    for (int k = 0; k < kFusedMaxNC; ++k) ot[k] = s.kin[(int)((row_slots >> (8 * k)) & 0xffull)];
+    const float* view = robot_sim ? s.rview : s.hview;
+    const float rsum = view[q] + view[ol];
+    const float odx = me.x - other.x, ody = me.y - other.y;
+    const float mine = odx * odx + ody * ody;
+    int rank = 0, within = 0;
+    {
+        // squared distances are +0 .. +inf: their bit patterns order like the floats, so "v < mine, or v == mine and
+        // k < c" is bit 31 of v - (mine + [k < c]) and "v < range" is bit 31 of v - range as 32-bit integers: the sign
+        // bits are shifted into two words (v_alignbit_b32) and counted once — no compare through VCC / SGPR pairs, no
+        // scalar mask logic, none of the hazard s_nop between them (round 6; the shard's rank loop does the same)
+        const uint32_t mb = __float_as_uint(mine), rb = __float_as_uint(range_sq);
+        uint32_t before = 0u, inside = 0u;
+#pragma unroll
+        for (int k = 0; k < kFusedMaxNC; ++k) {
+            const float dx = me.x - ot[k].x, dy = me.y - ot[k].y;
+            const uint32_t vb = __float_as_uint(dx * dx + dy * dy);  // +inf for a pair that does not exist: never in range
+            const uint32_t tie = (uint32_t)(k - c) >> 31;           // k < c
+            before = __builtin_amdgcn_alignbit(before, vb - mb - tie, 31);
+            inside = __builtin_amdgcn_alignbit(inside, vb - rb, 31);
+        }
+        within = __popc(inside);
+        rank = __popc(before & inside);
+    }
+    mid();
+    if (c == 0) s.count[q] = within < P.orca.max_neighbors ? within : P.orca.max_neighbors;
+    if (mine < range_sq && rank < P.orca.max_neighbors)
+        s.lines[q * kLineStride + rank] =
+            make_half_plane(P.orca, me.x, me.y, me.z, me.w, other.x, other.y, other.z, other.w, rsum);
+}
+
+// candidates: lane = (agent, half-plane)
+template <int MAXL>
+__device__ __forceinline__ void fused_candidates(const Params& P, const Smem& s, int lane) {
+    if (lane < P.nA * MAXL) {
+        const int q = lane / MAXL, k = lane - q * MAXL;
+        const float4 so = s.sol[q];
+        const float4* lq = s.lines + q * kLineStride;
+        s.cand2[q * kLineStride + k] = lp_line_candidate_pairs5(lq, k, lane, so.z, so.x, so.y);
+    }
+}
+
+// solve: the planar scan, then the candidate-form 3-D fallback for the infeasible agents (wave-uniform branch).  Agent
+// lanes with `solve` leave their new velocity in (rx, ry), every other lane (0, 0).  Returns whether the wave took the fallback.
+// BASE_PRIO: the issue priority a wave goes back to on its first step without the fallback.
+template <int MAXL, int BASE_PRIO = 0>
+__device__ __forceinline__ bool fused_solve(const Params& P, const Smem& s, int lane, bool solve, float& rx, float& ry,
+                                            PhaseClock* clk) {
+    (void)P, (void)clk;
+    rx = 0.0f, ry = 0.0f;
+    int n = 0, fail = 0;
+    if (solve) {
+        n = s.count[lane];
+        const float4 start = s.res[lane];
+        rx = start.x, ry = start.y;
+        fail = lp_planar_scan<MAXL>(s.lines + lane * kLineStride, s.cand2 + lane * kLineStride, n, rx, ry);
+    }
+    CN_TICK(clk, 3);
+    const bool need = solve && fail < n;
+    const unsigned long long nm = __ballot(need);
+#ifdef CN_PHASE_TIMING
+    if (clk) clk->acc[9] += __popcll(nm);
+#endif
+    if (nm == 0ull) __builtin_amdgcn_s_setprio(BASE_PRIO);
+    if (nm != 0ull) {  // wave-uniform: some agent of this wave was infeasible
+        __builtin_amdgcn_s_setprio(3);
+        constexpr int kPairs = MAXL * (MAXL - 1) / 2;
+        const int n_todo = __popcll(nm);
+        bool one_pass_done = false;  // (wave-uniform)
+        if (n_todo * kPairs <= kWave) {
+            // one pass: item = lane = (t, m); the t-th infeasible agent is the t-th set bit of the ballot (scalar bit
+            // tricks, no LDS list), and the item's half-planes are requested once for both stages
+            const int t = lane / kPairs, m = lane - t * kPairs;
+            int a = 0;
+            unsigned long long rest = nm;
+#pragma unroll
+            for (int u = 0; u < kWave / kPairs; ++u) {
+                const int bit = rest ? __ffsll((long long)rest) - 1 : 0;
+                a = (u == t) ? bit : a;
+                rest &= rest - 1ull;
+            }
+            const bool item = lane < n_todo * kPairs;
+            const int i = lp3_program_of(m), base = i * (i - 1) / 2;
+            const float4* la = s.lines + a * kLineStride;
+            const float4 li = la[i], lj = la[m - base];
+            const float radius = s.sol[a].z;
+            const float4 pr = lp3_project(li, lj);
+            if (item) s.proj[a * kLineStride + m] = pr;
+            CN_FUSED_SYNC();
+            if (item) {
+                // (one (projected line, earlier line) pair per item lane + two shuffle rounds instead of these three masked pairs
+                // was built and measured neutral in round 6: 1 229.6 / 1 238.8 vs 1 229.9 / 1 233.7 M — profiles/HISTORY.md)
+                const float4* pa = s.proj + a * kLineStride + base;
+                s.cand3[a * kLineStride + m] = lp_line_candidate<MAXL - 2>(pa[m - base], pa, m - base, radius, -li.w, li.z, true);
+            }
+            CN_FUSED_SYNC();
+            // the four planar programs of an infeasible agent side by side: the item lane of slot (i, 0) runs program i
+            // and leaves its solution in the agent's cand2 row (free since the planar scan above), slot i
+            if (item && m == base)
+                s.cand2[a * kLineStride + i] = lp3_inner_program(s.proj + a * kLineStride, s.cand3 + a * kLineStride, i, li, radius);
+            CN_FUSED_SYNC();
+            if (need)
+                lp3_outer_scan(s.lines + lane * kLineStride, s.cand2 + lane * kLineStride, n, fail, s.sol[lane].z, rx, ry);
+            one_pass_done = true;
+        } else {
+            if (need) s.todo[__popcll(nm & ((1ull << lane) - 1ull))] = lane;
+            CN_FUSED_SYNC();
+            const int items = n_todo * kPairs;
+            for (int p = lane; p < items; p += kWave) {  // projections: lane = (agent, i, j)
+                const int t = p / kPairs, m = p - t * kPairs;
+                const int a = s.todo[t];
+                const int i = lp3_program_of(m), j = m - i * (i - 1) / 2;
+                const float4* la = s.lines + a * kLineStride;
+                s.proj[a * kLineStride + m] = lp3_project(la[i], la[j]);
+            }
+            CN_FUSED_SYNC();
+            for (int p = lane; p < items; p += kWave) {  // their candidates: lane = (agent, i, k)
+                const int t = p / kPairs, m = p - t * kPairs;
+                const int a = s.todo[t];
+                const int i = lp3_program_of(m), base = i * (i - 1) / 2;
+                const float4 li = s.lines[a * kLineStride + i];
+                const float4* pa = s.proj + a * kLineStride + base;
+                s.cand3[a * kLineStride + m] = lp_line_candidate<MAXL - 2>(pa[m - base], pa, m - base, s.sol[a].z, -li.w, li.z, true);
+            }
+            CN_FUSED_SYNC();
+        }
+        if (need && !one_pass_done)
+            lp3_scan(s.lines + lane * kLineStride, s.proj + lane * kLineStride, s.cand3 + lane * kLineStride, n,
+                     fail, s.sol[lane].z, rx, ry);
+    }
+    return nm != 0ull;
+}
+
+// The eight float64 parameters of a step, pinned in vector registers (in_vgpr).
+struct StepConsts {
+    double dt, limit, limit1, success, collision, ddist, dfactor, hsafety;
+};
+__device__ __forceinline__ StepConsts step_consts(const Params& P) {
+    StepConsts K;
+    K.dt = in_vgpr(P.dt), K.limit = in_vgpr(P.time_limit), K.limit1 = in_vgpr(P.time_limit - 1.0);
+    K.success = in_vgpr(P.success_reward), K.collision = in_vgpr(P.collision_penalty);
+    K.ddist = in_vgpr(P.discomfort_dist), K.dfactor = in_vgpr(P.discomfort_factor);
+    K.hsafety = in_vgpr(P.human_safety);
+    return K;
+}
+
+// One float64 distance per agent lane (crowd_sim.py:331-351 for a human, :364-366 for the robot): a human's closest approach
+// to the robot during the step, boundary to boundary; the robot's distance to its goal at the end of the step.
+//   r: the agent at the START of the step; rp: the robot's position then; act: the robot's new velocity; new_v: this agent's
+__device__ __forceinline__ double swept_distance(const AgentRegs& r, bool human, double2 rp, double act_x, double act_y,
+                                                 double new_vx, double new_vy, double dt, double robot_rad) {
+    const double x1 = r.px - rp.x, y1 = r.py - rp.y;
+    const double wx = r.vx - act_x, wy = r.vy - act_y;
+    const double x2 = x1 + wx * dt, y2 = y1 + wy * dt;
+    const double sx = x2 - x1, sy = y2 - y1;
+    double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
+    u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
+    const bool degenerate = (sx == 0.0 && sy == 0.0);  // utils.py:11-13
+    const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
+    const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
+    const double endx = r.px + new_vx * dt, endy = r.py + new_vy * dt;
+    const double d = norm2(human ? cx : endx - r.gx, human ? cy : endy - r.gy);
+    return human ? d - r.rad - robot_rad : d;
+}
+
+// reduce (every lane of the env, identically): the env's distances (Smem::closest) to reward / done / info.
+struct StepOutcome {
+    double reward, dmin;
+    int info;
+    bool done;
+};
+__device__ __forceinline__ StepOutcome reduce_env(const Params& P, const Smem& s, int ebase, double gtime, const StepConsts& K) {
+    // LDS requests first: the env's distances, the robot's radius
+    const double goal_dist = s.closest[ebase];
+    const double robot_rad = s.rad[ebase];
+    // the reference stops scanning at the first colliding human (dmin keeps the minimum seen before it)
+    double dmin = std::numeric_limits<double>::infinity();
+    bool collision = false;
+    for (int i = 1; i < P.A; ++i) {
+        const double c = s.closest[ebase + i];
+        const bool hit = c < 0.0;
+        dmin = (!collision & !hit & (c < dmin)) ? c : dmin;
+        collision = collision | hit;
+    }
+    // crowd_sim.py:364-389 as a priority chain of selects (timeout > collision > goal > danger > nothing): the
+    // same values as the if / elif ladder without its nested branches
+    const bool timeout = gtime >= K.limit1;
+    const bool reaching = goal_dist < robot_rad;
+    const bool danger = dmin < K.ddist;
+    double reward = danger ? (dmin - K.ddist) * K.dfactor * K.dt : 0.0;
+    int info = danger ? CN_DANGER : CN_NOTHING;
+    reward = reaching ? K.success : reward, info = reaching ? CN_REACH_GOAL : info;
+    reward = collision ? K.collision : reward, info = collision ? CN_COLLISION : info;
+    reward = timeout ? 0.0 : reward, info = timeout ? CN_TIMEOUT : info;
+    const bool done = timeout | collision | reaching;
+    return StepOutcome{reward, dmin, info, done};
+}
+
+// explorer.py:50-72: the finished episode's record (robot lane)
+__device__ __forceinline__ void write_record(const cn_rollout_io& io, int env, int ep_count, int info, int cur_steps,
+                                             double cur_return, double time, int cur_danger, double cur_dsum) {
+    if (io.record_capacity > 0) {
+        const size_t k = (size_t)env * io.record_capacity + (ep_count % io.record_capacity);
+        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
+        if (io.ep_steps) io.ep_steps[k] = cur_steps;
+        if (io.ep_return) io.ep_return[k] = cur_return;
+        if (io.ep_time) io.ep_time[k] = time;
+        if (io.ep_danger) io.ep_danger[k] = cur_danger;
+        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
+    }
+}
+
 // CN_WAVE_TRACE (profiling builds): every wave leaves four 100 MHz timestamps (kernel entry, step loop entry / exit, kernel
 // exit) and how many of its steps took the 3-D fallback / ended an episode: scripts/probes/wave_trace.py
 #ifdef CN_WAVE_TRACE
 static __device__ unsigned long long cn_wave_trace[8192 * 6];
 #endif
 
-template <bool HEADLINE>
+// ---------------------------------------------------------------------------------------------- the two-wave kernel
+// SPLIT: the headline geometry as a workgroup of TWO waves serving the same 2 envs.
+//   env wave  (threads 0-63)    everything float64: AgentRegs / EpisodeRegs, preferred velocity + start point, swept
+//                               distance, reduce / reward / done, integrate, accumulators, records, scenario loads; the launch
+//                               prologue and epilogue are the one-wave kernel's own code
+//   ORCA wave (threads 64-127)  pairs, candidates, planar scan, 3-D fallback; it carries the float64 positions only to form
+//                               the next float32 view with the same `px + vx * dt` as the env wave
+// The waves meet at two s_barrier per step.  Iteration of the loop, u = the step whose velocities the ORCA wave computes:
+//   barrier 1   both read what the other left: the ORCA wave the "episode ended" word, the env wave the velocities of u - 1
+//     ORCA wave: stage kin(u) from its registers, pairs(u)          env wave: integrate u - 1, publish sol / res of u
+//   barrier 2
+//     ORCA wave: candidates, scan (+ fallback) of u, publish vel(u) env wave: swept distance, reduce, bookkeeping of u - 1
+// Both sides of an iteration ASSUME that step u - 1 ended no episode.  When it did, the env wave (which now holds the state
+// after the episode end: next scenario loaded, env paused or retired) re-stages kin / posd / rad / hview of its lanes and
+// posts the word; at barrier 1 the ORCA wave then drops the velocities it has just published — they touched LDS only —
+// re-reads its positions and computes step u again, while the env wave publishes sol / res of the true state and idles
+// past barrier 2.  One ORCA step is redone per episode end of a workgroup (~1 in 21 wave-steps at the headline shape).
+// The step counters, the discount index and every store to global memory live in the env wave.
+// What the waves exchange lives in arrays of the LDS layout that the fused kernels do not otherwise use: Smem::act (the
+// published velocities, as float2) and Smem::flag[0] (the word).
+// Issue priority: the ORCA wave is the critical path of a step, the env wave has slack in both windows, and four waves share
+// a SIMD — so the ORCA wave runs at priority 1 where the env wave stays at 0 (measured: 1 380 -> 1 473 M env-steps/s at
+// 4096 envs x 1000 steps); a jammed wave's 3 during the fallback stands above both.
+constexpr int kSplitOrcaPrio = 1;
+__device__ __forceinline__ void split_barrier() {
+    // every LDS write of this wave has landed (a wave's LDS operations complete in order) before the other wave is released
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+template <int MAXL>
+__device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, int n_steps) {
+    const int lane = (int)threadIdx.x - kWave;
+    float2* const vel = reinterpret_cast<float2*>(s.act);
+    const float range_sq = P.orca.neighbor_dist * P.orca.neighbor_dist;
+    const double c_dt = in_vgpr(P.dt);
+    split_barrier();  // the env wave's prologue: pinfo, rview, the staged state of step 0, word = 1
+    __builtin_amdgcn_s_setprio(kSplitOrcaPrio);
+    const PairRow pr = pair_row_of(P, s, lane);
+    double px = 0.0, py = 0.0;
+    float rx = 0.0f, ry = 0.0f;
+    bool solved = false;
+    for (int u = 0;;) {
+        split_barrier();  // 1
+        const bool ended = __builtin_amdgcn_readfirstlane(s.flag[0]) != 0;
+        if (!ended) ++u;
+        if (u >= n_steps) {  // the env wave finishes step n_steps - 1 alone
+            split_barrier();  // 2
+            break;
+        }
+        if (lane < P.nA) {
+            if (ended) {  // the env wave staged the true state
+                const double2 p = s.posd[lane];
+                px = p.x, py = p.y;
+            } else if (solved) {  // Agent.step (agent.py:127-135), as the env wave does it
+                px = px + (double)rx * c_dt;
+                py = py + (double)ry * c_dt;
+                s.kin[lane] = make_float4((float)px, (float)py, rx, ry);
+            }
+        }
+        CN_FUSED_SYNC();
+        if (lane < P.pairs) fused_pair_phase(P, s, pr, range_sq, [] {});
+        split_barrier();  // 2: sol / res of step u
+        fused_candidates<MAXL>(P, s, lane);
+        CN_FUSED_SYNC();
+        solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
+        fused_solve<MAXL, kSplitOrcaPrio>(P, s, lane, solved, rx, ry, nullptr);
+        if (lane < P.nA) vel[lane] = make_float2(rx, ry);
+    }
+}
+
+template <bool HEADLINE, bool SPLIT = false>
 // (the headline instantiation is compiled for three waves per SIMD: with the hint hipcc settles on 163-167 VGPRs and a schedule
-// worth 1.2 % at 4096 envs, 2.6 % in the 20-step shape; compiled for two it loses 3 %, for four — 128 VGPRs, 42 spilled — 11 %)
-__global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kernel(Params P_in, const StateView* Sd, const int* ring_filled_in,
-                                                              RolloutView R, int n_steps, const double* ext_action) {
+// worth 1.2 % at 4096 envs, 2.6 % in the 20-step shape; compiled for two it loses 3 %, for four — 128 VGPRs, 42 spilled — 11 %;
+// the two-wave kernel is built for four: 2048 workgroups x 2 waves on 1024 SIMDs)
+__global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 : 1)) void rollout_fused_kernel(
+    Params P_in, const StateView* Sd, const int* ring_filled_in, RolloutView R, int n_steps, const double* ext_action) {
+    static_assert(HEADLINE || !SPLIT, "the two-wave kernel exists for the headline geometry only");
 #ifdef CN_WAVE_TRACE
     const unsigned long long wt_entry = __builtin_amdgcn_s_memrealtime();
     unsigned long long wt_fallbacks = 0ull, wt_ends = 0ull;
@@ -101,6 +430,12 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
         P.A = 6, P.NC = 5, P.E = 2, P.nA = 12, P.pairs = 60, P.threads = 64;
     }
     const Smem s = carve<MAXL>(P);
+    if constexpr (SPLIT) {
+        if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= kWave) {
+            split_orca_wave<MAXL>(P, s, n_steps);
+            return;
+        }
+    }
     const Lane L = lane_of(P);
     AgentRegs r = {};
     float robot_max_speed = 0.0f;
@@ -159,33 +494,12 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
         theta = 1.5707963267948966;
     }
     unsigned int transitions = 0;
-    for (int t = threadIdx.x; t < kMaxDiscount; t += blockDim.x) s.disc[t] = t < R.discount_len ? R.discount[t] : 0.0;
+    for (int t = threadIdx.x; t < kMaxDiscount; t += P.threads) s.disc[t] = t < R.discount_len ? R.discount[t] : 0.0;
     CN_FUSED_SYNC();  // pinfo, rview
-    // this pair lane's row: the kin slots of its agent's candidates (8 bits each).  A pair that does not exist (robot
-    // invisible to the humans, env beyond the batch, fewer than 5 candidates) points at slot nA = (+inf, +inf): its squared
-    // distance is +inf without a select, so the pair phase below has no data-dependent control flow at all.
-    int my_info = 0;
-    unsigned long long row_slots = 0ull;
-    int my_slot = P.nA;
     if (L.lane == 0) s.kin[P.nA] = make_float4(std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity(), 0.0f, 0.0f);
-    if (L.lane < P.pairs) {
-        my_info = s.pinfo[L.lane];
-        const int c = (my_info >> 16) & 0xff;
-        for (int k = 0; k < kFusedMaxNC; ++k) {
-            int slot = P.nA;
-            if (k < P.NC) {
-                const int ik = s.pinfo[L.lane - c + k];
-                slot = ((ik >> 24) & 1) ? ((ik >> 8) & 0xff) : P.nA;
-            }
-            row_slots |= (unsigned long long)slot << (8 * k);
-        }
-        my_slot = (int)((row_slots >> (8 * c)) & 0xffull);
-    }
-    const double c_dt = in_vgpr(P.dt), c_limit = in_vgpr(P.time_limit), c_limit1 = in_vgpr(P.time_limit - 1.0);
-    const double c_success = in_vgpr(P.success_reward), c_collision = in_vgpr(P.collision_penalty);
-    const double c_ddist = in_vgpr(P.discomfort_dist), c_dfactor = in_vgpr(P.discomfort_factor);
-    const double c_hsafety = in_vgpr(P.human_safety);
-    stage_agent(P, s, L, r, c_hsafety);
+    const PairRow pr = pair_row_of(P, s, L.lane);
+    const StepConsts K = step_consts(P);
+    stage_agent(P, s, L, r, K.hsafety);
     CN_FUSED_SYNC();
 
 #ifdef CN_PHASE_TIMING
@@ -200,51 +514,97 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
 #ifdef CN_WAVE_TRACE
     const unsigned long long wt_loop = __builtin_amdgcn_s_memrealtime();
 #endif
-    for (int step = 0; step < n_steps; ++step) {
+    if constexpr (SPLIT) {
+        float2* const vel = reinterpret_cast<float2*>(s.act);
+        if (L.lane == 0) s.flag[0] = 1;
+        split_barrier();  // prologue staged
+        bool skip = true;  // the state of step u is already in registers: nothing to integrate, nothing to book
+        for (int u = 0;;) {
+            split_barrier();  // 1: vel(u - 1)
+            if (!skip) ++u;
+            const bool running = L.valid && ep.state == kRunning;
+            const AgentRegs r0 = r;  // the agent at the start of step u - 1
+            double act_x = 0.0, act_y = 0.0, new_vx = 0.0, new_vy = 0.0;
+            if (!skip && L.lane < P.nA) {
+                const float2 mine = vel[L.lane], robots = vel[L.ebase];
+                act_x = (double)robots.x, act_y = (double)robots.y;
+                new_vx = (L.a == 0) ? act_x : (double)mine.x;
+                new_vy = (L.a == 0) ? act_y : (double)mine.y;
+                if (running) {  // Agent.step (agent.py:127-135)
+                    r.px = r.px + new_vx * K.dt;
+                    r.py = r.py + new_vy * K.dt;
+                    r.vx = new_vx;
+                    r.vy = new_vy;
+                }
+            }
+            if (u < n_steps && L.lane < P.nA) {
+                float4 sol4, start4;
+                preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, running && (L.a > 0 || P.robot_orca), sol4, start4);
+                s.sol[L.lane] = sol4;
+                s.res[L.lane] = start4;
+            }
+            split_barrier();  // 2
+            bool ended = false;
+            if (!skip) {
+                // the robot's position at the start of the step: from its lane's registers (posd holds re-staged states only)
+                const double2 rp = make_double2(__shfl(r0.px, L.ebase), __shfl(r0.py, L.ebase));
+                if (L.valid) s.closest[L.lane] = swept_distance(r0, L.a > 0, rp, act_x, act_y, new_vx, new_vy, K.dt, s.rad[L.ebase]);
+                CN_FUSED_SYNC();
+                bool done = false;
+                if (running) {
+                    const double disc_t = s.disc[cur_steps < kMaxDiscount ? cur_steps : kMaxDiscount - 1];
+                    const StepOutcome o = reduce_env(P, s, L.ebase, ep.gtime, K);
+                    done = o.done;
+                    ep.gtime += K.dt;
+                    ++transitions;
+                    cur_return = cur_return + (cur_steps < kMaxDiscount ? disc_t : 0.0) * o.reward;  // python sum(): left to right
+                    ++cur_steps;
+                    cur_danger += o.info == CN_DANGER ? 1 : 0;
+                    cur_dsum = o.info == CN_DANGER ? cur_dsum + o.dmin : cur_dsum;
+                    if (done) {  // explorer.py:50-72: record, then the env's next episode
+                        // every load of the episode end first (the io block, the state pointers, the next scenario — in
+                        // bounds whether or not it is taken), then the record stores: one memory round trip in the shadow
+                        // of the ORCA wave's step
+                        const cn_rollout_io io = *iop;
+                        const StateView S = *Sd;
+                        AgentRegs next = r;
+                        load_from_ring(P, S, L, (ep.ep_count + 1) % P.ring_depth, next);
+                        if (L.a == 0) write_record(io, L.env, ep.ep_count, o.info, cur_steps, cur_return, (o.info == CN_TIMEOUT) ? K.limit : ep.gtime, cur_danger, cur_dsum);
+                        cur_steps = 0, cur_return = 0.0, cur_danger = 0, cur_dsum = 0.0;
+                        ++ep.ep_count;
+                        ep.gtime = 0.0;
+                        const int64_t c = episode_id(io, L.env, ep.ep_count);
+                        if (io.episode_limit >= 0 && c >= io.episode_limit) {
+                            ep.state = kRetired;
+                        } else if (ep.ep_count < ep.ring_filled) {
+                            r = next;
+                            theta = 1.5707963267948966;  // robot.set(..., np.pi / 2)
+                        } else {
+                            ep.state = kWaitingScenario;  // ring ran dry: pause this env until the next launch has refilled it
+                        }
+                    }
+                }
+                ended = __ballot(done) != 0ull;
+            }
+            // per-episode constants (rad, hview) and the float32 view are staged here and in the prologue only
+            if (ended) stage_agent(P, s, L, r, K.hsafety);
+            if (L.lane == 0) s.flag[0] = ended ? 1 : 0;
+            skip = ended;
+            if (u >= n_steps) break;
+        }
+    }
+    const int one_wave_steps = SPLIT ? 0 : n_steps;
+    for (int step = 0; step < one_wave_steps; ++step) {
         const bool running = L.valid && ep.state == kRunning;
         const bool solve = running && (L.a > 0 || P.robot_orca);
 
         // ---- pairs: candidate distances (Appendix A.2), stable rank = RVO2's sorted-insertion slot, half-plane (A.3)
         if (L.lane < P.pairs) {
-            const int q = my_info & 0xff, c = (my_info >> 16) & 0xff;
-            const int ol = (my_info >> 8) & 0xff;
-            const bool robot_sim = (my_info >> 25) & 1;
-            // every LDS request of the phase first, none of them behind a condition
-            const float4 me = s.kin[q];
-            const float4 other = s.kin[my_slot];
-            float4 ot[kFusedMaxNC];
-#pragma unroll
-            for (int k = 0; k < kFusedMaxNC; ++k) ot[k] = s.kin[(int)((row_slots >> (8 * k)) & 0xffull)];
-            const float* view = robot_sim ? s.rview : s.hview;
-            const float rsum = view[q] + view[ol];
-            const float odx = me.x - other.x, ody = me.y - other.y;
-            const float mine = odx * odx + ody * ody;
-            int rank = 0, within = 0;
-            {
-                // squared distances are +0 .. +inf: their bit patterns order like the floats, so "v < mine, or v == mine and
-                // k < c" is bit 31 of v - (mine + [k < c]) and "v < range" is bit 31 of v - range as 32-bit integers: the sign
-                // bits are shifted into two words (v_alignbit_b32) and counted once — no compare through VCC / SGPR pairs, no
-                // scalar mask logic, none of the hazard s_nop between them (round 6; the shard's rank loop does the same)
-                const uint32_t mb = __float_as_uint(mine), rb = __float_as_uint(range_sq);
-                uint32_t before = 0u, inside = 0u;
-#pragma unroll
-                for (int k = 0; k < kFusedMaxNC; ++k) {
-                    const float dx = me.x - ot[k].x, dy = me.y - ot[k].y;
-                    const uint32_t vb = __float_as_uint(dx * dx + dy * dy);  // +inf for a pair that does not exist: never in range
-                    const uint32_t tie = (uint32_t)(k - c) >> 31;           // k < c
-                    before = __builtin_amdgcn_alignbit(before, vb - mb - tie, 31);
-                    inside = __builtin_amdgcn_alignbit(inside, vb - rb, 31);
-                }
-                within = __popc(inside);
-                rank = __popc(before & inside);
-            }
             // (agent lanes are pair lanes too: their preferred velocity, same block)
             float4 sol4, start4;
-            preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, solve, sol4, start4);
-            if (c == 0) s.count[q] = within < P.orca.max_neighbors ? within : P.orca.max_neighbors;
-            if (mine < range_sq && rank < P.orca.max_neighbors)
-                s.lines[q * kLineStride + rank] =
-                    make_half_plane(P.orca, me.x, me.y, me.z, me.w, other.x, other.y, other.z, other.w, rsum);
+            fused_pair_phase(P, s, pr, range_sq, [&] {
+                preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, solve, sol4, start4);
+            });
             if (L.lane < P.nA) {
                 s.sol[L.lane] = sol4;
                 s.res[L.lane] = start4;
@@ -254,99 +614,16 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
         CN_TICK(clk, 2);
 
         // ---- candidates: lane = (agent, half-plane)
-        if (L.lane < P.nA * MAXL) {
-            const int q = L.lane / MAXL, k = L.lane - q * MAXL;
-            const float4 so = s.sol[q];
-            const float4* lq = s.lines + q * kLineStride;
-            s.cand2[q * kLineStride + k] = lp_line_candidate_pairs5(lq, k, L.lane, so.z, so.x, so.y);
-        }
+        fused_candidates<MAXL>(P, s, L.lane);
         CN_FUSED_SYNC();
 
         // ---- solve: scan, then the candidate-form fallback for the infeasible agents
-        float rx = 0.0f, ry = 0.0f;
-        int n = 0, fail = 0;
-        if (solve) {
-            n = s.count[L.lane];
-            const float4 start = s.res[L.lane];
-            rx = start.x, ry = start.y;
-            fail = lp_planar_scan<MAXL>(s.lines + L.lane * kLineStride, s.cand2 + L.lane * kLineStride, n, rx, ry);
-        }
-        CN_TICK(clk, 3);
-        const bool need = solve && fail < n;
-        const unsigned long long nm = __ballot(need);
-#ifdef CN_PHASE_TIMING
-        clock.acc[9] += __popcll(nm);
-#endif
-        if (nm == 0ull) __builtin_amdgcn_s_setprio(0);
-        if (nm != 0ull) {  // wave-uniform: some agent of this wave was infeasible
+        float rx, ry;
+        const bool fell_back = fused_solve<MAXL>(P, s, L.lane, solve, rx, ry, clk);
+        (void)fell_back;
 #ifdef CN_WAVE_TRACE
-            ++wt_fallbacks;
+        if (fell_back) ++wt_fallbacks;
 #endif
-            __builtin_amdgcn_s_setprio(3);
-            constexpr int kPairs = MAXL * (MAXL - 1) / 2;
-            const int n_todo = __popcll(nm);
-            bool one_pass_done = false;  // (wave-uniform)
-            if (n_todo * kPairs <= kWave) {
-                // one pass: item = lane = (t, m); the t-th infeasible agent is the t-th set bit of the ballot (scalar bit
-                // tricks, no LDS list), and the item's half-planes are requested once for both stages
-                const int t = L.lane / kPairs, m = L.lane - t * kPairs;
-                int a = 0;
-                unsigned long long rest = nm;
-#pragma unroll
-                for (int u = 0; u < kWave / kPairs; ++u) {
-                    const int bit = rest ? __ffsll((long long)rest) - 1 : 0;
-                    a = (u == t) ? bit : a;
-                    rest &= rest - 1ull;
-                }
-                const bool item = L.lane < n_todo * kPairs;
-                const int i = lp3_program_of(m), base = i * (i - 1) / 2;
-                const float4* la = s.lines + a * kLineStride;
-                const float4 li = la[i], lj = la[m - base];
-                const float radius = s.sol[a].z;
-                const float4 pr = lp3_project(li, lj);
-                if (item) s.proj[a * kLineStride + m] = pr;
-                CN_FUSED_SYNC();
-                if (item) {
-                    // (one (projected line, earlier line) pair per item lane + two shuffle rounds instead of these three masked pairs
-                    // was built and measured neutral in round 6: 1 229.6 / 1 238.8 vs 1 229.9 / 1 233.7 M — profiles/HISTORY.md)
-                    const float4* pa = s.proj + a * kLineStride + base;
-                    s.cand3[a * kLineStride + m] = lp_line_candidate<MAXL - 2>(pa[m - base], pa, m - base, radius, -li.w, li.z, true);
-                }
-                CN_FUSED_SYNC();
-                // the four planar programs of an infeasible agent side by side: the item lane of slot (i, 0) runs program i
-                // and leaves its solution in the agent's cand2 row (free since the planar scan above), slot i
-                if (item && m == base)
-                    s.cand2[a * kLineStride + i] = lp3_inner_program(s.proj + a * kLineStride, s.cand3 + a * kLineStride, i, li, radius);
-                CN_FUSED_SYNC();
-                if (need)
-                    lp3_outer_scan(s.lines + L.lane * kLineStride, s.cand2 + L.lane * kLineStride, n, fail, s.sol[L.lane].z, rx, ry);
-                one_pass_done = true;
-            } else {
-                if (need) s.todo[__popcll(nm & ((1ull << L.lane) - 1ull))] = L.lane;
-                CN_FUSED_SYNC();
-                const int items = n_todo * kPairs;
-                for (int p = L.lane; p < items; p += kWave) {  // projections: lane = (agent, i, j)
-                    const int t = p / kPairs, m = p - t * kPairs;
-                    const int a = s.todo[t];
-                    const int i = lp3_program_of(m), j = m - i * (i - 1) / 2;
-                    const float4* la = s.lines + a * kLineStride;
-                    s.proj[a * kLineStride + m] = lp3_project(la[i], la[j]);
-                }
-                CN_FUSED_SYNC();
-                for (int p = L.lane; p < items; p += kWave) {  // their candidates: lane = (agent, i, k)
-                    const int t = p / kPairs, m = p - t * kPairs;
-                    const int a = s.todo[t];
-                    const int i = lp3_program_of(m), base = i * (i - 1) / 2;
-                    const float4 li = s.lines[a * kLineStride + i];
-                    const float4* pa = s.proj + a * kLineStride + base;
-                    s.cand3[a * kLineStride + m] = lp_line_candidate<MAXL - 2>(pa[m - base], pa, m - base, s.sol[a].z, -li.w, li.z, true);
-                }
-                CN_FUSED_SYNC();
-            }
-            if (need && !one_pass_done)
-                lp3_scan(s.lines + L.lane * kLineStride, s.proj + L.lane * kLineStride, s.cand3 + L.lane * kLineStride, n,
-                         fail, s.sol[L.lane].z, rx, ry);
-        }
         CN_TICK(clk, 8);
 
         // ---- the robot's action reaches every lane of its env (wave shuffle; caller-supplied actions: one load per lane)
@@ -362,54 +639,21 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
         const double new_vy = (L.a == 0) ? act_y : (double)ry;
 
         // ---- one float64 distance per agent lane (crowd_sim.py:331-351 for a human, :364-366 for the robot)
-        if (L.valid) {
-            const bool human = L.a > 0;
-            const double2 rp = s.posd[L.ebase];
-            const double x1 = r.px - rp.x, y1 = r.py - rp.y;
-            const double wx = r.vx - act_x, wy = r.vy - act_y;
-            const double x2 = x1 + wx * c_dt, y2 = y1 + wy * c_dt;
-            const double sx = x2 - x1, sy = y2 - y1;
-            double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-            u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-            const bool degenerate = (sx == 0.0 && sy == 0.0);  // utils.py:11-13
-            const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
-            const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
-            const double endx = r.px + new_vx * c_dt, endy = r.py + new_vy * c_dt;
-            const double d = norm2(human ? cx : endx - r.gx, human ? cy : endy - r.gy);
-            s.closest[L.lane] = human ? d - r.rad - s.rad[L.ebase] : d;
-        }
+        if (L.valid)
+            s.closest[L.lane] = swept_distance(r, L.a > 0, s.posd[L.ebase], act_x, act_y, new_vx, new_vy, K.dt, s.rad[L.ebase]);
         CN_FUSED_SYNC();
         CN_TICK(clk, 5);
 
         // ---- reduce (every lane of the env, identically), integrate, episode bookkeeping, stage the next step
         if (running) {
-            // LDS requests first: the env's distances, the robot's radius, this step's discount factor
-            const double goal_dist = s.closest[L.ebase];
-            const double robot_rad = s.rad[L.ebase];
             const double disc_t = s.disc[cur_steps < kMaxDiscount ? cur_steps : kMaxDiscount - 1];
-            // the reference stops scanning at the first colliding human (dmin keeps the minimum seen before it)
-            double dmin = std::numeric_limits<double>::infinity();
-            bool collision = false;
-            for (int i = 1; i < P.A; ++i) {
-                const double c = s.closest[L.ebase + i];
-                const bool hit = c < 0.0;
-                dmin = (!collision & !hit & (c < dmin)) ? c : dmin;
-                collision = collision | hit;
-            }
-            // crowd_sim.py:364-389 as a priority chain of selects (timeout > collision > goal > danger > nothing): the
-            // same values as the if / elif ladder without its nested branches
-            const bool timeout = ep.gtime >= c_limit1;
-            const bool reaching = goal_dist < robot_rad;
-            const bool danger = dmin < c_ddist;
-            double reward = danger ? (dmin - c_ddist) * c_dfactor * c_dt : 0.0;
-            int info = danger ? CN_DANGER : CN_NOTHING;
-            reward = reaching ? c_success : reward, info = reaching ? CN_REACH_GOAL : info;
-            reward = collision ? c_collision : reward, info = collision ? CN_COLLISION : info;
-            reward = timeout ? 0.0 : reward, info = timeout ? CN_TIMEOUT : info;
-            const bool done = timeout | collision | reaching;
-            ep.gtime += c_dt;
-            r.px = r.px + new_vx * c_dt;  // Agent.step (agent.py:127-135)
-            r.py = r.py + new_vy * c_dt;
+            const StepOutcome o = reduce_env(P, s, L.ebase, ep.gtime, K);
+            const double reward = o.reward, dmin = o.dmin;
+            const int info = o.info;
+            const bool done = o.done;
+            ep.gtime += K.dt;
+            r.px = r.px + new_vx * K.dt;  // Agent.step (agent.py:127-135)
+            r.py = r.py + new_vy * K.dt;
             r.vx = new_vx;
             r.vy = new_vy;
             // return / danger accumulators: every lane of the env carries them (only the robot lane's copy is written out)
@@ -423,17 +667,7 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
 #endif
             if (done) {  // explorer.py:50-72: record, then the env's next episode
                 const cn_rollout_io io = *iop;
-                if (L.a == 0) {
-                    if (io.record_capacity > 0) {
-                        const size_t k = (size_t)L.env * io.record_capacity + (ep.ep_count % io.record_capacity);
-                        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
-                        if (io.ep_steps) io.ep_steps[k] = cur_steps;
-                        if (io.ep_return) io.ep_return[k] = cur_return;
-                        if (io.ep_time) io.ep_time[k] = (info == CN_TIMEOUT) ? c_limit : ep.gtime;
-                        if (io.ep_danger) io.ep_danger[k] = cur_danger;
-                        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
-                    }
-                }
+                if (L.a == 0) write_record(io, L.env, ep.ep_count, info, cur_steps, cur_return, (info == CN_TIMEOUT) ? K.limit : ep.gtime, cur_danger, cur_dsum);
                 cur_steps = 0, cur_return = 0.0, cur_danger = 0, cur_dsum = 0.0;
                 ++ep.ep_count;
                 ep.gtime = 0.0;
@@ -448,7 +682,7 @@ __global__ __launch_bounds__(kWave, (HEADLINE ? 3 : 1)) void rollout_fused_kerne
                 }
             }
         }
-        stage_agent(P, s, L, r, c_hsafety);
+        stage_agent(P, s, L, r, K.hsafety);
         CN_FUSED_SYNC();
         CN_TICK(clk, 7);
     }

@@ -332,6 +332,14 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_launch_counts(self._h, out))
         return dict(zip(_lib.LAUNCH_COUNTERS, (int(v) for v in out)))
 
+    def rollout_route(self, n_steps):
+        """Which transition kernel rollout(n_steps) would launch now (cn_rollout_route): one of _lib.ROLLOUT_ROUTES — 'generic',
+        'fused' (one wave per workgroup), 'fused_split' (an ORCA wave and an env wave per workgroup) or 'shard'.  Host-side,
+        launches nothing."""
+        route = C.c_int(-1)
+        check(self._lib.cn_rollout_route(self._h, int(n_steps), C.byref(route)))
+        return _lib.ROLLOUT_ROUTES[route.value]
+
     def mt_random(self, seed, n):
         out = self._new((n,), torch.float64)
         check(self._lib.cn_mt_random(self._h, int(seed), int(n), _ptr(out)))

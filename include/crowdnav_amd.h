@@ -248,6 +248,20 @@ enum {
 #define CN_LAUNCH_COUNTERS 6
 int cn_launch_counts(cn_engine* e, uint64_t* counts_host);
 
+/* (no ABI bump: a new symbol only) which transition kernel cn_rollout(e, io, n_steps) would launch NOW — route_host: HOST int,
+ * one of CN_ROUTE_*.  Host-only: launches nothing, counts nothing.  The fused two-wave kernel (rollout_fused.h) takes the
+ * headline geometry — 5 humans + ORCA robot, 2 envs per workgroup — when every workgroup of the launch is resident at once
+ * (workgroups <= CUs x the occupancy the runtime reports for the kernel) and CROWDNAV_AMD_FUSED_SPLIT is not 0 (read by
+ * cn_create, like CROWDNAV_AMD_FUSED; 2 takes it for launches of several rounds as well — slower there, for measurements); its
+ * results are bit-identical to the one-wave kernel's. */
+enum {
+    CN_ROUTE_GENERIC = 0,     /* rollout_kernel, the phase kernel */
+    CN_ROUTE_FUSED = 1,       /* rollout_fused_kernel, one wave per workgroup */
+    CN_ROUTE_FUSED_SPLIT = 2, /* rollout_fused_kernel, an ORCA wave and an env wave per workgroup */
+    CN_ROUTE_SHARD = 3        /* the 20-human shard's kernel, under a schedule or not */
+};
+int cn_rollout_route(cn_engine* e, int n_steps, int* route_host);
+
 /* ------------------------------------------------------------------------------------------------------
  * SARL robot decision (crowd_nav/policy/sarl.py:9-86 on top of multi_human_rl.py:11-63, cadrl.py:82-222).
  * Needs robot_policy == CN_ROBOT_EXTERNAL: the chosen action is then applied with cn_step(action). */
