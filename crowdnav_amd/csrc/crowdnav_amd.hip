@@ -128,11 +128,16 @@ int cn_create(const cn_config* c, cn_engine** out) {
     e->use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
     // 0: the one-wave fused kernel everywhere (A/B runs); 2: the two-wave kernel also for launches of several rounds (measurements)
     e->fused_split = env_int("CROWDNAV_AMD_FUSED_SPLIT", 1);
+    // what the env wave of the two-wave kernel takes off the ORCA wave's chain (rollout_fused.h: ASSIST): 1 (default) = the head
+    // of the 3-D fallback for the agents predicted infeasible; 0 = nothing (A/B runs)
+    e->split_assist = env_int("CROWDNAV_AMD_SPLIT_ASSIST", 1) != 0 ? cn::kAssistHead : 0;
     e->split_slots = 0;
     if (headline_geometry(P)) {  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
         int per_cu = 0;
         hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true>, 2 * cn::kWave, e->smem) == hipSuccess &&
+        const bool head = (e->split_assist & cn::kAssistHead) != 0;
+        if ((head ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true, cn::kAssistHead>, 2 * cn::kWave, e->smem)
+                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true>, 2 * cn::kWave, e->smem)) == hipSuccess &&
             hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
             e->split_slots = per_cu * prop.multiProcessorCount;
     }
@@ -614,8 +619,12 @@ static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, 
     const uint64_t kernels_before = e->launch_counts[CN_COUNT_ROLLOUT_KERNELS];
     const int route = rollout_route(e, action);
     if (route == CN_ROUTE_FUSED_SPLIT) {
-        hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem, e->stream, e->P,
-                           (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
+        if (e->split_assist & cn::kAssistHead)
+            hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true, cn::kAssistHead>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem,
+                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
+        else
+            hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem, e->stream, e->P,
+                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
     } else if (route == CN_ROUTE_FUSED) {
         if (headline_geometry(P))
             hipLaunchKernelGGL((cn::rollout_fused_kernel<true>), dim3(grid_envs(e)), dim3(64), e->smem, e->stream, e->P,
@@ -881,6 +890,16 @@ extern "C" int cn_debug_lazy_counts(unsigned long long* out8, int reset) {
     if (reset) {
         unsigned long long zero[16] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(cn::cn_lazy_counts), zero, sizeof(zero)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
+#ifdef CN_SPLIT_PROBE
+extern "C" int cn_debug_split_probe(unsigned long long* out32, int reset) {
+    if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(cn::cn_split_probe), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long zero[32] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(cn::cn_split_probe), zero, sizeof(zero)) != hipSuccess) return -1;
     }
     return 0;
 }

@@ -81,6 +81,7 @@ struct cn_engine {
     bool sched_force, sched_dynamic;
     bool use_fused;   // CROWDNAV_AMD_FUSED (rollout_route)
     int fused_split;  // CROWDNAV_AMD_FUSED_SPLIT: 0 never, 1 launches of one round (default), 2 always
+    int split_assist;  // CROWDNAV_AMD_SPLIT_ASSIST: rollout_fused.h's ASSIST (0, or kAssistHead = fallback head on the env wave; default)
     int split_slots;              // workgroups of the two-wave fused kernel the device holds at once (occupancy query, cn_create)
     bool scenario_cache;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
     uint64_t launch_counts[CN_LAUNCH_COUNTERS];  // cn_launch_counts: what the host enqueued since cn_create

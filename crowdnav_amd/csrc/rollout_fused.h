@@ -163,12 +163,83 @@ __device__ __forceinline__ void fused_candidates(const Params& P, const Smem& s,
     }
 }
 
+// Barrier of the two-wave kernel (further down): every LDS write of this wave has landed (a wave's LDS operations complete
+// in order) before the other wave is released.
+__device__ __forceinline__ void split_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// One item of the one-pass 3-D fallback: lane = (t, m), the t-th agent of `mask` (its t-th set bit: scalar bit tricks, no LDS
+// list) and slot m = i (i - 1) / 2 + j of its projections; the item's half-planes are requested once for both stages.
+struct Lp3Item {
+    int a, m, i, base;
+    bool item;
+    float4 li, lj;
+    float radius;
+};
+template <int MAXL>
+__device__ __forceinline__ Lp3Item lp3_item_of(const Smem& s, int lane, unsigned long long mask) {
+    constexpr int kPairs = MAXL * (MAXL - 1) / 2;
+    Lp3Item it;
+    const int t = lane / kPairs;
+    it.m = lane - t * kPairs;
+    it.a = 0;
+    unsigned long long rest = mask;
+#pragma unroll
+    for (int u = 0; u < kWave / kPairs; ++u) {
+        const int bit = rest ? __ffsll((long long)rest) - 1 : 0;
+        it.a = (u == t) ? bit : it.a;
+        rest &= rest - 1ull;
+    }
+    it.item = lane < (int)__popcll(mask) * kPairs;
+    it.i = lp3_program_of(it.m), it.base = it.i * (it.i - 1) / 2;
+    const float4* la = s.lines + it.a * kLineStride;
+    it.li = la[it.i], it.lj = la[it.m - it.base];
+    it.radius = s.sol[it.a].z;
+    return it;
+}
+// The head of the one-pass fallback: the item's projection (lp3_project) into the agent's proj row, then the 1-D solution of
+// its projected line against the earlier ones of program i into the cand3 row.  Reads only the agent's half-planes and
+// sol[a].z — both complete once the pair phase is — so in the two-wave kernel EITHER wave can run it (split_has_head).
+template <int MAXL>
+__device__ __forceinline__ void lp3_head(const Smem& s, const Lp3Item& it) {
+    const float4 pr = lp3_project(it.li, it.lj);
+    if (it.item) s.proj[it.a * kLineStride + it.m] = pr;
+    CN_FUSED_SYNC();
+    if (it.item) {
+        // (one (projected line, earlier line) pair per item lane + two shuffle rounds instead of these three masked pairs
+        // was built and measured neutral in round 6: 1 229.6 / 1 238.8 vs 1 229.9 / 1 233.7 M — profiles/HISTORY.md)
+        const float4* pa = s.proj + it.a * kLineStride + it.base;
+        s.cand3[it.a * kLineStride + it.m] =
+            lp_line_candidate<MAXL - 2>(pa[it.m - it.base], pa, it.m - it.base, it.radius, -it.li.w, it.li.z, true);
+    }
+}
+
+// The barrier-3 rule of the two-wave kernel, stated ONCE for both waves: an iteration has a third split_barrier exactly when
+// this holds.  `pred` is the prediction word (the agents that were infeasible one step ago), which both waves read from LDS
+// after barrier 1 of the iteration, and `u` the step counter both keep identically — so the two waves cannot disagree.  The
+// agents of pred must fit the one-pass item layout; the iteration in which the ORCA wave leaves its loop (u == n_steps)
+// computes nothing.
+template <int MAXL>
+__device__ __forceinline__ bool split_has_head(unsigned int pred, int u, int n_steps) {
+    return pred != 0u && __popc(pred) * (MAXL * (MAXL - 1) / 2) <= kWave && u < n_steps;
+}
+
 // solve: the planar scan, then the candidate-form 3-D fallback for the infeasible agents (wave-uniform branch).  Agent
-// lanes with `solve` leave their new velocity in (rx, ry), every other lane (0, 0).  Returns whether the wave took the fallback.
+// lanes with `solve` leave their new velocity in (rx, ry), every other lane (0, 0).  Returns the ballot of the infeasible
+// agents (non-zero: the wave took the fallback).
 // BASE_PRIO: the issue priority a wave goes back to on its first step without the fallback.
-template <int MAXL, int BASE_PRIO = 0>
-__device__ __forceinline__ bool fused_solve(const Params& P, const Smem& s, int lane, bool solve, float& rx, float& ry,
-                                            PhaseClock* clk) {
+// Two-wave kernel, ORCA wave: `after_scan` runs behind the planar scan (barrier 3 of an iteration that has one) and `have`
+// are the agents whose fallback head (lp3_head) the env wave has left in proj / cand3 by then: when every infeasible agent is
+// among them the fallback starts at the inner programs.  Otherwise the full path runs — behind barrier 3 the env wave no
+// longer writes those rows.
+struct NoOp {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int MAXL, int BASE_PRIO = 0, typename AfterScan = NoOp>
+__device__ __forceinline__ unsigned long long fused_solve(const Params& P, const Smem& s, int lane, bool solve, float& rx,
+                                                          float& ry, PhaseClock* clk, unsigned long long have = 0ull,
+                                                          AfterScan&& after_scan = NoOp{}) {
     (void)P, (void)clk;
     rx = 0.0f, ry = 0.0f;
     int n = 0, fail = 0;
@@ -184,6 +255,7 @@ __device__ __forceinline__ bool fused_solve(const Params& P, const Smem& s, int 
 #ifdef CN_PHASE_TIMING
     if (clk) clk->acc[9] += __popcll(nm);
 #endif
+    after_scan();
     if (nm == 0ull) __builtin_amdgcn_s_setprio(BASE_PRIO);
     if (nm != 0ull) {  // wave-uniform: some agent of this wave was infeasible
         __builtin_amdgcn_s_setprio(3);
@@ -191,32 +263,17 @@ __device__ __forceinline__ bool fused_solve(const Params& P, const Smem& s, int 
         const int n_todo = __popcll(nm);
         bool one_pass_done = false;  // (wave-uniform)
         if (n_todo * kPairs <= kWave) {
-            // one pass: item = lane = (t, m); the t-th infeasible agent is the t-th set bit of the ballot (scalar bit
-            // tricks, no LDS list), and the item's half-planes are requested once for both stages
-            const int t = lane / kPairs, m = lane - t * kPairs;
-            int a = 0;
-            unsigned long long rest = nm;
-#pragma unroll
-            for (int u = 0; u < kWave / kPairs; ++u) {
-                const int bit = rest ? __ffsll((long long)rest) - 1 : 0;
-                a = (u == t) ? bit : a;
-                rest &= rest - 1ull;
+            // one pass: item = lane = (t, m)
+            const Lp3Item it = lp3_item_of<MAXL>(s, lane, nm);
+            const bool item = it.item;
+            const int a = it.a, i = it.i, m = it.m, base = it.base;
+            const float4 li = it.li;
+            const float radius = it.radius;
+            const bool hit = (nm & ~have) == 0ull;  // every infeasible agent's head is there already
+            if (!hit) {
+                lp3_head<MAXL>(s, it);
+                CN_FUSED_SYNC();
             }
-            const bool item = lane < n_todo * kPairs;
-            const int i = lp3_program_of(m), base = i * (i - 1) / 2;
-            const float4* la = s.lines + a * kLineStride;
-            const float4 li = la[i], lj = la[m - base];
-            const float radius = s.sol[a].z;
-            const float4 pr = lp3_project(li, lj);
-            if (item) s.proj[a * kLineStride + m] = pr;
-            CN_FUSED_SYNC();
-            if (item) {
-                // (one (projected line, earlier line) pair per item lane + two shuffle rounds instead of these three masked pairs
-                // was built and measured neutral in round 6: 1 229.6 / 1 238.8 vs 1 229.9 / 1 233.7 M — profiles/HISTORY.md)
-                const float4* pa = s.proj + a * kLineStride + base;
-                s.cand3[a * kLineStride + m] = lp_line_candidate<MAXL - 2>(pa[m - base], pa, m - base, radius, -li.w, li.z, true);
-            }
-            CN_FUSED_SYNC();
             // the four planar programs of an infeasible agent side by side: the item lane of slot (i, 0) runs program i
             // and leaves its solution in the agent's cand2 row (free since the planar scan above), slot i
             if (item && m == base)
@@ -251,7 +308,7 @@ __device__ __forceinline__ bool fused_solve(const Params& P, const Smem& s, int 
             lp3_scan(s.lines + lane * kLineStride, s.proj + lane * kLineStride, s.cand3 + lane * kLineStride, n,
                      fail, s.sol[lane].z, rx, ry);
     }
-    return nm != 0ull;
+    return nm;
 }
 
 // The eight float64 parameters of a step, pinned in vector registers (in_vgpr).
@@ -358,17 +415,87 @@ static __device__ unsigned long long cn_wave_trace[8192 * 6];
 // past barrier 2.  One ORCA step is redone per episode end of a workgroup (~1 in 21 wave-steps at the headline shape).
 // The step counters, the discount index and every store to global memory live in the env wave.
 // What the waves exchange lives in arrays of the LDS layout that the fused kernels do not otherwise use: Smem::act (the
-// published velocities, as float2) and Smem::flag[0] (the word).
+// published velocities, as float2), Smem::flag[0] (the word) and, with ASSIST, Smem::flag[1] (the prediction word: an
+// iteration whose prediction word is non-zero has a third barrier, between the ORCA wave's planar scan and its fallback).
 // Issue priority: the ORCA wave is the critical path of a step, the env wave has slack in both windows, and four waves share
 // a SIMD — so the ORCA wave runs at priority 1 where the env wave stays at 0 (measured: 1 380 -> 1 473 M env-steps/s at
 // 4096 envs x 1000 steps); a jammed wave's 3 during the fallback stands above both.
 constexpr int kSplitOrcaPrio = 1;
-__device__ __forceinline__ void split_barrier() {
-    // every LDS write of this wave has landed (a wave's LDS operations complete in order) before the other wave is released
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+// ASSIST (CROWDNAV_AMD_SPLIT_ASSIST, cn_create): work of the ORCA wave's chain that the env wave's slack absorbs.
+//   kAssistHead  the head of the one-pass 3-D fallback (lp3_head) for the agents that were infeasible ONE STEP AGO — jams
+//                persist: that predicts every agent of ~3 in 4 fallback steps.  The ORCA wave leaves its ballot of infeasible
+//                agents in Smem::flag[1] beside the velocities; in an iteration whose word is non-zero (split_has_head) the env
+//                wave runs the head right behind barrier 2, while the ORCA wave still has candidates and the planar scan in
+//                front of it, and the waves meet at a THIRD barrier behind the planar scan.  A hit (every infeasible agent was
+//                predicted) starts the ORCA wave's fallback at the inner programs; a miss runs the whole fallback as before
+//                (the env wave's rows are overwritten with the same values); a false alarm costs the barrier.
+//                The word is stale after an episode end and 0 at launch start: it is a prediction, never a result.
+constexpr int kAssistHead = 1;
+// the env wave's issue priority while it runs the head: the ORCA wave will wait for it behind its planar scan
+#ifndef CN_SPLIT_HEAD_PRIO
+#define CN_SPLIT_HEAD_PRIO 2
+#endif
+// ... and for the rest of window 2 of such an iteration (its float64 work starts late)
+#ifndef CN_SPLIT_HEAD_TAIL_PRIO
+#define CN_SPLIT_HEAD_TAIL_PRIO 1
+#endif
 
-template <int MAXL>
+// CN_SPLIT_PROBE (profiling builds; keeps the two-wave route): per launch, summed over the workgroups — iterations, redone
+// iterations, fallback steps, iterations with the third barrier, head hits / misses / false alarms, and the shader-clock
+// ticks (__builtin_readcyclecounter) each wave waited at barriers 1 / 2 / 3.  The wait at barrier 1 — where window 2 of the
+// PREVIOUS iteration ends — is also booked by what that iteration was: one whose step took the fallback (the ORCA wave's
+// ballot, which the probe build publishes in Smem::flag[1] whatever ASSIST is), one that had the third barrier.
+// scripts/probes/split_probe.py
+#ifdef CN_SPLIT_PROBE
+constexpr bool kSplitProbe = true;
+static __device__ unsigned long long cn_split_probe[32];
+#define SPLIT_PROBE_DECL()                                                                                   \
+    unsigned long long sp_cnt[7] = {}, sp_wait[3] = {}, sp_w1[2] = {}, sp_n1[2] = {}, sp_dt = 0ull; \
+    bool sp_prev_head = false
+#define SPLIT_PROBE_WAIT(k, barrier)                                   \
+    do {                                                               \
+        const unsigned long long sp_t0 = __builtin_readcyclecounter(); \
+        barrier;                                                       \
+        sp_dt = __builtin_readcyclecounter() - sp_t0;                  \
+        sp_wait[k] += sp_dt;                                           \
+    } while (0)
+// behind barrier 1: `word` = the ballot of the previous iteration's infeasible agents; `head`: has THIS iteration the third barrier
+#define SPLIT_PROBE_AFTER_1(word, head)                               \
+    do {                                                               \
+        if ((word) != 0u) sp_w1[0] += sp_dt, ++sp_n1[0];               \
+        if (sp_prev_head) sp_w1[1] += sp_dt, ++sp_n1[1];               \
+        sp_prev_head = (head);                                         \
+    } while (0)
+#define SPLIT_PROBE_STEP(ended, nm, head, pred)                                  \
+    do {                                                                         \
+        const bool sp_hit = (head) && (nm) != 0ull && ((nm) & ~(unsigned long long)(pred)) == 0ull; \
+        ++sp_cnt[0], sp_cnt[1] += (ended) ? 1 : 0, sp_cnt[2] += (nm) != 0ull ? 1 : 0, sp_cnt[3] += (head) ? 1 : 0; \
+        sp_cnt[4] += sp_hit ? 1 : 0, sp_cnt[5] += ((nm) != 0ull && !sp_hit) ? 1 : 0, sp_cnt[6] += ((head) && (nm) == 0ull) ? 1 : 0; \
+    } while (0)
+// cn_split_probe: [0..6] the ORCA wave's counters; [7..9] / [10..12] the ORCA / env wave's waits at barriers 1 / 2 / 3;
+// [13 + 4 w ..]: wave w's (0 ORCA, 1 env) barrier-1 waits behind {fallback, third-barrier} iterations, then how many
+#define SPLIT_PROBE_FLUSH(lane, base)                                                        \
+    do {                                                                                     \
+        if ((lane) == 0) {                                                                   \
+            if ((base) == 0)                                                                 \
+                for (int k = 0; k < 7; ++k) atomicAdd(&cn_split_probe[k], sp_cnt[k]);        \
+            for (int k = 0; k < 3; ++k) atomicAdd(&cn_split_probe[((base) ? 10 : 7) + k], sp_wait[k]); \
+            for (int k = 0; k < 2; ++k) {                                                    \
+                atomicAdd(&cn_split_probe[((base) ? 17 : 13) + k], sp_w1[k]);                \
+                atomicAdd(&cn_split_probe[((base) ? 19 : 15) + k], sp_n1[k]);                \
+            }                                                                                \
+        }                                                                                    \
+    } while (0)
+#else
+constexpr bool kSplitProbe = false;
+#define SPLIT_PROBE_DECL() (void)0
+#define SPLIT_PROBE_WAIT(k, barrier) barrier
+#define SPLIT_PROBE_AFTER_1(word, head) (void)0
+#define SPLIT_PROBE_STEP(ended, nm, head, pred) (void)0
+#define SPLIT_PROBE_FLUSH(lane, base) (void)0
+#endif
+
+template <int MAXL, int ASSIST>
 __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, int n_steps) {
     const int lane = (int)threadIdx.x - kWave;
     float2* const vel = reinterpret_cast<float2*>(s.act);
@@ -380,14 +507,18 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
     double px = 0.0, py = 0.0;
     float rx = 0.0f, ry = 0.0f;
     bool solved = false;
+    SPLIT_PROBE_DECL();
     for (int u = 0;;) {
-        split_barrier();  // 1
+        SPLIT_PROBE_WAIT(0, split_barrier());  // 1
         const bool ended = __builtin_amdgcn_readfirstlane(s.flag[0]) != 0;
+        const unsigned int pred = ((ASSIST & kAssistHead) || kSplitProbe) ? (unsigned int)__builtin_amdgcn_readfirstlane(s.flag[1]) : 0u;
         if (!ended) ++u;
         if (u >= n_steps) {  // the env wave finishes step n_steps - 1 alone
             split_barrier();  // 2
             break;
         }
+        const bool head = (ASSIST & kAssistHead) ? split_has_head<MAXL>(pred, u, n_steps) : false;
+        SPLIT_PROBE_AFTER_1(pred, head);
         if (lane < P.nA) {
             if (ended) {  // the env wave staged the true state
                 const double2 p = s.posd[lane];
@@ -400,22 +531,28 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
         }
         CN_FUSED_SYNC();
         if (lane < P.pairs) fused_pair_phase(P, s, pr, range_sq, [] {});
-        split_barrier();  // 2: sol / res of step u
+        SPLIT_PROBE_WAIT(1, split_barrier());  // 2: sol / res of step u
         fused_candidates<MAXL>(P, s, lane);
         CN_FUSED_SYNC();
         solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
-        fused_solve<MAXL, kSplitOrcaPrio>(P, s, lane, solved, rx, ry, nullptr);
+        const unsigned long long nm = fused_solve<MAXL, kSplitOrcaPrio>(P, s, lane, solved, rx, ry, nullptr, head ? pred : 0u, [&] {
+            if (head) SPLIT_PROBE_WAIT(2, split_barrier());  // 3: the env wave's proj / cand3 rows of the agents of pred
+        });
         if (lane < P.nA) vel[lane] = make_float2(rx, ry);
+        if (((ASSIST & kAssistHead) || kSplitProbe) && lane == 0) s.flag[1] = (int)nm;  // the next iteration's prediction word
+        SPLIT_PROBE_STEP(ended, nm, head, pred);
     }
+    SPLIT_PROBE_FLUSH(lane, 0);
 }
 
-template <bool HEADLINE, bool SPLIT = false>
+template <bool HEADLINE, bool SPLIT = false, int ASSIST = 0>
 // (the headline instantiation is compiled for three waves per SIMD: with the hint hipcc settles on 163-167 VGPRs and a schedule
 // worth 1.2 % at 4096 envs, 2.6 % in the 20-step shape; compiled for two it loses 3 %, for four — 128 VGPRs, 42 spilled — 11 %;
 // the two-wave kernel is built for four: 2048 workgroups x 2 waves on 1024 SIMDs)
 __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 : 1)) void rollout_fused_kernel(
     Params P_in, const StateView* Sd, const int* ring_filled_in, RolloutView R, int n_steps, const double* ext_action) {
     static_assert(HEADLINE || !SPLIT, "the two-wave kernel exists for the headline geometry only");
+    static_assert(SPLIT || ASSIST == 0, "the env wave assists an ORCA wave: two-wave kernel only");
 #ifdef CN_WAVE_TRACE
     const unsigned long long wt_entry = __builtin_amdgcn_s_memrealtime();
     unsigned long long wt_fallbacks = 0ull, wt_ends = 0ull;
@@ -432,7 +569,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     const Smem s = carve<MAXL>(P);
     if constexpr (SPLIT) {
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= kWave) {
-            split_orca_wave<MAXL>(P, s, n_steps);
+            split_orca_wave<MAXL, ASSIST>(P, s, n_steps);
             return;
         }
     }
@@ -516,12 +653,15 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
 #endif
     if constexpr (SPLIT) {
         float2* const vel = reinterpret_cast<float2*>(s.act);
-        if (L.lane == 0) s.flag[0] = 1;
+        if (L.lane == 0) s.flag[0] = 1, s.flag[1] = 0;  // "re-read the staged state"; no agent predicted infeasible
         split_barrier();  // prologue staged
         bool skip = true;  // the state of step u is already in registers: nothing to integrate, nothing to book
+        SPLIT_PROBE_DECL();
         for (int u = 0;;) {
-            split_barrier();  // 1: vel(u - 1)
+            SPLIT_PROBE_WAIT(0, split_barrier());  // 1: vel(u - 1)
             if (!skip) ++u;
+            const unsigned int pred = ((ASSIST & kAssistHead) || kSplitProbe) ? (unsigned int)__builtin_amdgcn_readfirstlane(s.flag[1]) : 0u;
+            SPLIT_PROBE_AFTER_1(pred, (ASSIST & kAssistHead) != 0 && split_has_head<MAXL>(pred, u, n_steps));
             const bool running = L.valid && ep.state == kRunning;
             const AgentRegs r0 = r;  // the agent at the start of step u - 1
             double act_x = 0.0, act_y = 0.0, new_vx = 0.0, new_vy = 0.0;
@@ -543,7 +683,16 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                 s.sol[L.lane] = sol4;
                 s.res[L.lane] = start4;
             }
-            split_barrier();  // 2
+            SPLIT_PROBE_WAIT(1, split_barrier());  // 2
+            if constexpr ((ASSIST & kAssistHead) != 0) {
+                if (split_has_head<MAXL>(pred, u, n_steps)) {  // lines and sol of step u are complete: the fallback's head
+                    __builtin_amdgcn_s_setprio(CN_SPLIT_HEAD_PRIO);
+                    const Lp3Item it = lp3_item_of<MAXL>(s, L.lane, (unsigned long long)pred);
+                    lp3_head<MAXL>(s, it);
+                    __builtin_amdgcn_s_setprio(CN_SPLIT_HEAD_TAIL_PRIO);
+                    SPLIT_PROBE_WAIT(2, split_barrier());  // 3
+                }
+            }
             bool ended = false;
             if (!skip) {
                 // the robot's position at the start of the step: from its lane's registers (posd holds re-staged states only)
@@ -590,8 +739,10 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             if (ended) stage_agent(P, s, L, r, K.hsafety);
             if (L.lane == 0) s.flag[0] = ended ? 1 : 0;
             skip = ended;
+            if constexpr ((ASSIST & kAssistHead) != 0 && CN_SPLIT_HEAD_TAIL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
             if (u >= n_steps) break;
         }
+        SPLIT_PROBE_FLUSH(L.lane, 10);
     }
     const int one_wave_steps = SPLIT ? 0 : n_steps;
     for (int step = 0; step < one_wave_steps; ++step) {
@@ -619,7 +770,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
 
         // ---- solve: scan, then the candidate-form fallback for the infeasible agents
         float rx, ry;
-        const bool fell_back = fused_solve<MAXL>(P, s, L.lane, solve, rx, ry, clk);
+        const bool fell_back = fused_solve<MAXL>(P, s, L.lane, solve, rx, ry, clk) != 0ull;
         (void)fell_back;
 #ifdef CN_WAVE_TRACE
         if (fell_back) ++wt_fallbacks;
