@@ -75,6 +75,7 @@ def lib():
         L.co_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.co_orca.argtypes = [C.c_void_p, C.c_void_p]
         L.co_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.co_last_fallback.argtypes = [C.c_void_p, C.c_void_p]
         L.co_rollout.restype = C.c_int64
         L.co_rollout.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int] + [C.c_void_p] * 7
         L.co_rollout_full.restype = C.c_int64
@@ -168,6 +169,13 @@ class CrowdOracle(object):
         lib().co_step(self._h, _p(a), int(bool(update)), _p(reward), _p(done), _p(info), _p(dmin),
                       _p(act), _p(vel))
         return dict(reward=reward, done=done, info=info, dmin=dmin, action=act, orca_vel=vel)
+
+    def last_fallback(self):
+        """[B, A] bool: whose last ORCA solve (step / orca) took the 3-D fallback, i.e. linearProgram2 failed and
+        linearProgram3 ran; False for a robot whose action the caller supplied."""
+        out = np.empty((self.B, self.A), dtype=np.uint8)
+        lib().co_last_fallback(self._h, _p(out))
+        return out.astype(bool)
 
     def rollout(self, n_steps, seed_base, seed_mod, max_ep, ep_index, cur_steps, cur_return):
         B = self.B

@@ -319,7 +319,8 @@ void Simulator::computeNewVelocity(std::size_t i) {
     }
 
     const std::size_t fail = lp2(a.lines, a.maxSpeed, a.prefVelocity, false, a.newVelocity);
-    if (fail < a.lines.size()) lp3(a.lines, numObstLines, fail, a.maxSpeed, a.newVelocity);
+    a.fellBack = fail < a.lines.size();
+    if (a.fellBack) lp3(a.lines, numObstLines, fail, a.maxSpeed, a.newVelocity);
 }
 
 void Simulator::solveOnly(std::size_t i) {

@@ -42,6 +42,7 @@ struct AgentRec {
     std::size_t maxNeighbors = 0;
     std::vector<std::pair<float, std::size_t>> neighbors;  // (distSq, agent id), ascending
     std::vector<HalfPlane> lines;
+    bool fellBack = false;  // the last solve: linearProgram2 failed, linearProgram3 ran
 };
 
 class Simulator {

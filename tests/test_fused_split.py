@@ -9,10 +9,10 @@ The geometry is always the headline one — 5 humans, a visible ORCA robot, 2 en
 below 2049 envs the engine would otherwise put one env in a workgroup) — at the smallest sizes at which the split can go
 wrong; every case asserts through rollout_route that the two engines really took different kernels.
 
-Multi-pass 3-D fallback (more than six infeasible agents of a wave in one step): counted with a scratch build that prints
-from that branch, over every case of this file, both kernels — it never ran (0 times; the one-pass form ran in 744 steps of
-workgroup 0 alone, with 1, 2 or 3 infeasible agents).  At these sizes the multi-pass form is therefore covered only by code
-sharing: it is the same `fused_solve` the one-wave kernel calls."""
+Multi-pass 3-D fallback (more than six infeasible agents of a workgroup in one step): the seeded cases of this file never reach
+it (they produce 1, 2 or 3 infeasible agents per step).  test_fused_jam_parity.py does, from the huddles of jam_scenes.py — 7 to 10
+infeasible agents of a workgroup, on the one-wave and both two-wave kernels, step for step against the oracle — and
+test_jam_scenes_host.py proves on the oracle that those scenes reach it."""
 import contextlib
 import os
 
