@@ -27,19 +27,42 @@ void cn_launch_orca(cn_engine* e, float* out_vel) {
     });
 }
 
-extern "C" {
-
-const char* cn_last_error(void) { return cn_g_err; }
-int cn_abi_version(void) { return CN_ABI_VERSION; }
-
 // BASELINE configs[1]: 5 humans + robot, 2 envs per workgroup — the geometry the fused kernels hold as compile-time constants
 static bool headline_geometry(const cn::Params& P) {
     return P.A == 6 && P.NC == 5 && P.E == 2 && P.nA == 12 && P.pairs == 60 && P.threads == 64;
 }
 
-int cn_create(const cn_config* c, cn_engine** out) {
-    if (!c || !out) return fail(CN_ERR_INVALID, "cn_create: NULL argument");
-    *out = nullptr;
+// the two-wave kernel's and the one-wave kernels' instantiations of rollout_fused_kernel: f(kernel, threads per workgroup) for
+// the one a route of this engine runs (CN_ROUTE_FUSED_SPLIT or CN_ROUTE_FUSED) — the launch and the occupancy query name it HERE
+template <class F>
+static void pick_fused(const cn_engine* e, int route, F&& f) {
+    if (route == CN_ROUTE_FUSED_SPLIT) {
+        if (e->split_assist & cn::kAssistHead) f(cn::rollout_fused_kernel<true, true, cn::kAssistHead>, 2 * cn::kWave);
+        else f(cn::rollout_fused_kernel<true, true>, 2 * cn::kWave);
+    } else if (headline_geometry(e->P)) {
+        f(cn::rollout_fused_kernel<true>, cn::kWave);
+    } else {
+        f(cn::rollout_fused_kernel<false>, cn::kWave);
+    }
+}
+
+// waits for the side streams of the asynchronous scenario fill (none without it); the first error, all streams waited for
+static hipError_t sync_fill_streams(const cn_engine* e) {
+    hipError_t first = hipSuccess;
+    for (int i = 0; i < cn_engine::kFillStreams; ++i)
+        if (e->fill_streams[i]) {
+            const hipError_t err = hipStreamSynchronize(e->fill_streams[i]);
+            if (first == hipSuccess) first = err;
+        }
+    return first;
+}
+
+extern "C" {
+
+const char* cn_last_error(void) { return cn_g_err; }
+int cn_abi_version(void) { return CN_ABI_VERSION; }
+
+static int check_config(const cn_config* c) {
     if (c->num_envs < 1) return fail(CN_ERR_INVALID, "num_envs must be >= 1 (got %d)", c->num_envs);
     if (c->num_humans < 1 || c->num_humans > 63)
         return fail(CN_ERR_UNSUPPORTED, "num_humans must be in 1..63 (got %d)", c->num_humans);
@@ -63,33 +86,53 @@ int cn_create(const cn_config* c, cn_engine** out) {
         return fail(CN_ERR_INVALID, "robot_kinematics %d unknown", c->robot_kinematics);
     if (c->robot_kinematics == CN_UNICYCLE && c->robot_policy == CN_ROBOT_ORCA)
         return fail(CN_ERR_INVALID, "the ORCA robot policy is holonomic (orca.py:59); a unicycle robot needs CN_ROBOT_EXTERNAL");
-
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(CN_ERR_NO_DEVICE, "no HIP device visible: the MI355X engine has no CPU fallback");
     if (c->device < 0 || c->device >= ndev) return fail(CN_ERR_INVALID, "device %d out of range", c->device);
-    CN_HIP(hipSetDevice(c->device));
+    return CN_OK;
+}
 
-    cn_engine* e = new (std::nothrow) cn_engine();
-    if (!e) return fail(CN_ERR_INVALID, "out of host memory");
-    e->cfg = *c;
-    e->stream = nullptr;
-    e->io_valid = false;
-    e->steps_since_fill = -1;
-    e->sarl = nullptr;
-    e->orca_fresh = false;
-    e->async_fill = false;
-    e->rollout_done = nullptr;
-    e->next_fill_stream = 0;
-    for (int i = 0; i < cn_engine::kFillStreams; ++i) e->fill_streams[i] = nullptr;
-    for (uint64_t& c : e->launch_counts) c = 0;
+// what the kernels and the scenario generators take from the caller's configuration as it stands
+static void copy_config(cn_engine* e) {
+    const cn_config* c = &e->cfg;
+    cn::Params& P = e->P;
+    P.robot_visible = c->robot_visible ? 1 : 0;
+    P.robot_orca = c->robot_policy == CN_ROBOT_ORCA;
+    P.robot_unicycle = c->robot_kinematics == CN_UNICYCLE;
+    P.dt = c->time_step;
+    P.time_limit = c->time_limit;
+    P.success_reward = c->success_reward;
+    P.collision_penalty = c->collision_penalty;
+    P.discomfort_dist = c->discomfort_dist;
+    P.discomfort_factor = c->discomfort_penalty_factor;
+    P.robot_safety = c->robot_safety_space;
+    P.human_safety = c->human_safety_space;
+    P.orca.neighbor_dist = (float)c->neighbor_dist;
+    P.orca.inv_time_horizon = 1.0f / (float)c->time_horizon;
+    P.orca.inv_time_step = 1.0f / (float)c->time_step;
+    P.orca.max_neighbors = c->max_neighbors;
+    e->C.num_agents = c->num_humans + 1;
+    e->C.rule = c->scenario_rule;
+    e->C.randomize = c->randomize_attributes ? 1 : 0;
+    e->C.circle_radius = c->circle_radius;
+    e->C.square_width = c->square_width;
+    e->C.discomfort_dist = c->discomfort_dist;
+    e->C.human_radius = c->human_radius;
+    e->C.human_v_pref = c->human_v_pref;
+    e->C.robot_radius = c->robot_radius;
+    e->C.robot_v_pref = c->robot_v_pref;
+}
+
+// Workgroup geometry.  E envs per workgroup (agents = lanes of wave 0), W waves sharing the per-pair phases.
+// Defaults from the MI355X sweep in DESIGN.md; CROWDNAV_AMD_ENVS_PER_WAVE / CROWDNAV_AMD_WAVES_PER_BLOCK
+// override them for tuning.  And the generator family with the ring depth that goes with it.
+static void pick_geometry(cn_engine* e) {
+    const cn_config* c = &e->cfg;
     cn::Params& P = e->P;
     P.B = c->num_envs;
     P.A = c->num_humans + 1;
     P.NC = P.A - 1;
-    // Workgroup geometry.  E envs per workgroup (agents = lanes of wave 0), W waves sharing the per-pair phases.
-    // Defaults from the MI355X sweep in DESIGN.md; CROWDNAV_AMD_ENVS_PER_WAVE / CROWDNAV_AMD_WAVES_PER_BLOCK
-    // override them for tuning.
     const int e_max = cn::kWave / P.A;
     // <= 5 half-planes per agent: 2048 workgroups (2 waves per SIMD) were fastest; the 10-half-plane kernels hold
     // 187 VGPRs (2 resident waves per SIMD) and loop over many more pairs, so they get one env per wave up to
@@ -106,82 +149,64 @@ int cn_create(const cn_config* c, cn_engine** out) {
     P.threads = cn::kWave * (w_want < 1 ? 1 : w_want);
     P.nA = P.E * P.A;
     P.pairs = P.nA * P.NC;
-    P.ring_depth = env_int("CROWDNAV_AMD_RING_DEPTH", 48);
-    if (P.ring_depth < 1) P.ring_depth = 1;
-    e->maxl = ((P.NC < c->max_neighbors ? P.NC : c->max_neighbors) <= 5) ? 5 : 10;
+    e->maxl = small_lp ? 5 : 10;
     P.kd = P.A > cn::kKdLeaf ? 1 : 0;  // a simulator of more than 10 agents splits its kd-tree: visiting order matters at ties
-    P.sched = -1;
-    e->sched_min = env_int("CROWDNAV_AMD_SCHED_MIN_STEPS", 24);  // shortest call that runs under a schedule (static: at least 48)
-    e->sched_force = env_int("CROWDNAV_AMD_SCHED_FORCE", 0) != 0;
-    e->sched_reserve = env_int("CROWDNAV_AMD_DYN_RESERVE", 0);  // slots left free beside a dynamic launch under the asynchronous fill
-    e->sched_dynamic = env_int("CROWDNAV_AMD_SCHED_DYNAMIC", 1) != 0;
-    e->scenario_cache = env_int("CROWDNAV_AMD_SCENARIO_CACHE", 1) != 0;
-    e->dyn_visits = env_int("CROWDNAV_AMD_DYN_VISITS", 0);  // 0: by call length (launch_rollout)
-    P.dyn_visits = 3;
-    {
-        hipDeviceProp_t prop;
-        const bool ok = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0;
-        e->sched_slots = 12 * (ok ? prop.multiProcessorCount : 256);
-    }
     P.kdl = cn::kd_layout(P.nA, P.A, P.E);
     e->smem = cn::smem_bytes(P.nA, P.pairs, e->maxl, P.A, P.E);
-    e->use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
-    // 0: the one-wave fused kernel everywhere (A/B runs); 2: the two-wave kernel also for launches of several rounds (measurements)
-    e->fused_split = env_int("CROWDNAV_AMD_FUSED_SPLIT", 1);
-    // what the env wave of the two-wave kernel takes off the ORCA wave's chain (rollout_fused.h: ASSIST): 1 (default) = the head
-    // of the 3-D fallback for the agents predicted infeasible; 0 = nothing (A/B runs)
-    e->split_assist = env_int("CROWDNAV_AMD_SPLIT_ASSIST", 1) != 0 ? cn::kAssistHead : 0;
-    e->split_slots = 0;
-    if (headline_geometry(P)) {  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        const bool head = (e->split_assist & cn::kAssistHead) != 0;
-        if ((head ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true, cn::kAssistHead>, 2 * cn::kWave, e->smem)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cn::rollout_fused_kernel<true, true>, 2 * cn::kWave, e->smem)) == hipSuccess &&
-            hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
-            e->split_slots = per_cu * prop.multiProcessorCount;
-    }
     e->gen_wave = env_int("CROWDNAV_AMD_WAVE_SCENARIOS", c->num_humans > 8 ? 1 : 0) != 0;
-    P.robot_visible = c->robot_visible ? 1 : 0;
-    P.robot_orca = c->robot_policy == CN_ROBOT_ORCA;
-    P.robot_unicycle = c->robot_kinematics == CN_UNICYCLE;
     e->async_fill = (c->flags & CN_FLAG_ASYNC_SCENARIO_FILL) != 0 && e->gen_wave;
     P.async_fill = e->async_fill ? 1 : 0;
     // Asynchronous fill: a slot is refilled by the fill launch AFTER the call that consumed it, behind up to one call's worth of
     // other scenarios, and a hard scenario of the reference geometry (20 humans on the 4 m circle: up to 3 M attempts) is tens
     // of milliseconds of one wave — so the ring is the latency buffer.  Measured (r06, 4096 x 20, 999-step calls, every
     // scenario generated afresh): depth 48 / 96 / 144 = 16 % / 3 % / 0 % of the env-steps paused.  0.6 GB of the 288.
+    P.ring_depth = env_int("CROWDNAV_AMD_RING_DEPTH", 48);
+    if (P.ring_depth < 1) P.ring_depth = 1;
     if (e->async_fill && !getenv("CROWDNAV_AMD_RING_DEPTH")) P.ring_depth = 144;
-    e->fill_queue_wgs = env_int("CROWDNAV_AMD_FILL_QUEUE_WGS", 1024);  // 0: one workgroup per (env, slot) (rounds 2-5)
-    P.dt = c->time_step;
-    P.time_limit = c->time_limit;
-    P.success_reward = c->success_reward;
-    P.collision_penalty = c->collision_penalty;
-    P.discomfort_dist = c->discomfort_dist;
-    P.discomfort_factor = c->discomfort_penalty_factor;
-    P.robot_safety = c->robot_safety_space;
-    P.human_safety = c->human_safety_space;
-    P.orca.neighbor_dist = (float)c->neighbor_dist;
-    P.orca.inv_time_horizon = 1.0f / (float)c->time_horizon;
-    P.orca.inv_time_step = 1.0f / (float)c->time_step;
-    P.orca.max_neighbors = c->max_neighbors;
-    e->C.num_agents = P.A;
-    e->C.rule = c->scenario_rule;
-    e->C.randomize = c->randomize_attributes ? 1 : 0;
-    e->C.circle_radius = c->circle_radius;
-    e->C.square_width = c->square_width;
-    e->C.discomfort_dist = c->discomfort_dist;
-    e->C.human_radius = c->human_radius;
-    e->C.human_v_pref = c->human_v_pref;
-    e->C.robot_radius = c->robot_radius;
-    e->C.robot_v_pref = c->robot_v_pref;
+}
+
+// The run-time switches and what they are weighed against: the device's size.
+static void read_knobs(cn_engine* e) {
+    const cn_config* c = &e->cfg;
+    cn::Params& P = e->P;
+    P.sched = -1;
+    e->sched_min = env_int("CROWDNAV_AMD_SCHED_MIN_STEPS", 24);  // shortest call that runs under a schedule (static: at least 48)
+    e->sched_force = env_int("CROWDNAV_AMD_SCHED_FORCE", 0) != 0;
+    e->sched_reserve = env_int("CROWDNAV_AMD_DYN_RESERVE", 0);  // slots left free beside a dynamic launch under the asynchronous fill
+    e->sched_dynamic = env_int("CROWDNAV_AMD_SCHED_DYNAMIC", 1) != 0;
+    e->scenario_cache = env_int("CROWDNAV_AMD_SCENARIO_CACHE", 1) != 0;
+    e->dyn_visits = env_int("CROWDNAV_AMD_DYN_VISITS", 0);  // 0: by call length (launch_shard)
+    P.dyn_visits = 3;
+    e->use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
+    // 0: the one-wave fused kernel everywhere (A/B runs); 2: the two-wave kernel also for launches of several rounds (measurements)
+    e->fused_split = env_int("CROWDNAV_AMD_FUSED_SPLIT", 1);
+    // what the env wave of the two-wave kernel takes off the ORCA wave's chain (rollout_fused.h: ASSIST): 1 (default) = the head
+    // of the 3-D fallback for the agents predicted infeasible; 0 = nothing (A/B runs)
+    e->split_assist = env_int("CROWDNAV_AMD_SPLIT_ASSIST", 1) != 0 ? cn::kAssistHead : 0;
+    // generator workgroups of an asynchronous fill launch (step_kernels.h: ring_fill_jobs_kernel), at least one
+    e->fill_queue_wgs = env_int("CROWDNAV_AMD_FILL_QUEUE_WGS", 1024);
+    if (e->fill_queue_wgs < 1) e->fill_queue_wgs = 1;
     // give-up threshold of the rejection sampling: ~seconds of GPU time in either generator family
     int cap_log2 = env_int("CROWDNAV_AMD_MAX_ATTEMPTS_LOG2", c->num_humans > 8 ? 23 : 20);
     if (cap_log2 < 6) cap_log2 = 6;
     if (cap_log2 > 40) cap_log2 = 40;
     e->C.max_attempts = 1ull << cap_log2;
-    e->C.error = nullptr;
+    hipDeviceProp_t prop;
+    const bool ok = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0;
+    e->sched_slots = 12 * (ok ? prop.multiProcessorCount : 256);
+    e->split_slots = 0;
+    if (ok && headline_geometry(P))  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
+        pick_fused(e, CN_ROUTE_FUSED_SPLIT, [&](auto kernel, int threads) {
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, e->smem) == hipSuccess)
+                e->split_slots = per_cu * prop.multiProcessorCount;
+        });
+}
 
+// every device buffer of the engine, the device copy of the state view and the side streams of the asynchronous fill (the
+// caller destroys the engine if this fails)
+static int alloc_state(cn_engine* e) {
+    const cn::Params& P = e->P;
     const size_t n = (size_t)P.B * P.A;
     int rc = CN_OK;
     cn::StateView& S = e->S;
@@ -212,44 +237,48 @@ int cn_create(const cn_config* c, cn_engine** out) {
         (rc = dev_alloc(e, &S.group_partial, (size_t)cn::kEpilogueGroups * (CN_SUMMARY_FIELDS + 1))) ||
         (rc = dev_alloc(e, &S.tickets, (size_t)(cn::kEpilogueGroups + 1) * cn::kTicketStride)) ||
         (rc = dev_alloc(e, &e->io_dev, (size_t)1)) || (rc = dev_alloc(e, &e->C.error, (size_t)1)) ||
-        (rc = dev_alloc(e, &e->S_dev, (size_t)1))) {
-        cn_destroy(e);
+        (rc = dev_alloc(e, &e->S_dev, (size_t)1)))
         return rc;
-    }
     e->S.error = e->C.error;
-    if (hipMemcpy(e->S_dev, &e->S, sizeof(cn::StateView), hipMemcpyHostToDevice) != hipSuccess) {
-        cn_destroy(e);
+    if (hipMemcpy(e->S_dev, &e->S, sizeof(cn::StateView), hipMemcpyHostToDevice) != hipSuccess)
         return fail(CN_ERR_HIP, "cn_create: state view upload failed");
-    }
     if (e->async_fill) {
         bool ok = hipEventCreateWithFlags(&e->rollout_done, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; ok && i < cn_engine::kFillStreams; ++i)
             ok = hipStreamCreateWithFlags(&e->fill_streams[i], hipStreamNonBlocking) == hipSuccess;
-        if (!ok) {
-            cn_destroy(e);
-            return fail(CN_ERR_HIP, "cn_create: side streams for the asynchronous scenario fill");
-        }
+        if (!ok) return fail(CN_ERR_HIP, "cn_create: side streams for the asynchronous scenario fill");
     }
-    e->discount = nullptr;
-    e->discount_len = 0;
-    *out = e;
-    rc = cn_set_gamma(e, 0.9);
-    if (rc) {
+    return CN_OK;
+}
+
+int cn_create(const cn_config* c, cn_engine** out) {
+    if (!c || !out) return fail(CN_ERR_INVALID, "cn_create: NULL argument");
+    *out = nullptr;
+    int rc = check_config(c);
+    if (rc) return rc;
+    CN_HIP(hipSetDevice(c->device));
+
+    cn_engine* e = new (std::nothrow) cn_engine();
+    if (!e) return fail(CN_ERR_INVALID, "out of host memory");
+    e->cfg = *c;
+    copy_config(e);
+    pick_geometry(e);
+    read_knobs(e);
+    if ((rc = alloc_state(e)) || (rc = cn_set_gamma(e, 0.9))) {
         cn_destroy(e);
-        *out = nullptr;
+        return rc;
     }
-    return rc;
+    *out = e;
+    return CN_OK;
 }
 
 int cn_destroy(cn_engine* e) {
     if (!e) return CN_OK;
     (void)hipSetDevice(e->cfg.device);
     (void)hipStreamSynchronize(e->stream);
-    for (int i = 0; i < cn_engine::kFillStreams; ++i)
-        if (e->fill_streams[i]) {
-            (void)hipStreamSynchronize(e->fill_streams[i]);
-            (void)hipStreamDestroy(e->fill_streams[i]);
-        }
+    (void)sync_fill_streams(e);
+    for (hipStream_t fs : e->fill_streams)
+        if (fs) (void)hipStreamDestroy(fs);
     if (e->rollout_done) (void)hipEventDestroy(e->rollout_done);
     e->alloc_rollback(cn_engine::AllocMark{});
     if (e->discount) (void)hipFree(e->discount);
@@ -269,8 +298,7 @@ int cn_sync(cn_engine* e) {
     int rc = bind(e);
     if (rc) return rc;
     CN_HIP(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < cn_engine::kFillStreams; ++i)
-        if (e->fill_streams[i]) CN_HIP(hipStreamSynchronize(e->fill_streams[i]));
+    CN_HIP(sync_fill_streams(e));
     int gen_error = 0;
     CN_HIP(hipMemcpy(&gen_error, e->C.error, sizeof(int), hipMemcpyDeviceToHost));
     if (gen_error) {
@@ -477,9 +505,7 @@ int cn_set_gamma(cn_engine* e, double gamma) {
 // bookkeeping) the host waits for them: a straggler of the previous rollout must not publish a scenario of the old seed
 // numbering into the new one's ring, nor read buffers the caller is about to free.
 static int drain_fill_streams(cn_engine* e) {
-    if (!e->async_fill) return CN_OK;
-    for (int i = 0; i < cn_engine::kFillStreams; ++i)
-        if (e->fill_streams[i]) CN_HIP(hipStreamSynchronize(e->fill_streams[i]));
+    CN_HIP(sync_fill_streams(e));
     return CN_OK;
 }
 
@@ -500,7 +526,6 @@ static int upload_io(cn_engine* e, const cn_rollout_io* io) {
 }
 
 static int check_io(const cn_engine* e, const cn_rollout_io* io) {
-    (void)e;
     if (!io) return fail(CN_ERR_INVALID, "rollout io is NULL");
     if (io->seed_mod == 0) return fail(CN_ERR_INVALID, "seed_mod must be >= 1");
     if (!io->ep_count || !io->cur_steps || !io->cur_return || !io->active)
@@ -545,21 +570,17 @@ static int fill_ring_if_needed(cn_engine* e, const cn::RolloutView& R, int n_ste
         e->next_fill_stream = (e->next_fill_stream + 1) % cn_engine::kFillStreams;
         CN_HIP(hipEventRecord(e->rollout_done, e->stream));
         CN_HIP(hipStreamWaitEvent(fs, e->rollout_done, 0));
-        // (tried and dropped: 4 workgroups per env walking its slots in order — 4.0 M instead of 20.8 M env-steps/s at the
-        // reference geometry, a workgroup stuck on a hard scenario delays its env's later slots.  Round 2's claim-then-work-list
-        // pair of kernels "hung on the GPU box"; round 6 found why — a generator loop of the shape `for (;;) { lane 0 pops with
-        // atomicAdd; j = readfirstlane; if (j >= jobs) break; generate }` never terminates as compiled (the popping loop below is
-        // written around a ballot instead) — and the pair is now the default: CROWDNAV_AMD_FILL_QUEUE_WGS generator workgroups)
-        if (e->fill_queue_wgs > 0) {  // scan + persistent generator workgroups on a job list (step_kernels.h); the default
-            int* list = e->fill_list + (size_t)this_stream * (2 + 2 * (size_t)e->P.B * e->P.ring_depth);
-            CN_HIP(hipMemsetAsync(list, 0, 2 * sizeof(int), fs));
-            const int items = e->P.B * e->P.ring_depth;
-            hipLaunchKernelGGL(cn::ring_fill_scan_kernel, dim3((items + 255) / 256), dim3(256), 0, fs, e->P, e->S, R, list);
-            hipLaunchKernelGGL(cn::ring_fill_jobs_kernel, dim3(e->fill_queue_wgs), dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, list);
-        } else {
-            hipLaunchKernelGGL(cn::ring_fill_wave_async_kernel, dim3(e->P.B * e->P.ring_depth), dim3(cn::kWave), 0, fs, e->P, e->C,
-                               e->S, R);
-        }
+        // scan + persistent generator workgroups on a job list (step_kernels.h).  (Tried and dropped: 4 workgroups per env walking
+        // its slots in order — 4.0 M instead of 20.8 M env-steps/s at the reference geometry, a workgroup stuck on a hard scenario
+        // delays its env's later slots; and, rounds 2-5, one workgroup per (env, slot): profiles/HISTORY.md.  Round 2's first
+        // attempt at this pair of kernels "hung on the GPU box"; round 6 found why — a generator loop of the shape `for (;;) {
+        // lane 0 pops with atomicAdd; j = readfirstlane; if (j >= jobs) break; generate }` never terminates as compiled, so the
+        // popping loop of ring_fill_jobs_kernel is written around a ballot instead.)
+        int* list = e->fill_list + (size_t)this_stream * (2 + 2 * (size_t)e->P.B * e->P.ring_depth);
+        CN_HIP(hipMemsetAsync(list, 0, 2 * sizeof(int), fs));
+        const int items = e->P.B * e->P.ring_depth;
+        hipLaunchKernelGGL(cn::ring_fill_scan_kernel, dim3((items + 255) / 256), dim3(256), 0, fs, e->P, e->S, R, list);
+        hipLaunchKernelGGL(cn::ring_fill_jobs_kernel, dim3(e->fill_queue_wgs), dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, list);
         e->launch_counts[CN_COUNT_ASYNC_FILLS] += 1;
         e->steps_since_fill = 0;
         return CN_OK;
@@ -614,104 +635,110 @@ static int rollout_route(const cn_engine* e, const double* action) {
     return CN_ROUTE_GENERIC;
 }
 
-static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
+// The 20-human shard's kernel (CN_ROUTE_SHARD) under one of its two schedules, or plain.
+static void launch_shard(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
     const cn::Params& P = e->P;
-    const uint64_t kernels_before = e->launch_counts[CN_COUNT_ROLLOUT_KERNELS];
+    const size_t smem20 = cn::smem_bytes_compact(P.nA, P.pairs, P.A, P.E);
+    const auto launch = [&](const cn::Params& Pk, int grid, int steps) {
+        hipLaunchKernelGGL((cn::rollout_kernel<10, false, true, true>), dim3(grid), dim3(64), smem20, e->stream, Pk,
+                           (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, steps, action);
+    };
+    // Three resident waves per SIMD (step_kernels.h: kGeom20Waves): 3072 one-wave workgroups fill the chip, so B = 4096 envs would run as
+    // a full round plus a third of one.  A call of 3 q + r steps becomes one launch of r steps over all envs (if r > 0) and
+    // FOUR launches of q steps over 3 B / 4 workgroups each, sub-launch k leaving out env 3 - k of every group of four
+    // (step_kernels.h: Params::sched): every env makes its steps in order, every launch is one round.
+    // Worth it when it saves rounds: with S = 12 workgroups x CUs resident, a plain launch takes ceil(B / S) rounds of
+    // n steps, the schedule 4 ceil(0.75 B / S) rounds of n / 3 (B = 4096 on 256 CUs: 2 vs 1.33; B = 3072: 1 vs 1.33 - plain).
+    // CROWDNAV_AMD_SCHED_MIN_STEPS / CROWDNAV_AMD_SCHED_FORCE (read_knobs): shortest call that is split; split
+    // whatever the round count (the parity tests run the schedule on a handful of envs).
+    cn::Params Pk = e->P;
+    Pk.sched = -1;
+    const int slots = e->sched_slots;
+    // Dynamic schedule (step_kernels.h: kSchedDynamic): ONE launch of persistent workgroups taking (env, visit) items from a
+    // device queue — wherever thirds of a call balance the chip better than whole calls (ceil(3 B / G) < 3 ceil(B / G)), and
+    // always beside the asynchronous scenario fill, whose generator workgroups must find room WITHOUT sending a step workgroup
+    // to a second round: the grid then leaves `sched_reserve` of the resident slots free (CROWDNAV_AMD_DYN_RESERVE).  Callers that
+    // want the in-kernel summary / record blocks get the static 3-of-4 schedule below.
+    const int reserve = e->async_fill ? e->sched_reserve : 0;
+    const int G = P.B < slots - reserve ? P.B : slots - reserve;
+    // visits per env and call: ~56 steps each (measured at 4096 envs on the 12 m circle: 999-step calls 129 / 137 / 141 /
+    // 143 / 143 / 136 / 110 M env-steps/s at 3 / 6 / 9 / 18 / 27 / 54 / 108 visits, 500-step calls 125 / 137 / 136 / 126 M
+    // at 3 / 9 / 18 / 36 — shorter visits balance better until the per-visit prologue and the release / acquire of the
+    // env's state show), at least three
+    int visits = e->dyn_visits > 0 ? e->dyn_visits : (n_steps + 28) / 56;
+    if (visits < 3) visits = 3;
+    if (visits > n_steps) visits = n_steps;
+    Pk.dyn_visits = visits;
+    // work-conserving: worth it whenever the envs do not all fit at once (a plain launch then runs ceil(B / G) rounds)
+    const bool helps = e->sched_force || e->async_fill || P.B > G;
+    if (e->sched_dynamic && G > 0 && n_steps >= e->sched_min && action == nullptr && helps && !e->io_host.summary &&
+        !e->io_host.blocks) {
+        (void)hipMemsetAsync(e->S.dyn_queue, 0, sizeof(int) * ((size_t)P.B + 1), e->stream);
+        Pk.sched = cn::kSchedDynamic;
+        e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
+        e->launch_counts[CN_COUNT_SCHEDULED_KERNELS] += 1;
+        launch(Pk, G, n_steps);
+        return;
+    }
+    const int rounds_plain = (P.B + slots - 1) / slots, rounds_sched = (P.B / 4 * 3 + slots - 1) / slots;
+    const bool sched = P.B % 4 == 0 && n_steps >= (e->sched_min > 48 ? e->sched_min : 48) && action == nullptr &&
+                       (e->sched_force || 4 * rounds_sched < 3 * rounds_plain);
+    const int q = sched ? n_steps / 3 : 0, rest = n_steps - 3 * q;
+    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += (rest > 0 ? 1 : 0) + (q > 0 ? 4 : 0);
+    e->launch_counts[CN_COUNT_SCHEDULED_KERNELS] += q > 0 ? 4 : 0;
+    if (rest > 0) launch(Pk, grid_envs(e), rest);
+    for (int k = 0; k < 4 && q > 0; ++k) {
+        Pk.sched = k;
+        launch(Pk, P.B / 4 * 3, q);
+    }
+}
+
+// n_steps >= 1 transitions of every env, by the kernel rollout_route names
+static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
     const int route = rollout_route(e, action);
-    if (route == CN_ROUTE_FUSED_SPLIT) {
-        if (e->split_assist & cn::kAssistHead)
-            hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true, cn::kAssistHead>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem,
-                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-        else
-            hipLaunchKernelGGL((cn::rollout_fused_kernel<true, true>), dim3(grid_envs(e)), dim3(2 * cn::kWave), e->smem, e->stream, e->P,
-                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-    } else if (route == CN_ROUTE_FUSED) {
-        if (headline_geometry(P))
-            hipLaunchKernelGGL((cn::rollout_fused_kernel<true>), dim3(grid_envs(e)), dim3(64), e->smem, e->stream, e->P,
-                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-        else
-            hipLaunchKernelGGL((cn::rollout_fused_kernel<false>), dim3(grid_envs(e)), dim3(64), e->smem, e->stream, e->P,
-                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-    } else if (route == CN_ROUTE_SHARD) {
-        const size_t smem20 = cn::smem_bytes_compact(P.nA, P.pairs, P.A, P.E);
-        // Three resident waves per SIMD (step_kernels.h: kGeom20Waves): 3072 one-wave workgroups fill the chip, so B = 4096 envs would run as
-        // a full round plus a third of one.  A call of 3 q + r steps becomes one launch of r steps over all envs (if r > 0) and
-        // FOUR launches of q steps over 3 B / 4 workgroups each, sub-launch k leaving out env 3 - k of every group of four
-        // (step_kernels.h: Params::sched): every env makes its steps in order, every launch is one round.
-        // Worth it when it saves rounds: with S = 12 workgroups x CUs resident, a plain launch takes ceil(B / S) rounds of
-        // n steps, the schedule 4 ceil(0.75 B / S) rounds of n / 3 (B = 4096 on 256 CUs: 2 vs 1.33; B = 3072: 1 vs 1.33 - plain).
-        // CROWDNAV_AMD_SCHED_MIN_STEPS / CROWDNAV_AMD_SCHED_FORCE (read by cn_create): shortest call that is split; split
-        // whatever the round count (the parity tests run the schedule on a handful of envs).
-        cn::Params Pk = e->P;
-        Pk.sched = -1;
-        const int slots = e->sched_slots;
-        // Dynamic schedule (step_kernels.h: kSchedDynamic): ONE launch of persistent workgroups taking (env, visit) items from a
-        // device queue — wherever thirds of a call balance the chip better than whole calls (ceil(3 B / G) < 3 ceil(B / G)), and
-        // always beside the asynchronous scenario fill, whose generator workgroups must find room WITHOUT sending a step workgroup
-        // to a second round: the grid then leaves `sched_reserve` of the resident slots free (CROWDNAV_AMD_DYN_RESERVE).  Callers that
-        // want the in-kernel summary / record blocks get the static 3-of-4 schedule below.
-        {
-            const bool use_dynamic = e->sched_dynamic;
-            const int reserve = e->async_fill ? e->sched_reserve : 0;
-            const int G = P.B < slots - reserve ? P.B : slots - reserve;
-            // visits per env and call: ~56 steps each (measured at 4096 envs on the 12 m circle: 999-step calls 129 / 137 / 141 /
-            // 143 / 143 / 136 / 110 M env-steps/s at 3 / 6 / 9 / 18 / 27 / 54 / 108 visits, 500-step calls 125 / 137 / 136 / 126 M
-            // at 3 / 9 / 18 / 36 — shorter visits balance better until the per-visit prologue and the release / acquire of the
-            // env's state show), at least three
-            int visits = e->dyn_visits > 0 ? e->dyn_visits : (n_steps + 28) / 56;
-            if (visits < 3) visits = 3;
-            if (visits > n_steps) visits = n_steps;
-            Pk.dyn_visits = visits;
-            // work-conserving: worth it whenever the envs do not all fit at once (a plain launch then runs ceil(B / G) rounds)
-            const bool helps = e->sched_force || e->async_fill || P.B > G;
-            if (use_dynamic && G > 0 && n_steps >= e->sched_min && action == nullptr && helps && !e->io_host.summary &&
-                !e->io_host.blocks) {
-                (void)hipMemsetAsync(e->S.dyn_queue, 0, sizeof(int) * ((size_t)P.B + 1), e->stream);
-                Pk.sched = cn::kSchedDynamic;
-                e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
-                e->launch_counts[CN_COUNT_SCHEDULED_KERNELS] += 1;
-                hipLaunchKernelGGL((cn::rollout_kernel<10, false, true, true>), dim3(G), dim3(64), smem20, e->stream, Pk,
-                                   (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, action);
-                return;
-            }
-        }
-        const int rounds_plain = (P.B + slots - 1) / slots, rounds_sched = (P.B / 4 * 3 + slots - 1) / slots;
-        const bool sched = P.B % 4 == 0 && n_steps >= (e->sched_min > 48 ? e->sched_min : 48) && action == nullptr &&
-                           (e->sched_force || 4 * rounds_sched < 3 * rounds_plain);
-        const int q = sched ? n_steps / 3 : 0, rest = n_steps - 3 * q;
-        e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += (rest > 0 ? 1 : 0) + (q > 0 ? 4 : 0);
-        e->launch_counts[CN_COUNT_SCHEDULED_KERNELS] += q > 0 ? 4 : 0;
-        if (rest > 0)
-            hipLaunchKernelGGL((cn::rollout_kernel<10, false, true, true>), dim3(grid_envs(e)), dim3(64), smem20, e->stream, Pk,
-                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, rest, action);
-        for (int k = 0; k < 4 && q > 0; ++k) {
-            Pk.sched = k;
-            hipLaunchKernelGGL((cn::rollout_kernel<10, false, true, true>), dim3(P.B / 4 * 3), dim3(64), smem20, e->stream, Pk,
-                               (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, q, action);
-        }
-    } else {
+    if (route == CN_ROUTE_SHARD) return launch_shard(e, R, n_steps, action);  // (counts its own launches)
+    if (route == CN_ROUTE_GENERIC)
         pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
             hipLaunchKernelGGL((cn::rollout_kernel<decltype(maxl)::value, decltype(uni)::value, false, decltype(kd)::value>),
                                dim3(grid_envs(e)), dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
                                (const int*)e->S.ring_filled_in, R, n_steps, action);
         });
-    }
-    if (e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] == kernels_before) e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
+    else
+        pick_fused(e, route, [&](auto kernel, int threads) {
+            hipLaunchKernelGGL(kernel, dim3(grid_envs(e)), dim3(threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
+                               (const int*)e->S.ring_filled_in, R, n_steps, action);
+        });
+    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
 }
 
-int cn_rollout(cn_engine* e, const cn_rollout_io* io, int n_steps) {
+// What cn_rollout, cn_rollout_trace and cn_rollout_step do before they launch: bind, check the io block and the call's length,
+// upload the io block, top up the scenario ring for n_steps transitions.  CN_OK: *R is what the transition kernel takes.
+// kNothingToLaunch: n_steps == 0.  kWrongRobotPolicy: the engine's robot policy is not the one the entry point is for;
+// kNoAction: an external robot's entry point was given no action — no error text yet for these two, the entry point words it.
+enum { kNothingToLaunch = 1, kWrongRobotPolicy = 2, kNoAction = 3 };
+static int rollout_prepare(cn_engine* e, const cn_rollout_io* io, int n_steps, bool need_orca_robot, cn::RolloutView* R,
+                           const double* action = nullptr) {
     int rc = bind(e);
     if (rc) return rc;
     if ((rc = check_io(e, io))) return rc;
     if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
-    if (n_steps == 0) return CN_OK;
-    if (!e->P.robot_orca)
+    if (n_steps == 0) return kNothingToLaunch;
+    if ((e->P.robot_orca != 0) != need_orca_robot) return kWrongRobotPolicy;
+    if (!need_orca_robot && !action) return kNoAction;
+    if ((rc = upload_io(e, io))) return rc;
+    *R = cn::RolloutView{e->io_dev, e->discount, e->discount_len};
+    return fill_ring_if_needed(e, *R, n_steps);
+}
+
+int cn_rollout(cn_engine* e, const cn_rollout_io* io, int n_steps) {
+    cn::RolloutView R;
+    const int rc = rollout_prepare(e, io, n_steps, true, &R);
+    if (rc == kNothingToLaunch) return CN_OK;
+    if (rc == kWrongRobotPolicy)
         return fail(CN_ERR_UNSUPPORTED, "cn_rollout needs an on-device robot policy (robot_policy == CN_ROBOT_ORCA); with "
                                         "CN_ROBOT_EXTERNAL use cn_rollout_step(action)");
-    if ((rc = upload_io(e, io))) return rc;
-    cn::RolloutView R{e->io_dev, e->discount, e->discount_len};
-    if ((rc = fill_ring_if_needed(e, R, n_steps))) return rc;  // then the fused transitions
-    launch_rollout(e, R, n_steps, nullptr);
+    if (rc) return rc;
+    launch_rollout(e, R, n_steps, nullptr);  // the fused transitions
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -727,14 +754,10 @@ int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const c
     if (!e->P.robot_orca)
         return fail(CN_ERR_UNSUPPORTED, "cn_rollout_trace needs an on-device robot policy (robot_policy == CN_ROBOT_ORCA); with "
                                         "CN_ROBOT_EXTERNAL use cn_rollout_step(action)");
-    int rc = bind(e);
+    cn::RolloutView R;
+    const int rc = rollout_prepare(e, io, n_steps, true, &R);
+    if (rc == kNothingToLaunch) return CN_OK;
     if (rc) return rc;
-    if ((rc = check_io(e, io))) return rc;
-    if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
-    if (n_steps == 0) return CN_OK;
-    if ((rc = upload_io(e, io))) return rc;
-    cn::RolloutView R{e->io_dev, e->discount, e->discount_len};
-    if ((rc = fill_ring_if_needed(e, R, n_steps))) return rc;
     const cn_trace_out T = *out;
     pick_maxl(e, [&](auto maxl) {
         pick_bool(e->P.kd, [&](auto kd) {
@@ -749,14 +772,11 @@ int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const c
 }
 
 int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action) {
-    int rc = bind(e);
+    cn::RolloutView R;
+    const int rc = rollout_prepare(e, io, 1, false, &R, action);
+    if (rc == kWrongRobotPolicy) return fail(CN_ERR_INVALID, "cn_rollout_step is for CN_ROBOT_EXTERNAL engines (use cn_rollout)");
+    if (rc == kNoAction) return fail(CN_ERR_INVALID, "cn_rollout_step: action is NULL");
     if (rc) return rc;
-    if ((rc = check_io(e, io))) return rc;
-    if (e->P.robot_orca) return fail(CN_ERR_INVALID, "cn_rollout_step is for CN_ROBOT_EXTERNAL engines (use cn_rollout)");
-    if (!action) return fail(CN_ERR_INVALID, "cn_rollout_step: action is NULL");
-    if ((rc = upload_io(e, io))) return rc;
-    cn::RolloutView R{e->io_dev, e->discount, e->discount_len};
-    if ((rc = fill_ring_if_needed(e, R, 1))) return rc;
     launch_rollout(e, R, 1, action);
     CN_HIP(hipGetLastError());
     return CN_OK;

@@ -46,45 +46,45 @@ namespace {
 }  // namespace
 
 struct cn_engine {
-    cn_config cfg;
-    cn::Params P;
-    cn::ScenarioCfg C;
-    cn::StateView S;
-    hipStream_t stream;
-    cn_rollout_io io_host;   // last cn_rollout_io uploaded to io_dev
-    cn_rollout_io* io_dev;   // device copy the rollout kernels read through
-    cn::StateView* S_dev;    // device copy of S (the fused rollout kernel re-reads state pointers instead of holding them)
+    cn_config cfg{};
+    cn::Params P{};
+    cn::ScenarioCfg C{};
+    cn::StateView S{};
+    hipStream_t stream = nullptr;
+    cn_rollout_io io_host{};           // last cn_rollout_io uploaded to io_dev
+    cn_rollout_io* io_dev = nullptr;   // device copy the rollout kernels read through
+    cn::StateView* S_dev = nullptr;    // device copy of S (the fused rollout kernel re-reads state pointers instead of holding them)
     // CN_FLAG_ASYNC_SCENARIO_FILL: fill kernels go round-robin over side streams (a launch stuck on a hard scenario must
     // not hold back the next one) and start once the previous transition kernel has written its episode counters
     static constexpr int kFillStreams = 8;
-    bool async_fill;
-    hipStream_t fill_streams[kFillStreams];
+    bool async_fill = false;
+    hipStream_t fill_streams[kFillStreams] = {};
     int* fill_list = nullptr;    // [kFillStreams][2 + 2 B D] job lists of ring_fill_scan_kernel / ring_fill_jobs_kernel, one per side stream
-    int fill_queue_wgs = 0;      // persistent generator workgroups of an asynchronous fill launch (0: one workgroup per slot)
-    hipEvent_t rollout_done;
-    int next_fill_stream;
-    bool io_valid;
+    int fill_queue_wgs = 1;      // persistent generator workgroups of an asynchronous fill launch (CROWDNAV_AMD_FILL_QUEUE_WGS, at least 1)
+    hipEvent_t rollout_done = nullptr;
+    int next_fill_stream = 0;
+    bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one
     uint32_t begin_seed_base = 0, begin_seed_mod = 0;  // (the scenario cache is sized and keyed by them)
-    int steps_since_fill;    // transitions launched since the scenario ring was last topped up; < 0 = never filled
-    struct cn_sarl* sarl;    // SARL decision state (sarl_abi.hip), NULL until cn_sarl_configure
-    bool orca_fresh;         // cn_sarl_sample_step: the humans' ORCA velocities of the CURRENT state are in sarl->orca_vel (left by the
-                             // previous call's transition kernel); cleared by every other entry point (bind)
-    double* discount;
-    int discount_len;
-    uint32_t* probe_key;
-    double* summary_scratch;  // records_summary_kernel: per-workgroup partials + ticket counter
-    int maxl;          // half-planes held in VGPRs by the solve phase: 5 or 10
-    bool gen_wave;     // wave-per-scenario generators (64 rejection attempts at a time): long chains, H > 8
-    size_t smem;       // dynamic LDS bytes per workgroup
-    int sched_min, sched_slots, sched_reserve, dyn_visits;  // the 20-human shard kernel's schedules (launch_rollout): shortest call split, resident workgroups, slots left free beside the asynchronous fill
-    bool sched_force, sched_dynamic;
-    bool use_fused;   // CROWDNAV_AMD_FUSED (rollout_route)
-    int fused_split;  // CROWDNAV_AMD_FUSED_SPLIT: 0 never, 1 launches of one round (default), 2 always
-    int split_assist;  // CROWDNAV_AMD_SPLIT_ASSIST: rollout_fused.h's ASSIST (0, or kAssistHead = fallback head on the env wave; default)
-    int split_slots;              // workgroups of the two-wave fused kernel the device holds at once (occupancy query, cn_create)
-    bool scenario_cache;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
-    uint64_t launch_counts[CN_LAUNCH_COUNTERS];  // cn_launch_counts: what the host enqueued since cn_create
+    int steps_since_fill = -1;     // transitions launched since the scenario ring was last topped up; < 0 = never filled
+    struct cn_sarl* sarl = nullptr;  // SARL decision state (sarl_abi.hip), NULL until cn_sarl_configure
+    bool orca_fresh = false;  // cn_sarl_sample_step: the humans' ORCA velocities of the CURRENT state are in sarl->orca_vel (left by the
+                              // previous call's transition kernel); cleared by every other entry point (bind)
+    double* discount = nullptr;
+    int discount_len = 0;
+    uint32_t* probe_key = nullptr;
+    double* summary_scratch = nullptr;  // records_summary_kernel: per-workgroup partials + ticket counter
+    int maxl = 10;           // half-planes held in VGPRs by the solve phase: 5 or 10
+    bool gen_wave = false;   // wave-per-scenario generators (64 rejection attempts at a time): long chains, H > 8
+    size_t smem = 0;         // dynamic LDS bytes per workgroup
+    int sched_min = 0, sched_slots = 0, sched_reserve = 0, dyn_visits = 0;  // the 20-human shard kernel's schedules (launch_shard): shortest call split, resident workgroups, slots left free beside the asynchronous fill
+    bool sched_force = false, sched_dynamic = true;
+    bool use_fused = true;  // CROWDNAV_AMD_FUSED (rollout_route)
+    int fused_split = 1;    // CROWDNAV_AMD_FUSED_SPLIT: 0 never, 1 launches of one round (default), 2 always
+    int split_assist = 0;   // CROWDNAV_AMD_SPLIT_ASSIST: rollout_fused.h's ASSIST (0, or kAssistHead = fallback head on the env wave; default)
+    int split_slots = 0;    // workgroups of the two-wave fused kernel the device holds at once (occupancy query, read_knobs)
+    bool scenario_cache = true;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
+    uint64_t launch_counts[CN_LAUNCH_COUNTERS] = {};  // cn_launch_counts: what the host enqueued since cn_create
     // Device memory comes from a few large slabs, not one hipMalloc per buffer: an engine has ~60 device buffers, most of them a
     // few KiB; one 32 MiB slab (plus one per buffer larger than that) is 2-4 mappings to create and - each hipFree being a device
     // synchronisation - 2-4 to tear down, and cn_sarl_configure can roll a failed configuration back to a mark.

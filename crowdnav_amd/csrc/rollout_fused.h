@@ -376,20 +376,6 @@ __device__ __forceinline__ StepOutcome reduce_env(const Params& P, const Smem& s
     return StepOutcome{reward, dmin, info, done};
 }
 
-// explorer.py:50-72: the finished episode's record (robot lane)
-__device__ __forceinline__ void write_record(const cn_rollout_io& io, int env, int ep_count, int info, int cur_steps,
-                                             double cur_return, double time, int cur_danger, double cur_dsum) {
-    if (io.record_capacity > 0) {
-        const size_t k = (size_t)env * io.record_capacity + (ep_count % io.record_capacity);
-        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
-        if (io.ep_steps) io.ep_steps[k] = cur_steps;
-        if (io.ep_return) io.ep_return[k] = cur_return;
-        if (io.ep_time) io.ep_time[k] = time;
-        if (io.ep_danger) io.ep_danger[k] = cur_danger;
-        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
-    }
-}
-
 // CN_WAVE_TRACE (profiling builds): every wave leaves four 100 MHz timestamps (kernel entry, step loop entry / exit, kernel
 // exit) and how many of its steps took the 3-D fallback / ended an episode: scripts/probes/wave_trace.py
 #ifdef CN_WAVE_TRACE

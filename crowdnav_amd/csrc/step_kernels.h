@@ -47,9 +47,9 @@ struct Params {
     int robot_visible, robot_orca;
     int robot_unicycle;  // external robot actions are ActionRot(v, r) (agent.py:115-135)
     int async_fill;      // CN_FLAG_ASYNC_SCENARIO_FILL: ring slots are published one by one (StateView::ring_ready)
-    int sched;           // the 20-human shard's kernel: sub-launch 0..3 of the 3-of-4 env schedule (launch_rollout), -1 = all envs,
+    int sched;           // the 20-human shard's kernel: sub-launch 0..3 of the 3-of-4 env schedule (launch_shard), -1 = all envs,
                          // kSchedDynamic = persistent workgroups taking (env, visit) items from a device queue
-    int dyn_visits;      // ... visits per env and call under the dynamic schedule (launch_rollout: ~56 steps per visit)
+    int dyn_visits;      // ... visits per env and call under the dynamic schedule (launch_shard: ~56 steps per visit)
     int kd;              // A > 10: some rvo2 simulator of an env holds more than 10 agents and splits its kd-tree (kd_order.h)
     KdLayout kdl;        // ... and where its bookkeeping lives in LDS (offsets from Smem::kd_off)
     double dt, time_limit, success_reward, collision_penalty, discomfort_dist, discomfort_factor;
@@ -1211,6 +1211,14 @@ __device__ __forceinline__ uint64_t generate_scenario_lane(const ScenarioCfg& C,
     return n;
 }
 
+// New episode of env b: new Human objects, new ORCA policies, new rvo2 simulators (the robot's persists) — their kd-tree orders
+// start as the identity.  Lanes first, first + stride, ... of kd_valid[1..A): (1, 1) from a kernel with one lane per env,
+// (1 + threadIdx.x, blockDim.x) from one with a workgroup per env.
+__device__ __forceinline__ void clear_human_sims(const Params& P, const StateView& S, int b, int first, int stride) {
+    if (P.kd)
+        for (int a = first; a < P.A; a += stride) S.kd_valid[(size_t)b * P.A + a] = 0;
+}
+
 // np.random.seed(seed) + scenario of one env per lane (lane = env)
 __global__ __launch_bounds__(kWave) void reset_kernel(Params P, ScenarioCfg C, StateView S, const uint32_t* seeds,
                                                      const uint8_t* mask, uint64_t* draws) {
@@ -1222,8 +1230,7 @@ __global__ __launch_bounds__(kWave) void reset_kernel(Params P, ScenarioCfg C, S
     S.gtime[b] = 0.0;
     S.theta[b] = 1.5707963267948966;  // robot.set(..., np.pi / 2)
     if (draws) draws[b] = n;
-    if (P.kd)  // new Human objects, new ORCA policies, new rvo2 simulators (the robot's persists)
-        for (int a = 1; a < P.A; ++a) S.kd_valid[(size_t)b * P.A + a] = 0;
+    clear_human_sims(P, S, b, 1, 1);
 }
 
 __global__ void mt_probe_kernel(uint32_t* key, uint32_t seed, int n, double* out) {
@@ -1252,13 +1259,36 @@ __device__ __forceinline__ uint32_t episode_seed(const cn_rollout_io& io, int64_
     return io.seed_base + (uint32_t)((uint64_t)c % io.seed_mod);
 }
 
-// (re)start bookkeeping: env b begins its episode ordinal 0
-__global__ __launch_bounds__(kWave) void rollout_begin_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= P.B) return;
-    const cn_rollout_io io = *R.io;
-    const int64_t c0 = episode_id(io, b, 0);
-    const bool on = io.episode_limit < 0 || c0 < io.episode_limit;
+// ---- the rules of the scenario ring, each stated once ------------------------------------------------------------
+// the episode limit of a rollout (io.episode_limit < 0: none): episode c is not run
+__device__ __forceinline__ bool past_episode_limit(const cn_rollout_io& io, int64_t c) {
+    return io.episode_limit >= 0 && c >= io.episode_limit;
+}
+// first ordinal the rollout may still ask for (an env waiting for a scenario has not consumed ep_count yet).  A fill that
+// runs BESIDE a transition kernel takes both arguments from one load of StateView::ep_word — (state, episodes finished) of the
+// env as ONE word, stored once by the transition kernel when it ends: two separate loads of io->active / io->ep_count could
+// pair an old state with a new count and claim a slot whose scenario has not been consumed yet
+__device__ __forceinline__ int ring_next_ordinal(int ep_count, int state) { return ep_count + (state == kWaitingScenario ? 0 : 1); }
+// the one ordinal of [next, next + D) that lives in ring slot `slot` (ordinal o lives in slot o % D)
+__device__ __forceinline__ int ring_slot_ordinal(int next, int slot, int D) { return next + ((slot - next % D) + D) % D; }
+// Asynchronous fill: claim slot idx = (env, ordinal % D) for `ordinal`.  False: resident already, or another fill launch is
+// generating (or has generated) exactly this scenario.  Only slots whose scenario the env consumed before the transition
+// kernel running beside the fill was launched are ever overwritten.
+__device__ __forceinline__ bool ring_claim_slot(const StateView& S, int idx, int ordinal) {
+    const int want = ordinal + 1;
+    const int have = S.ring_claim[idx];
+    return have < want && atomicCAS(&S.ring_claim[idx], have, want) == have;
+}
+// ... and publish it, by the whole workgroup that wrote the scenario: a device-scope release store of ordinal + 1 to
+// ring_ready (scenario_ready is the acquire side)
+__device__ __forceinline__ void ring_publish_slot(const StateView& S, int idx, int ordinal) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // (a cached copy is written by A lanes, not by lane 0 alone)
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(&S.ring_ready[idx], ordinal + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (re)start bookkeeping of env b, which begins its episode ordinal 0 with nothing in its ring (`on`: it runs at all)
+__device__ __forceinline__ void begin_env(const StateView& S, const cn_rollout_io& io, int b, bool on) {
     io.active[b] = on ? kRunning : kRetired;
     S.ep_word[b] = on ? kRunning : kRetired;
     io.ep_count[b] = 0;
@@ -1268,8 +1298,16 @@ __global__ __launch_bounds__(kWave) void rollout_begin_kernel(Params P, Scenario
     if (io.cur_danger_dmin_sum) io.cur_danger_dmin_sum[b] = 0.0;
     S.ring_filled_in[b] = 0;
     S.ring_filled_out[b] = 0;
-    if (P.kd)
-        for (int a = 1; a < P.A; ++a) S.kd_valid[(size_t)b * P.A + a] = 0;
+}
+
+__global__ __launch_bounds__(kWave) void rollout_begin_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const cn_rollout_io io = *R.io;
+    const int64_t c0 = episode_id(io, b, 0);
+    const bool on = !past_episode_limit(io, c0);
+    begin_env(S, io, b, on);
+    clear_human_sims(P, S, b, 1, 1);
     if (!on) return;
     generate_scenario_lane(C, episode_seed(io, c0), (size_t)b * P.A, S.pos, S.vel, S.goal, S.rv, S.mt_key + b,
                                    P.B, false, nullptr);
@@ -1290,14 +1328,13 @@ __global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg 
     const int b = idx / D, slot = idx - b * D;
     const cn_rollout_io* io = R.io;
     const int state = io->active[b];
-    // first ordinal the rollout may still ask for (an env waiting for a scenario has not consumed ep_count yet)
-    const int next = io->ep_count[b] + (state == kWaitingScenario ? 0 : 1);
+    const int next = ring_next_ordinal(io->ep_count[b], state);
     if (slot == 0) S.ring_filled_out[b] = next + D;
     if (state == kRetired) return;
-    const int ordinal = next + ((slot - next % D) + D) % D;
+    const int ordinal = ring_slot_ordinal(next, slot, D);
     if (ordinal < S.ring_filled_in[b]) return;  // still resident from an earlier fill
     const int64_t c = episode_id(*io, b, ordinal);
-    if (io->episode_limit >= 0 && c >= io->episode_limit) return;
+    if (past_episode_limit(*io, c)) return;
     const uint32_t seed = episode_seed(*io, c);
     const size_t base = ((size_t)b * D + slot) * P.A;
     Mt19937Head head;
@@ -1305,7 +1342,7 @@ __global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg 
     if (head.dead()) S.redo_list[atomicAdd(S.redo_count, 1)] = make_int2(idx, (int)seed);
 }
 
-// The scenarios ring_fill_kernel<false> queued: a fixed grid of kRedoLanes lanes strides over the list, each lane with
+// The scenarios ring_fill_kernel queued: a fixed grid of kRedoLanes lanes strides over the list, each lane with
 // its own column of the word-major generator pool.
 __global__ __launch_bounds__(kWave) void ring_redo_kernel(Params P, ScenarioCfg C, StateView S) {
     const int lane = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1331,8 +1368,7 @@ __global__ __launch_bounds__(kWave) void reset_wave_kernel(Params P, ScenarioCfg
         S.theta[b] = 1.5707963267948966;
         if (draws) draws[b] = n;
     }
-    if (P.kd)
-        for (int a = 1 + threadIdx.x; a < P.A; a += blockDim.x) S.kd_valid[(size_t)b * P.A + a] = 0;
+    clear_human_sims(P, S, b, 1 + threadIdx.x, blockDim.x);
 }
 
 __global__ __launch_bounds__(kWave) void rollout_begin_wave_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
@@ -1340,22 +1376,13 @@ __global__ __launch_bounds__(kWave) void rollout_begin_wave_kernel(Params P, Sce
     const int b = blockIdx.x;
     const cn_rollout_io io = *R.io;
     const int64_t c0 = episode_id(io, b, 0);
-    const bool on = io.episode_limit < 0 || c0 < io.episode_limit;
+    const bool on = !past_episode_limit(io, c0);
     if (threadIdx.x == 0) {
-        io.active[b] = on ? kRunning : kRetired;
-        S.ep_word[b] = on ? kRunning : kRetired;
-        io.ep_count[b] = 0;
-        io.cur_steps[b] = 0;
-        io.cur_return[b] = 0.0;
-        if (io.cur_danger) io.cur_danger[b] = 0;
-        if (io.cur_danger_dmin_sum) io.cur_danger_dmin_sum[b] = 0.0;
-        S.ring_filled_in[b] = 0;
-        S.ring_filled_out[b] = 0;
+        begin_env(S, io, b, on);
         S.gtime[b] = 0.0;
         S.mt_pos[b] = -1;
     }
-    if (P.kd)
-        for (int a = 1 + threadIdx.x; a < P.A; a += blockDim.x) S.kd_valid[(size_t)b * P.A + a] = 0;
+    clear_human_sims(P, S, b, 1 + threadIdx.x, blockDim.x);
     if (P.async_fill)
         for (int t = threadIdx.x; t < P.ring_depth; t += blockDim.x) {  // nothing resident, nothing claimed
             S.ring_ready[(size_t)b * P.ring_depth + t] = 0;
@@ -1408,59 +1435,27 @@ __global__ __launch_bounds__(kWave) void ring_fill_wave_kernel(Params P, Scenari
     const int b = idx / D, slot = idx - b * D;
     const cn_rollout_io io = *R.io;
     const int state = io.active[b];
-    const int next = io.ep_count[b] + (state == kWaitingScenario ? 0 : 1);
+    const int next = ring_next_ordinal(io.ep_count[b], state);
     if (slot == 0 && threadIdx.x == 0) S.ring_filled_out[b] = next + D;
     if (state == kRetired) return;
-    const int ordinal = next + ((slot - next % D) + D) % D;
+    const int ordinal = ring_slot_ordinal(next, slot, D);
     if (ordinal < S.ring_filled_in[b]) return;
     const int64_t c = episode_id(io, b, ordinal);
-    if (io.episode_limit >= 0 && c >= io.episode_limit) return;
+    if (past_episode_limit(io, c)) return;
     cached_scenario_wave(P, C, S, scratch, io, c, ((size_t)b * D + slot) * P.A);
 }
 
-// Asynchronous flavour (CN_FLAG_ASYNC_SCENARIO_FILL): runs on a side stream NEXT to the transition kernel.  A slot is
-// claimed for the ordinal the env will need there (an earlier fill launch may still be working on it: atomicCAS on
-// ring_claim), generated, and published with a device-scope release store of ordinal + 1 to ring_ready.  Only slots whose
-// scenario the env consumed before the transition kernel running beside the fill was launched are ever overwritten.
-__global__ __launch_bounds__(kWave) void ring_fill_wave_async_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
-    __shared__ WaveScratchFill scratch;
-    __shared__ int go;
-    const int idx = blockIdx.x;  // workgroup = (env, slot)
-    const int D = P.ring_depth;
-    const int b = idx / D, slot = idx - b * D;
-    const cn_rollout_io* io = R.io;
-    // (state, episodes finished) of the env as ONE word: the transition kernel running beside this launch stores it once
-    // when it ends — two separate loads of io->active / io->ep_count could pair an old state with a new count and claim a
-    // slot whose scenario has not been consumed yet
-    const int word = __hip_atomic_load(&S.ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int state = word & 3;
-    if (state == kRetired) return;
-    const int next = (word >> 2) + (state == kWaitingScenario ? 0 : 1);
-    const int ordinal = next + ((slot - next % D) + D) % D;
-    const int64_t c = episode_id(*io, b, ordinal);
-    if (io->episode_limit >= 0 && c >= io->episode_limit) return;
-    if (threadIdx.x == 0) {
-        const int want = ordinal + 1;
-        const int have = S.ring_claim[idx];
-        go = (have < want && atomicCAS(&S.ring_claim[idx], have, want) == have) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!go) return;  // resident already, or another launch is generating exactly this scenario
-    cached_scenario_wave(P, C, S, scratch, *io, c, ((size_t)b * D + slot) * P.A);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // (a cached copy is written by A lanes, not by lane 0 alone)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(&S.ring_ready[idx], ordinal + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The same fill as a WORK LIST (round 6; the default) instead of one workgroup per (env, slot) — 4096 x 144 = 590 k workgroups of
-// which a fifth have something to do cost a 999-step call 4.5 ms of dispatch beside its transition kernel.  Two launches on the
-// fill stream: ring_fill_scan_kernel examines the (env, urgency) items — urgency u = how many episodes ahead of the env's next
-// one the scenario lies — one per lane, claims the slots exactly as above and appends the claimed (env, ordinal) pairs to a job
-// list, URGENCY-MAJOR (every env's nearest missing scenario before anybody's far one: a hard scenario — tens of milliseconds
-// of one wave — far ahead in the ring has the whole ring's worth of steps to finish); ring_fill_jobs_kernel is a fixed grid of
-// persistent one-wave generator workgroups that pop kFillJobBatch jobs at a time.  No workgroup ever waits for another one.
-// Measured (r06, 4096 x 20 on the 4 m circle, 999-step calls): every scenario generated afresh 91.9 -> 94.3 M env-steps/s,
-// scenario cache on 125.2 -> 139.4 M; 256 / 512 / 1024 / 2048 generator workgroups: 74.7 / 86.3 / 94.3 / 89.1 M.
+// Asynchronous flavour (CN_FLAG_ASYNC_SCENARIO_FILL): runs on a side stream NEXT to the transition kernel, as a WORK LIST.  Two
+// launches on the fill stream: ring_fill_scan_kernel examines the (env, urgency) items — urgency u = how many episodes ahead of
+// the env's next one the scenario lies — one per lane, claims the slot for the ordinal the env will need there (an earlier fill
+// launch may still be working on it: ring_claim_slot) and appends the claimed (env, ordinal) pairs to a job list, URGENCY-MAJOR
+// (every env's nearest missing scenario before anybody's far one: a hard scenario — tens of milliseconds of one wave — far
+// ahead in the ring has the whole ring's worth of steps to finish); ring_fill_jobs_kernel is a fixed grid of persistent one-wave
+// generator workgroups (CROWDNAV_AMD_FILL_QUEUE_WGS) that pop kFillJobBatch jobs at a time, generate them and publish each
+// (ring_publish_slot).  No workgroup ever waits for another one.
+// (Rounds 2-5 ran one workgroup per (env, slot) instead: 4096 x 144 = 590 k workgroups of which a fifth have something to do cost
+// a 999-step call 4.5 ms of dispatch beside its transition kernel.  The figures of both, and of 256 .. 2048 generator
+// workgroups, are in profiles/HISTORY.md.)
 //   list: int [2 + 2 * B * D]: [0] jobs appended, [1] jobs popped, then the (env, ordinal) pairs; [0] and [1] are zeroed on the
 //   fill stream in front of the scan (one list per side stream: fill launches overlap)
 __global__ __launch_bounds__(256) void ring_fill_scan_kernel(Params P, StateView S, RolloutView R, int* list) {
@@ -1475,13 +1470,8 @@ __global__ __launch_bounds__(256) void ring_fill_scan_kernel(Params P, StateView
         const int word = __hip_atomic_load(&S.ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (state, episodes finished)
         const int state = word & 3;
         if (state != kRetired) {
-            ordinal = (word >> 2) + (state == kWaitingScenario ? 0 : 1) + u;
-            const int64_t c = episode_id(*io, b, ordinal);
-            if (!(io->episode_limit >= 0 && c >= io->episode_limit)) {
-                const int idx = b * D + ordinal % D, want = ordinal + 1;
-                const int have = S.ring_claim[idx];
-                claimed = have < want && atomicCAS(&S.ring_claim[idx], have, want) == have;
-            }
+            ordinal = ring_next_ordinal(word >> 2, state) + u;
+            if (!past_episode_limit(*io, episode_id(*io, b, ordinal))) claimed = ring_claim_slot(S, b * D + ordinal % D, ordinal);
         }
     }
     // one atomic per wave: the wave's claimed items go to consecutive list entries in lane (= env) order
@@ -1520,9 +1510,7 @@ __global__ __launch_bounds__(kWave) void ring_fill_jobs_kernel(Params P, Scenari
             const int b = __shfl(jb, src), ord = __shfl(jord, src);
             const int idx = b * D + ord % D;
             cached_scenario_wave(P, C, S, scratch, *io, episode_id(*io, b, ord), (size_t)idx * P.A);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // (a cached copy is written by A lanes, not by lane 0 alone)
-            __syncthreads();
-            if (lane == 0) __hip_atomic_store(&S.ring_ready[idx], ord + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            ring_publish_slot(S, idx, ord);
         }
     } while (first + kFillJobBatch < jobs);
 }
@@ -1542,25 +1530,30 @@ __device__ __forceinline__ void load_from_ring(const Params& P, const StateView&
     r.px = p.x, r.py = p.y, r.vx = 0.0, r.vy = 0.0, r.gx = g.x, r.gy = g.y, r.rad = q.x, r.vpref = q.y;
 }
 
-// Episode end on the robot lane (explorer.py:50-72): append the record, pick the next episode.  Returns the
+// explorer.py:50-72: the finished episode's record (robot lane)
+__device__ __forceinline__ void write_record(const cn_rollout_io& io, int env, int ep_count, int info, int cur_steps,
+                                             double cur_return, double time, int cur_danger, double cur_dsum) {
+    if (io.record_capacity > 0) {
+        const size_t k = (size_t)env * io.record_capacity + (ep_count % io.record_capacity);
+        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
+        if (io.ep_steps) io.ep_steps[k] = cur_steps;
+        if (io.ep_return) io.ep_return[k] = cur_return;
+        if (io.ep_time) io.ep_time[k] = time;
+        if (io.ep_danger) io.ep_danger[k] = cur_danger;
+        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
+    }
+}
+
+// Episode end on the robot lane: append the record, pick the next episode.  Returns the
 // per-env flag: 0 = stop stepping (retired, or waiting for the ring to be refilled), 2 + slot = load ring slot.
 __device__ __forceinline__ int finish_episode(const Params& P, const StateView& S, const RolloutView R, int env, int ring_depth,
                                           int ring_filled, double time_limit, int info, double gtime, int& ep_count,
                                           int cur_steps, double cur_return, int cur_danger, double cur_dsum,
                                           int& state) {
     const cn_rollout_io io = *R.io;
-    if (io.record_capacity > 0) {
-        const size_t k = (size_t)env * io.record_capacity + (ep_count % io.record_capacity);
-        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
-        if (io.ep_steps) io.ep_steps[k] = cur_steps;
-        if (io.ep_return) io.ep_return[k] = cur_return;
-        if (io.ep_time) io.ep_time[k] = (info == CN_TIMEOUT) ? time_limit : gtime;
-        if (io.ep_danger) io.ep_danger[k] = cur_danger;
-        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
-    }
+    write_record(io, env, ep_count, info, cur_steps, cur_return, (info == CN_TIMEOUT) ? time_limit : gtime, cur_danger, cur_dsum);
     ++ep_count;
-    const int64_t c = episode_id(io, env, ep_count);
-    if (io.episode_limit >= 0 && c >= io.episode_limit) {
+    if (past_episode_limit(io, episode_id(io, env, ep_count))) {
         state = kRetired;
         return 0;
     }

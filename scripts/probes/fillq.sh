@@ -13,8 +13,6 @@ run "nocache list1024       " CROWDNAV_AMD_SCENARIO_CACHE=0
 run "nocache list512        " CROWDNAV_AMD_SCENARIO_CACHE=0 CROWDNAV_AMD_FILL_QUEUE_WGS=512
 run "nocache list256        " CROWDNAV_AMD_SCENARIO_CACHE=0 CROWDNAV_AMD_FILL_QUEUE_WGS=256
 run "nocache list2048       " CROWDNAV_AMD_SCENARIO_CACHE=0 CROWDNAV_AMD_FILL_QUEUE_WGS=2048
-run "nocache per-slot grid  " CROWDNAV_AMD_SCENARIO_CACHE=0 CROWDNAV_AMD_FILL_QUEUE_WGS=0
 run "nocache list1024 d96   " CROWDNAV_AMD_SCENARIO_CACHE=0 CROWDNAV_AMD_RING_DEPTH=96
 run "cache   list1024       " CROWDNAV_AMD_SCENARIO_CACHE=1
-run "cache   per-slot grid  " CROWDNAV_AMD_SCENARIO_CACHE=1 CROWDNAV_AMD_FILL_QUEUE_WGS=0
 bash scripts/probes/async_trace.sh

@@ -156,19 +156,31 @@ def test_full_depth_ring_2500_steps(amd, oracle_mod):
     assert np.abs(_np(eng.get_state()[0]) - o.get_state()[0]).max() <= 1e-9
 
 
-@pytest.mark.parametrize('depth,launches', [(5, [10] * 42), (3, [1, 2, 7, 50, 3, 120, 17, 200, 20])])
-def test_asynchronous_fill_with_a_shallow_ring(amd, oracle_mod, depth, launches):
+@pytest.mark.parametrize('depth,launches,B,generator_wgs', [
+    pytest.param(5, [10] * 42, 48, None, id='5-launches0'),
+    pytest.param(3, [1, 2, 7, 50, 3, 120, 17, 200, 20], 48, None, id='3-launches1'),
+    pytest.param(3, [1, 2, 7, 50, 3, 120, 17], 12, 0, id='3-launches2-one_generator_workgroup')])
+def test_asynchronous_fill_with_a_shallow_ring(amd, oracle_mod, monkeypatch, depth, launches, B, generator_wgs):
     """CN_FLAG_ASYNC_SCENARIO_FILL with a ring of 5 / 3 slots: every slot is claimed, generated and published many times
-    over (ring_claim / ring_ready carry episode ordinals, step_kernels.h: ring_fill_wave_async_kernel), fill launches of
-    consecutive rollout calls overlap on the side streams.  Timing decides when an env pauses, never what it plays: its
-    finished episodes are the oracle's, in order, bit for bit; and the run makes progress (no env starves)."""
-    B, K = 48, 64
+    over (ring_claim / ring_ready carry episode ordinals; step_kernels.h: ring_fill_scan_kernel claims and lists the slots,
+    ring_fill_jobs_kernel generates and publishes them), fill launches of consecutive rollout calls overlap on the side
+    streams.  Timing decides when an env pauses, never what it plays: its finished episodes are the oracle's, in order, bit
+    for bit; and the run makes progress (no env starves).
+    The last case sets CROWDNAV_AMD_FILL_QUEUE_WGS=0, which cn_create clamps to ONE generator workgroup: it pops the whole
+    job list by itself, the popping loop at its most iterations.  How far the envs get is then a matter of timing, so the
+    progress share is asserted for the default number of generator workgroups only."""
+    K = 64
+    if generator_wgs is not None:
+        monkeypatch.setenv('CROWDNAV_AMD_FILL_QUEUE_WGS', str(generator_wgs))  # (cn_create reads it when the engine is built)
     steps = sum(launches)
     cfg = dict(num_humans=10, circle_radius=3.2, robot_visible=1)
     o, total, rec, cur_steps, cur_ret = _oracle(oracle_mod, B, steps, K, **cfg)
     eng, bufs = _engine(amd, B, launches, K, depth, flags=amd.FLAG_ASYNC_SCENARIO_FILL, **cfg)
+    assert eng.launch_counts()['async_fills'] == len(launches)  # one fill launch beside every call
     cnt = _records_in_order(bufs, rec, K)
-    assert cnt.min() >= 1 and cnt.sum() >= 0.25 * rec['count'].sum()
+    assert cnt.min() >= 1
+    if generator_wgs is None:
+        assert cnt.sum() >= 0.25 * rec['count'].sum()
     ran = _np(bufs['ep_steps']).astype(np.int64)
     per_env = np.array([ran[b, :cnt[b]].sum() for b in range(B)]) + _np(bufs['cur_steps'])
     assert int(_np(bufs['transitions'])[0]) == per_env.sum()

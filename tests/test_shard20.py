@@ -1,6 +1,6 @@
 """The 20-human shard's kernel (BASELINE configs[3]: `rollout_kernel<10, false, true, true>`, step_kernels.h) since round 4:
 compact LDS layout (12 workgroups per CU), step parameters / episode bookkeeping / per-episode agent constants in LDS instead of
-registers (three resident waves per SIMD), and the 3-of-4 env schedule of `launch_rollout` (crowdnav_amd.hip): a call of
+registers (three resident waves per SIMD), and the 3-of-4 env schedule of `launch_shard` (crowdnav_amd.hip): a call of
 3 q + r steps runs as one launch of r steps over all envs and FOUR launches of q steps over 3 B / 4 workgroups, sub-launch k
 leaving out env 3 - k of every group of four.  None of this may change a bit of what an env plays: everything is compared
 with the oracle's rollout (oracle/crowd_oracle.cpp: co_rollout, the restatement of crowd_sim.py:317-420 + explorer.py:50-72),

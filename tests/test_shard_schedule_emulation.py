@@ -1,5 +1,5 @@
 """The 3-of-4 env schedule of the 20-human shard's kernel as plain arithmetic (crowdnav_amd/csrc/step_kernels.h: rollout_body's
-`env_block` / `extra_env`; crowdnav_amd.hip: launch_rollout).  A call of 3 q steps is four launches of q steps over 3 B / 4
+`env_block` / `extra_env`; crowdnav_amd.hip: launch_shard).  A call of 3 q steps is four launches of q steps over 3 B / 4
 workgroups; workgroup w of sub-launch k plays env 4 (w / 3) + (w % 3) + [w % 3 >= 3 - k].  Checked here for every B that is a
 multiple of four: each sub-launch maps its workgroups onto distinct envs, every env is played in exactly three of the four
 sub-launches (so it makes 3 q steps, in launch order), the env a group leaves out in the LAST sub-launch is the one its first
@@ -85,7 +85,7 @@ def test_dynamic_schedule_runs_every_envs_visits_in_order_without_deadlock(B, V,
 
 @pytest.mark.parametrize('n,want', [(999, 18), (500, 9), (150, 3), (47, 3), (24, 3), (2997, 54)])
 def test_visits_per_call_and_their_lengths(n, want):
-    visits = max(3, (n + 28) // 56)          # crowdnav_amd.hip: launch_rollout (~56 steps per visit, at least three)
+    visits = max(3, (n + 28) // 56)          # crowdnav_amd.hip: launch_shard (~56 steps per visit, at least three)
     visits = min(visits, n)
     assert visits == want
     q, rem = divmod(n, visits)
