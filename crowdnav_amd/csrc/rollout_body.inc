@@ -93,8 +93,7 @@
     float robot_max_speed = 0.0f;
     const bool robot = L.valid && L.a == 0;
     double theta = 0.0;  // heading of a unicycle robot (external actions only)
-    double gtime = 0.0, cur_return = 0.0, cur_dsum = 0.0;
-    int cur_steps = 0, cur_danger = 0, ep_count = 0, ring_filled = 0, state = kRetired;
+    EpisodeBook ep = {};  // (state = kRetired)
     {
         const StateView S = *Sd;
         if (L.valid) load_agent(S, L.gi, r);
@@ -106,19 +105,12 @@
     if (robot) {
         const StateView S = *Sd;
         const cn_rollout_io io = *R.io;
-        gtime = S.gtime[L.env];
-        state = io.active[L.env];
-        ep_count = io.ep_count[L.env];
-        cur_steps = io.cur_steps[L.env];
-        cur_return = io.cur_return[L.env];
-        if (io.cur_danger) cur_danger = io.cur_danger[L.env];
-        if (io.cur_danger_dmin_sum) cur_dsum = io.cur_danger_dmin_sum[L.env];
-        ring_filled = ring_filled_in[L.env];
-        int f = state == kRunning ? 1 : 0;
-        if (state == kWaitingScenario && scenario_ready(P, S, L.env, ep_count, ring_filled)) {  // produced since
-            f = 2 + ep_count % P.ring_depth;
-            state = kRunning;
-            gtime = 0.0;
+        CN_LOAD_EPISODE(ep, S, io, ring_filled_in, L.env);
+        int f = ep.state == kRunning ? 1 : 0;
+        if (ep.state == kWaitingScenario && scenario_ready(P, S, L.env, ep.ep_count, ep.ring_filled)) {  // produced since
+            f = 2 + ep.ep_count % P.ring_depth;
+            ep.state = kRunning;
+            ep.gtime = 0.0;
         }
         s.flag[L.lane] = f;
     }
@@ -142,13 +134,9 @@
     if (!COMPACT)
         for (int t = threadIdx.x; t < kMaxDiscount; t += blockDim.x) s.disc[t] = t < R.discount_len ? R.discount[t] : 0.0;
     // COMPACT: the robot lane's episode bookkeeping waits in LDS while a transition is computed (12 VGPRs the step loop
-    // does not hold across the pair and solve phases)
+    // does not hold across the pair and solve phases); `ep` is its copy in registers while a transition is booked
     EpisodeLds* const eps = reinterpret_cast<EpisodeLds*>(s.disc + 8);
-    if (COMPACT && robot) {
-        eps->gtime = gtime, eps->cur_return = cur_return, eps->cur_dsum = cur_dsum;
-        eps->cur_steps = cur_steps, eps->cur_danger = cur_danger, eps->ep_count = ep_count;
-        eps->ring_filled = ring_filled, eps->state = state, eps->transitions = 0u;
-    }
+    if (COMPACT && robot) eps->book = ep, eps->transitions = 0u;
     __syncthreads();
     const int disc_len = R.discount_len < kMaxDiscount ? R.discount_len : kMaxDiscount;
 
@@ -178,8 +166,8 @@
                 dst[2] = make_double2(r.gx, r.gy), dst[3] = make_double2(r.rad, r.vpref);
             }
             if (robot) {
-                T.episode[trace_row] = state == kRunning ? ep_count : -1;  // -1: retired, or waiting for its next scenario
-                if (state == kRunning) T.step[trace_row] = cur_steps;
+                T.episode[trace_row] = ep.state == kRunning ? ep.ep_count : -1;  // -1: retired, or waiting for its next scenario
+                if (ep.state == kRunning) T.step[trace_row] = ep.cur_steps;
             }
         }
 #endif
@@ -187,40 +175,40 @@
         StepResult res;
         double nvx, nvy;
         if constexpr (COMPACT) {
-            // no LDS copy of the discount table: this step's factor is requested here, a whole transition before its use
+            // The book lives in LDS (eps->book) and comes into registers field by field, for the bookkeeping only: what every
+            // transition touches (`e`), and episodes finished / fill level / state at an episode end alone.  No LDS copy of the
+            // discount table either: this step's factor is requested here, a whole transition before its use, with global_time.
+            // (The whole book copied in and out, as one struct, cost the shard's kernel 1.9 %: profiles/episode_book_refactor.txt)
+            EpisodeBook& book = eps->book;
             double disc_now = 0.0, gt = 0.0;
             if (robot) {
-                const int cs = eps->cur_steps;
-                gt = eps->gtime;
+                const int cs = book.cur_steps;
+                gt = book.gtime;
                 if (cs < disc_len) disc_now = R.discount[cs];
             }
             step_core<MAXL, UNI, KD, true>(P, s, Ls, r, gt, robot_max_speed, ext_action, 1, res, nvx, nvy, &theta, clk);
-            if (robot && eps->state == kRunning) {
+            if (robot && book.state == kRunning) {
                 int next_flag = 1;
-                int e_steps = eps->cur_steps, e_danger = eps->cur_danger;
-                double e_return = eps->cur_return, e_dsum = eps->cur_dsum;
+                EpisodeBook e;
+                e.cur_steps = book.cur_steps, e.cur_danger = book.cur_danger;
+                e.cur_return = book.cur_return, e.cur_dsum = book.cur_dsum;
+                e.gtime = gt;
                 eps->transitions += 1u;
-                e_return = e_return + disc_now * res.reward;  // python sum(): left to right
-                ++e_steps;
-                if (res.info == CN_DANGER) {
-                    ++e_danger;
-                    e_dsum += res.dmin;
-                }
+                CN_BOOK_TRANSITION(e, disc_now, res.reward, res.info, res.dmin);
                 if (res.done) {
-                    int e_count = eps->ep_count, e_state = kRunning;
-                    next_flag = finish_episode(P, *Sd, R, L.env, P.ring_depth, eps->ring_filled, s.disc[kParLimit], res.info, gt,
-                                               e_count, e_steps, e_return, e_danger, e_dsum, e_state);
-                    eps->ep_count = e_count, eps->state = e_state;
-                    e_steps = 0, e_return = 0.0, e_danger = 0, e_dsum = 0.0;
-                    gt = 0.0;
+                    e.ep_count = book.ep_count, e.ring_filled = book.ring_filled, e.state = kRunning;
+                    const cn_rollout_io io = *R.io;
+                    next_flag = 0;
+                    CN_END_EPISODE(P, *Sd, io, L.env, true, s.disc[kParLimit], res.info, e, next_flag = 2 + e.ep_count % P.ring_depth);
+                    book.ep_count = e.ep_count, book.state = e.state;
                 }
-                eps->gtime = gt;
-                eps->cur_steps = e_steps, eps->cur_danger = e_danger, eps->cur_return = e_return, eps->cur_dsum = e_dsum;
+                book.gtime = e.gtime;
+                book.cur_steps = e.cur_steps, book.cur_danger = e.cur_danger, book.cur_return = e.cur_return, book.cur_dsum = e.cur_dsum;
                 s.flag[L.lane] = next_flag;
             }
         } else {
-            step_core<MAXL, UNI, KD>(P, s, Ls, r, gtime, robot_max_speed, ext_action, 1, res, nvx, nvy, &theta, clk);
-            if (robot && state == kRunning) {
+            step_core<MAXL, UNI, KD>(P, s, Ls, r, ep.gtime, robot_max_speed, ext_action, 1, res, nvx, nvy, &theta, clk);
+            if (robot && ep.state == kRunning) {
                 int next_flag = 1;
                 ++transitions;
 #ifdef CN_ROLLOUT_TRACE
@@ -228,18 +216,12 @@
                 if (T.info) T.info[trace_row] = res.info;
                 if (T.dmin) T.dmin[trace_row] = res.dmin;
 #endif
-                const double disc = cur_steps < kMaxDiscount ? s.disc[cur_steps] : 0.0;
-                cur_return = cur_return + disc * res.reward;  // python sum(): left to right
-                ++cur_steps;
-                if (res.info == CN_DANGER) {
-                    ++cur_danger;
-                    cur_dsum += res.dmin;
-                }
-                if (res.done) {
-                    next_flag = finish_episode(P, *Sd, R, L.env, P.ring_depth, ring_filled, P.time_limit, res.info, gtime, ep_count,
-                                               cur_steps, cur_return, cur_danger, cur_dsum, state);
-                    cur_steps = 0, cur_return = 0.0, cur_danger = 0, cur_dsum = 0.0;
-                    gtime = 0.0;
+                const double disc = ep.cur_steps < kMaxDiscount ? s.disc[ep.cur_steps] : 0.0;
+                CN_BOOK_TRANSITION(ep, disc, res.reward, res.info, res.dmin);
+                if (res.done) {  // 0 = the env stops stepping (retired, or waiting for its scenario), 2 + slot = every lane loads it
+                    const cn_rollout_io io = *R.io;
+                    next_flag = 0;
+                    CN_END_EPISODE(P, *Sd, io, L.env, true, P.time_limit, res.info, ep, next_flag = 2 + ep.ep_count % P.ring_depth);
                 }
                 s.flag[L.lane] = next_flag;
             }
@@ -257,11 +239,7 @@
         const double2 g = s.goal2[L.lane];
         r.gx = g.x, r.gy = g.y, r.vpref = s.vpref[L.lane], r.rad = s.rad[L.lane];
     }
-    if (COMPACT && robot) {
-        gtime = eps->gtime, cur_return = eps->cur_return, cur_dsum = eps->cur_dsum;
-        cur_steps = eps->cur_steps, cur_danger = eps->cur_danger, ep_count = eps->ep_count;
-        state = eps->state, transitions = eps->transitions;
-    }
+    if (COMPACT && robot) ep = eps->book, transitions = eps->transitions;
 #ifdef CN_PHASE_TIMING
     if ((threadIdx.x & (kWave - 1)) == 0) {
         for (int k = 0; k < 10; ++k) atomicAdd(&cn_phase_cycles[k], clock.acc[k]);
@@ -271,24 +249,10 @@
 
     const StateView S = *Sd;
     if (KD) kd_store(P, S, s, L);
-    if (L.valid) {
-        S.pos[L.gi] = make_double2(r.px, r.py);
-        S.vel[L.gi] = make_double2(r.vx, r.vy);
-        S.goal[L.gi] = make_double2(r.gx, r.gy);
-        S.rv[L.gi] = make_double2(r.rad, r.vpref);
-    }
+    if (L.valid) CN_STORE_AGENT(S, L.gi, r);
     if (robot) {
         const cn_rollout_io io = *R.io;
-        S.gtime[L.env] = gtime;
-        S.theta[L.env] = theta;
-        if (P.robot_orca) S.rsim_valid[L.env] = 1;
-        io.active[L.env] = (uint8_t)state;
-        io.ep_count[L.env] = ep_count;
-        io.cur_steps[L.env] = cur_steps;
-        io.cur_return[L.env] = cur_return;
-        if (io.cur_danger) io.cur_danger[L.env] = cur_danger;
-        if (io.cur_danger_dmin_sum) io.cur_danger_dmin_sum[L.env] = cur_dsum;
-        S.ep_word[L.env] = (ep_count << 2) | state;
+        CN_STORE_EPISODE(P, S, io, L.env, ep, theta);
     }
     if (kDyn && dynamic) {
         if (robot) {
@@ -303,7 +267,7 @@
             __hip_atomic_store(Sd->dyn_queue + 1 + dyn_env, dyn_k + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         continue;
     }
-    rollout_epilogue(P, S, *R.io, L, robot, transitions, ep_count, reinterpret_cast<double*>(s.lines), extra_env);
+    rollout_epilogue(P, S, *R.io, L, robot, transitions, ep.ep_count, reinterpret_cast<double*>(s.lines), extra_env);
     }  // visits
     if (kDyn && dynamic) {
         // the job-wide transitions counter, if the caller keeps one (per-env counters were added visit by visit; the in-kernel

@@ -12,8 +12,9 @@
 //                           otherwise), so the episode bookkeeping that decides what the agents do next — advance, load the
 //                           next scenario from the ring, pause — needs no flag broadcast; integrate; stage the next step
 //                                                                                                                -> barrier 4
-// Per-env episode state (global_time, episodes finished, ring fill level, running / waiting / retired) is replicated on
-// the env's lanes; only the robot lane keeps the return / danger accumulators and writes records.
+// The env's episode bookkeeping (step_kernels.h: EpisodeBook — global_time, the return / danger accumulators, episodes
+// finished, ring fill level, running / waiting / retired) is replicated on the env's lanes; only the robot lane writes it
+// out: records, and the book at the end of the launch.
 // Launch conditions (cn_rollout / cn_rollout_step check them, everything else runs rollout_kernel): 5-half-plane
 // instantiation, NC <= 5, pairs <= 64, nA * 5 <= 64, 64 threads, holonomic robot.
 // SPLIT (further down): the headline geometry's cn_rollout as TWO waves per workgroup — the phases above, dealt to an ORCA
@@ -24,11 +25,6 @@
 namespace cn {
 
 constexpr int kFusedMaxNC = 5;
-
-struct EpisodeRegs {  // replicated on every agent lane of the env
-    double gtime;
-    int state, ep_count, ring_filled;
-};
 
 // A wave-uniform value pinned in vector registers.  The eight float64 parameters of the step (dt, time limit, rewards,
 // discomfort distance / factor, safety space) arrive as kernel arguments in SGPRs; with ~100 SGPRs live in the step loop the
@@ -376,6 +372,13 @@ __device__ __forceinline__ StepOutcome reduce_env(const Params& P, const Smem& s
     return StepOutcome{reward, dmin, info, done};
 }
 
+// reduce -> account -> episode end of a transition run on every lane of a running env identically (the book is carried
+// redundantly; the robot lane writes the record), with the shared statements of step_kernels.h: CN_BOOK_TRANSITION, and at an
+// episode end CN_END_EPISODE, whose decision is ep.state (kRunning: load ring slot ep.ep_count % P.ring_depth).  The one-wave
+// step loop and the env wave each spell the dozen lines around them themselves: the one-wave loop integrates between the
+// reduce and the accounting, the env wave requests the next scenario before the record stores, and as ONE helper — function
+// or macro — that sequence cost the one-wave kernels 1.1 % (profiles/episode_book_refactor.txt).
+
 // CN_WAVE_TRACE (profiling builds): every wave leaves four 100 MHz timestamps (kernel entry, step loop entry / exit, kernel
 // exit) and how many of its steps took the 3-D fallback / ended an episode: scripts/probes/wave_trace.py
 #ifdef CN_WAVE_TRACE
@@ -384,7 +387,7 @@ static __device__ unsigned long long cn_wave_trace[8192 * 6];
 
 // ---------------------------------------------------------------------------------------------- the two-wave kernel
 // SPLIT: the headline geometry as a workgroup of TWO waves serving the same 2 envs.
-//   env wave  (threads 0-63)    everything float64: AgentRegs / EpisodeRegs, preferred velocity + start point, swept
+//   env wave  (threads 0-63)    everything float64: AgentRegs / EpisodeBook, preferred velocity + start point, swept
 //                               distance, reduce / reward / done, integrate, accumulators, records, scenario loads; the launch
 //                               prologue and epilogue are the one-wave kernel's own code
 //   ORCA wave (threads 64-127)  pairs, candidates, planar scan, 3-D fallback; it carries the float64 positions only to form
@@ -549,6 +552,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     // between launches, hence a direct argument.
     constexpr int MAXL = 5;
     Params P = P_in;
+    P.async_fill = 0;  // (rollout_route: never beside the asynchronous fill — scenario_ready is the fill-level comparison)
     if (HEADLINE) {  // BASELINE configs[1]: 5 humans + robot, 2 envs per wave, 60 pairs, as compile-time constants
         P.A = 6, P.NC = 5, P.E = 2, P.nA = 12, P.pairs = 60, P.threads = 64;
     }
@@ -567,9 +571,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     // the device copy there (scalar loads) instead of occupying SGPRs across the step loop
     const cn_rollout_io* iop = R.io;
     double theta = 0.0;
-    EpisodeRegs ep{0.0, kRetired, 0, 0};
-    double cur_return = 0.0, cur_dsum = 0.0;
-    int cur_steps = 0, cur_danger = 0;
+    EpisodeBook ep = {};  // (state = kRetired)
     {
         // Launch prologue in TWO memory round trips: every pointer it needs in one batch of scalar loads (both structs are
         // dead again before the step loop), then every per-lane value in one batch of vector loads — unconditional, on clamped
@@ -584,17 +586,12 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
         const bool have = P.robot_orca ? S.rsim_valid[env] != 0 : false;
         const float rr_kept = P.robot_orca ? S.rsim_radius[gi] : 0.0f;
         const float ms_kept = P.robot_orca ? S.rsim_max_speed[env] : 0.0f;
-        const double theta0 = S.theta[env], gtime0 = S.gtime[env];
-        const int state0 = io.active[env], count0 = io.ep_count[env], filled0 = ring_filled_in[env];
-        const int steps0 = io.cur_steps[env];
-        const double return0 = io.cur_return[env];
-        const int danger0 = io.cur_danger ? io.cur_danger[env] : 0;
-        const double dsum0 = io.cur_danger_dmin_sum ? io.cur_danger_dmin_sum[env] : 0.0;
+        const double theta0 = S.theta[env];
+        EpisodeBook ep0;
+        CN_LOAD_EPISODE(ep0, S, io, ring_filled_in, env);
         if (L.valid) {
             r.px = p0.x, r.py = p0.y, r.vx = v0.x, r.vy = v0.y, r.gx = g0.x, r.gy = g0.y, r.rad = q0.x, r.vpref = q0.y;
-            ep.gtime = gtime0, ep.state = state0, ep.ep_count = count0, ep.ring_filled = filled0;
-            // (every lane of the env: the accumulators are carried redundantly, see the reduce phase)
-            cur_steps = steps0, cur_return = return0, cur_danger = danger0, cur_dsum = dsum0;
+            ep = ep0;  // (every lane of the env: the book is carried redundantly, see the step loop)
             if (L.a == 0) theta = theta0;
             if (P.robot_orca) {  // load_robot_view (step_kernels.h), without its dependent loads
                 const float rr = have ? rr_kept : (float)(r.rad + 0.01 + P.robot_safety);
@@ -609,8 +606,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     }
     build_pairs(P, s);
 
-    if (L.valid && ep.state == kWaitingScenario && ep.ep_count < ep.ring_filled) {  // the fill kernel has just produced it
-        // (the asynchronous fill is for the wave generators, more than 8 humans: never this kernel)
+    if (L.valid && ep.state == kWaitingScenario && scenario_ready(P, *Sd, L.env, ep.ep_count, ep.ring_filled)) {  // produced since
         load_from_ring(P, *Sd, L, ep.ep_count % P.ring_depth, r);
         ep.state = kRunning;
         ep.gtime = 0.0;
@@ -687,15 +683,12 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                 CN_FUSED_SYNC();
                 bool done = false;
                 if (running) {
-                    const double disc_t = s.disc[cur_steps < kMaxDiscount ? cur_steps : kMaxDiscount - 1];
+                    const double disc_t = s.disc[ep.cur_steps < kMaxDiscount ? ep.cur_steps : kMaxDiscount - 1];
                     const StepOutcome o = reduce_env(P, s, L.ebase, ep.gtime, K);
                     done = o.done;
                     ep.gtime += K.dt;
                     ++transitions;
-                    cur_return = cur_return + (cur_steps < kMaxDiscount ? disc_t : 0.0) * o.reward;  // python sum(): left to right
-                    ++cur_steps;
-                    cur_danger += o.info == CN_DANGER ? 1 : 0;
-                    cur_dsum = o.info == CN_DANGER ? cur_dsum + o.dmin : cur_dsum;
+                    CN_BOOK_TRANSITION(ep, ep.cur_steps < kMaxDiscount ? disc_t : 0.0, o.reward, o.info, o.dmin);
                     if (done) {  // explorer.py:50-72: record, then the env's next episode
                         // every load of the episode end first (the io block, the state pointers, the next scenario — in
                         // bounds whether or not it is taken), then the record stores: one memory round trip in the shadow
@@ -704,19 +697,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                         const StateView S = *Sd;
                         AgentRegs next = r;
                         load_from_ring(P, S, L, (ep.ep_count + 1) % P.ring_depth, next);
-                        if (L.a == 0) write_record(io, L.env, ep.ep_count, o.info, cur_steps, cur_return, (o.info == CN_TIMEOUT) ? K.limit : ep.gtime, cur_danger, cur_dsum);
-                        cur_steps = 0, cur_return = 0.0, cur_danger = 0, cur_dsum = 0.0;
-                        ++ep.ep_count;
-                        ep.gtime = 0.0;
-                        const int64_t c = episode_id(io, L.env, ep.ep_count);
-                        if (io.episode_limit >= 0 && c >= io.episode_limit) {
-                            ep.state = kRetired;
-                        } else if (ep.ep_count < ep.ring_filled) {
-                            r = next;
-                            theta = 1.5707963267948966;  // robot.set(..., np.pi / 2)
-                        } else {
-                            ep.state = kWaitingScenario;  // ring ran dry: pause this env until the next launch has refilled it
-                        }
+                        CN_END_EPISODE(P, S, io, L.env, L.a == 0, K.limit, o.info, ep, r = next; theta = 1.5707963267948966);
                     }
                 }
                 ended = __ballot(done) != 0ull;
@@ -783,7 +764,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
 
         // ---- reduce (every lane of the env, identically), integrate, episode bookkeeping, stage the next step
         if (running) {
-            const double disc_t = s.disc[cur_steps < kMaxDiscount ? cur_steps : kMaxDiscount - 1];
+            const double disc_t = s.disc[ep.cur_steps < kMaxDiscount ? ep.cur_steps : kMaxDiscount - 1];
             const StepOutcome o = reduce_env(P, s, L.ebase, ep.gtime, K);
             const double reward = o.reward, dmin = o.dmin;
             const int info = o.info;
@@ -793,30 +774,16 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             r.py = r.py + new_vy * K.dt;
             r.vx = new_vx;
             r.vy = new_vy;
-            // return / danger accumulators: every lane of the env carries them (only the robot lane's copy is written out)
+            // the book: every lane of the env carries it (only the robot lane's copy is written out)
             ++transitions;
-            cur_return = cur_return + (cur_steps < kMaxDiscount ? disc_t : 0.0) * reward;  // python sum(): left to right
-            ++cur_steps;
-            cur_danger += info == CN_DANGER ? 1 : 0;
-            cur_dsum = info == CN_DANGER ? cur_dsum + dmin : cur_dsum;
+            CN_BOOK_TRANSITION(ep, ep.cur_steps < kMaxDiscount ? disc_t : 0.0, reward, info, dmin);
 #ifdef CN_WAVE_TRACE
             if (__ballot(done) != 0ull) ++wt_ends;
 #endif
             if (done) {  // explorer.py:50-72: record, then the env's next episode
                 const cn_rollout_io io = *iop;
-                if (L.a == 0) write_record(io, L.env, ep.ep_count, info, cur_steps, cur_return, (info == CN_TIMEOUT) ? K.limit : ep.gtime, cur_danger, cur_dsum);
-                cur_steps = 0, cur_return = 0.0, cur_danger = 0, cur_dsum = 0.0;
-                ++ep.ep_count;
-                ep.gtime = 0.0;
-                const int64_t c = episode_id(io, L.env, ep.ep_count);
-                if (io.episode_limit >= 0 && c >= io.episode_limit) {
-                    ep.state = kRetired;
-                } else if (ep.ep_count < ep.ring_filled) {
-                    load_from_ring(P, *Sd, L, ep.ep_count % P.ring_depth, r);
-                    theta = 1.5707963267948966;  // robot.set(..., np.pi / 2)
-                } else {
-                    ep.state = kWaitingScenario;  // ring ran dry: pause this env until the next launch has refilled it
-                }
+                CN_END_EPISODE(P, *Sd, io, L.env, L.a == 0, K.limit, info, ep,
+                               load_from_ring(P, *Sd, L, ep.ep_count % P.ring_depth, r); theta = 1.5707963267948966);
             }
         }
         stage_agent(P, s, L, r, K.hsafety);
@@ -840,25 +807,9 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     const unsigned long long wt_exit = __builtin_amdgcn_s_memrealtime();
 #endif
     const StateView S = *Sd;
-    if (L.valid) {
-        S.pos[L.gi] = make_double2(r.px, r.py);
-        S.vel[L.gi] = make_double2(r.vx, r.vy);
-        S.goal[L.gi] = make_double2(r.gx, r.gy);
-        S.rv[L.gi] = make_double2(r.rad, r.vpref);
-    }
+    if (L.valid) CN_STORE_AGENT(S, L.gi, r);
     const cn_rollout_io io = *iop;
-    if (robot) {
-        S.gtime[L.env] = ep.gtime;
-        S.theta[L.env] = theta;
-        if (P.robot_orca) S.rsim_valid[L.env] = 1;
-        io.active[L.env] = (uint8_t)ep.state;
-        io.ep_count[L.env] = ep.ep_count;
-        io.cur_steps[L.env] = cur_steps;
-        io.cur_return[L.env] = cur_return;
-        if (io.cur_danger) io.cur_danger[L.env] = cur_danger;
-        if (io.cur_danger_dmin_sum) io.cur_danger_dmin_sum[L.env] = cur_dsum;
-        S.ep_word[L.env] = (ep.ep_count << 2) | ep.state;
-    }
+    if (robot) CN_STORE_EPISODE(P, S, io, L.env, ep, theta);
     // transitions counter, record blocks, explorer.py:74-90 sums: the launch's own tail (step_kernels.h: rollout_epilogue)
     rollout_epilogue(P, S, io, L, robot, transitions, ep.ep_count, reinterpret_cast<double*>(s.lines));
 #ifdef CN_WAVE_TRACE

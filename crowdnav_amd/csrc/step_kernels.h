@@ -218,7 +218,7 @@ __device__ __forceinline__ Smem carve(const Params& P) {
 
 // COMPACT (the 20-human shard's kernel): the seven float64 parameters of a step are not held in registers across the step
 // loop (14 VGPRs) but kept in LDS — Smem::disc[0..6], written once per launch — and requested where a phase needs them;
-// Smem::disc[8..13] hold the robot lane's episode bookkeeping between steps (EpisodeLds).
+// Smem::disc[8..14] hold the robot lane's episode bookkeeping between steps (EpisodeLds, further down).
 enum { kParDt = 0, kParLimit, kParSuccess, kParCollision, kParDDist, kParDFactor, kParHSafety, kParCount };
 template <bool COMPACT>
 __device__ __forceinline__ double step_param(const Params& P, const Smem& s, int which) {
@@ -227,13 +227,6 @@ __device__ __forceinline__ double step_param(const Params& P, const Smem& s, int
            which == kParCollision ? P.collision_penalty : which == kParDDist ? P.discomfort_dist :
            which == kParDFactor ? P.discomfort_factor : P.human_safety;
 }
-struct EpisodeLds {  // at Smem::disc + 8 (one robot per workgroup)
-    double gtime, cur_return, cur_dsum;
-    int cur_steps, cur_danger, ep_count, ring_filled, state;
-    unsigned int transitions;
-    unsigned int dyn_total;  // dynamic schedule: transitions of all the visits this workgroup ran (not a register held across them)
-};
-static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLds outgrew its LDS slot");
 
 // Workgroup barrier of the step / rollout kernels.  A workgroup of ONE wave (P.threads == 64: a compile-time fact in the
 // 20-human shard's instantiation, a uniform branch elsewhere) needs no s_barrier: a wave's LDS instructions execute in order,
@@ -1544,23 +1537,94 @@ __device__ __forceinline__ void write_record(const cn_rollout_io& io, int env, i
     }
 }
 
-// Episode end on the robot lane: append the record, pick the next episode.  Returns the
-// per-env flag: 0 = stop stepping (retired, or waiting for the ring to be refilled), 2 + slot = load ring slot.
-__device__ __forceinline__ int finish_episode(const Params& P, const StateView& S, const RolloutView R, int env, int ring_depth,
-                                          int ring_filled, double time_limit, int info, double gtime, int& ep_count,
-                                          int cur_steps, double cur_return, int cur_danger, double cur_dsum,
-                                          int& state) {
-    const cn_rollout_io io = *R.io;
-    write_record(io, env, ep_count, info, cur_steps, cur_return, (info == CN_TIMEOUT) ? time_limit : gtime, cur_danger, cur_dsum);
-    ++ep_count;
-    if (past_episode_limit(io, episode_id(io, env, ep_count))) {
-        state = kRetired;
-        return 0;
-    }
-    if (scenario_ready(P, S, env, ep_count, ring_filled)) return 2 + ep_count % ring_depth;
-    state = kWaitingScenario;  // ring ran dry (or this scenario is still being generated): pause until a later launch
-    return 0;
-}
+// ---- the episode bookkeeping of explorer.py:50-72, each piece stated once ------------------------------------------
+// What an env carries from step to step and from call to call.  The generic kernels keep it in the robot lane's registers,
+// the shard's kernel in LDS between steps (EpisodeLds), the fused kernels on every lane of the env.
+struct EpisodeBook {
+    double gtime, cur_return, cur_dsum;  // global_time; the running episode's discounted return and sum of Danger min_dist
+    int cur_steps, cur_danger;           // ... its transitions and its Danger steps
+    int ep_count, ring_filled, state;    // episodes finished; the launch-time ring fill level; kRunning / kWaitingScenario / kRetired
+};
+struct EpisodeLds {  // at Smem::disc + 8 (COMPACT: one robot per workgroup)
+    EpisodeBook book;
+    unsigned int transitions;
+    unsigned int dyn_total;  // dynamic schedule: transitions of all the visits this workgroup ran (not a register held across them)
+};
+static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLds outgrew its LDS slot");
+
+// The four pieces below are MACROS, expanded in rollout_body.inc and rollout_fused.h, for the reason rollout_body.inc is
+// included text: as __device__ __forceinline__ functions (the book by reference, or returned by value) hipcc gave every
+// rollout_kernel instantiation another instruction stream with one to seventeen more spilled SGPRs, and the generic
+// 10-half-plane kernel lost 1.3 % (profiles/episode_book_refactor.txt); expanded as text they compile to the code the kernels
+// had when each spelled them out.  `io` is a cn_rollout_io (a local copy of the device block), `S` a StateView expression.
+//
+// The book of env `env` as the previous call left it.  Straight-line loads, none under another's result: a caller that wants
+// them issued in one batch with its other loads expands this unconditionally on a clamped index (rollout_fused.h).
+#define CN_LOAD_EPISODE(e, S, io, ring_filled_in, env)                                            \
+    do {                                                                                          \
+        (e).gtime = (S).gtime[env];                                                               \
+        (e).state = (io).active[env];                                                             \
+        (e).ep_count = (io).ep_count[env];                                                        \
+        (e).ring_filled = (ring_filled_in)[env];                                                  \
+        (e).cur_steps = (io).cur_steps[env];                                                      \
+        (e).cur_return = (io).cur_return[env];                                                    \
+        (e).cur_danger = (io).cur_danger ? (io).cur_danger[env] : 0;                              \
+        (e).cur_dsum = (io).cur_danger_dmin_sum ? (io).cur_danger_dmin_sum[env] : 0.0;            \
+    } while (0)
+// ... and as this call leaves it (robot lane), with the robot's heading, the "robot's simulator exists" mark and ep_word;
+// beside it the agent's own state (every agent lane)
+#define CN_STORE_EPISODE(P, S, io, env, e, theta)                                                 \
+    do {                                                                                          \
+        (S).gtime[env] = (e).gtime;                                                               \
+        (S).theta[env] = (theta);                                                                 \
+        if ((P).robot_orca) (S).rsim_valid[env] = 1;                                              \
+        (io).active[env] = (uint8_t)(e).state;                                                    \
+        (io).ep_count[env] = (e).ep_count;                                                        \
+        (io).cur_steps[env] = (e).cur_steps;                                                      \
+        (io).cur_return[env] = (e).cur_return;                                                    \
+        if ((io).cur_danger) (io).cur_danger[env] = (e).cur_danger;                               \
+        if ((io).cur_danger_dmin_sum) (io).cur_danger_dmin_sum[env] = (e).cur_dsum;               \
+        (S).ep_word[env] = ((e).ep_count << 2) | (e).state;                                       \
+    } while (0)
+#define CN_STORE_AGENT(S, gi, r)                                                                  \
+    do {                                                                                          \
+        (S).pos[gi] = make_double2((r).px, (r).py);                                               \
+        (S).vel[gi] = make_double2((r).vx, (r).vy);                                               \
+        (S).goal[gi] = make_double2((r).gx, (r).gy);                                              \
+        (S).rv[gi] = make_double2((r).rad, (r).vpref);                                            \
+    } while (0)
+
+// One transition of the running episode: `disc` is gamma ** (cur_steps * dt * v_pref) of THIS step.
+#define CN_BOOK_TRANSITION(e, disc, reward, info, dmin)                                           \
+    do {                                                                                          \
+        (e).cur_return = (e).cur_return + (disc) * (reward); /* python sum(): left to right */    \
+        ++(e).cur_steps;                                                                          \
+        if ((info) == CN_DANGER) {                                                                \
+            ++(e).cur_danger;                                                                     \
+            (e).cur_dsum += (dmin);                                                               \
+        }                                                                                         \
+    } while (0)
+
+// Episode end: append the record (the lane with `write`), start the book afresh, pick the next episode.  The decision is the
+// env's new state, (e).state: kRetired; kWaitingScenario (ring ran dry, or this scenario is still being generated: pause until a
+// later launch); kRunning = go on with the scenario of ordinal (e).ep_count — then, and only then, the statement
+// NEXT_SCENARIO runs: what the kernel does to take it from ring slot (e).ep_count % P.ring_depth.
+#define CN_END_EPISODE(P, S, io, env, write, time_limit, info, e, NEXT_SCENARIO)                                              \
+    do {                                                                                                                      \
+        if (write)                                                                                                            \
+            write_record(io, env, (e).ep_count, info, (e).cur_steps, (e).cur_return, ((info) == CN_TIMEOUT) ? (time_limit) : (e).gtime, \
+                         (e).cur_danger, (e).cur_dsum);                                                                       \
+        (e).cur_steps = 0, (e).cur_return = 0.0, (e).cur_danger = 0, (e).cur_dsum = 0.0;                                      \
+        (e).gtime = 0.0;                                                                                                      \
+        ++(e).ep_count;                                                                                                       \
+        if (past_episode_limit(io, episode_id(io, env, (e).ep_count))) {                                                      \
+            (e).state = kRetired;                                                                                             \
+        } else if (scenario_ready(P, S, env, (e).ep_count, (e).ring_filled)) {                                                \
+            NEXT_SCENARIO;                                                                                                    \
+        } else {                                                                                                              \
+            (e).state = kWaitingScenario;                                                                                     \
+        }                                                                                                                     \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------------- launch epilogue
 // Behind every rollout launch there used to be three more kernels on the stream: rollout_finish_kernel (the transitions

@@ -193,6 +193,34 @@ def test_asynchronous_fill_with_a_shallow_ring(amd, oracle_mod, monkeypatch, dep
     _records_in_order(bufs2, rec, K)
 
 
+@pytest.mark.parametrize('H,R,B', [(5, 4.0, 6), (8, 2.6, 6), (12, 6.0, 4), (20, 9.0, 4)])
+def test_envs_retire_at_the_episode_limit(amd, oracle_mod, H, R, B):
+    """episode_limit = 2 B + B // 2: env b plays the global episodes b, b + B, .. below the limit — three for the first half
+    of the envs, two for the rest — and retires, some envs inside the first launch, some in the third.  The fused (or
+    two-wave) kernel, the generic 5- and 10-half-plane kernels and the 20-human shard's: every record is the oracle's
+    unlimited rollout's record of the same ordinal, nothing runs past the limit, and the transitions counter is what the
+    records add up to."""
+    K, launches = 16, [60, 1, 139]
+    limit = 2 * B + B // 2
+    cfg = dict(num_humans=H, circle_radius=R, robot_visible=1)
+    _, _, rec, _, _ = _oracle(oracle_mod, B, sum(launches), K, **cfg)
+    want = np.array([len(range(b, limit, B)) for b in range(B)])
+    assert sorted(set(want.tolist())) == [2, 3]
+    for b in range(B):  # the launches are long enough for every env to get there: the case cannot pass vacuously
+        assert rec['count'][b] >= want[b] and rec['steps'][b, :want[b]].sum() <= sum(launches), b
+    eng = amd.BatchedCrowdSim(num_envs=B, robot_policy=amd.ROBOT_ORCA, **cfg)
+    bufs = eng.rollout_begin(seed_base=1000, seed_mod=500, episode_limit=limit, record_capacity=K)
+    for n in launches:
+        eng.rollout(n)
+    eng.sync()
+    assert (_np(bufs['active']) == 0).all()
+    cnt = _records_in_order(bufs, rec, K)
+    assert np.array_equal(cnt, want)
+    assert (_np(bufs['cur_steps']) == 0).all()
+    ran = _np(bufs['ep_steps']).astype(np.int64)
+    assert int(_np(bufs['transitions'])[0]) == sum(ran[b, :cnt[b]].sum() for b in range(B))
+
+
 def test_rollout_step_with_a_shallow_ring(amd, oracle_mod):
     """cn_rollout_step (the value-network rollouts' transition: one bookkept step per call, actions from outside) with a
     3-deep ring: 400 calls, every env ~12 episodes, vs the oracle stepped and reset by hand."""
