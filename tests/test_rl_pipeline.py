@@ -101,12 +101,12 @@ def test_td_value_graph_follows_parameters_that_move():
     x = torch.randn(9, 5, 13, device=dev)
     with torch.no_grad():
         v0 = ex._td_values(x).clone()
-        assert ex._td_graph is not None and torch.allclose(v0, ex.target_model(x).reshape(-1), atol=1e-6)
-        graph0 = ex._td_graph['graph']
+        assert ex.td.graph is not None and torch.allclose(v0, ex.target_model(x).reshape(-1), atol=1e-6)
+        graph0 = ex.td.graph['graph']
         for p_ in ex.target_model.parameters():              # the same module, other storage, other values
             p_.data = p_.data.clone() * 0.5
         v1 = ex._td_values(x)
-        assert ex._td_graph['graph'] is not graph0
+        assert ex.td.graph['graph'] is not graph0
         assert torch.allclose(v1, ex.target_model(x).reshape(-1), atol=1e-6) and not torch.allclose(v1, v0)
 
 
@@ -178,34 +178,34 @@ def test_single_episode_sampling_with_pinned_histories_off_the_two_launch_route(
     states = torch.stack([mem[i][0].cpu() for i in range(len(mem))]).numpy()
     values = torch.cat([mem[i][1].cpu() for i in range(len(mem))]).numpy()
     assert np.abs(states - g['memory_states']).max() <= 5e-6 and np.abs(values - g['memory_values']).max() <= 1e-6
-    counts = ex._rl_engine_cache[1].launch_counts()
+    counts = ex.rl.eng.launch_counts()
     if route == 'CROWDNAV_AMD_RL_PINNED':
-        assert counts['sarl_decide_steps'] == counts['sarl_narrow'] > 0 and not ex._rl_hist[3].is_cuda and ex._rl_hist[2].is_cuda
+        assert counts['sarl_decide_steps'] == counts['sarl_narrow'] > 0 and not ex.rl.hist.info.is_cuda and ex.rl.hist.rew.is_cuda
     else:
-        assert counts['sarl_decide_steps'] == 0 and not ex._rl_hist[2].is_cuda   # pinned histories, the host waited
+        assert counts['sarl_decide_steps'] == 0 and not ex.rl.hist.rew.is_cuda   # pinned histories, the host waited
 
 
 @pytest.mark.gpu
 def test_rl_engine_cache_follows_everything_the_engine_is_built_from():
-    """Explorer._rl_engine keeps ONE engine between the 10 000 single-episode calls of train.py — found again by a fast key of
+    """RlSampler.engine (Explorer.rl) keeps ONE engine between the 10 000 single-episode calls of train.py — found again by a fast key of
     what engine_config reads (by value, or by identity for the config object, the policy and its action-space list): any of
     those changing must give another engine, nothing else may."""
     g = load_golden('rl_sarl_plain.npz')
     c, env, robot, policy = _setup(g)
     policy.build_action_space(robot.v_pref)
     ex = c.Explorer(env, robot, torch.device('cpu'), None, float(g['gamma']), target_policy=policy)
-    e0 = ex._rl_engine(1, 5, 'circle_crossing')
-    assert ex._rl_engine(1, 5, 'circle_crossing') is e0           # the fast path
+    e0 = ex.rl.engine(env, robot, 1, 5, 'circle_crossing')
+    assert ex.rl.engine(env, robot, 1, 5, 'circle_crossing') is e0           # the fast path
     env.discomfort_dist = env.discomfort_dist + 0.05             # a value engine_config reads
-    e1 = ex._rl_engine(1, 5, 'circle_crossing')
-    assert e1 is not e0 and ex._rl_engine(1, 5, 'circle_crossing') is e1
+    e1 = ex.rl.engine(env, robot, 1, 5, 'circle_crossing')
+    assert e1 is not e0 and ex.rl.engine(env, robot, 1, 5, 'circle_crossing') is e1
     policy.action_space = list(policy.action_space)              # a rebuilt table (same values: still a new engine, by identity)
-    e2 = ex._rl_engine(1, 5, 'circle_crossing')
+    e2 = ex.rl.engine(env, robot, 1, 5, 'circle_crossing')
     assert e2 is not e1
-    assert ex._rl_engine(2, 5, 'circle_crossing') is not e2      # another batch size
+    assert ex.rl.engine(env, robot, 2, 5, 'circle_crossing') is not e2      # another batch size
     robot.time_step = 0.25                                       # not part of the engine: no new engine
-    e3 = ex._rl_engine(2, 5, 'circle_crossing')
-    assert ex._rl_engine(2, 5, 'circle_crossing') is e3
+    e3 = ex.rl.engine(env, robot, 2, 5, 'circle_crossing')
+    assert ex.rl.engine(env, robot, 2, 5, 'circle_crossing') is e3
 
 
 @pytest.mark.gpu
@@ -445,9 +445,9 @@ def test_single_episode_sampling_calls_reproduce_the_reference_memory(name, mode
     if model_on_gpu and name in ('rl_sarl_plain.npz', 'rl_lstm_rl.npz'):
         # 13-wide rows (round 6, ABI v11): the TD targets are cn_sarl_values on an engine that only holds the target's weights —
         # uploaded again after the second update_target_model (the scrambled ones would fail the 1e-6 above)
-        assert ex._td_engine is not None and getattr(ex, '_td_graph', None) is None
+        assert ex.td.engine is not None and ex.td.graph is None
         kept = sum(1 for o in lb['outcome'] if o in (2, 3))   # ReachGoal / Collision episodes enter the memory: one launch each
-        assert ex._td_engine['eng'].launch_counts()['sarl_narrow'] == kept >= 1
+        assert ex.td.engine['eng'].launch_counts()['sarl_narrow'] == kept >= 1
         # ... and follows the target's parameters: changed in place (version counters) or given new storage (addresses)
         x = torch.stack([mem[i][0] for i in range(min(len(mem), 7))]).reshape(-1, states.shape[1], 13)
         with torch.no_grad():
@@ -461,10 +461,10 @@ def test_single_episode_sampling_calls_reproduce_the_reference_memory(name, mode
             v2 = ex._td_values(x)
             assert torch.allclose(v2, ex.target_model(x).reshape(-1), atol=2e-6) and torch.allclose(v2, v0, atol=2e-6)
     elif model_on_gpu and not name.startswith('rl_lstm_rl'):
-        assert ex._td_graph is not None   # (an nn.LSTM forward may refuse capture: then the eager path ran, with a warning)
+        assert ex.td.graph is not None   # (an nn.LSTM forward may refuse capture: then the eager path ran, with a warning)
     # which route sampled: SARL and LSTM-RL (with or without occupancy maps: round 6) and CADRL take the narrow tiles + the fused
     # decision / transition kernel — two launches per streamed step
-    counts = ex._rl_engine_cache[1].launch_counts()
+    counts = ex.rl.eng.launch_counts()
     steps_issued = counts['sarl_narrow']
     assert steps_issued >= int(g['ep_steps'].sum()) and counts['sarl_decide_steps'] == steps_issued
 
