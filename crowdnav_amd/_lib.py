@@ -21,6 +21,9 @@ HOLONOMIC, UNICYCLE = 0, 1
 RECORD_FIELDS, SUMMARY_FIELDS = 6, 8
 LAUNCH_COUNTERS = ('rollout_kernels', 'scheduled_kernels', 'ring_fills', 'async_fills', 'sarl_narrow', 'sarl_decide_steps')  # CN_COUNT_*
 ROLLOUT_ROUTES = ('generic', 'fused', 'fused_split', 'shard')  # CN_ROUTE_*
+SARL_ROUTES = ('lds_tile', 'lds_chunked', 'narrow', 'reg_sarl', 'reg_sarl_chunk', 'reg_cadrl', 'reg_lstm', 'reg_lstm2',
+               'split_f16')  # CN_SARL_ROUTE_*
+PRECISIONS = ('f32', 'f16x2')  # CN_PRECISION_*
 FLAG_ASYNC_SCENARIO_FILL = 1
 
 
@@ -81,7 +84,7 @@ class CnSarlConfig(C.Structure):
         ('cell_size', C.c_double), ('gamma', C.c_double), ('with_global_state', C.c_int32),
         ('mlp1_dims', C.c_int32 * 2), ('mlp2_dims', C.c_int32 * 2), ('attention_dims', C.c_int32 * 3),
         ('mlp3_dims', C.c_int32 * 4), ('model', C.c_int32), ('interaction_dims', C.c_int32 * 4),
-        ('constant_velocity_model', C.c_int32), ('reserved', C.c_int32),
+        ('constant_velocity_model', C.c_int32), ('precision', C.c_int32),
     ]
 
 
@@ -134,6 +137,8 @@ SYMBOLS = {
     'cn_rollout_trace': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnTraceOut)]),
     # which transition kernel cn_rollout would launch (added after v12, no version bump)
     'cn_rollout_route': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    # which kernel family runs the value network (added after v12, no version bump)
+    'cn_sarl_network_route': (C.c_int, [_P, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -272,7 +272,7 @@ class CrowdSim(_Base):
         if self._rule == 'mixed' and eng.H != 5:
             raise NotImplementedError('value networks under the mixed rule need the 5 human slots the rule can draw')
         if getattr(eng, 'sarl', None) is None:
-            eng.sarl_configure(**policy.engine_kwargs())
+            policy.configure_engine(eng)
         # re-upload the parameters only when the Trainer (or a load_state_dict) has changed them: torch bumps a
         # tensor's _version on every eager in-place update; a replayed hipGraph step does not, so the Trainer also counts
         # its steps on the module (_cn_weights_epoch)

@@ -237,6 +237,7 @@ class Explorer(object):
         env, policy = self.env, self.robot.policy
         orca = is_device_orca(policy)
         human_num, rule, offset, start, size, _, max_steps = self._begin_phase(phase, None if orca else policy)
+        network_route = None  # value-network policies: the kernel family that took the decisions (sarl_network_route)
         B = int(min(k, self.max_envs))
         per_env = (k + B - 1) // B
         names = ('ep_outcome', 'ep_steps', 'ep_return', 'ep_time', 'ep_danger', 'ep_danger_dmin_sum')
@@ -260,7 +261,8 @@ class Explorer(object):
             rec = {n: bufs[n].cpu().numpy() for n in names}
         else:  # SARL value network: select + step + masked reset per batched step
             eng = BatchedCrowdSim(**env.engine_config(B, human_num, rule, _lib.ROBOT_EXTERNAL))
-            eng.sarl_configure(**policy.engine_kwargs())
+            policy.configure_engine(eng)
+            network_route = eng.sarl_network_route()
             eng.sarl_set_weights(policy.model.state_dict())
             ro = SarlRollout(eng, self.gamma, seed_base=offset + start, seed_mod=size, episode_limit=k,
                              record_capacity=per_env)
@@ -274,7 +276,7 @@ class Explorer(object):
         times = [float(rec['ep_time'][b, j]) for b, j in order]
         returns = [float(rec['ep_return'][b, j]) for b, j in order]
         self.last_batch = dict(outcome=outcome, nav_time=times, discounted_return=returns,
-                               steps=[int(rec['ep_steps'][b, j]) for b, j in order])
+                               steps=[int(rec['ep_steps'][b, j]) for b, j in order], network_route=network_route)
         if traces:  # global episode id c of the rollout = case c of this call
             per_episode = trace_episodes(traces)
             self.last_batch['trajectories'] = [per_episode[c]['state8'] for c in range(k)]

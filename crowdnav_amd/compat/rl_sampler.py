@@ -79,7 +79,7 @@ class RlSampler(object):
         key = (tuple(sorted(cfg.items())), id(policy), id(policy.action_space))
         if self.eng is None or self._key != key:
             eng = BatchedCrowdSim(**cfg)
-            eng.sarl_configure(**policy.engine_kwargs())
+            policy.configure_engine(eng)
             self.eng, self.config, self._key, self._space = eng, cfg, key, policy.action_space
         self._quick = (quick, env.config)  # (holds the config object: its id cannot be recycled)
         return self.eng

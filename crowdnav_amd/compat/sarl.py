@@ -4,6 +4,7 @@ checkpoints (il_model.pth / rl_model.pth) and the PyTorch-ROCm Trainer work unch
 the device through cn_sarl_select."""
 import itertools
 import logging
+import os
 
 import numpy as np
 import torch
@@ -171,6 +172,23 @@ class SARL(Policy):
     def engine_kwargs(self):
         """Arguments of BatchedCrowdSim.sarl_configure for this policy."""
         return dict(actions=self.action_table(), **self.net_cfg)
+
+    def configure_engine(self, eng):
+        """eng.sarl_configure for the engine that takes this policy's decisions.  CROWDNAV_AMD_SARL_PRECISION=f16x2 asks for the
+        split-f16 value-network route; where the library refuses it (another model, other widths, more than 5
+        humans, the mixed rule): one log line, then fp32 for the rest of the run."""
+        kwargs = self.engine_kwargs()
+        want = os.environ.get('CROWDNAV_AMD_SARL_PRECISION', 'f32')
+        if want != 'f32' and not getattr(self, '_precision_off', False):
+            from .._lib import CN_ERR_UNSUPPORTED, CrowdNavAmdError
+            try:
+                return eng.sarl_configure(precision=want, **kwargs)
+            except CrowdNavAmdError as exc:
+                if exc.status != CN_ERR_UNSUPPORTED:
+                    raise
+                logging.warning('CROWDNAV_AMD_SARL_PRECISION=%s: %s; the value network stays in fp32', want, exc)
+                self._precision_off = True
+        return eng.sarl_configure(**kwargs)
 
     def predict(self, state):
         if self.phase is None or self.device is None:

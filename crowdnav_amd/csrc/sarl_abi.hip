@@ -6,6 +6,7 @@
 #include "sarl_lds_kernels.h"
 #include "sarl_narrow_kernel.h"
 #include "sarl_reg_kernel.h"
+#include "sarl_f16_kernel.h"
 #include "sarl_step_fused.h"
 
 // The kernel family that runs the value network: chosen once per configuration (sarl_choose_route), then read by
@@ -16,7 +17,14 @@ enum class SarlRoute {
     Narrow,        // sarl_narrow_kernel<LSTM, ATT>: a few decisions (train.py's single-episode sampling) on tiles of 16 / H groups, one per workgroup
     RegSarl, RegSarlChunk,        // activations in registers: sarl_reg_kernel<4, NT, PRE, ATT> (1..5 humans), sarl_reg_chunk_kernel<NT, PRE, ATT> (6+)
     RegCadrl, RegLstm, RegLstm2,  // cadrl_reg_kernel<NT>, lstm_reg_kernel<4 / 16>, lstm2_reg_kernel<4 / 16> (lstm_rl.ValueNetwork2)
+    SplitF16,      // sarl_f16_kernel<XKB, NT, ATT>: CN_PRECISION_F16X2, activations in registers, split-f16 matrix instructions
 };
+// cn_sarl_network_route reports the route as CN_SARL_ROUTE_*: the same order
+static_assert((int)SarlRoute::LdsTile == CN_SARL_ROUTE_LDS_TILE && (int)SarlRoute::LdsChunked == CN_SARL_ROUTE_LDS_CHUNKED &&
+              (int)SarlRoute::Narrow == CN_SARL_ROUTE_NARROW && (int)SarlRoute::RegSarl == CN_SARL_ROUTE_REG_SARL &&
+              (int)SarlRoute::RegSarlChunk == CN_SARL_ROUTE_REG_SARL_CHUNK && (int)SarlRoute::RegCadrl == CN_SARL_ROUTE_REG_CADRL &&
+              (int)SarlRoute::RegLstm == CN_SARL_ROUTE_REG_LSTM && (int)SarlRoute::RegLstm2 == CN_SARL_ROUTE_REG_LSTM2 &&
+              (int)SarlRoute::SplitF16 == CN_SARL_ROUTE_SPLIT_F16);
 
 struct cn_sarl {
     cn_sarl_config cfg = {};
@@ -50,6 +58,8 @@ struct cn_sarl {
     int n_cus = 0;
     size_t narrow_tiles = 0, narrow_lds = 0;
     bool fused_step = false;        // cn_sarl_sample_step on the narrow route: decision + transition + next ORCA as one kernel (CROWDNAV_AMD_SARL_FUSED_STEP)
+    _Float16* f16_stream = nullptr; // SplitF16: Wh / Wl of every (output tile, input block) in the order of use (sarl_f16_pack_kernel)
+    float* f16_bias = nullptr;      // ... and the biases in accumulator order
     int* narrow_counter = nullptr;  // cn_sarl_sample_step: workgroups of sarl_narrow_kernel that have written their V
     double* narrow_value = nullptr; // ... and reward + gamma V per (env, action), each written by the tile that computed V
     cn::PackJobs pack_jobs = {};    // cn_sarl_set_weights: the layers to repack, run as one launch (sarl_pack_flush)
@@ -70,6 +80,8 @@ int om_width(const cn_sarl_config& c) { return c.with_om ? c.cell_num * c.cell_n
 
 int sarl_validate(const cn_sarl_config* c, int H) {
     if (c->n_actions < 1) return fail(CN_ERR_INVALID, "n_actions must be >= 1");
+    if (c->precision != CN_PRECISION_F32 && c->precision != CN_PRECISION_F16X2)
+        return fail(CN_ERR_INVALID, "unknown precision %d (CN_PRECISION_F32 = 0, CN_PRECISION_F16X2 = 1)", c->precision);
     if (c->with_om && (c->cell_num < 1 || c->om_channel_size < 1 || c->om_channel_size > 3 || !(c->cell_size > 0)))
         return fail(CN_ERR_INVALID, "bad occupancy-map parameters");
     if (c->with_om && H < 2) return fail(CN_ERR_INVALID, "occupancy maps need at least 2 humans (multi_human_rl.py:117)");
@@ -197,8 +209,29 @@ bool sarl_shipped_widths(const cn_sarl_config& c, int in_dim) {
            c.attention_dims[0] == 100 && c.attention_dims[1] == 100;
 }
 
+// CN_PRECISION_F16X2 is for what sarl_f16_kernel is compiled for; anything else is refused with its reason, never run in fp32
+int sarl_f16_supported(const cn_engine* e, const cn_sarl_config& c, int H, int in_dim) {
+    const char* why = is_cadrl(c)                     ? "CADRL has no split-f16 kernel (CN_MODEL_SARL only)"
+                      : is_lstm(c)                    ? "LSTM-RL has no split-f16 kernel (CN_MODEL_SARL only)"
+                      : !c.with_global_state          ? "with_global_state = 0 has no split-f16 kernel"
+                      : !sarl_shipped_widths(c, in_dim) ? "the split-f16 kernel is compiled for the shipped layer widths (mlp1 150-100, mlp2 100-50, "
+                                                        "attention 100-100-1, mlp3 150-100-100-1 on 13- or 61-wide rows)"
+                      : H < 1 || H > cn::kRegHumans   ? "the split-f16 kernel holds the activations of 1..5 humans"
+                      : e->cfg.scenario_rule == CN_MIXED ? "the split-f16 kernel does not run under the mixed rule"
+                                                      : nullptr;
+    return why ? fail(CN_ERR_UNSUPPORTED, "CN_PRECISION_F16X2: %s (%d humans)", why, H) : CN_OK;
+}
+
+SarlRoute sarl_route_f32(const cn_sarl* s, bool lds_chunked);
 // THE route decision, from the validated and sized configuration (lds_chunked: sarl_size's answer).
 SarlRoute sarl_choose_route(const cn_sarl* s, bool lds_chunked) {
+    const SarlRoute r = sarl_route_f32(s, lds_chunked);
+    // CN_PRECISION_F16X2 (sarl_f16_supported has passed) takes over the throughput routes; the narrow tiles are latency-bound and stay
+    if (s->cfg.precision == CN_PRECISION_F16X2 && (r == SarlRoute::LdsTile || r == SarlRoute::RegSarl)) return SarlRoute::SplitF16;
+    return r;
+}
+// ... of CN_PRECISION_F32
+SarlRoute sarl_route_f32(const cn_sarl* s, bool lds_chunked) {
     const cn_sarl_config& c = s->cfg;
     const cn::SarlCfg& C = s->C;
     const cn::SarlNet& net = s->net;
@@ -252,6 +285,14 @@ int sarl_alloc_route(cn_engine* e, cn_sarl* s) {
             break;
         case SarlRoute::RegLstm: s->stream_key = cn::kRegLstmGates + ks_in, key2 = cn::kRegLstmHead; break;
         case SarlRoute::RegLstm2: s->stream_key = cn::kRegLstmMlp1 + ks_in, key2 = cn::kRegLstmHead, key3 = cn::kRegLstmGates + cn::kRegLstmKs; break;
+        case SarlRoute::SplitF16: {
+            const int xkb = cn::f16_key(s->net.in_dim == 13 ? 1 : 2, H);
+            int rc;
+            if ((rc = dev_alloc(e, &s->f16_stream, cn::f16_stream_bytes(xkb) / sizeof(_Float16))) ||
+                (rc = dev_alloc(e, &s->f16_bias, (size_t)cn::f16_total_tiles(xkb) * 256)))
+                return rc;
+            return CN_OK;
+        }
         default: return CN_OK;
     }
     int rc;
@@ -400,6 +441,14 @@ int sarl_set_weights_sarl(cn_engine* e, const float* const* p) {
         if ((rc = sarl_pack(e, L, p[2 * i], p[2 * i + 1], L.N, Ktot, 0))) return rc;
         if (net.with_global && (rc = sarl_pack(e, net.L[cn::kL_att0_global], p[2 * i], nullptr, L.N, Ktot, half))) return rc;
     }
+    if (s->route == SarlRoute::SplitF16) {  // Wh / Wl in the matrix instruction's operand order, the biases in accumulator order: one launch
+        cn::F16PackPlan plan{};
+        plan.xkb = cn::f16_key(net.in_dim == 13 ? 1 : 2, s->C.H);
+        for (int l = 0; l < 11; ++l) plan.W[l] = p[2 * l], plan.b[l] = p[2 * l + 1];
+        const int total = cn::f16_total_items(plan.xkb) * 512 + cn::f16_total_tiles(plan.xkb) * 256;
+        hipLaunchKernelGGL(cn::sarl_f16_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, e->stream, plan, s->f16_stream, s->f16_bias);
+        CN_HIP(hipGetLastError());
+    }
     if (s->route != SarlRoute::RegSarl && s->route != SarlRoute::RegSarlChunk) return CN_OK;
     sarl_reg_pack(e, p);
     if (s->pre)  // mlp1.0's map columns and bias
@@ -464,6 +513,22 @@ int launch_reg_sarl(cn_engine* e, float* att) {
                 hipLaunchKernelGGL((cn::sarl_reg_kernel<4, decltype(nt)::value, decltype(pre)::value, decltype(a)::value>), grid,
                                    kRegBlock, 0, e->stream, s->reg_stream, s->X, s->V, (int)s->n_groups, (int)s->n_tiles, s->net.ks_x,
                                    s->hcount, (const float*)s->om_term, s->C.n_actions, att);
+            });
+        });
+    });
+    return ok ? CN_OK : bad_humans(H);
+}
+
+int launch_split_f16(cn_engine* e, float* att) {
+    const cn_sarl* s = e->sarl;
+    const int H = s->C.H;
+    const dim3 grid = reg_grid(s, 1);  // one wave per SIMD at every crowd size (more than 256 registers; scripts/kernel_resources.py)
+    const bool ok = pick_int<1, 2, 3, 4, 5>(H, [&](auto nt) {
+        pick_bool(s->net.in_dim != 13, [&](auto wide) {
+            pick_bool(att != nullptr, [&](auto a) {
+                hipLaunchKernelGGL((cn::sarl_f16_kernel<cn::f16_key(decltype(wide)::value ? 2 : 1, decltype(nt)::value), decltype(nt)::value, decltype(a)::value>), grid,
+                                   kRegBlock, 0, e->stream, (const _Float16*)s->f16_stream, (const float*)s->f16_bias, (const float*)s->X,
+                                   s->V, (int)s->n_groups, (int)s->n_tiles, s->net.ks_x, (const int*)s->hcount, att);
             });
         });
     });
@@ -567,6 +632,7 @@ int sarl_select(cn_engine* e, double* values, int32_t* best, double* action, flo
         }
         case SarlRoute::RegSarl: rc = launch_reg_sarl(e, att); break;
         case SarlRoute::RegSarlChunk: rc = launch_reg_sarl_chunk(e, att); break;
+        case SarlRoute::SplitF16: rc = launch_split_f16(e, att); break;
         case SarlRoute::RegCadrl: rc = launch_reg_cadrl(e); break;
         case SarlRoute::RegLstm:
         case SarlRoute::RegLstm2: launch_reg_lstm(e); break;
@@ -625,6 +691,7 @@ int cn_sarl_configure(cn_engine* e, const cn_sarl_config* c, const double* actio
     C.cadrl = c->model == CN_MODEL_CADRL ? 1 : 0;
     C.sort_lookahead = (C.const_vel && c->model == CN_MODEL_LSTM_RL) ? 1 : 0;
     s->net.in_dim = 13 + om_width(*c), s->net.with_global = c->with_global_state ? 1 : 0, s->net.H = H;
+    if (c->precision == CN_PRECISION_F16X2 && (rc = sarl_f16_supported(e, *c, H, s->net.in_dim))) return rc;
     bool lds_chunked = false;
     if ((rc = dev_alloc(e, &s->arena, kSarlArenaFloats)) || (rc = sarl_size_network(s, &lds_chunked))) return rc;
     s->route = sarl_choose_route(s, lds_chunked);
@@ -700,6 +767,14 @@ int cn_sarl_select_attention(cn_engine* e, double* values, int32_t* best, double
             return fail(CN_ERR_UNSUPPORTED, "cn_sarl_select_attention: only sarl.ValueNetwork has attention weights");
     }
     return sarl_select(e, values, best, action, attention);
+}
+
+int cn_sarl_network_route(cn_engine* e, int* route_host) {
+    if (!e) return fail(CN_ERR_INVALID, "engine is NULL");
+    if (!e->sarl) return fail(CN_ERR_INVALID, "cn_sarl_network_route: cn_sarl_configure first");
+    if (!route_host) return fail(CN_ERR_INVALID, "cn_sarl_network_route: route_host is NULL");
+    *route_host = (int)e->sarl->route;
+    return CN_OK;
 }
 
 int cn_sarl_explore(cn_engine* e, double epsilon, const uint8_t* mask, int32_t* best, double* action,

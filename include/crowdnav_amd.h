@@ -304,8 +304,22 @@ typedef struct cn_sarl_config {
                                    time limit); for CN_MODEL_LSTM_RL the humans then enter the network in the order
                                    LstmRL.predict sorted them (decreasing distance to the robot, lstm_rl.py:96-103).
                                    SARL / LSTM-RL only: CADRL.predict always queries the env. */
-    int32_t reserved;
+    int32_t precision;          /* (the former `reserved` word: no ABI bump, zero keeps every caller's meaning) CN_PRECISION_*:
+                                   the arithmetic of the value network's linear layers in cn_sarl_select /
+                                   cn_sarl_select_attention / cn_sarl_sample_step at the sizes that leave the narrow tiles.
+                                   CN_PRECISION_F32 (0): fp32 matrix instructions, as ever.  CN_PRECISION_F16X2 (1): the
+                                   split-f16 route — every weight and every activation as two f16 terms (x ~ xh + xl / 2^11),
+                                   three f16 matrix products per layer in two fp32 accumulators, everything between the
+                                   layers in fp32: values within 1e-6 of the fp32 routes on the shipped networks (DESIGN.md
+                                   §3.9).  CN_MODEL_SARL at the shipped layer widths (13- or 61-wide rows, with_global_state
+                                   = 1) and 1..5 humans, not under the `mixed` rule; cn_sarl_configure returns
+                                   CN_ERR_UNSUPPORTED with the reason for anything else (it never falls back) and
+                                   CN_ERR_INVALID for any other value of this word.  An activation beyond the f16 range
+                                   (|a| > 65504; the shipped networks stay below 100) makes that env's values NaN, hence
+                                   best = -2: never a wrong finite value.  The narrow tiles (a few envs) and cn_sarl_values
+                                   stay fp32. */
 } cn_sarl_config;
+enum { CN_PRECISION_F32 = 0, CN_PRECISION_F16X2 = 1 };
 
 /* replaces SARL.configure + CADRL.build_action_space: actions_host = double [n_actions][2] (ActionXY table, HOST
  * pointer, computed by the caller exactly as cadrl.py:86-99 does).  Synchronous; once per engine.
@@ -336,6 +350,20 @@ int cn_sarl_select(cn_engine* e, double* values, int32_t* best, double* action);
  * bit-identical to cn_sarl_select's on the same state, and attention == NULL IS cn_sarl_select.  CN_MODEL_SARL only:
  * CN_MODEL_CADRL and CN_MODEL_LSTM_RL (no attention in the reference) return CN_ERR_UNSUPPORTED. */
 int cn_sarl_select_attention(cn_engine* e, double* values, int32_t* best, double* action, float* attention);
+/* (no ABI bump: a new symbol only) which kernel family runs the value network of this configuration — route_host: HOST int,
+ * one of CN_SARL_ROUTE_*, chosen once by cn_sarl_configure.  Host-only: launches nothing, counts nothing. */
+enum {
+    CN_SARL_ROUTE_LDS_TILE = 0,       /* a tile's activations in LDS, a workgroup per tile */
+    CN_SARL_ROUTE_LDS_CHUNKED = 1,    /* ... the humans streamed through the tile in chunks */
+    CN_SARL_ROUTE_NARROW = 2,         /* a few decisions on 16-row tiles */
+    CN_SARL_ROUTE_REG_SARL = 3,       /* activations in registers, a wave per tile: sarl.ValueNetwork, 1..5 humans */
+    CN_SARL_ROUTE_REG_SARL_CHUNK = 4, /* ... 6+ humans */
+    CN_SARL_ROUTE_REG_CADRL = 5,
+    CN_SARL_ROUTE_REG_LSTM = 6,
+    CN_SARL_ROUTE_REG_LSTM2 = 7,
+    CN_SARL_ROUTE_SPLIT_F16 = 8       /* CN_PRECISION_F16X2: activations in registers, split-f16 matrix instructions */
+};
+int cn_sarl_network_route(cn_engine* e, int* route_host);
 /* replaces the epsilon-greedy branch of MultiHumanRL.predict in the train phase (multi_human_rl.py:28-31), applied to
  * the best/action a cn_sarl_select just produced: per env (mask == NULL or mask[b] != 0, and not already at its goal)
  *   probability = np.random.random(); if probability < epsilon: action_space[np.random.choice(n_actions)]
