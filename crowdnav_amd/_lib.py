@@ -126,6 +126,7 @@ SYMBOLS = {
     'cn_records_summary': (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     'cn_rollout_summary': (C.c_int, [_P, C.POINTER(CnRolloutIo), _P]),
     'cn_launch_counts': (C.c_int, [_P, _P]),
+    'cn_lagged_fills': (C.c_int, [_P, _P]),
     'cn_mt_random': (C.c_int, [_P, C.c_uint32, C.c_int, _P]),
     # device SGD step (added after v12, no version bump)
     'cn_trainer_create': (C.c_int, [C.POINTER(CnSarlConfig), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -57,6 +57,20 @@ static hipError_t sync_fill_streams(const cn_engine* e) {
     return first;
 }
 
+// CN_FLAG_ASYNC_SCENARIO_FILL: fill kernels still in flight on the side streams read the device copy of the io block, the
+// caller's buffers behind it and the claim / ready flags.  Before any of those change hands (a new io block, a restart of the
+// bookkeeping) the host waits for them: a straggler of the previous rollout must not publish a scenario of the old seed
+// numbering into the new one's ring, nor read buffers the caller is about to free.  The lagged fill (fill_plan.h) reads the io
+// block and the envs' episode words in the same way; once it has been waited for, its levels are the ring's.
+static int drain_fill_streams(cn_engine* e) {
+    CN_HIP(sync_fill_streams(e));
+    if (e->lag_pending) std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
+    e->lag_pending = false;
+    return CN_OK;
+}
+// ... by the entry points that read or write env state from outside a rollout: nothing to wait for unless a lagged fill is out
+static int settle_lagged_fill(cn_engine* e) { return e->lag_pending ? drain_fill_streams(e) : CN_OK; }
+
 extern "C" {
 
 const char* cn_last_error(void) { return cn_g_err; }
@@ -163,6 +177,10 @@ static void pick_geometry(cn_engine* e) {
     P.ring_depth = env_int("CROWDNAV_AMD_RING_DEPTH", 48);
     if (P.ring_depth < 1) P.ring_depth = 1;
     if (e->async_fill && !getenv("CROWDNAV_AMD_RING_DEPTH")) P.ring_depth = 144;
+    // Lagged fill (fill_plan.h; CROWDNAV_AMD_LAGGED_FILL, default on): the lane-per-scenario generator's ring gets 2 D slots per
+    // env and its top-ups run on a side stream beside the launches.  0: D slots, every fill in front of the launch that needs it.
+    e->plan.configure(P.ring_depth, !e->gen_wave && !e->async_fill && env_int("CROWDNAV_AMD_LAGGED_FILL", 1) != 0);
+    P.ring_mod = e->plan.C;
 }
 
 // The run-time switches and what they are weighed against: the device's size.
@@ -194,6 +212,13 @@ static void read_knobs(cn_engine* e) {
     hipDeviceProp_t prop;
     const bool ok = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0;
     e->sched_slots = 12 * (ok ? prop.multiProcessorCount : 256);
+    // The lagged fill pays where a launch is ONE round of workgroups: its waves then run in the launch's tail.  Beside a launch of
+    // several rounds they take slots from queued workgroups instead (32768 envs: 1.2 % slower than the fill in front).  Two waves
+    // per SIMD is what every rollout kernel fits: 8 one-wave workgroups per CU.
+    if (e->plan.lagged() && grid_envs(e) > 8 * (ok ? prop.multiProcessorCount : 256)) {
+        e->plan.configure(P.ring_depth, false);
+        P.ring_mod = e->plan.C;
+    }
     e->split_slots = 0;
     if (ok && headline_geometry(P))  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
         pick_fused(e, CN_ROUTE_FUSED_SPLIT, [&](auto kernel, int threads) {
@@ -216,10 +241,11 @@ static int alloc_state(cn_engine* e) {
         (rc = dev_alloc(e, &S.rsim_radius, n)) || (rc = dev_alloc(e, &S.rsim_max_speed, (size_t)P.B)) ||
         (rc = dev_alloc(e, &S.rsim_valid, (size_t)P.B)) || (rc = dev_alloc(e, &S.mt_key, (size_t)624 * P.B)) ||
         (rc = dev_alloc(e, &S.mt_pos, (size_t)P.B)) || (rc = dev_alloc(e, &e->probe_key, (size_t)624)) ||
-        (rc = dev_alloc(e, &S.ring_pos, n * P.ring_depth)) || (rc = dev_alloc(e, &S.ring_goal, n * P.ring_depth)) ||
-        (rc = dev_alloc(e, &S.ring_rv, n * P.ring_depth)) ||
+        (rc = dev_alloc(e, &S.ring_pos, n * P.ring_mod)) || (rc = dev_alloc(e, &S.ring_goal, n * P.ring_mod)) ||
+        (rc = dev_alloc(e, &S.ring_rv, n * P.ring_mod)) ||
         (rc = dev_alloc(e, &S.ring_mt_key, e->gen_wave ? (size_t)64 : (size_t)624 * cn::kRedoLanes)) ||
-        (rc = dev_alloc(e, &S.redo_list, e->gen_wave ? (size_t)1 : (size_t)P.B * P.ring_depth)) ||
+        (rc = dev_alloc(e, &S.redo_list, e->gen_wave ? (size_t)1 : (size_t)P.B * P.ring_mod)) ||
+        (rc = dev_alloc(e, &e->ep_snap, e->plan.lagged() ? (size_t)P.B : (size_t)1)) ||
         (rc = dev_alloc(e, &S.redo_count, (size_t)1)) ||
         (rc = dev_alloc(e, &e->summary_scratch, (size_t)cn::kSummaryBlocks * cn::kSummaryFields + 1)) ||
         (rc = dev_alloc(e, &S.ring_filled_in, (size_t)P.B)) || (rc = dev_alloc(e, &S.ring_filled_out, (size_t)P.B)) ||
@@ -247,6 +273,16 @@ static int alloc_state(cn_engine* e) {
         for (int i = 0; ok && i < cn_engine::kFillStreams; ++i)
             ok = hipStreamCreateWithFlags(&e->fill_streams[i], hipStreamNonBlocking) == hipSuccess;
         if (!ok) return fail(CN_ERR_HIP, "cn_create: side streams for the asynchronous scenario fill");
+    }
+    if (e->plan.lagged()) {
+        // lowest priority: the launch it runs beside becomes ready at the same moment and must get the chip first; the fill's
+        // waves take the slots that launch leaves or gives back
+        int least = 0, greatest = 0;
+        if (hipEventCreateWithFlags(&e->rollout_done, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&e->fill_done, hipEventDisableTiming) != hipSuccess ||
+            hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
+            hipStreamCreateWithPriority(&e->fill_streams[0], hipStreamNonBlocking, least) != hipSuccess)
+            return fail(CN_ERR_HIP, "cn_create: side stream for the lagged scenario fill");
     }
     return CN_OK;
 }
@@ -280,6 +316,7 @@ int cn_destroy(cn_engine* e) {
     for (hipStream_t fs : e->fill_streams)
         if (fs) (void)hipStreamDestroy(fs);
     if (e->rollout_done) (void)hipEventDestroy(e->rollout_done);
+    if (e->fill_done) (void)hipEventDestroy(e->fill_done);
     e->alloc_rollback(cn_engine::AllocMark{});
     if (e->discount) (void)hipFree(e->discount);
     cn_sarl_release(e);
@@ -298,7 +335,7 @@ int cn_sync(cn_engine* e) {
     int rc = bind(e);
     if (rc) return rc;
     CN_HIP(hipStreamSynchronize(e->stream));
-    CN_HIP(sync_fill_streams(e));
+    if ((rc = drain_fill_streams(e))) return rc;
     int gen_error = 0;
     CN_HIP(hipMemcpy(&gen_error, e->C.error, sizeof(int), hipMemcpyDeviceToHost));
     if (gen_error) {
@@ -345,7 +382,7 @@ __global__ void unpack_state_kernel(int n, double* state8, cn::StateView S) {
 
 int cn_set_state(cn_engine* e, const double* state8, const double* global_time) {
     int rc = bind(e);
-    if (rc) return rc;
+    if (rc || (rc = settle_lagged_fill(e))) return rc;
     const int n = e->P.B * e->P.A;
     if (state8) hipLaunchKernelGGL(pack_state_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, state8, e->S);
     if (global_time)
@@ -356,7 +393,7 @@ int cn_set_state(cn_engine* e, const double* state8, const double* global_time) 
 
 int cn_get_state(cn_engine* e, double* state8, double* global_time) {
     int rc = bind(e);
-    if (rc) return rc;
+    if (rc || (rc = settle_lagged_fill(e))) return rc;
     const int n = e->P.B * e->P.A;
     if (state8) hipLaunchKernelGGL(unpack_state_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, state8, e->S);
     if (global_time)
@@ -443,7 +480,7 @@ int cn_drop_sims(cn_engine* e) {
 
 int cn_reset(cn_engine* e, const uint32_t* seeds, const uint8_t* mask, uint64_t* draws) {
     int rc = bind(e);
-    if (rc) return rc;
+    if (rc || (rc = settle_lagged_fill(e))) return rc;
     if (!seeds) return fail(CN_ERR_INVALID, "cn_reset: seeds is NULL");
     if (e->gen_wave)
         hipLaunchKernelGGL(cn::reset_wave_kernel, dim3(e->P.B), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, seeds, mask,
@@ -467,7 +504,7 @@ int cn_orca(cn_engine* e, float* out_vel) {
 int cn_step(cn_engine* e, const double* action, int update, double* reward, uint8_t* done, uint8_t* info,
             double* dmin, double* action_out, float* orca_vel, double* obs) {
     int rc = bind(e);
-    if (rc) return rc;
+    if (rc || (rc = settle_lagged_fill(e))) return rc;
     if (!reward || !done || !info) return fail(CN_ERR_INVALID, "cn_step: reward/done/info must not be NULL");
     if (e->P.robot_orca && action)
         return fail(CN_ERR_INVALID, "cn_step: action must be NULL when robot_policy == CN_ROBOT_ORCA");
@@ -497,15 +534,6 @@ int cn_set_gamma(cn_engine* e, double gamma) {
     CN_HIP(hipMalloc(reinterpret_cast<void**>(&e->discount), sizeof(double) * len));
     CN_HIP(hipMemcpy(e->discount, table.data(), sizeof(double) * len, hipMemcpyHostToDevice));
     e->discount_len = len;
-    return CN_OK;
-}
-
-// CN_FLAG_ASYNC_SCENARIO_FILL: fill kernels still in flight on the side streams read the device copy of the io block, the
-// caller's buffers behind it and the claim / ready flags.  Before any of those change hands (a new io block, a restart of the
-// bookkeeping) the host waits for them: a straggler of the previous rollout must not publish a scenario of the old seed
-// numbering into the new one's ring, nor read buffers the caller is about to free.
-static int drain_fill_streams(cn_engine* e) {
-    CN_HIP(sync_fill_streams(e));
     return CN_OK;
 }
 
@@ -554,13 +582,14 @@ int cn_rollout_begin(cn_engine* e, const cn_rollout_io* io) {
     else
         hipLaunchKernelGGL(cn::rollout_begin_kernel, dim3(grid_lanes(e)), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
     CN_HIP(hipGetLastError());
-    e->steps_since_fill = -1;
+    e->plan.begin();
     return CN_OK;
 }
 
-// Top the scenario ring up to ring_depth episodes ahead of every env.  An env consumes at most one ring scenario per
-// transition, so after a fill the next ring_depth transitions cannot run it dry: launches inside that budget skip the
-// fill kernels altogether (a 20-step cn_rollout call used to spend more time here than in its transitions).
+// Top the scenario ring up ahead of every env.  An env consumes at most one ring scenario per transition, so after a fill
+// the next ring_depth transitions cannot run it dry: launches inside that budget skip the fill kernels altogether (a 20-step
+// cn_rollout call used to spend more time here than in its transitions).  Which calls fill, and whether in front of their
+// launch or beside it, is fill_plan.h's rule.
 static int fill_ring_if_needed(cn_engine* e, const cn::RolloutView& R, int n_steps) {
     if (e->async_fill) {
         // a fill launch per transition launch, on the next side stream, ordered after the PREVIOUS transition kernel (whose
@@ -582,26 +611,54 @@ static int fill_ring_if_needed(cn_engine* e, const cn::RolloutView& R, int n_ste
         hipLaunchKernelGGL(cn::ring_fill_scan_kernel, dim3((items + 255) / 256), dim3(256), 0, fs, e->P, e->S, R, list);
         hipLaunchKernelGGL(cn::ring_fill_jobs_kernel, dim3(e->fill_queue_wgs), dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, list);
         e->launch_counts[CN_COUNT_ASYNC_FILLS] += 1;
-        e->steps_since_fill = 0;
         return CN_OK;
     }
-    if (e->steps_since_fill >= 0 && e->steps_since_fill + n_steps <= e->P.ring_depth) {
-        e->steps_since_fill += n_steps;
-        return CN_OK;
+    if (e->lag_pending) {  // the fill that ran beside the previous launch: this launch waits for it and takes its levels
+        CN_HIP(hipStreamWaitEvent(e->stream, e->fill_done, 0));
+        std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
+        e->lag_pending = false;
     }
-    const int fill_lanes = e->P.B * e->P.ring_depth;
-    const dim3 fill_grid((fill_lanes + cn::kWave - 1) / cn::kWave);
-    if (e->gen_wave) {
-        hipLaunchKernelGGL(cn::ring_fill_wave_kernel, dim3(fill_lanes), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
-    } else {
-        CN_HIP(hipMemsetAsync(e->S.redo_count, 0, sizeof(int), e->stream));
-        hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
-        hipLaunchKernelGGL(cn::ring_redo_kernel, dim3(cn::kRedoLanes / cn::kWave), dim3(cn::kWave), 0, e->stream, e->P, e->C,
-                           e->S);
+    e->lag_due = false;
+    const cn::FillPlan::Decision plan = e->plan.call(n_steps);
+    const int fill_lanes = e->P.B * e->P.ring_mod;
+    const dim3 fill_grid((fill_lanes + cn::kWave - 1) / cn::kWave), redo_grid(cn::kRedoLanes / cn::kWave);
+    if (plan.sync_fill) {
+        if (e->gen_wave) {
+            hipLaunchKernelGGL(cn::ring_fill_wave_kernel, dim3(fill_lanes), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
+        } else {
+            CN_HIP(hipMemsetAsync(e->S.redo_count, 0, sizeof(int), e->stream));
+            hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R, nullptr);
+            hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S);
+        }
+        std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
+        e->launch_counts[CN_COUNT_RING_FILLS] += 1;
     }
-    std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
+    if (plan.lagged_fill) {
+        // ordered behind everything in front of the launch about to be enqueued (the previous launch's episode words, the levels
+        // a synchronous fill just wrote); the fill itself is enqueued behind that launch (enqueue_lagged_fill)
+        CN_HIP(hipEventRecord(e->rollout_done, e->stream));
+        e->lag_due = true;
+    }
+    return CN_OK;
+}
+
+// The lagged fill fill_ring_if_needed decided on, enqueued once the launch it runs beside has been: it reads ring_filled_in, as
+// that launch does, and writes ring_filled_out and ring slots of ordinals >= the level the launch was given.
+static int enqueue_lagged_fill(cn_engine* e, const cn::RolloutView& R) {
+    if (!e->lag_due) return CN_OK;
+    e->lag_due = false;
+    hipStream_t fs = e->fill_streams[0];
+    const int fill_lanes = e->P.B * e->P.ring_mod;
+    CN_HIP(hipStreamWaitEvent(fs, e->rollout_done, 0));
+    hipLaunchKernelGGL(cn::ring_fill_begin_kernel, dim3(grid_lanes(e)), dim3(cn::kWave), 0, fs, e->P.B, e->S.ep_word, e->ep_snap,
+                       e->S.redo_count);
+    hipLaunchKernelGGL(cn::ring_fill_kernel, dim3((fill_lanes + cn::kWave - 1) / cn::kWave), dim3(cn::kWave), 0, fs, e->P, e->C, e->S,
+                       R, (const int*)e->ep_snap);
+    hipLaunchKernelGGL(cn::ring_redo_kernel, dim3(cn::kRedoLanes / cn::kWave), dim3(cn::kWave), 0, fs, e->P, e->C, e->S);
+    CN_HIP(hipEventRecord(e->fill_done, fs));
+    e->lag_pending = true;
     e->launch_counts[CN_COUNT_RING_FILLS] += 1;
-    e->steps_since_fill = n_steps;
+    e->lagged_fills += 1;
     return CN_OK;
 }
 
@@ -740,7 +797,7 @@ int cn_rollout(cn_engine* e, const cn_rollout_io* io, int n_steps) {
     if (rc) return rc;
     launch_rollout(e, R, n_steps, nullptr);  // the fused transitions
     CN_HIP(hipGetLastError());
-    return CN_OK;
+    return enqueue_lagged_fill(e, R);
 }
 
 // cn_rollout with the per-step rows of `out`: cn_rollout's host path, then ONE launch of rollout_trace_kernel — the generic
@@ -768,7 +825,7 @@ int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const c
     });
     e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
     CN_HIP(hipGetLastError());
-    return CN_OK;
+    return enqueue_lagged_fill(e, R);
 }
 
 int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action) {
@@ -779,13 +836,19 @@ int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action)
     if (rc) return rc;
     launch_rollout(e, R, 1, action);
     CN_HIP(hipGetLastError());
-    return CN_OK;
+    return enqueue_lagged_fill(e, R);
 }
 
 int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
     if (!e || !route_host) return fail(CN_ERR_INVALID, "cn_rollout_route: NULL argument");
     if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
     *route_host = rollout_route(e, nullptr);  // (no route depends on the call's length today; the shard's schedules are not routes)
+    return CN_OK;
+}
+
+int cn_lagged_fills(cn_engine* e, uint64_t* count_host) {
+    if (!e || !count_host) return fail(CN_ERR_INVALID, "cn_lagged_fills: NULL argument");
+    *count_host = e->lagged_fills;
     return CN_OK;
 }
 

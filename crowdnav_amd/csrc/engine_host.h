@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/crowdnav_amd.h"
+#include "fill_plan.h"
 #include "step_kernels.h"
 
 
@@ -66,7 +67,14 @@ struct cn_engine {
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one
     uint32_t begin_seed_base = 0, begin_seed_mod = 0;  // (the scenario cache is sized and keyed by them)
-    int steps_since_fill = -1;     // transitions launched since the scenario ring was last topped up; < 0 = never filled
+    // lane-per-scenario generator (!gen_wave, !async_fill): when the ring is filled (fill_plan.h).  A lagged fill runs on
+    // fill_streams[0] beside a launch, reading ep_snap; the next call's launch waits for fill_done and takes its levels
+    cn::FillPlan plan;
+    bool lag_due = false;          // fill_ring_if_needed decided on a lagged fill: enqueued right behind the launch
+    bool lag_pending = false;      // a lagged fill has been enqueued whose levels (ring_filled_out) no launch has taken yet
+    hipEvent_t fill_done = nullptr;
+    int* ep_snap = nullptr;        // [B] the lagged fill's copy of StateView::ep_word (ring_fill_begin_kernel)
+    uint64_t lagged_fills = 0;     // cn_lagged_fills: fills enqueued beside a launch (counted in CN_COUNT_RING_FILLS too)
     struct cn_sarl* sarl = nullptr;  // SARL decision state (sarl_abi.hip), NULL until cn_sarl_configure
     bool orca_fresh = false;  // cn_sarl_sample_step: the humans' ORCA velocities of the CURRENT state are in sarl->orca_vel (left by the
                               // previous call's transition kernel); cleared by every other entry point (bind)

@@ -105,10 +105,10 @@
     if (robot) {
         const StateView S = *Sd;
         const cn_rollout_io io = *R.io;
-        CN_LOAD_EPISODE(ep, S, io, ring_filled_in, L.env);
+        CN_LOAD_EPISODE(P, ep, S, io, ring_filled_in, L.env);
         int f = ep.state == kRunning ? 1 : 0;
         if (ep.state == kWaitingScenario && scenario_ready(P, S, L.env, ep.ep_count, ep.ring_filled)) {  // produced since
-            f = 2 + ep.ep_count % P.ring_depth;
+            f = 2 + ep.ep_count % P.ring_mod;
             ep.state = kRunning;
             ep.gtime = 0.0;
         }
@@ -199,7 +199,7 @@
                     e.ep_count = book.ep_count, e.ring_filled = book.ring_filled, e.state = kRunning;
                     const cn_rollout_io io = *R.io;
                     next_flag = 0;
-                    CN_END_EPISODE(P, *Sd, io, L.env, true, s.disc[kParLimit], res.info, e, next_flag = 2 + e.ep_count % P.ring_depth);
+                    CN_END_EPISODE(P, *Sd, io, L.env, true, s.disc[kParLimit], res.info, e, next_flag = 2 + e.ep_count % P.ring_mod);
                     book.ep_count = e.ep_count, book.state = e.state;
                 }
                 book.gtime = e.gtime;
@@ -221,7 +221,7 @@
                 if (res.done) {  // 0 = the env stops stepping (retired, or waiting for its scenario), 2 + slot = every lane loads it
                     const cn_rollout_io io = *R.io;
                     next_flag = 0;
-                    CN_END_EPISODE(P, *Sd, io, L.env, true, P.time_limit, res.info, ep, next_flag = 2 + ep.ep_count % P.ring_depth);
+                    CN_END_EPISODE(P, *Sd, io, L.env, true, P.time_limit, res.info, ep, next_flag = 2 + ep.ep_count % P.ring_mod);
                 }
                 s.flag[L.lane] = next_flag;
             }

@@ -374,7 +374,7 @@ __device__ __forceinline__ StepOutcome reduce_env(const Params& P, const Smem& s
 
 // reduce -> account -> episode end of a transition run on every lane of a running env identically (the book is carried
 // redundantly; the robot lane writes the record), with the shared statements of step_kernels.h: CN_BOOK_TRANSITION, and at an
-// episode end CN_END_EPISODE, whose decision is ep.state (kRunning: load ring slot ep.ep_count % P.ring_depth).  The one-wave
+// episode end CN_END_EPISODE, whose decision is ep.state (kRunning: load ring slot ep.ep_count % P.ring_mod).  The one-wave
 // step loop and the env wave each spell the dozen lines around them themselves: the one-wave loop integrates between the
 // reduce and the accounting, the env wave requests the next scenario before the record stores, and as ONE helper — function
 // or macro — that sequence cost the one-wave kernels 1.1 % (profiles/episode_book_refactor.txt).
@@ -588,7 +588,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
         const float ms_kept = P.robot_orca ? S.rsim_max_speed[env] : 0.0f;
         const double theta0 = S.theta[env];
         EpisodeBook ep0;
-        CN_LOAD_EPISODE(ep0, S, io, ring_filled_in, env);
+        CN_LOAD_EPISODE(P, ep0, S, io, ring_filled_in, env);
         if (L.valid) {
             r.px = p0.x, r.py = p0.y, r.vx = v0.x, r.vy = v0.y, r.gx = g0.x, r.gy = g0.y, r.rad = q0.x, r.vpref = q0.y;
             ep = ep0;  // (every lane of the env: the book is carried redundantly, see the step loop)
@@ -607,7 +607,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     build_pairs(P, s);
 
     if (L.valid && ep.state == kWaitingScenario && scenario_ready(P, *Sd, L.env, ep.ep_count, ep.ring_filled)) {  // produced since
-        load_from_ring(P, *Sd, L, ep.ep_count % P.ring_depth, r);
+        load_from_ring(P, *Sd, L, ep.ep_count % P.ring_mod, r);
         ep.state = kRunning;
         ep.gtime = 0.0;
         theta = 1.5707963267948966;
@@ -696,7 +696,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                         const cn_rollout_io io = *iop;
                         const StateView S = *Sd;
                         AgentRegs next = r;
-                        load_from_ring(P, S, L, (ep.ep_count + 1) % P.ring_depth, next);
+                        load_from_ring(P, S, L, (ep.ep_count + 1) % P.ring_mod, next);
                         CN_END_EPISODE(P, S, io, L.env, L.a == 0, K.limit, o.info, ep, r = next; theta = 1.5707963267948966);
                     }
                 }
@@ -783,7 +783,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             if (done) {  // explorer.py:50-72: record, then the env's next episode
                 const cn_rollout_io io = *iop;
                 CN_END_EPISODE(P, *Sd, io, L.env, L.a == 0, K.limit, info, ep,
-                               load_from_ring(P, *Sd, L, ep.ep_count % P.ring_depth, r); theta = 1.5707963267948966);
+                               load_from_ring(P, *Sd, L, ep.ep_count % P.ring_mod, r); theta = 1.5707963267948966);
             }
         }
         stage_agent(P, s, L, r, K.hsafety);

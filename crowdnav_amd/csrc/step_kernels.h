@@ -43,7 +43,7 @@ struct Params {
     int nA;            // E * A agent lanes
     int NC;            // A - 1 candidate neighbours per agent
     int pairs;         // nA * NC
-    int ring_depth;    // scenarios kept ahead per env
+    int ring_depth;    // D: scenarios a launch may look ahead of an env's next one
     int robot_visible, robot_orca;
     int robot_unicycle;  // external robot actions are ActionRot(v, r) (agent.py:115-135)
     int async_fill;      // CN_FLAG_ASYNC_SCENARIO_FILL: ring slots are published one by one (StateView::ring_ready)
@@ -55,6 +55,8 @@ struct Params {
     double dt, time_limit, success_reward, collision_penalty, discomfort_dist, discomfort_factor;
     double robot_safety, human_safety;
     OrcaParams orca;
+    int ring_mod;      // C: ring slots per env, ordinal o lives in slot o % C (D, or 2 D with the lagged fill: fill_plan.h); last,
+                       // so that every other field keeps its place in the kernels' argument blocks
 };
 
 struct StateView {
@@ -69,11 +71,11 @@ struct StateView {
     uint8_t* rsim_valid;    // [B]
     uint32_t* mt_key;       // [624][B]   generator state of the env's own stream
     uint32_t* ring_mt_key;  // [624][kRedoLanes] HBM generator scratch of ring_redo_kernel (scenarios the head generator gave up on)
-    int2* redo_list;        // [B*D] (ring index, seed) of those scenarios; redo_count [1] = how many (zeroed before a fill)
+    int2* redo_list;        // [B*C] (ring index, seed) of those scenarios; redo_count [1] = how many (zeroed before a fill)
     int* redo_count;
     int* mt_pos;            // [B]
     // scenario ring: the next ring_depth episodes of every env, generated ahead of the rollout
-    double2* ring_pos;      // [B][D][A]
+    double2* ring_pos;      // [B][C][A]
     double2* ring_goal;
     double2* ring_rv;
     int* ring_filled_in;    // [B] episode ordinals < this have been generated (read side)
@@ -1262,7 +1264,7 @@ __device__ __forceinline__ bool past_episode_limit(const cn_rollout_io& io, int6
 // env as ONE word, stored once by the transition kernel when it ends: two separate loads of io->active / io->ep_count could
 // pair an old state with a new count and claim a slot whose scenario has not been consumed yet
 __device__ __forceinline__ int ring_next_ordinal(int ep_count, int state) { return ep_count + (state == kWaitingScenario ? 0 : 1); }
-// the one ordinal of [next, next + D) that lives in ring slot `slot` (ordinal o lives in slot o % D)
+// the one ordinal of [next, next + D) that lives in ring slot `slot` (ordinal o lives in slot o % D; D = Params::ring_mod)
 __device__ __forceinline__ int ring_slot_ordinal(int next, int slot, int D) { return next + ((slot - next % D) + D) % D; }
 // Asynchronous fill: claim slot idx = (env, ordinal % D) for `ordinal`.  False: resident already, or another fill launch is
 // generating (or has generated) exactly this scenario.  Only slots whose scenario the env consumed before the transition
@@ -1308,31 +1310,44 @@ __global__ __launch_bounds__(kWave) void rollout_begin_kernel(Params P, Scenario
     S.gtime[b] = 0.0;
 }
 
-// Scenario ring fill: one lane per (env, ring slot) generates the episode whose ordinal maps to that slot
-// if it has not been generated yet, so that ordinals [next, next + D) are resident when the rollout
+// Scenario ring fill: one lane per (env, missing scenario) generates an episode that has not been generated yet, so that ordinals [next, next + D) are resident when the rollout
 // launch that follows needs them.  The lane runs the register-only head generator; the
 // rare scenario whose rejection chain outruns its 227 words is queued in redo_list and regenerated by ring_redo_kernel
 // with a memory-backed generator from a small fixed pool (624 x kRedoLanes words, not 624 x B x D).
 constexpr int kRedoLanes = 4096;
-__global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
+// ep_snap != NULL (the lagged fill, beside a transition kernel: fill_plan.h): (state, episodes finished) of env b comes from
+// ep_snap[b], the copy of StateView::ep_word that ring_fill_begin_kernel took in front of this launch — ONE reading per env
+// for all its lanes, whether that env's workgroup of the running launch had stored the word yet or not.
+__global__ __launch_bounds__(kWave) void ring_fill_begin_kernel(int B, const int* ep_word, int* ep_snap, int* redo_count) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) *redo_count = 0;
+    if (b < B) ep_snap[b] = __hip_atomic_load(&ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R, const int* ep_snap) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int D = P.ring_depth;
+    const int D = P.ring_mod;  // slots per env; the fill tops up to next + D and publishes that level
     if (idx >= P.B * D) return;
-    const int b = idx / D, slot = idx - b * D;
+    // D slots per env (synchronous ring): lane (b, slot), neighbouring lanes write neighbouring slots.  2 D slots (lagged fill):
+    // lane (k, b), k-major, the k-th scenario env b is missing — an env misses as many as it has consumed since the previous
+    // fill, so the lanes with work are the first rows of this numbering, whole waves of them; numbered by slot the same
+    // scenarios sat scattered over twice as many half-empty waves (and, beside a launch, nobody waits for the scattered stores).
+    const bool by_slot = D == P.ring_depth;
+    const int k = by_slot ? idx % D : idx / P.B, b = by_slot ? idx / D : idx - k * P.B;
     const cn_rollout_io* io = R.io;
-    const int state = io->active[b];
-    const int next = ring_next_ordinal(io->ep_count[b], state);
-    if (slot == 0) S.ring_filled_out[b] = next + D;
+    const int state = ep_snap ? ep_snap[b] & 3 : io->active[b];
+    const int next = ring_next_ordinal(ep_snap ? ep_snap[b] >> 2 : io->ep_count[b], state);
+    if (k == 0) S.ring_filled_out[b] = next + D;
     if (state == kRetired) return;
-    const int ordinal = ring_slot_ordinal(next, slot, D);
-    if (ordinal < S.ring_filled_in[b]) return;  // still resident from an earlier fill
+    const int level = S.ring_filled_in[b];  // (ordinals below the stored level are resident from earlier fills)
+    const int ordinal = by_slot ? ring_slot_ordinal(next, k, D) : max(level, next) + k;
+    if (ordinal < level || ordinal >= next + D) return;
     const int64_t c = episode_id(*io, b, ordinal);
     if (past_episode_limit(*io, c)) return;
     const uint32_t seed = episode_seed(*io, c);
-    const size_t base = ((size_t)b * D + slot) * P.A;
+    const int ring_idx = b * D + ordinal % D;
     Mt19937Head head;
-    generate_scenario(C, head, seed, base, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
-    if (head.dead()) S.redo_list[atomicAdd(S.redo_count, 1)] = make_int2(idx, (int)seed);
+    generate_scenario(C, head, seed, (size_t)ring_idx * P.A, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
+    if (head.dead()) S.redo_list[atomicAdd(S.redo_count, 1)] = make_int2(ring_idx, (int)seed);
 }
 
 // The scenarios ring_fill_kernel queued: a fixed grid of kRedoLanes lanes strides over the list, each lane with
@@ -1518,7 +1533,7 @@ __device__ __forceinline__ bool scenario_ready(const Params& P, const StateView&
 
 __device__ __forceinline__ void load_from_ring(const Params& P, const StateView& S, const Lane& L, int slot,
                                                AgentRegs& r) {
-    const size_t ri = ((size_t)L.env * P.ring_depth + slot) * P.A + L.a;
+    const size_t ri = ((size_t)L.env * P.ring_mod + slot) * P.A + L.a;
     const double2 p = S.ring_pos[ri], g = S.ring_goal[ri], q = S.ring_rv[ri];
     r.px = p.x, r.py = p.y, r.vx = 0.0, r.vy = 0.0, r.gx = g.x, r.gy = g.y, r.rad = q.x, r.vpref = q.y;
 }
@@ -1560,7 +1575,7 @@ static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLd
 //
 // The book of env `env` as the previous call left it.  Straight-line loads, none under another's result: a caller that wants
 // them issued in one batch with its other loads expands this unconditionally on a clamped index (rollout_fused.h).
-#define CN_LOAD_EPISODE(e, S, io, ring_filled_in, env)                                            \
+#define CN_LOAD_EPISODE(P, e, S, io, ring_filled_in, env)                                         \
     do {                                                                                          \
         (e).gtime = (S).gtime[env];                                                               \
         (e).state = (io).active[env];                                                             \
@@ -1570,6 +1585,8 @@ static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLd
         (e).cur_return = (io).cur_return[env];                                                    \
         (e).cur_danger = (io).cur_danger ? (io).cur_danger[env] : 0;                              \
         (e).cur_dsum = (io).cur_danger_dmin_sum ? (io).cur_danger_dmin_sum[env] : 0.0;            \
+        /* a launch looks at most ring_depth scenarios ahead, however far the (lagged) fill has got */ \
+        (e).ring_filled = min((e).ring_filled, ring_next_ordinal((e).ep_count, (e).state) + (P).ring_depth); \
     } while (0)
 // ... and as this call leaves it (robot lane), with the robot's heading, the "robot's simulator exists" mark and ep_word;
 // beside it the agent's own state (every agent lane)
@@ -1608,7 +1625,7 @@ static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLd
 // Episode end: append the record (the lane with `write`), start the book afresh, pick the next episode.  The decision is the
 // env's new state, (e).state: kRetired; kWaitingScenario (ring ran dry, or this scenario is still being generated: pause until a
 // later launch); kRunning = go on with the scenario of ordinal (e).ep_count — then, and only then, the statement
-// NEXT_SCENARIO runs: what the kernel does to take it from ring slot (e).ep_count % P.ring_depth.
+// NEXT_SCENARIO runs: what the kernel does to take it from ring slot (e).ep_count % P.ring_mod.
 #define CN_END_EPISODE(P, S, io, env, write, time_limit, info, e, NEXT_SCENARIO)                                              \
     do {                                                                                                                      \
         if (write)                                                                                                            \

@@ -327,10 +327,13 @@ class BatchedCrowdSim(object):
 
     def launch_counts(self):
         """What the host has enqueued for this engine since it was created (cn_launch_counts): dict of _lib.LAUNCH_COUNTERS ->
-        int.  Host-side, no device work: the difference of two calls says which launches a region contained."""
+        int, and 'lagged_fills' (cn_lagged_fills): how many of 'ring_fills' ran on the side stream beside a launch instead of in
+        front of one.  Host-side, no device work: the difference of two calls says which launches a region contained."""
         out = (C.c_uint64 * len(_lib.LAUNCH_COUNTERS))()
         check(self._lib.cn_launch_counts(self._h, out))
-        return dict(zip(_lib.LAUNCH_COUNTERS, (int(v) for v in out)))
+        lagged = C.c_uint64()
+        check(self._lib.cn_lagged_fills(self._h, C.byref(lagged)))
+        return dict(zip(_lib.LAUNCH_COUNTERS, (int(v) for v in out)), lagged_fills=int(lagged.value))
 
     def rollout_route(self, n_steps):
         """Which transition kernel rollout(n_steps) would launch now (cn_rollout_route): one of _lib.ROLLOUT_ROUTES — 'generic',

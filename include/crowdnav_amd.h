@@ -239,7 +239,8 @@ enum {
     CN_COUNT_ROLLOUT_KERNELS = 0,   /* transition kernels launched by cn_rollout / cn_rollout_step */
     CN_COUNT_SCHEDULED_KERNELS = 1, /* ... of which launches of the shard kernel's schedules: one per call under the dynamic
                                        schedule, four per call (sub-launches) under the static 3-of-4 one */
-    CN_COUNT_RING_FILLS = 2,        /* synchronous scenario-ring fills (one per cn_rollout call that needed one) */
+    CN_COUNT_RING_FILLS = 2,        /* scenario-ring fills of the lane-per-scenario and the synchronous wave generators: one per
+                                       cn_rollout call that carried one, in front of its launch or (lagged fill) beside it */
     CN_COUNT_ASYNC_FILLS = 3,       /* fill launches on the side streams (CN_FLAG_ASYNC_SCENARIO_FILL: one per call) */
     CN_COUNT_SARL_NARROW = 4,       /* (ABI v9) value-network launches on the narrow tiles (cn_sarl_select / cn_sarl_sample_step
                                        of a few envs): which route a decision took */
@@ -247,6 +248,13 @@ enum {
 };
 #define CN_LAUNCH_COUNTERS 6
 int cn_launch_counts(cn_engine* e, uint64_t* counts_host);
+
+/* (no ABI bump: a new symbol only) how many of the CN_COUNT_RING_FILLS fills were LAGGED — count_host: HOST uint64.  Engines of
+ * at most 8 humans without CN_FLAG_ASYNC_SCENARIO_FILL keep 2 D ring slots per env (D = CROWDNAV_AMD_RING_DEPTH, default 48) and
+ * top the ring up on a side stream beside a launch, for the call after it, whenever a repeat of the current call would need a
+ * fill; a launch still sees at most D scenarios ahead of each env, so results are those of the synchronous fill.
+ * CROWDNAV_AMD_LAGGED_FILL=0 (read by cn_create) keeps D slots and fills in front of the launch only. */
+int cn_lagged_fills(cn_engine* e, uint64_t* count_host);
 
 /* (no ABI bump: a new symbol only) which transition kernel cn_rollout(e, io, n_steps) would launch NOW — route_host: HOST int,
  * one of CN_ROUTE_*.  Host-only: launches nothing, counts nothing.  The fused two-wave kernel (rollout_fused.h) takes the
