@@ -140,6 +140,8 @@ SYMBOLS = {
     'cn_rollout_route': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     # which kernel family runs the value network (added after v12, no version bump)
     'cn_sarl_network_route': (C.c_int, [_P, C.POINTER(C.c_int)]),
+    # n cn_rollout_step calls with a table of actions as one launch (added after v12, no version bump)
+    'cn_rollout_actions': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, _P, C.POINTER(CnTraceOut)]),
 }
 
 _lib = None

@@ -839,6 +839,38 @@ int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action)
     return enqueue_lagged_fill(e, R);
 }
 
+// n_steps cn_rollout_step calls as one launch: cn_rollout's host path, then the generic phase kernel's table instantiation
+// (rollout_actions_kernel, or rollout_actions_trace_kernel with the rows of `out`) whatever the geometry.  What depends on the
+// arguments alone is refused first, then what depends on the engine; nothing is enqueued before the last check.
+int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const double* actions, const cn_trace_out* out) {
+    if (!actions) return fail(CN_ERR_INVALID, "cn_rollout_actions: actions is NULL");
+    if (out && !out->state8) return fail(CN_ERR_INVALID, "cn_rollout_actions: out->state8 is NULL");
+    if (out && !out->episode) return fail(CN_ERR_INVALID, "cn_rollout_actions: out->episode is NULL");
+    if (out && !out->step) return fail(CN_ERR_INVALID, "cn_rollout_actions: out->step is NULL");
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");
+    if (!e) return fail(CN_ERR_INVALID, "cn_rollout_actions: engine is NULL");
+    if (e->P.robot_orca)
+        return fail(CN_ERR_INVALID, "cn_rollout_actions is for CN_ROBOT_EXTERNAL engines (use cn_rollout)");
+    cn::RolloutView R;
+    const int rc = rollout_prepare(e, io, n_steps, false, &R, actions);
+    if (rc == kNothingToLaunch) return CN_OK;
+    if (rc) return rc;
+    pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
+        constexpr int kMaxl = decltype(maxl)::value;
+        constexpr bool kUni = decltype(uni)::value, kKd = decltype(kd)::value;
+        if (out)
+            hipLaunchKernelGGL((cn::rollout_actions_trace_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads), e->smem,
+                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, actions,
+                               *out);
+        else
+            hipLaunchKernelGGL((cn::rollout_actions_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads), e->smem,
+                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, actions);
+    });
+    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
+    CN_HIP(hipGetLastError());
+    return enqueue_lagged_fill(e, R);
+}
+
 int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
     if (!e || !route_host) return fail(CN_ERR_INVALID, "cn_rollout_route: NULL argument");
     if (n_steps < 0) return fail(CN_ERR_INVALID, "n_steps must be >= 0");

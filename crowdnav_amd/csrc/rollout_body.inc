@@ -1,6 +1,8 @@
-// The body of rollout_kernel and rollout_trace_kernel (step_kernels.h), included once into each: one source, two kernels.
+// The body of rollout_kernel, rollout_trace_kernel and the two rollout_actions kernels (step_kernels.h), included once into
+// each: one source, four kernels.
 // In scope where it is included: MAXL, UNI, HEADLINE, KD (compile-time), P_in, Sd, ring_filled_in, R, n_steps, ext_action,
-// and under CN_ROLLOUT_TRACE the caller's cn_trace_out T.
+// and under CN_ROLLOUT_TRACE the caller's cn_trace_out T.  Under CN_ROLLOUT_ACTIONS the call's action table
+// action_table (double [B][n_steps][2]) takes the place of ext_action.
 // Why an include and not a __device__ __forceinline__ template with a TRACE parameter: with the body behind a call, its
 // arguments passed by value or by reference alike, hipcc gave every existing rollout_kernel instantiation a different
 // instruction stream (a hundred instructions more or fewer each, the 20-human shard's kernel included).  Included text leaves
@@ -172,6 +174,13 @@
         }
 #endif
 
+#ifdef CN_ROLLOUT_ACTIONS
+        // step_core reads the robot lane's action at ext_action[2 * env]: from this base that is action_table[env][step].  Only
+        // the robot lane of a running env reads it (a retired or waiting env ignores its row); the other lanes form no address
+        // outside the table.
+        const double* const ext_action =
+            robot ? action_table + 2 * ((size_t)L.env * (size_t)(n_steps_call - 1) + (size_t)step) : action_table;
+#endif
         StepResult res;
         double nvx, nvy;
         if constexpr (COMPACT) {

@@ -1831,6 +1831,32 @@ __global__ __launch_bounds__(kMaxBlock, 1) void rollout_trace_kernel(Params P_in
 #undef CN_ROLLOUT_TRACE
 }
 
+// cn_rollout_actions: the generic rollout_kernel<MAXL, UNI, false, KD> of an external robot with the call's action table
+// (double [B][n_steps][2]) in place of the one action block every step of a launch shares — the same body under
+// CN_ROLLOUT_ACTIONS, which moves ext_action to the step's row before step_core reads it.  n_steps cn_rollout_step launches
+// as one.  rollout_actions_trace_kernel is the same with the CN_ROLLOUT_TRACE stores (out != NULL): two kernels rather than
+// one that tests T's pointers, so that an untraced call — a planner's — holds no trace registers across the step loop.
+template <int MAXL, bool UNI, bool KD>
+__global__ __launch_bounds__(kMaxBlock, 1) void rollout_actions_kernel(Params P_in, const StateView* Sd, const int* ring_filled_in,
+                                                                       RolloutView R, int n_steps, const double* action_table) {
+    constexpr bool HEADLINE = false;
+#define CN_ROLLOUT_ACTIONS
+#include "rollout_body.inc"
+#undef CN_ROLLOUT_ACTIONS
+}
+
+template <int MAXL, bool UNI, bool KD>
+__global__ __launch_bounds__(kMaxBlock, 1) void rollout_actions_trace_kernel(Params P_in, const StateView* Sd,
+                                                                             const int* ring_filled_in, RolloutView R, int n_steps,
+                                                                             const double* action_table, const cn_trace_out T) {
+    constexpr bool HEADLINE = false;
+#define CN_ROLLOUT_ACTIONS
+#define CN_ROLLOUT_TRACE
+#include "rollout_body.inc"
+#undef CN_ROLLOUT_TRACE
+#undef CN_ROLLOUT_ACTIONS
+}
+
 #endif  // CN_SARL_TU
 
 }  // namespace cn

@@ -241,6 +241,16 @@ class BatchedCrowdSim(object):
         chunks, or pass the previous call's dict as `out` to reuse it (validated; episode is refilled with -1).
         One launch of the generic phase kernel whatever the geometry: slower than rollout(), which it may be mixed with freely.
         crowdnav_amd.trace.episodes() splits the result into episodes on the host."""
+        out = self._trace_out('rollout_trace', n_steps, rewards, out)
+        if out['episode'].shape[1] == 0:  # a no-op, as rollout(0) is (empty tensors have no address to hand over)
+            return out
+        tr = CnTraceOut(**{k: v.data_ptr() for k, v in out.items()})
+        check(self._lib.cn_rollout_trace(self._h, C.byref(self._rollout[0]), int(n_steps), C.byref(tr)))
+        return out
+
+    def _trace_out(self, who, n_steps, rewards, out):
+        """The dict of per-step rows a traced call of n_steps writes (rollout_trace, rollout_actions): fresh tensors, or the
+        caller's `out` validated; episode filled with -1."""
         if self._rollout is None:
             raise RuntimeError('call rollout_begin() first')
         n = int(n_steps)
@@ -257,13 +267,9 @@ class BatchedCrowdSim(object):
                 t = out.get(k)
                 if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape
                         or not t.is_contiguous()):
-                    raise ValueError('rollout_trace: out[%r] must be a contiguous %s %s tensor on %s' % (k, dt, shape, self.device))
+                    raise ValueError('%s: out[%r] must be a contiguous %s %s tensor on %s' % (who, k, dt, shape, self.device))
             out = {k: out[k] for k in spec}
         out['episode'].fill_(-1)
-        if n == 0:  # a no-op, as rollout(0) is (empty tensors have no address to hand over)
-            return out
-        tr =CnTraceOut(**{k: v.data_ptr() for k, v in out.items()})
-        check(self._lib.cn_rollout_trace(self._h, C.byref(self._rollout[0]), n, C.byref(tr)))
         return out
 
     def rollout_step(self, action):
@@ -276,6 +282,30 @@ class BatchedCrowdSim(object):
         if not (torch.is_tensor(action) and a.data_ptr() == action.data_ptr()):
             self.sync()
         return self._rollout[1]
+
+    def rollout_actions(self, actions, trace=False, rewards=False, out=None):
+        """n bookkept transitions of every running env with the actions known in advance, in ONE launch (cn_rollout_actions):
+        what n rollout_step(actions[:, t]) calls do, bit for bit, and may be mixed with.  actions: [B, n, 2] float64 — (vx, vy),
+        or (v, r) for a unicycle robot; row [b, t] is env b's action at step t of THIS call, ignored where the env is retired or
+        waiting for a scenario.  A contiguous float64 tensor on the engine's device is read where it lies (keep it alive until
+        the call has run); anything else is copied and the call synchronises, as rollout_step does.
+        Returns the rollout's bufs; with trace=True the dict rollout_trace returns instead (state8 / episode / step, and with
+        rewards=True reward / info / dmin, rows [b, t]; `out` reuses a previous call's dict) — one launch either way.
+        crowdnav_amd.trace.episodes() cuts it into episodes."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        shape = tuple(getattr(actions, 'shape', np.shape(actions)))
+        if len(shape) != 3 or shape[0] != self.B or shape[2] != 2:
+            raise ValueError('rollout_actions: actions must be [%d, n, 2], got %s' % (self.B, shape))
+        n = int(shape[1])
+        rows = self._trace_out('rollout_actions', n, rewards, out) if trace else None
+        if n > 0:
+            a = self._dev(actions, torch.float64, (self.B, n, 2))
+            tr = None if rows is None else C.byref(CnTraceOut(**{k: v.data_ptr() for k, v in rows.items()}))
+            check(self._lib.cn_rollout_actions(self._h, C.byref(self._rollout[0]), n, _ptr(a), tr))
+            if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
+                self.sync()  # `a` is a temporary copy
+        return rows if trace else self._rollout[1]
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):

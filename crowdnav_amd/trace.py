@@ -1,7 +1,7 @@
-"""Host-side reading of BatchedCrowdSim.rollout_trace results (numpy only, no device work).
+"""Host-side reading of BatchedCrowdSim.rollout_trace / rollout_actions(trace=True) results (numpy only, no device work).
 
-A trace is the dict rollout_trace returns: state8 [B, n, A, 8], episode [B, n], step [B, n] and, with rewards, reward / info /
-dmin [B, n] — row [b, t] is the t-th step of that call (include/crowdnav_amd.h: cn_rollout_trace).  episodes() cuts one trace,
+A trace is the dict either of them returns: state8 [B, n, A, 8], episode [B, n], step [B, n] and, with rewards, reward / info /
+dmin [B, n] — row [b, t] is the t-th step of that call (include/crowdnav_amd.h: cn_rollout_trace, cn_rollout_actions).  episodes() cuts one trace,
 or the traces of consecutive calls, into the episodes the envs ran: what the reference keeps as env.states per episode
 (crowd_sim/envs/crowd_sim.py:246,393)."""
 import numpy as np

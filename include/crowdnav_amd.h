@@ -539,6 +539,30 @@ typedef struct cn_trace_out {      /* all DEVICE pointers */
 } cn_trace_out;
 int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const cn_trace_out* out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Open-loop action table (added after v12, no version bump: purely additive).  Replaces the `while not done: action =
+ * robot.act(ob); env.step(action)` loop of Explorer.run_k_episodes (explorer.py:41-48) for a robot whose actions are KNOWN IN
+ * ADVANCE — a planner scoring candidate action sequences, the recorded actions of an evaluation replayed for its states, the
+ * reference's own episodes re-run: cn_rollout_actions(e, io, n, actions, out) does exactly what n consecutive
+ * cn_rollout_step(e, io, a_t) calls do, with a_t[b] = actions[b][t], in ONE call and one launch — the same transitions,
+ * bookkeeping, seeded auto-reset from the scenario ring, per-env counters, records, transitions / env_transitions, summary /
+ * blocks, the same checks and scenario-ring fill as cn_rollout(e, io, n); it may be mixed freely with cn_rollout_step on one
+ * rollout.
+ *   - actions: DEVICE double [B][n_steps][2].  Row t belongs to step t of THIS call, not to a step index inside an episode;
+ *     an env that is retired or waiting for a scenario at step t ignores its row t.  Holonomic engines read a row as (vx, vy),
+ *     CN_UNICYCLE engines as (v, r): the heading is carried across the steps and is pi / 2 at every episode start.
+ *   - as in cn_rollout, an env that finishes more episodes inside one call than the ring holds ahead of it pauses until the
+ *     next call.
+ *   - out (optional, NULL = no per-step rows): the rows of cn_rollout_trace, by its rules — state8, episode and step required,
+ *     reward, info and dmin optional, arrays [B][n_steps], episode pre-filled with -1 by the caller.
+ * Always ONE launch of the generic phase kernel's table instantiation (counted under CN_COUNT_ROLLOUT_KERNELS, never under
+ * CN_COUNT_SCHEDULED_KERNELS); the fused small-crowd kernels and the 20-human shard kernel are not involved.
+ * Refused before anything is enqueued: NULL e or actions, out with a required array NULL, n_steps < 0: CN_ERR_INVALID; a
+ * CN_ROBOT_ORCA engine: CN_ERR_INVALID (use cn_rollout); an io that does not fit: as cn_rollout.  n_steps == 0: CN_OK, nothing
+ * launched, nothing counted.  Asynchronous on the engine's stream: `actions` and the arrays of `out` must stay valid until the
+ * launch has run. */
+int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const double* actions, const cn_trace_out* out);
+
 #ifdef __cplusplus
 }
 #endif
