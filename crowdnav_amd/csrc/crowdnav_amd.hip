@@ -1,4 +1,5 @@
-// libcrowdnav_amd.so — the C ABI declared in include/crowdnav_amd.h over the HIP kernels of step_kernels.h.
+// libcrowdnav_amd.so — the C ABI declared in include/crowdnav_amd.h over the HIP kernels of step_kernels.h, scenario_ring.h,
+// rollout_kernels.h and rollout_fused.h.
 //
 // Hot path replaced (reference file:line, /root/reference):
 //   CrowdSim.step / onestep_lookahead          crowd_sim/envs/crowd_sim.py:314-420
@@ -12,6 +13,7 @@
 // Built with -ffp-contract=off: float32 ORCA and float64 env arithmetic must round exactly like the CPU
 // reference; the only fused operation is the explicit fma in norm2().
 #include "engine_host.h"
+#include "scenario_ring_host.h"
 #include "rollout_fused.h"
 #include "records_kernels.h"
 
@@ -45,31 +47,6 @@ static void pick_fused(const cn_engine* e, int route, F&& f) {
         f(cn::rollout_fused_kernel<false>, cn::kWave);
     }
 }
-
-// waits for the side streams of the asynchronous scenario fill (none without it); the first error, all streams waited for
-static hipError_t sync_fill_streams(const cn_engine* e) {
-    hipError_t first = hipSuccess;
-    for (int i = 0; i < cn_engine::kFillStreams; ++i)
-        if (e->fill_streams[i]) {
-            const hipError_t err = hipStreamSynchronize(e->fill_streams[i]);
-            if (first == hipSuccess) first = err;
-        }
-    return first;
-}
-
-// CN_FLAG_ASYNC_SCENARIO_FILL: fill kernels still in flight on the side streams read the device copy of the io block, the
-// caller's buffers behind it and the claim / ready flags.  Before any of those change hands (a new io block, a restart of the
-// bookkeeping) the host waits for them: a straggler of the previous rollout must not publish a scenario of the old seed
-// numbering into the new one's ring, nor read buffers the caller is about to free.  The lagged fill (fill_plan.h) reads the io
-// block and the envs' episode words in the same way; once it has been waited for, its levels are the ring's.
-static int drain_fill_streams(cn_engine* e) {
-    CN_HIP(sync_fill_streams(e));
-    if (e->lag_pending) std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
-    e->lag_pending = false;
-    return CN_OK;
-}
-// ... by the entry points that read or write env state from outside a rollout: nothing to wait for unless a lagged fill is out
-static int settle_lagged_fill(cn_engine* e) { return e->lag_pending ? drain_fill_streams(e) : CN_OK; }
 
 extern "C" {
 
@@ -140,7 +117,7 @@ static void copy_config(cn_engine* e) {
 
 // Workgroup geometry.  E envs per workgroup (agents = lanes of wave 0), W waves sharing the per-pair phases.
 // Defaults from the MI355X sweep in DESIGN.md; CROWDNAV_AMD_ENVS_PER_WAVE / CROWDNAV_AMD_WAVES_PER_BLOCK
-// override them for tuning.  And the generator family with the ring depth that goes with it.
+// override them for tuning.
 static void pick_geometry(cn_engine* e) {
     const cn_config* c = &e->cfg;
     cn::Params& P = e->P;
@@ -167,23 +144,9 @@ static void pick_geometry(cn_engine* e) {
     P.kd = P.A > cn::kKdLeaf ? 1 : 0;  // a simulator of more than 10 agents splits its kd-tree: visiting order matters at ties
     P.kdl = cn::kd_layout(P.nA, P.A, P.E);
     e->smem = cn::smem_bytes(P.nA, P.pairs, e->maxl, P.A, P.E);
-    e->gen_wave = env_int("CROWDNAV_AMD_WAVE_SCENARIOS", c->num_humans > 8 ? 1 : 0) != 0;
-    e->async_fill = (c->flags & CN_FLAG_ASYNC_SCENARIO_FILL) != 0 && e->gen_wave;
-    P.async_fill = e->async_fill ? 1 : 0;
-    // Asynchronous fill: a slot is refilled by the fill launch AFTER the call that consumed it, behind up to one call's worth of
-    // other scenarios, and a hard scenario of the reference geometry (20 humans on the 4 m circle: up to 3 M attempts) is tens
-    // of milliseconds of one wave — so the ring is the latency buffer.  Measured (r06, 4096 x 20, 999-step calls, every
-    // scenario generated afresh): depth 48 / 96 / 144 = 16 % / 3 % / 0 % of the env-steps paused.  0.6 GB of the 288.
-    P.ring_depth = env_int("CROWDNAV_AMD_RING_DEPTH", 48);
-    if (P.ring_depth < 1) P.ring_depth = 1;
-    if (e->async_fill && !getenv("CROWDNAV_AMD_RING_DEPTH")) P.ring_depth = 144;
-    // Lagged fill (fill_plan.h; CROWDNAV_AMD_LAGGED_FILL, default on): the lane-per-scenario generator's ring gets 2 D slots per
-    // env and its top-ups run on a side stream beside the launches.  0: D slots, every fill in front of the launch that needs it.
-    e->plan.configure(P.ring_depth, !e->gen_wave && !e->async_fill && env_int("CROWDNAV_AMD_LAGGED_FILL", 1) != 0);
-    P.ring_mod = e->plan.C;
 }
 
-// The run-time switches and what they are weighed against: the device's size.
+// The run-time switches and what they are weighed against: the device's size.  The scenario ring reads its own.
 static void read_knobs(cn_engine* e) {
     const cn_config* c = &e->cfg;
     cn::Params& P = e->P;
@@ -192,7 +155,6 @@ static void read_knobs(cn_engine* e) {
     e->sched_force = env_int("CROWDNAV_AMD_SCHED_FORCE", 0) != 0;
     e->sched_reserve = env_int("CROWDNAV_AMD_DYN_RESERVE", 0);  // slots left free beside a dynamic launch under the asynchronous fill
     e->sched_dynamic = env_int("CROWDNAV_AMD_SCHED_DYNAMIC", 1) != 0;
-    e->scenario_cache = env_int("CROWDNAV_AMD_SCENARIO_CACHE", 1) != 0;
     e->dyn_visits = env_int("CROWDNAV_AMD_DYN_VISITS", 0);  // 0: by call length (launch_shard)
     P.dyn_visits = 3;
     e->use_fused = env_int("CROWDNAV_AMD_FUSED", 1) != 0;
@@ -201,9 +163,6 @@ static void read_knobs(cn_engine* e) {
     // what the env wave of the two-wave kernel takes off the ORCA wave's chain (rollout_fused.h: ASSIST): 1 (default) = the head
     // of the 3-D fallback for the agents predicted infeasible; 0 = nothing (A/B runs)
     e->split_assist = env_int("CROWDNAV_AMD_SPLIT_ASSIST", 1) != 0 ? cn::kAssistHead : 0;
-    // generator workgroups of an asynchronous fill launch (step_kernels.h: ring_fill_jobs_kernel), at least one
-    e->fill_queue_wgs = env_int("CROWDNAV_AMD_FILL_QUEUE_WGS", 1024);
-    if (e->fill_queue_wgs < 1) e->fill_queue_wgs = 1;
     // give-up threshold of the rejection sampling: ~seconds of GPU time in either generator family
     int cap_log2 = env_int("CROWDNAV_AMD_MAX_ATTEMPTS_LOG2", c->num_humans > 8 ? 23 : 20);
     if (cap_log2 < 6) cap_log2 = 6;
@@ -212,13 +171,7 @@ static void read_knobs(cn_engine* e) {
     hipDeviceProp_t prop;
     const bool ok = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0;
     e->sched_slots = 12 * (ok ? prop.multiProcessorCount : 256);
-    // The lagged fill pays where a launch is ONE round of workgroups: its waves then run in the launch's tail.  Beside a launch of
-    // several rounds they take slots from queued workgroups instead (32768 envs: 1.2 % slower than the fill in front).  Two waves
-    // per SIMD is what every rollout kernel fits: 8 one-wave workgroups per CU.
-    if (e->plan.lagged() && grid_envs(e) > 8 * (ok ? prop.multiProcessorCount : 256)) {
-        e->plan.configure(P.ring_depth, false);
-        P.ring_mod = e->plan.C;
-    }
+    e->ring.configure(e, ok ? prop.multiProcessorCount : 256);
     e->split_slots = 0;
     if (ok && headline_geometry(P))  // the two-wave kernel is for launches that fit the device in one round (rollout_route)
         pick_fused(e, CN_ROUTE_FUSED_SPLIT, [&](auto kernel, int threads) {
@@ -228,8 +181,8 @@ static void read_knobs(cn_engine* e) {
         });
 }
 
-// every device buffer of the engine, the device copy of the state view and the side streams of the asynchronous fill (the
-// caller destroys the engine if this fails)
+// every device buffer of the engine — the scenario ring allocates its own — and the device copy of the state view (the caller
+// destroys the engine if this fails)
 static int alloc_state(cn_engine* e) {
     const cn::Params& P = e->P;
     const size_t n = (size_t)P.B * P.A;
@@ -241,22 +194,9 @@ static int alloc_state(cn_engine* e) {
         (rc = dev_alloc(e, &S.rsim_radius, n)) || (rc = dev_alloc(e, &S.rsim_max_speed, (size_t)P.B)) ||
         (rc = dev_alloc(e, &S.rsim_valid, (size_t)P.B)) || (rc = dev_alloc(e, &S.mt_key, (size_t)624 * P.B)) ||
         (rc = dev_alloc(e, &S.mt_pos, (size_t)P.B)) || (rc = dev_alloc(e, &e->probe_key, (size_t)624)) ||
-        (rc = dev_alloc(e, &S.ring_pos, n * P.ring_mod)) || (rc = dev_alloc(e, &S.ring_goal, n * P.ring_mod)) ||
-        (rc = dev_alloc(e, &S.ring_rv, n * P.ring_mod)) ||
-        (rc = dev_alloc(e, &S.ring_mt_key, e->gen_wave ? (size_t)64 : (size_t)624 * cn::kRedoLanes)) ||
-        (rc = dev_alloc(e, &S.redo_list, e->gen_wave ? (size_t)1 : (size_t)P.B * P.ring_mod)) ||
-        (rc = dev_alloc(e, &e->ep_snap, e->plan.lagged() ? (size_t)P.B : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.redo_count, (size_t)1)) ||
+        (rc = e->ring.create(e)) ||
         (rc = dev_alloc(e, &e->summary_scratch, (size_t)cn::kSummaryBlocks * cn::kSummaryFields + 1)) ||
-        (rc = dev_alloc(e, &S.ring_filled_in, (size_t)P.B)) || (rc = dev_alloc(e, &S.ring_filled_out, (size_t)P.B)) ||
-        (rc = dev_alloc(e, &S.ring_ready, e->async_fill ? (size_t)P.B * P.ring_depth : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.ring_claim, e->async_fill ? (size_t)P.B * P.ring_depth : (size_t)1)) ||
         (rc = dev_alloc(e, &S.ep_word, (size_t)P.B)) || (rc = dev_alloc(e, &S.dyn_queue, (size_t)P.B + 1)) ||
-        (rc = dev_alloc(e, &e->fill_list, e->async_fill ? (size_t)cn_engine::kFillStreams * (2 + 2 * (size_t)P.B * P.ring_depth) : (size_t)2)) ||
-        (rc = dev_alloc(e, &S.cache_pos, e->gen_wave ? (size_t)cn::kScenarioCacheMax * P.A : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.cache_goal, e->gen_wave ? (size_t)cn::kScenarioCacheMax * P.A : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.cache_rv, e->gen_wave ? (size_t)cn::kScenarioCacheMax * P.A : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.cache_state, (size_t)cn::kScenarioCacheMax)) ||
         (rc = dev_alloc(e, &S.kd_order, P.kd ? n * cn::kd_row_bytes(P.A) : (size_t)4)) ||
         (rc = dev_alloc(e, &S.kd_valid, P.kd ? n : (size_t)4)) ||
         (rc = dev_alloc(e, &S.wg_partial, (size_t)P.B * (CN_SUMMARY_FIELDS + 1))) ||
@@ -268,22 +208,6 @@ static int alloc_state(cn_engine* e) {
     e->S.error = e->C.error;
     if (hipMemcpy(e->S_dev, &e->S, sizeof(cn::StateView), hipMemcpyHostToDevice) != hipSuccess)
         return fail(CN_ERR_HIP, "cn_create: state view upload failed");
-    if (e->async_fill) {
-        bool ok = hipEventCreateWithFlags(&e->rollout_done, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; ok && i < cn_engine::kFillStreams; ++i)
-            ok = hipStreamCreateWithFlags(&e->fill_streams[i], hipStreamNonBlocking) == hipSuccess;
-        if (!ok) return fail(CN_ERR_HIP, "cn_create: side streams for the asynchronous scenario fill");
-    }
-    if (e->plan.lagged()) {
-        // lowest priority: the launch it runs beside becomes ready at the same moment and must get the chip first; the fill's
-        // waves take the slots that launch leaves or gives back
-        int least = 0, greatest = 0;
-        if (hipEventCreateWithFlags(&e->rollout_done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->fill_done, hipEventDisableTiming) != hipSuccess ||
-            hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-            hipStreamCreateWithPriority(&e->fill_streams[0], hipStreamNonBlocking, least) != hipSuccess)
-            return fail(CN_ERR_HIP, "cn_create: side stream for the lagged scenario fill");
-    }
     return CN_OK;
 }
 
@@ -312,11 +236,7 @@ int cn_destroy(cn_engine* e) {
     if (!e) return CN_OK;
     (void)hipSetDevice(e->cfg.device);
     (void)hipStreamSynchronize(e->stream);
-    (void)sync_fill_streams(e);
-    for (hipStream_t fs : e->fill_streams)
-        if (fs) (void)hipStreamDestroy(fs);
-    if (e->rollout_done) (void)hipEventDestroy(e->rollout_done);
-    if (e->fill_done) (void)hipEventDestroy(e->fill_done);
+    e->ring.destroy();
     e->alloc_rollback(cn_engine::AllocMark{});
     if (e->discount) (void)hipFree(e->discount);
     cn_sarl_release(e);
@@ -335,7 +255,7 @@ int cn_sync(cn_engine* e) {
     int rc = bind(e);
     if (rc) return rc;
     CN_HIP(hipStreamSynchronize(e->stream));
-    if ((rc = drain_fill_streams(e))) return rc;
+    if ((rc = e->ring.drain(e))) return rc;
     int gen_error = 0;
     CN_HIP(hipMemcpy(&gen_error, e->C.error, sizeof(int), hipMemcpyDeviceToHost));
     if (gen_error) {
@@ -382,7 +302,7 @@ __global__ void unpack_state_kernel(int n, double* state8, cn::StateView S) {
 
 int cn_set_state(cn_engine* e, const double* state8, const double* global_time) {
     int rc = bind(e);
-    if (rc || (rc = settle_lagged_fill(e))) return rc;
+    if (rc || (rc = e->ring.settle(e))) return rc;
     const int n = e->P.B * e->P.A;
     if (state8) hipLaunchKernelGGL(pack_state_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, state8, e->S);
     if (global_time)
@@ -393,7 +313,7 @@ int cn_set_state(cn_engine* e, const double* state8, const double* global_time) 
 
 int cn_get_state(cn_engine* e, double* state8, double* global_time) {
     int rc = bind(e);
-    if (rc || (rc = settle_lagged_fill(e))) return rc;
+    if (rc || (rc = e->ring.settle(e))) return rc;
     const int n = e->P.B * e->P.A;
     if (state8) hipLaunchKernelGGL(unpack_state_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, state8, e->S);
     if (global_time)
@@ -480,9 +400,9 @@ int cn_drop_sims(cn_engine* e) {
 
 int cn_reset(cn_engine* e, const uint32_t* seeds, const uint8_t* mask, uint64_t* draws) {
     int rc = bind(e);
-    if (rc || (rc = settle_lagged_fill(e))) return rc;
+    if (rc || (rc = e->ring.settle(e))) return rc;
     if (!seeds) return fail(CN_ERR_INVALID, "cn_reset: seeds is NULL");
-    if (e->gen_wave)
+    if (e->ring.gen_wave)
         hipLaunchKernelGGL(cn::reset_wave_kernel, dim3(e->P.B), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, seeds, mask,
                            draws);
     else
@@ -504,7 +424,7 @@ int cn_orca(cn_engine* e, float* out_vel) {
 int cn_step(cn_engine* e, const double* action, int update, double* reward, uint8_t* done, uint8_t* info,
             double* dmin, double* action_out, float* orca_vel, double* obs) {
     int rc = bind(e);
-    if (rc || (rc = settle_lagged_fill(e))) return rc;
+    if (rc || (rc = e->ring.settle(e))) return rc;
     if (!reward || !done || !info) return fail(CN_ERR_INVALID, "cn_step: reward/done/info must not be NULL");
     if (e->P.robot_orca && action)
         return fail(CN_ERR_INVALID, "cn_step: action must be NULL when robot_policy == CN_ROBOT_ORCA");
@@ -545,7 +465,7 @@ static int upload_io(cn_engine* e, const cn_rollout_io* io) {
     if (e->rollout_begun && (io->seed_base != e->begin_seed_base || io->seed_mod != e->begin_seed_mod))
         return fail(CN_ERR_INVALID, "rollout io: seed_base / seed_mod (%u / %u) differ from cn_rollout_begin's (%u / %u); call "
                     "cn_rollout_begin to renumber the episodes", io->seed_base, io->seed_mod, e->begin_seed_base, e->begin_seed_mod);
-    int rc = drain_fill_streams(e);
+    int rc = e->ring.drain(e);
     if (rc) return rc;
     e->io_host = *io;
     CN_HIP(hipMemcpyAsync(e->io_dev, &e->io_host, sizeof(*io), hipMemcpyHostToDevice, e->stream));
@@ -568,98 +488,11 @@ static int check_io(const cn_engine* e, const cn_rollout_io* io) {
 int cn_rollout_begin(cn_engine* e, const cn_rollout_io* io) {
     int rc = bind(e);
     if (rc) return rc;
-    if ((rc = check_io(e, io)) || (rc = drain_fill_streams(e))) return rc;
+    if ((rc = check_io(e, io)) || (rc = e->ring.drain(e))) return rc;
     e->rollout_begun = false;
     if ((rc = upload_io(e, io))) return rc;
     e->rollout_begun = true, e->begin_seed_base = io->seed_base, e->begin_seed_mod = io->seed_mod;
-    cn::RolloutView R{e->io_dev, e->discount, e->discount_len};
-    // scenario cache (step_kernels.h: cached_scenario_wave): on for the wave generators when the episode seeds come from a small
-    // set; a new rollout may number its seeds differently, so it starts empty
-    e->S.cache_n = (e->gen_wave && e->scenario_cache && io->seed_mod <= (uint32_t)cn::kScenarioCacheMax) ? (int)io->seed_mod : 0;
-    if (e->gen_wave) CN_HIP(hipMemsetAsync(e->S.cache_state, 0, sizeof(int) * cn::kScenarioCacheMax, e->stream));
-    if (e->gen_wave)
-        hipLaunchKernelGGL(cn::rollout_begin_wave_kernel, dim3(e->P.B), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
-    else
-        hipLaunchKernelGGL(cn::rollout_begin_kernel, dim3(grid_lanes(e)), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
-    CN_HIP(hipGetLastError());
-    e->plan.begin();
-    return CN_OK;
-}
-
-// Top the scenario ring up ahead of every env.  An env consumes at most one ring scenario per transition, so after a fill
-// the next ring_depth transitions cannot run it dry: launches inside that budget skip the fill kernels altogether (a 20-step
-// cn_rollout call used to spend more time here than in its transitions).  Which calls fill, and whether in front of their
-// launch or beside it, is fill_plan.h's rule.
-static int fill_ring_if_needed(cn_engine* e, const cn::RolloutView& R, int n_steps) {
-    if (e->async_fill) {
-        // a fill launch per transition launch, on the next side stream, ordered after the PREVIOUS transition kernel (whose
-        // episode counters it reads) and beside the one about to be launched; nobody waits for it
-        const int this_stream = e->next_fill_stream;
-        hipStream_t fs = e->fill_streams[this_stream];
-        e->next_fill_stream = (e->next_fill_stream + 1) % cn_engine::kFillStreams;
-        CN_HIP(hipEventRecord(e->rollout_done, e->stream));
-        CN_HIP(hipStreamWaitEvent(fs, e->rollout_done, 0));
-        // scan + persistent generator workgroups on a job list (step_kernels.h).  (Tried and dropped: 4 workgroups per env walking
-        // its slots in order — 4.0 M instead of 20.8 M env-steps/s at the reference geometry, a workgroup stuck on a hard scenario
-        // delays its env's later slots; and, rounds 2-5, one workgroup per (env, slot): profiles/HISTORY.md.  Round 2's first
-        // attempt at this pair of kernels "hung on the GPU box"; round 6 found why — a generator loop of the shape `for (;;) {
-        // lane 0 pops with atomicAdd; j = readfirstlane; if (j >= jobs) break; generate }` never terminates as compiled, so the
-        // popping loop of ring_fill_jobs_kernel is written around a ballot instead.)
-        int* list = e->fill_list + (size_t)this_stream * (2 + 2 * (size_t)e->P.B * e->P.ring_depth);
-        CN_HIP(hipMemsetAsync(list, 0, 2 * sizeof(int), fs));
-        const int items = e->P.B * e->P.ring_depth;
-        hipLaunchKernelGGL(cn::ring_fill_scan_kernel, dim3((items + 255) / 256), dim3(256), 0, fs, e->P, e->S, R, list);
-        hipLaunchKernelGGL(cn::ring_fill_jobs_kernel, dim3(e->fill_queue_wgs), dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, list);
-        e->launch_counts[CN_COUNT_ASYNC_FILLS] += 1;
-        return CN_OK;
-    }
-    if (e->lag_pending) {  // the fill that ran beside the previous launch: this launch waits for it and takes its levels
-        CN_HIP(hipStreamWaitEvent(e->stream, e->fill_done, 0));
-        std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
-        e->lag_pending = false;
-    }
-    e->lag_due = false;
-    const cn::FillPlan::Decision plan = e->plan.call(n_steps);
-    const int fill_lanes = e->P.B * e->P.ring_mod;
-    const dim3 fill_grid((fill_lanes + cn::kWave - 1) / cn::kWave), redo_grid(cn::kRedoLanes / cn::kWave);
-    if (plan.sync_fill) {
-        if (e->gen_wave) {
-            hipLaunchKernelGGL(cn::ring_fill_wave_kernel, dim3(fill_lanes), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
-        } else {
-            CN_HIP(hipMemsetAsync(e->S.redo_count, 0, sizeof(int), e->stream));
-            hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R, nullptr);
-            hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S);
-        }
-        std::swap(e->S.ring_filled_in, e->S.ring_filled_out);
-        e->launch_counts[CN_COUNT_RING_FILLS] += 1;
-    }
-    if (plan.lagged_fill) {
-        // ordered behind everything in front of the launch about to be enqueued (the previous launch's episode words, the levels
-        // a synchronous fill just wrote); the fill itself is enqueued behind that launch (enqueue_lagged_fill)
-        CN_HIP(hipEventRecord(e->rollout_done, e->stream));
-        e->lag_due = true;
-    }
-    return CN_OK;
-}
-
-// The lagged fill fill_ring_if_needed decided on, enqueued once the launch it runs beside has been: it reads ring_filled_in, as
-// that launch does, and writes ring_filled_out and ring slots of ordinals >= the level the launch was given.
-static int enqueue_lagged_fill(cn_engine* e, const cn::RolloutView& R) {
-    if (!e->lag_due) return CN_OK;
-    e->lag_due = false;
-    hipStream_t fs = e->fill_streams[0];
-    const int fill_lanes = e->P.B * e->P.ring_mod;
-    CN_HIP(hipStreamWaitEvent(fs, e->rollout_done, 0));
-    hipLaunchKernelGGL(cn::ring_fill_begin_kernel, dim3(grid_lanes(e)), dim3(cn::kWave), 0, fs, e->P.B, e->S.ep_word, e->ep_snap,
-                       e->S.redo_count);
-    hipLaunchKernelGGL(cn::ring_fill_kernel, dim3((fill_lanes + cn::kWave - 1) / cn::kWave), dim3(cn::kWave), 0, fs, e->P, e->C, e->S,
-                       R, (const int*)e->ep_snap);
-    hipLaunchKernelGGL(cn::ring_redo_kernel, dim3(cn::kRedoLanes / cn::kWave), dim3(cn::kWave), 0, fs, e->P, e->C, e->S);
-    CN_HIP(hipEventRecord(e->fill_done, fs));
-    e->lag_pending = true;
-    e->launch_counts[CN_COUNT_RING_FILLS] += 1;
-    e->lagged_fills += 1;
-    return CN_OK;
+    return e->ring.begin(e, io->seed_mod);
 }
 
 // Which transition kernel a call runs: decided HERE, once (launch_rollout launches what this says; cn_rollout_route reports it).
@@ -675,7 +508,7 @@ static int rollout_route(const cn_engine* e, const double* action) {
     // became the headline path)
     // (the fused kernel reads the launch-time fill level only: never with the asynchronous fill, whose slots are published
     // one by one — CROWDNAV_AMD_WAVE_SCENARIOS=1 can switch that on for a small crowd)
-    if (e->use_fused && !e->async_fill && e->maxl == 5 && !P.robot_unicycle && P.NC <= cn::kFusedMaxNC && P.pairs <= cn::kWave &&
+    if (e->use_fused && e->ring.mode != ScenarioRing::Fill::WorkList && e->maxl == 5 && !P.robot_unicycle && P.NC <= cn::kFusedMaxNC && P.pairs <= cn::kWave &&
         P.nA * 5 <= cn::kWave && P.threads == cn::kWave) {
 #if defined(CN_PHASE_TIMING) || defined(CN_WAVE_TRACE)
         (void)action;
@@ -693,14 +526,14 @@ static int rollout_route(const cn_engine* e, const double* action) {
 }
 
 // The 20-human shard's kernel (CN_ROUTE_SHARD) under one of its two schedules, or plain.
-static void launch_shard(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
+static void launch_shard(cn_engine* e, const cn::RolloutView& R, const int* levels, int n_steps, const double* action) {
     const cn::Params& P = e->P;
     const size_t smem20 = cn::smem_bytes_compact(P.nA, P.pairs, P.A, P.E);
     const auto launch = [&](const cn::Params& Pk, int grid, int steps) {
         hipLaunchKernelGGL((cn::rollout_kernel<10, false, true, true>), dim3(grid), dim3(64), smem20, e->stream, Pk,
-                           (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, steps, action);
+                           (const cn::StateView*)e->S_dev, levels, R, steps, action);
     };
-    // Three resident waves per SIMD (step_kernels.h: kGeom20Waves): 3072 one-wave workgroups fill the chip, so B = 4096 envs would run as
+    // Three resident waves per SIMD (rollout_kernels.h: kGeom20Waves): 3072 one-wave workgroups fill the chip, so B = 4096 envs would run as
     // a full round plus a third of one.  A call of 3 q + r steps becomes one launch of r steps over all envs (if r > 0) and
     // FOUR launches of q steps over 3 B / 4 workgroups each, sub-launch k leaving out env 3 - k of every group of four
     // (step_kernels.h: Params::sched): every env makes its steps in order, every launch is one round.
@@ -711,12 +544,13 @@ static void launch_shard(cn_engine* e, const cn::RolloutView& R, int n_steps, co
     cn::Params Pk = e->P;
     Pk.sched = -1;
     const int slots = e->sched_slots;
-    // Dynamic schedule (step_kernels.h: kSchedDynamic): ONE launch of persistent workgroups taking (env, visit) items from a
+    // Dynamic schedule (rollout_kernels.h: kSchedDynamic): ONE launch of persistent workgroups taking (env, visit) items from a
     // device queue — wherever thirds of a call balance the chip better than whole calls (ceil(3 B / G) < 3 ceil(B / G)), and
     // always beside the asynchronous scenario fill, whose generator workgroups must find room WITHOUT sending a step workgroup
     // to a second round: the grid then leaves `sched_reserve` of the resident slots free (CROWDNAV_AMD_DYN_RESERVE).  Callers that
     // want the in-kernel summary / record blocks get the static 3-of-4 schedule below.
-    const int reserve = e->async_fill ? e->sched_reserve : 0;
+    const bool beside_generators = e->ring.mode == ScenarioRing::Fill::WorkList;
+    const int reserve = beside_generators ? e->sched_reserve : 0;
     const int G = P.B < slots - reserve ? P.B : slots - reserve;
     // visits per env and call: ~56 steps each (measured at 4096 envs on the 12 m circle: 999-step calls 129 / 137 / 141 /
     // 143 / 143 / 136 / 110 M env-steps/s at 3 / 6 / 9 / 18 / 27 / 54 / 108 visits, 500-step calls 125 / 137 / 136 / 126 M
@@ -727,7 +561,7 @@ static void launch_shard(cn_engine* e, const cn::RolloutView& R, int n_steps, co
     if (visits > n_steps) visits = n_steps;
     Pk.dyn_visits = visits;
     // work-conserving: worth it whenever the envs do not all fit at once (a plain launch then runs ceil(B / G) rounds)
-    const bool helps = e->sched_force || e->async_fill || P.B > G;
+    const bool helps = e->sched_force || beside_generators || P.B > G;
     if (e->sched_dynamic && G > 0 && n_steps >= e->sched_min && action == nullptr && helps && !e->io_host.summary &&
         !e->io_host.blocks) {
         (void)hipMemsetAsync(e->S.dyn_queue, 0, sizeof(int) * ((size_t)P.B + 1), e->stream);
@@ -750,30 +584,30 @@ static void launch_shard(cn_engine* e, const cn::RolloutView& R, int n_steps, co
     }
 }
 
-// n_steps >= 1 transitions of every env, by the kernel rollout_route names
-static void launch_rollout(cn_engine* e, const cn::RolloutView& R, int n_steps, const double* action) {
+// n_steps >= 1 transitions of every env, by the kernel rollout_route names (R, levels: ScenarioRing::around_launch's)
+static void launch_rollout(cn_engine* e, const cn::RolloutView& R, const int* levels, int n_steps, const double* action) {
     const int route = rollout_route(e, action);
-    if (route == CN_ROUTE_SHARD) return launch_shard(e, R, n_steps, action);  // (counts its own launches)
+    if (route == CN_ROUTE_SHARD) return launch_shard(e, R, levels, n_steps, action);  // (counts its own launches)
     if (route == CN_ROUTE_GENERIC)
         pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
             hipLaunchKernelGGL((cn::rollout_kernel<decltype(maxl)::value, decltype(uni)::value, false, decltype(kd)::value>),
                                dim3(grid_envs(e)), dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
-                               (const int*)e->S.ring_filled_in, R, n_steps, action);
+                               levels, R, n_steps, action);
         });
     else
         pick_fused(e, route, [&](auto kernel, int threads) {
             hipLaunchKernelGGL(kernel, dim3(grid_envs(e)), dim3(threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
-                               (const int*)e->S.ring_filled_in, R, n_steps, action);
+                               levels, R, n_steps, action);
         });
     e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
 }
 
-// What cn_rollout, cn_rollout_trace and cn_rollout_step do before they launch: bind, check the io block and the call's length,
-// upload the io block, top up the scenario ring for n_steps transitions.  CN_OK: *R is what the transition kernel takes.
+// What cn_rollout, cn_rollout_trace, cn_rollout_step and cn_rollout_actions do before they launch: bind, check the io block and
+// the call's length, upload the io block.  CN_OK: the entry point launches, through ScenarioRing::around_launch and in no other way.
 // kNothingToLaunch: n_steps == 0.  kWrongRobotPolicy: the engine's robot policy is not the one the entry point is for;
 // kNoAction: an external robot's entry point was given no action — no error text yet for these two, the entry point words it.
 enum { kNothingToLaunch = 1, kWrongRobotPolicy = 2, kNoAction = 3 };
-static int rollout_prepare(cn_engine* e, const cn_rollout_io* io, int n_steps, bool need_orca_robot, cn::RolloutView* R,
+static int rollout_prepare(cn_engine* e, const cn_rollout_io* io, int n_steps, bool need_orca_robot,
                            const double* action = nullptr) {
     int rc = bind(e);
     if (rc) return rc;
@@ -782,22 +616,19 @@ static int rollout_prepare(cn_engine* e, const cn_rollout_io* io, int n_steps, b
     if (n_steps == 0) return kNothingToLaunch;
     if ((e->P.robot_orca != 0) != need_orca_robot) return kWrongRobotPolicy;
     if (!need_orca_robot && !action) return kNoAction;
-    if ((rc = upload_io(e, io))) return rc;
-    *R = cn::RolloutView{e->io_dev, e->discount, e->discount_len};
-    return fill_ring_if_needed(e, *R, n_steps);
+    return upload_io(e, io);
 }
 
 int cn_rollout(cn_engine* e, const cn_rollout_io* io, int n_steps) {
-    cn::RolloutView R;
-    const int rc = rollout_prepare(e, io, n_steps, true, &R);
+    const int rc = rollout_prepare(e, io, n_steps, true);
     if (rc == kNothingToLaunch) return CN_OK;
     if (rc == kWrongRobotPolicy)
         return fail(CN_ERR_UNSUPPORTED, "cn_rollout needs an on-device robot policy (robot_policy == CN_ROBOT_ORCA); with "
                                         "CN_ROBOT_EXTERNAL use cn_rollout_step(action)");
     if (rc) return rc;
-    launch_rollout(e, R, n_steps, nullptr);  // the fused transitions
-    CN_HIP(hipGetLastError());
-    return enqueue_lagged_fill(e, R);
+    return e->ring.around_launch(e, n_steps, [&](const cn::RolloutView& R, const int* levels) {
+        launch_rollout(e, R, levels, n_steps, nullptr);  // the fused transitions
+    });
 }
 
 // cn_rollout with the per-step rows of `out`: cn_rollout's host path, then ONE launch of rollout_trace_kernel — the generic
@@ -811,32 +642,28 @@ int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const c
     if (!e->P.robot_orca)
         return fail(CN_ERR_UNSUPPORTED, "cn_rollout_trace needs an on-device robot policy (robot_policy == CN_ROBOT_ORCA); with "
                                         "CN_ROBOT_EXTERNAL use cn_rollout_step(action)");
-    cn::RolloutView R;
-    const int rc = rollout_prepare(e, io, n_steps, true, &R);
+    const int rc = rollout_prepare(e, io, n_steps, true);
     if (rc == kNothingToLaunch) return CN_OK;
     if (rc) return rc;
     const cn_trace_out T = *out;
-    pick_maxl(e, [&](auto maxl) {
-        pick_bool(e->P.kd, [&](auto kd) {
-            hipLaunchKernelGGL((cn::rollout_trace_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)),
-                               dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev,
-                               (const int*)e->S.ring_filled_in, R, n_steps, T);
+    return e->ring.around_launch(e, n_steps, [&](const cn::RolloutView& R, const int* levels) {
+        pick_maxl(e, [&](auto maxl) {
+            pick_bool(e->P.kd, [&](auto kd) {
+                hipLaunchKernelGGL((cn::rollout_trace_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)),
+                                   dim3(e->P.threads), e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev, levels, R, n_steps,
+                                   T);
+            });
         });
+        e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
     });
-    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
-    CN_HIP(hipGetLastError());
-    return enqueue_lagged_fill(e, R);
 }
 
 int cn_rollout_step(cn_engine* e, const cn_rollout_io* io, const double* action) {
-    cn::RolloutView R;
-    const int rc = rollout_prepare(e, io, 1, false, &R, action);
+    const int rc = rollout_prepare(e, io, 1, false, action);
     if (rc == kWrongRobotPolicy) return fail(CN_ERR_INVALID, "cn_rollout_step is for CN_ROBOT_EXTERNAL engines (use cn_rollout)");
     if (rc == kNoAction) return fail(CN_ERR_INVALID, "cn_rollout_step: action is NULL");
     if (rc) return rc;
-    launch_rollout(e, R, 1, action);
-    CN_HIP(hipGetLastError());
-    return enqueue_lagged_fill(e, R);
+    return e->ring.around_launch(e, 1, [&](const cn::RolloutView& R, const int* levels) { launch_rollout(e, R, levels, 1, action); });
 }
 
 // n_steps cn_rollout_step calls as one launch: cn_rollout's host path, then the generic phase kernel's table instantiation
@@ -851,24 +678,22 @@ int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const
     if (!e) return fail(CN_ERR_INVALID, "cn_rollout_actions: engine is NULL");
     if (e->P.robot_orca)
         return fail(CN_ERR_INVALID, "cn_rollout_actions is for CN_ROBOT_EXTERNAL engines (use cn_rollout)");
-    cn::RolloutView R;
-    const int rc = rollout_prepare(e, io, n_steps, false, &R, actions);
+    const int rc = rollout_prepare(e, io, n_steps, false, actions);
     if (rc == kNothingToLaunch) return CN_OK;
     if (rc) return rc;
-    pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
-        constexpr int kMaxl = decltype(maxl)::value;
-        constexpr bool kUni = decltype(uni)::value, kKd = decltype(kd)::value;
-        if (out)
-            hipLaunchKernelGGL((cn::rollout_actions_trace_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads), e->smem,
-                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, actions,
-                               *out);
-        else
-            hipLaunchKernelGGL((cn::rollout_actions_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads), e->smem,
-                               e->stream, e->P, (const cn::StateView*)e->S_dev, (const int*)e->S.ring_filled_in, R, n_steps, actions);
+    return e->ring.around_launch(e, n_steps, [&](const cn::RolloutView& R, const int* levels) {
+        pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
+            constexpr int kMaxl = decltype(maxl)::value;
+            constexpr bool kUni = decltype(uni)::value, kKd = decltype(kd)::value;
+            if (out)
+                hipLaunchKernelGGL((cn::rollout_actions_trace_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads),
+                                   e->smem, e->stream, e->P, (const cn::StateView*)e->S_dev, levels, R, n_steps, actions, *out);
+            else
+                hipLaunchKernelGGL((cn::rollout_actions_kernel<kMaxl, kUni, kKd>), dim3(grid_envs(e)), dim3(e->P.threads), e->smem,
+                                   e->stream, e->P, (const cn::StateView*)e->S_dev, levels, R, n_steps, actions);
+        });
+        e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
     });
-    e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
-    CN_HIP(hipGetLastError());
-    return enqueue_lagged_fill(e, R);
 }
 
 int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
@@ -880,7 +705,7 @@ int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
 
 int cn_lagged_fills(cn_engine* e, uint64_t* count_host) {
     if (!e || !count_host) return fail(CN_ERR_INVALID, "cn_lagged_fills: NULL argument");
-    *count_host = e->lagged_fills;
+    *count_host = e->ring.lagged_fills;
     return CN_OK;
 }
 

@@ -46,6 +46,40 @@ namespace {
 
 }  // namespace
 
+// Host side of the scenario ring: what cn_rollout_begin and the cn_rollout_* entry points keep about the ring between calls.
+// The methods are scenario_ring_host.h's (crowdnav_amd.hip only); the device side is scenario_ring.h, the rule for when a fill
+// runs fill_plan.h.  The ring's device buffers are StateView's ring_* / redo_* / cache_* pointers, allocated by create().
+struct ScenarioRing {
+    // Where a fill runs.  InFront: on the engine's stream, in front of the launch that needs it.  Beside: the lagged fill of the
+    // lane-per-scenario generators, on fill_streams[0] beside a launch, one call ahead (the ring then has 2 D slots per env).
+    // WorkList: CN_FLAG_ASYNC_SCENARIO_FILL with the wave-per-scenario generators — a scan + job-list launch per transition
+    // launch, round-robin over the side streams (a launch stuck on a hard scenario must not hold back the next one), each
+    // starting once the previous transition kernel has written its episode counters; slots are published one by one.
+    enum class Fill { InFront, Beside, WorkList };
+    static constexpr int kFillStreams = 8;
+    bool gen_wave = false;       // wave-per-scenario generators (64 rejection attempts at a time): long chains, H > 8
+    Fill mode = Fill::InFront;
+    bool scenario_cache = true;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
+    cn::FillPlan plan;           // InFront / Beside: which calls fill, and when the two level buffers change hands
+    hipStream_t fill_streams[kFillStreams] = {};
+    hipEvent_t rollout_done = nullptr;  // on the engine's stream: everything in front of the launch a fill runs beside
+    hipEvent_t fill_done = nullptr;     // Beside: the fill's end, which the launch that takes its levels waits for
+    int next_fill_stream = 0;
+    int* fill_list = nullptr;    // [kFillStreams][2 + 2 B D] job lists of ring_fill_scan_kernel / ring_fill_jobs_kernel, one per side stream
+    int fill_queue_wgs = 1;      // persistent generator workgroups of a WorkList fill launch (CROWDNAV_AMD_FILL_QUEUE_WGS, at least 1)
+    int* ep_snap = nullptr;      // [B] the Beside fill's copy of StateView::ep_word (ring_fill_begin_kernel)
+    uint64_t lagged_fills = 0;   // cn_lagged_fills: fills enqueued beside a launch (counted in CN_COUNT_RING_FILLS too)
+
+    void configure(cn_engine* e, int compute_units);
+    int create(cn_engine* e);
+    void destroy();
+    int begin(cn_engine* e, uint32_t seed_mod);
+    template <class Launch>
+    int around_launch(cn_engine* e, int n_steps, Launch&& launch);
+    int settle(cn_engine* e);
+    int drain(cn_engine* e);
+};
+
 struct cn_engine {
     cn_config cfg{};
     cn::Params P{};
@@ -55,26 +89,10 @@ struct cn_engine {
     cn_rollout_io io_host{};           // last cn_rollout_io uploaded to io_dev
     cn_rollout_io* io_dev = nullptr;   // device copy the rollout kernels read through
     cn::StateView* S_dev = nullptr;    // device copy of S (the fused rollout kernel re-reads state pointers instead of holding them)
-    // CN_FLAG_ASYNC_SCENARIO_FILL: fill kernels go round-robin over side streams (a launch stuck on a hard scenario must
-    // not hold back the next one) and start once the previous transition kernel has written its episode counters
-    static constexpr int kFillStreams = 8;
-    bool async_fill = false;
-    hipStream_t fill_streams[kFillStreams] = {};
-    int* fill_list = nullptr;    // [kFillStreams][2 + 2 B D] job lists of ring_fill_scan_kernel / ring_fill_jobs_kernel, one per side stream
-    int fill_queue_wgs = 1;      // persistent generator workgroups of an asynchronous fill launch (CROWDNAV_AMD_FILL_QUEUE_WGS, at least 1)
-    hipEvent_t rollout_done = nullptr;
-    int next_fill_stream = 0;
+    ScenarioRing ring;
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one
     uint32_t begin_seed_base = 0, begin_seed_mod = 0;  // (the scenario cache is sized and keyed by them)
-    // lane-per-scenario generator (!gen_wave, !async_fill): when the ring is filled (fill_plan.h).  A lagged fill runs on
-    // fill_streams[0] beside a launch, reading ep_snap; the next call's launch waits for fill_done and takes its levels
-    cn::FillPlan plan;
-    bool lag_due = false;          // fill_ring_if_needed decided on a lagged fill: enqueued right behind the launch
-    bool lag_pending = false;      // a lagged fill has been enqueued whose levels (ring_filled_out) no launch has taken yet
-    hipEvent_t fill_done = nullptr;
-    int* ep_snap = nullptr;        // [B] the lagged fill's copy of StateView::ep_word (ring_fill_begin_kernel)
-    uint64_t lagged_fills = 0;     // cn_lagged_fills: fills enqueued beside a launch (counted in CN_COUNT_RING_FILLS too)
     struct cn_sarl* sarl = nullptr;  // SARL decision state (sarl_abi.hip), NULL until cn_sarl_configure
     bool orca_fresh = false;  // cn_sarl_sample_step: the humans' ORCA velocities of the CURRENT state are in sarl->orca_vel (left by the
                               // previous call's transition kernel); cleared by every other entry point (bind)
@@ -83,7 +101,6 @@ struct cn_engine {
     uint32_t* probe_key = nullptr;
     double* summary_scratch = nullptr;  // records_summary_kernel: per-workgroup partials + ticket counter
     int maxl = 10;           // half-planes held in VGPRs by the solve phase: 5 or 10
-    bool gen_wave = false;   // wave-per-scenario generators (64 rejection attempts at a time): long chains, H > 8
     size_t smem = 0;         // dynamic LDS bytes per workgroup
     int sched_min = 0, sched_slots = 0, sched_reserve = 0, dyn_visits = 0;  // the 20-human shard kernel's schedules (launch_shard): shortest call split, resident workgroups, slots left free beside the asynchronous fill
     bool sched_force = false, sched_dynamic = true;
@@ -91,7 +108,6 @@ struct cn_engine {
     int fused_split = 1;    // CROWDNAV_AMD_FUSED_SPLIT: 0 never, 1 launches of one round (default), 2 always
     int split_assist = 0;   // CROWDNAV_AMD_SPLIT_ASSIST: rollout_fused.h's ASSIST (0, or kAssistHead = fallback head on the env wave; default)
     int split_slots = 0;    // workgroups of the two-wave fused kernel the device holds at once (occupancy query, read_knobs)
-    bool scenario_cache = true;  // wave generators keep the scenarios of a small seed set (CROWDNAV_AMD_SCENARIO_CACHE)
     uint64_t launch_counts[CN_LAUNCH_COUNTERS] = {};  // cn_launch_counts: what the host enqueued since cn_create
     // Device memory comes from a few large slabs, not one hipMalloc per buffer: an engine has ~60 device buffers, most of them a
     // few KiB; one 32 MiB slab (plus one per buffer larger than that) is 2-4 mappings to create and - each hipFree being a device

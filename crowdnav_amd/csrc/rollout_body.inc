@@ -1,4 +1,4 @@
-// The body of rollout_kernel, rollout_trace_kernel and the two rollout_actions kernels (step_kernels.h), included once into
+// The body of rollout_kernel, rollout_trace_kernel and the two rollout_actions kernels (rollout_kernels.h), included once into
 // each: one source, four kernels.
 // In scope where it is included: MAXL, UNI, HEADLINE, KD (compile-time), P_in, Sd, ring_filled_in, R, n_steps, ext_action,
 // and under CN_ROLLOUT_TRACE the caller's cn_trace_out T.  Under CN_ROLLOUT_ACTIONS the call's action table

@@ -1,5 +1,5 @@
 // The fused rollout for the small-crowd geometries (<= 5 candidate neighbours per agent, one wave per workgroup,
-// holonomic robot): the same transition as step_core / rollout_kernel (step_kernels.h) — same functions for every number
+// holonomic robot): the same transition as step_core (step_kernels.h) / rollout_kernel (rollout_kernels.h) — same functions for every number
 // it computes — with FOUR LDS exchange points per step instead of nine:
 //
 //   [stage]   agent lanes   float32 view of the agents, preferred velocities        (written at the END of the previous step)
@@ -12,7 +12,7 @@
 //                           otherwise), so the episode bookkeeping that decides what the agents do next — advance, load the
 //                           next scenario from the ring, pause — needs no flag broadcast; integrate; stage the next step
 //                                                                                                                -> barrier 4
-// The env's episode bookkeeping (step_kernels.h: EpisodeBook — global_time, the return / danger accumulators, episodes
+// The env's episode bookkeeping (rollout_kernels.h: EpisodeBook — global_time, the return / danger accumulators, episodes
 // finished, ring fill level, running / waiting / retired) is replicated on the env's lanes; only the robot lane writes it
 // out: records, and the book at the end of the launch.
 // Launch conditions (cn_rollout / cn_rollout_step check them, everything else runs rollout_kernel): 5-half-plane
@@ -20,7 +20,7 @@
 // SPLIT (further down): the headline geometry's cn_rollout as TWO waves per workgroup — the phases above, dealt to an ORCA
 // wave and an env wave that meet at two s_barrier per step.
 #pragma once
-#include "step_kernels.h"
+#include "rollout_kernels.h"
 
 namespace cn {
 
@@ -373,7 +373,7 @@ __device__ __forceinline__ StepOutcome reduce_env(const Params& P, const Smem& s
 }
 
 // reduce -> account -> episode end of a transition run on every lane of a running env identically (the book is carried
-// redundantly; the robot lane writes the record), with the shared statements of step_kernels.h: CN_BOOK_TRANSITION, and at an
+// redundantly; the robot lane writes the record), with the shared statements of rollout_kernels.h: CN_BOOK_TRANSITION, and at an
 // episode end CN_END_EPISODE, whose decision is ep.state (kRunning: load ring slot ep.ep_count % P.ring_mod).  The one-wave
 // step loop and the env wave each spell the dozen lines around them themselves: the one-wave loop integrates between the
 // reduce and the accounting, the env wave requests the next scenario before the record stores, and as ONE helper — function
@@ -810,7 +810,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     if (L.valid) CN_STORE_AGENT(S, L.gi, r);
     const cn_rollout_io io = *iop;
     if (robot) CN_STORE_EPISODE(P, S, io, L.env, ep, theta);
-    // transitions counter, record blocks, explorer.py:74-90 sums: the launch's own tail (step_kernels.h: rollout_epilogue)
+    // transitions counter, record blocks, explorer.py:74-90 sums: the launch's own tail (rollout_kernels.h: rollout_epilogue)
     rollout_epilogue(P, S, io, L, robot, transitions, ep.ep_count, reinterpret_cast<double*>(s.lines));
 #ifdef CN_WAVE_TRACE
     if (threadIdx.x == 0 && blockIdx.x < 8192) {

@@ -1,6 +1,5 @@
 // C ABI of the SARL robot decision (declared in include/crowdnav_amd.h): cn_sarl_* and the value-network kernels, a
 // translation unit of its own (engine_host.h has what it shares with crowdnav_amd.hip).
-#define CN_SARL_TU  // step_kernels.h: the ORCA / step kernels and the engine types, not the rollout and scenario kernels
 #include "engine_host.h"
 #include "sarl_kernels.h"
 #include "sarl_lds_kernels.h"

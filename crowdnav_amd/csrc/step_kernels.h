@@ -1185,678 +1185,4 @@ __global__ __launch_bounds__(kMaxBlock) void step_kernel(Params P, StateView S, 
     }
 }
 
-// Everything below — scenario generation, rollout bookkeeping, the rollout kernels — belongs to the env translation unit
-// (crowdnav_amd.hip).  sarl_abi.hip includes this header for orca_kernel / step_kernel's types only and defines CN_SARL_TU.
-#ifndef CN_SARL_TU
-// Lane-per-scenario generation: try the register-only head generator first (no memory traffic), redo the scenario
-// with the memory-backed one (word-major HBM scratch: any number of waves per CU) in the rare case its 227 words do not
-// suffice.  Returns random() calls consumed.
-__device__ __forceinline__ uint64_t generate_scenario_lane(const ScenarioCfg& C, uint32_t seed, size_t base,
-                                                           double2* pos, double2* vel, double2* goal, double2* rv,
-                                                           uint32_t* hbm_column, int hbm_stride, bool keep_state,
-                                                           int* pos_out) {
-    if (!keep_state) {
-        Mt19937Head head;
-        const uint64_t n = generate_scenario(C, head, seed, base, pos, vel, goal, rv);
-        if (!head.dead()) return n;
-    }
-    Mt19937 rng{hbm_column, hbm_stride, 0};
-    const uint64_t n = generate_scenario(C, rng, seed, base, pos, vel, goal, rv);
-    if (keep_state && pos_out) *pos_out = rng.pos;
-    return n;
-}
-
-// New episode of env b: new Human objects, new ORCA policies, new rvo2 simulators (the robot's persists) — their kd-tree orders
-// start as the identity.  Lanes first, first + stride, ... of kd_valid[1..A): (1, 1) from a kernel with one lane per env,
-// (1 + threadIdx.x, blockDim.x) from one with a workgroup per env.
-__device__ __forceinline__ void clear_human_sims(const Params& P, const StateView& S, int b, int first, int stride) {
-    if (P.kd)
-        for (int a = first; a < P.A; a += stride) S.kd_valid[(size_t)b * P.A + a] = 0;
-}
-
-// np.random.seed(seed) + scenario of one env per lane (lane = env)
-__global__ __launch_bounds__(kWave) void reset_kernel(Params P, ScenarioCfg C, StateView S, const uint32_t* seeds,
-                                                     const uint8_t* mask, uint64_t* draws) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= P.B) return;
-    if (mask && !mask[b]) return;
-    const uint64_t n = generate_scenario_lane(C, seeds[b], (size_t)b * P.A, S.pos, S.vel, S.goal, S.rv,
-                                                      S.mt_key + b, P.B, true, &S.mt_pos[b]);
-    S.gtime[b] = 0.0;
-    S.theta[b] = 1.5707963267948966;  // robot.set(..., np.pi / 2)
-    if (draws) draws[b] = n;
-    clear_human_sims(P, S, b, 1, 1);
-}
-
-__global__ void mt_probe_kernel(uint32_t* key, uint32_t seed, int n, double* out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Mt19937 rng{key, 1, 0};
-    rng.seed(seed);
-    for (int i = 0; i < n; ++i) out[i] = rng.random();
-}
-
-// Rollout bookkeeping lives behind ONE pointer to a device copy of the caller's cn_rollout_io: the ~20
-// pointers in it are needed only when an episode ends, and keeping them out of the kernel arguments keeps
-// them out of the SGPR file of the step loop.
-struct RolloutView {
-    const cn_rollout_io* io;
-    const double* discount;  // [discount_len]
-    int discount_len;
-};
-
-// io.active[] states
-enum { kRetired = 0, kRunning = 1, kWaitingScenario = 2 };
-
-__device__ __forceinline__ int64_t episode_id(const cn_rollout_io& io, int b, int ordinal) {
-    return io.env_offset + b + (int64_t)ordinal * io.env_stride;
-}
-__device__ __forceinline__ uint32_t episode_seed(const cn_rollout_io& io, int64_t c) {
-    return io.seed_base + (uint32_t)((uint64_t)c % io.seed_mod);
-}
-
-// ---- the rules of the scenario ring, each stated once ------------------------------------------------------------
-// the episode limit of a rollout (io.episode_limit < 0: none): episode c is not run
-__device__ __forceinline__ bool past_episode_limit(const cn_rollout_io& io, int64_t c) {
-    return io.episode_limit >= 0 && c >= io.episode_limit;
-}
-// first ordinal the rollout may still ask for (an env waiting for a scenario has not consumed ep_count yet).  A fill that
-// runs BESIDE a transition kernel takes both arguments from one load of StateView::ep_word — (state, episodes finished) of the
-// env as ONE word, stored once by the transition kernel when it ends: two separate loads of io->active / io->ep_count could
-// pair an old state with a new count and claim a slot whose scenario has not been consumed yet
-__device__ __forceinline__ int ring_next_ordinal(int ep_count, int state) { return ep_count + (state == kWaitingScenario ? 0 : 1); }
-// the one ordinal of [next, next + D) that lives in ring slot `slot` (ordinal o lives in slot o % D; D = Params::ring_mod)
-__device__ __forceinline__ int ring_slot_ordinal(int next, int slot, int D) { return next + ((slot - next % D) + D) % D; }
-// Asynchronous fill: claim slot idx = (env, ordinal % D) for `ordinal`.  False: resident already, or another fill launch is
-// generating (or has generated) exactly this scenario.  Only slots whose scenario the env consumed before the transition
-// kernel running beside the fill was launched are ever overwritten.
-__device__ __forceinline__ bool ring_claim_slot(const StateView& S, int idx, int ordinal) {
-    const int want = ordinal + 1;
-    const int have = S.ring_claim[idx];
-    return have < want && atomicCAS(&S.ring_claim[idx], have, want) == have;
-}
-// ... and publish it, by the whole workgroup that wrote the scenario: a device-scope release store of ordinal + 1 to
-// ring_ready (scenario_ready is the acquire side)
-__device__ __forceinline__ void ring_publish_slot(const StateView& S, int idx, int ordinal) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // (a cached copy is written by A lanes, not by lane 0 alone)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(&S.ring_ready[idx], ordinal + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// (re)start bookkeeping of env b, which begins its episode ordinal 0 with nothing in its ring (`on`: it runs at all)
-__device__ __forceinline__ void begin_env(const StateView& S, const cn_rollout_io& io, int b, bool on) {
-    io.active[b] = on ? kRunning : kRetired;
-    S.ep_word[b] = on ? kRunning : kRetired;
-    io.ep_count[b] = 0;
-    io.cur_steps[b] = 0;
-    io.cur_return[b] = 0.0;
-    if (io.cur_danger) io.cur_danger[b] = 0;
-    if (io.cur_danger_dmin_sum) io.cur_danger_dmin_sum[b] = 0.0;
-    S.ring_filled_in[b] = 0;
-    S.ring_filled_out[b] = 0;
-}
-
-__global__ __launch_bounds__(kWave) void rollout_begin_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= P.B) return;
-    const cn_rollout_io io = *R.io;
-    const int64_t c0 = episode_id(io, b, 0);
-    const bool on = !past_episode_limit(io, c0);
-    begin_env(S, io, b, on);
-    clear_human_sims(P, S, b, 1, 1);
-    if (!on) return;
-    generate_scenario_lane(C, episode_seed(io, c0), (size_t)b * P.A, S.pos, S.vel, S.goal, S.rv, S.mt_key + b,
-                                   P.B, false, nullptr);
-    S.mt_pos[b] = -1;
-    S.gtime[b] = 0.0;
-}
-
-// Scenario ring fill: one lane per (env, missing scenario) generates an episode that has not been generated yet, so that ordinals [next, next + D) are resident when the rollout
-// launch that follows needs them.  The lane runs the register-only head generator; the
-// rare scenario whose rejection chain outruns its 227 words is queued in redo_list and regenerated by ring_redo_kernel
-// with a memory-backed generator from a small fixed pool (624 x kRedoLanes words, not 624 x B x D).
-constexpr int kRedoLanes = 4096;
-// ep_snap != NULL (the lagged fill, beside a transition kernel: fill_plan.h): (state, episodes finished) of env b comes from
-// ep_snap[b], the copy of StateView::ep_word that ring_fill_begin_kernel took in front of this launch — ONE reading per env
-// for all its lanes, whether that env's workgroup of the running launch had stored the word yet or not.
-__global__ __launch_bounds__(kWave) void ring_fill_begin_kernel(int B, const int* ep_word, int* ep_snap, int* redo_count) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0) *redo_count = 0;
-    if (b < B) ep_snap[b] = __hip_atomic_load(&ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R, const int* ep_snap) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int D = P.ring_mod;  // slots per env; the fill tops up to next + D and publishes that level
-    if (idx >= P.B * D) return;
-    // D slots per env (synchronous ring): lane (b, slot), neighbouring lanes write neighbouring slots.  2 D slots (lagged fill):
-    // lane (k, b), k-major, the k-th scenario env b is missing — an env misses as many as it has consumed since the previous
-    // fill, so the lanes with work are the first rows of this numbering, whole waves of them; numbered by slot the same
-    // scenarios sat scattered over twice as many half-empty waves (and, beside a launch, nobody waits for the scattered stores).
-    const bool by_slot = D == P.ring_depth;
-    const int k = by_slot ? idx % D : idx / P.B, b = by_slot ? idx / D : idx - k * P.B;
-    const cn_rollout_io* io = R.io;
-    const int state = ep_snap ? ep_snap[b] & 3 : io->active[b];
-    const int next = ring_next_ordinal(ep_snap ? ep_snap[b] >> 2 : io->ep_count[b], state);
-    if (k == 0) S.ring_filled_out[b] = next + D;
-    if (state == kRetired) return;
-    const int level = S.ring_filled_in[b];  // (ordinals below the stored level are resident from earlier fills)
-    const int ordinal = by_slot ? ring_slot_ordinal(next, k, D) : max(level, next) + k;
-    if (ordinal < level || ordinal >= next + D) return;
-    const int64_t c = episode_id(*io, b, ordinal);
-    if (past_episode_limit(*io, c)) return;
-    const uint32_t seed = episode_seed(*io, c);
-    const int ring_idx = b * D + ordinal % D;
-    Mt19937Head head;
-    generate_scenario(C, head, seed, (size_t)ring_idx * P.A, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
-    if (head.dead()) S.redo_list[atomicAdd(S.redo_count, 1)] = make_int2(ring_idx, (int)seed);
-}
-
-// The scenarios ring_fill_kernel queued: a fixed grid of kRedoLanes lanes strides over the list, each lane with
-// its own column of the word-major generator pool.
-__global__ __launch_bounds__(kWave) void ring_redo_kernel(Params P, ScenarioCfg C, StateView S) {
-    const int lane = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = *S.redo_count;
-    for (int k = lane; k < n; k += kRedoLanes) {
-        const int2 job = S.redo_list[k];
-        Mt19937 rng{S.ring_mt_key + lane, kRedoLanes, 0};
-        generate_scenario(C, rng, (uint32_t)job.y, (size_t)job.x * P.A, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
-    }
-}
-
-// ---- wave-cooperative variants (scenario_wave.h): one 64-lane workgroup per scenario -----------------------------
-__global__ __launch_bounds__(kWave) void reset_wave_kernel(Params P, ScenarioCfg C, StateView S, const uint32_t* seeds,
-                                                          const uint8_t* mask, uint64_t* draws) {
-    __shared__ WaveScratch scratch;
-    const int b = blockIdx.x;
-    if (mask && !mask[b]) return;
-    // the env's own numpy stream continues where the scenario left it (cn_sarl_explore): mt_key [624][B], mt_pos [B]
-    const uint64_t n = generate_scenario_wave(C, scratch, seeds[b], (size_t)b * P.A, S.pos, S.vel, S.goal, S.rv, S.mt_key + b,
-                                              P.B, &S.mt_pos[b]);
-    if (threadIdx.x == 0) {
-        S.gtime[b] = 0.0;
-        S.theta[b] = 1.5707963267948966;
-        if (draws) draws[b] = n;
-    }
-    clear_human_sims(P, S, b, 1 + threadIdx.x, blockDim.x);
-}
-
-__global__ __launch_bounds__(kWave) void rollout_begin_wave_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
-    __shared__ WaveScratchFill scratch;
-    const int b = blockIdx.x;
-    const cn_rollout_io io = *R.io;
-    const int64_t c0 = episode_id(io, b, 0);
-    const bool on = !past_episode_limit(io, c0);
-    if (threadIdx.x == 0) {
-        begin_env(S, io, b, on);
-        S.gtime[b] = 0.0;
-        S.mt_pos[b] = -1;
-    }
-    clear_human_sims(P, S, b, 1 + threadIdx.x, blockDim.x);
-    if (P.async_fill)
-        for (int t = threadIdx.x; t < P.ring_depth; t += blockDim.x) {  // nothing resident, nothing claimed
-            S.ring_ready[(size_t)b * P.ring_depth + t] = 0;
-            S.ring_claim[(size_t)b * P.ring_depth + t] = 0;
-        }
-    if (!on) return;
-    generate_scenario_wave(C, scratch, episode_seed(io, c0), (size_t)b * P.A, S.pos, S.vel, S.goal, S.rv);
-}
-
-// A seeded scenario is a pure function of its seed, and the reference's own evaluation phases replay a fixed set of them
-// ('val': 100 cases, 'test': 500; crowd_sim.py:272-283).  With 20 humans on the 4 m circle 60 % of all rejection-sampling
-// attempts of the 1021 bench seeds belong to the ten hardest (up to 3.1 M attempts = 118 ms of one wave, each time) — so a
-// rollout whose episode seeds come from at most kScenarioCacheMax values keeps every scenario it has generated: the first
-// workgroup that needs seed index k generates it into the ring slot and copies it to the cache (release), later ones copy it
-// from there (acquire).  Two workgroups may generate the same seed at the same time: they write the same bits.
-constexpr int kScenarioCacheMax = 4096;
-template <class Scratch>
-__device__ __forceinline__ void cached_scenario_wave(const Params& P, const ScenarioCfg& C, const StateView& S, Scratch& scratch,
-                                                     const cn_rollout_io& io, int64_t c, size_t base) {
-    const int lane = threadIdx.x;
-    const bool use = S.cache_n > 0;
-    const int k = use ? (int)((uint64_t)c % io.seed_mod) : 0;
-    if (use && __hip_atomic_load(&S.cache_state[k], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
-        if (lane < P.A) {
-            const size_t ci = (size_t)k * P.A + lane;
-            S.ring_pos[base + lane] = S.cache_pos[ci];
-            S.ring_goal[base + lane] = S.cache_goal[ci];
-            S.ring_rv[base + lane] = S.cache_rv[ci];
-        }
-        return;
-    }
-    generate_scenario_wave(C, scratch, episode_seed(io, c), base, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
-    if (!use) return;
-    __syncthreads();  // (lane 0 wrote the slot; same workgroup: visible after the barrier)
-    if (lane < P.A) {
-        const size_t ci = (size_t)k * P.A + lane;
-        S.cache_pos[ci] = S.ring_pos[base + lane];
-        S.cache_goal[ci] = S.ring_goal[base + lane];
-        S.cache_rv[ci] = S.ring_rv[base + lane];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    if (lane == 0) __hip_atomic_store(&S.cache_state[k], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__global__ __launch_bounds__(kWave) void ring_fill_wave_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R) {
-    __shared__ WaveScratchFill scratch;
-    const int idx = blockIdx.x;  // (env, ring slot)
-    const int D = P.ring_depth;
-    const int b = idx / D, slot = idx - b * D;
-    const cn_rollout_io io = *R.io;
-    const int state = io.active[b];
-    const int next = ring_next_ordinal(io.ep_count[b], state);
-    if (slot == 0 && threadIdx.x == 0) S.ring_filled_out[b] = next + D;
-    if (state == kRetired) return;
-    const int ordinal = ring_slot_ordinal(next, slot, D);
-    if (ordinal < S.ring_filled_in[b]) return;
-    const int64_t c = episode_id(io, b, ordinal);
-    if (past_episode_limit(io, c)) return;
-    cached_scenario_wave(P, C, S, scratch, io, c, ((size_t)b * D + slot) * P.A);
-}
-
-// Asynchronous flavour (CN_FLAG_ASYNC_SCENARIO_FILL): runs on a side stream NEXT to the transition kernel, as a WORK LIST.  Two
-// launches on the fill stream: ring_fill_scan_kernel examines the (env, urgency) items — urgency u = how many episodes ahead of
-// the env's next one the scenario lies — one per lane, claims the slot for the ordinal the env will need there (an earlier fill
-// launch may still be working on it: ring_claim_slot) and appends the claimed (env, ordinal) pairs to a job list, URGENCY-MAJOR
-// (every env's nearest missing scenario before anybody's far one: a hard scenario — tens of milliseconds of one wave — far
-// ahead in the ring has the whole ring's worth of steps to finish); ring_fill_jobs_kernel is a fixed grid of persistent one-wave
-// generator workgroups (CROWDNAV_AMD_FILL_QUEUE_WGS) that pop kFillJobBatch jobs at a time, generate them and publish each
-// (ring_publish_slot).  No workgroup ever waits for another one.
-// (Rounds 2-5 ran one workgroup per (env, slot) instead: 4096 x 144 = 590 k workgroups of which a fifth have something to do cost
-// a 999-step call 4.5 ms of dispatch beside its transition kernel.  The figures of both, and of 256 .. 2048 generator
-// workgroups, are in profiles/HISTORY.md.)
-//   list: int [2 + 2 * B * D]: [0] jobs appended, [1] jobs popped, then the (env, ordinal) pairs; [0] and [1] are zeroed on the
-//   fill stream in front of the scan (one list per side stream: fill launches overlap)
-__global__ __launch_bounds__(256) void ring_fill_scan_kernel(Params P, StateView S, RolloutView R, int* list) {
-    const int D = P.ring_depth;
-    const int total = P.B * D;
-    const cn_rollout_io* io = R.io;
-    const int item = blockIdx.x * blockDim.x + threadIdx.x;
-    const int u = item / P.B, b = item - u * P.B;
-    int ordinal = 0;
-    bool claimed = false;
-    if (item < total) {
-        const int word = __hip_atomic_load(&S.ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (state, episodes finished)
-        const int state = word & 3;
-        if (state != kRetired) {
-            ordinal = ring_next_ordinal(word >> 2, state) + u;
-            if (!past_episode_limit(*io, episode_id(*io, b, ordinal))) claimed = ring_claim_slot(S, b * D + ordinal % D, ordinal);
-        }
-    }
-    // one atomic per wave: the wave's claimed items go to consecutive list entries in lane (= env) order
-    const unsigned long long m = __ballot(claimed);
-    if (m == 0ull) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    int base = 0;
-    if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&list[0], __popcll(m));
-    base = __shfl(base, __ffsll((long long)m) - 1);
-    if (claimed) {
-        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
-        list[2 + 2 * k] = b;
-        list[3 + 2 * k] = ordinal;
-    }
-}
-
-constexpr int kFillJobBatch = 4;  // jobs a generator workgroup pops at a time
-__global__ __launch_bounds__(kWave) void ring_fill_jobs_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R, int* list) {
-    __shared__ WaveScratchFill scratch;
-    const int lane = threadIdx.x;
-    const int D = P.ring_depth;
-    const cn_rollout_io* io = R.io;
-    const int jobs = list[0];  // (complete: the scan kernel ran in front of this one on the same stream)
-    int first = 0;
-    do {
-        if (lane == 0) first = atomicAdd(&list[1], kFillJobBatch);
-        first = __shfl(first, 0);
-        // lane l < kFillJobBatch holds job first + l; the batch's scenarios are generated one after the other by the whole wave
-        int jb = 0, jord = 0;
-        const bool have = lane < kFillJobBatch && first + lane < jobs;
-        if (have) jb = list[2 + 2 * (first + lane)], jord = list[3 + 2 * (first + lane)];
-        unsigned long long todo = __ballot(have);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1ull;
-            const int b = __shfl(jb, src), ord = __shfl(jord, src);
-            const int idx = b * D + ord % D;
-            cached_scenario_wave(P, C, S, scratch, *io, episode_id(*io, b, ord), (size_t)idx * P.A);
-            ring_publish_slot(S, idx, ord);
-        }
-    } while (first + kFillJobBatch < jobs);
-}
-
-// Is scenario `ordinal` of env b resident?  Synchronous fill: the launch-time fill level; asynchronous: the slot's own flag
-// (acquire at device scope: the scenario data written by the concurrently running fill kernel is visible after it).
-__device__ __forceinline__ bool scenario_ready(const Params& P, const StateView& S, int env, int ordinal, int ring_filled) {
-    if (!P.async_fill) return ordinal < ring_filled;
-    const int* flag = S.ring_ready + (size_t)env * P.ring_depth + ordinal % P.ring_depth;
-    return __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == ordinal + 1;
-}
-
-__device__ __forceinline__ void load_from_ring(const Params& P, const StateView& S, const Lane& L, int slot,
-                                               AgentRegs& r) {
-    const size_t ri = ((size_t)L.env * P.ring_mod + slot) * P.A + L.a;
-    const double2 p = S.ring_pos[ri], g = S.ring_goal[ri], q = S.ring_rv[ri];
-    r.px = p.x, r.py = p.y, r.vx = 0.0, r.vy = 0.0, r.gx = g.x, r.gy = g.y, r.rad = q.x, r.vpref = q.y;
-}
-
-// explorer.py:50-72: the finished episode's record (robot lane)
-__device__ __forceinline__ void write_record(const cn_rollout_io& io, int env, int ep_count, int info, int cur_steps,
-                                             double cur_return, double time, int cur_danger, double cur_dsum) {
-    if (io.record_capacity > 0) {
-        const size_t k = (size_t)env * io.record_capacity + (ep_count % io.record_capacity);
-        if (io.ep_outcome) io.ep_outcome[k] = (uint8_t)info;
-        if (io.ep_steps) io.ep_steps[k] = cur_steps;
-        if (io.ep_return) io.ep_return[k] = cur_return;
-        if (io.ep_time) io.ep_time[k] = time;
-        if (io.ep_danger) io.ep_danger[k] = cur_danger;
-        if (io.ep_danger_dmin_sum) io.ep_danger_dmin_sum[k] = cur_dsum;
-    }
-}
-
-// ---- the episode bookkeeping of explorer.py:50-72, each piece stated once ------------------------------------------
-// What an env carries from step to step and from call to call.  The generic kernels keep it in the robot lane's registers,
-// the shard's kernel in LDS between steps (EpisodeLds), the fused kernels on every lane of the env.
-struct EpisodeBook {
-    double gtime, cur_return, cur_dsum;  // global_time; the running episode's discounted return and sum of Danger min_dist
-    int cur_steps, cur_danger;           // ... its transitions and its Danger steps
-    int ep_count, ring_filled, state;    // episodes finished; the launch-time ring fill level; kRunning / kWaitingScenario / kRetired
-};
-struct EpisodeLds {  // at Smem::disc + 8 (COMPACT: one robot per workgroup)
-    EpisodeBook book;
-    unsigned int transitions;
-    unsigned int dyn_total;  // dynamic schedule: transitions of all the visits this workgroup ran (not a register held across them)
-};
-static_assert(sizeof(EpisodeLds) <= 8 * (kCompactScratchDoubles - 8), "EpisodeLds outgrew its LDS slot");
-
-// The four pieces below are MACROS, expanded in rollout_body.inc and rollout_fused.h, for the reason rollout_body.inc is
-// included text: as __device__ __forceinline__ functions (the book by reference, or returned by value) hipcc gave every
-// rollout_kernel instantiation another instruction stream with one to seventeen more spilled SGPRs, and the generic
-// 10-half-plane kernel lost 1.3 % (profiles/episode_book_refactor.txt); expanded as text they compile to the code the kernels
-// had when each spelled them out.  `io` is a cn_rollout_io (a local copy of the device block), `S` a StateView expression.
-//
-// The book of env `env` as the previous call left it.  Straight-line loads, none under another's result: a caller that wants
-// them issued in one batch with its other loads expands this unconditionally on a clamped index (rollout_fused.h).
-#define CN_LOAD_EPISODE(P, e, S, io, ring_filled_in, env)                                         \
-    do {                                                                                          \
-        (e).gtime = (S).gtime[env];                                                               \
-        (e).state = (io).active[env];                                                             \
-        (e).ep_count = (io).ep_count[env];                                                        \
-        (e).ring_filled = (ring_filled_in)[env];                                                  \
-        (e).cur_steps = (io).cur_steps[env];                                                      \
-        (e).cur_return = (io).cur_return[env];                                                    \
-        (e).cur_danger = (io).cur_danger ? (io).cur_danger[env] : 0;                              \
-        (e).cur_dsum = (io).cur_danger_dmin_sum ? (io).cur_danger_dmin_sum[env] : 0.0;            \
-        /* a launch looks at most ring_depth scenarios ahead, however far the (lagged) fill has got */ \
-        (e).ring_filled = min((e).ring_filled, ring_next_ordinal((e).ep_count, (e).state) + (P).ring_depth); \
-    } while (0)
-// ... and as this call leaves it (robot lane), with the robot's heading, the "robot's simulator exists" mark and ep_word;
-// beside it the agent's own state (every agent lane)
-#define CN_STORE_EPISODE(P, S, io, env, e, theta)                                                 \
-    do {                                                                                          \
-        (S).gtime[env] = (e).gtime;                                                               \
-        (S).theta[env] = (theta);                                                                 \
-        if ((P).robot_orca) (S).rsim_valid[env] = 1;                                              \
-        (io).active[env] = (uint8_t)(e).state;                                                    \
-        (io).ep_count[env] = (e).ep_count;                                                        \
-        (io).cur_steps[env] = (e).cur_steps;                                                      \
-        (io).cur_return[env] = (e).cur_return;                                                    \
-        if ((io).cur_danger) (io).cur_danger[env] = (e).cur_danger;                               \
-        if ((io).cur_danger_dmin_sum) (io).cur_danger_dmin_sum[env] = (e).cur_dsum;               \
-        (S).ep_word[env] = ((e).ep_count << 2) | (e).state;                                       \
-    } while (0)
-#define CN_STORE_AGENT(S, gi, r)                                                                  \
-    do {                                                                                          \
-        (S).pos[gi] = make_double2((r).px, (r).py);                                               \
-        (S).vel[gi] = make_double2((r).vx, (r).vy);                                               \
-        (S).goal[gi] = make_double2((r).gx, (r).gy);                                              \
-        (S).rv[gi] = make_double2((r).rad, (r).vpref);                                            \
-    } while (0)
-
-// One transition of the running episode: `disc` is gamma ** (cur_steps * dt * v_pref) of THIS step.
-#define CN_BOOK_TRANSITION(e, disc, reward, info, dmin)                                           \
-    do {                                                                                          \
-        (e).cur_return = (e).cur_return + (disc) * (reward); /* python sum(): left to right */    \
-        ++(e).cur_steps;                                                                          \
-        if ((info) == CN_DANGER) {                                                                \
-            ++(e).cur_danger;                                                                     \
-            (e).cur_dsum += (dmin);                                                               \
-        }                                                                                         \
-    } while (0)
-
-// Episode end: append the record (the lane with `write`), start the book afresh, pick the next episode.  The decision is the
-// env's new state, (e).state: kRetired; kWaitingScenario (ring ran dry, or this scenario is still being generated: pause until a
-// later launch); kRunning = go on with the scenario of ordinal (e).ep_count — then, and only then, the statement
-// NEXT_SCENARIO runs: what the kernel does to take it from ring slot (e).ep_count % P.ring_mod.
-#define CN_END_EPISODE(P, S, io, env, write, time_limit, info, e, NEXT_SCENARIO)                                              \
-    do {                                                                                                                      \
-        if (write)                                                                                                            \
-            write_record(io, env, (e).ep_count, info, (e).cur_steps, (e).cur_return, ((info) == CN_TIMEOUT) ? (time_limit) : (e).gtime, \
-                         (e).cur_danger, (e).cur_dsum);                                                                       \
-        (e).cur_steps = 0, (e).cur_return = 0.0, (e).cur_danger = 0, (e).cur_dsum = 0.0;                                      \
-        (e).gtime = 0.0;                                                                                                      \
-        ++(e).ep_count;                                                                                                       \
-        if (past_episode_limit(io, episode_id(io, env, (e).ep_count))) {                                                      \
-            (e).state = kRetired;                                                                                             \
-        } else if (scenario_ready(P, S, env, (e).ep_count, (e).ring_filled)) {                                                \
-            NEXT_SCENARIO;                                                                                                    \
-        } else {                                                                                                              \
-            (e).state = kWaitingScenario;                                                                                     \
-        }                                                                                                                     \
-    } while (0)
-
-// ---------------------------------------------------------------------------------------------- launch epilogue
-// Behind every rollout launch there used to be three more kernels on the stream: rollout_finish_kernel (the transitions
-// counter), records_pack_kernel (the shard's record blocks) and records_summary_kernel (explorer.py:74-90) — 18 us of
-// kernels plus their boundaries behind a 106 us launch in the driver's 20-step shape.  They are the tail of the rollout
-// kernel now: every workgroup leaves its share (its envs' record blocks; the sums over its envs' record rings and its
-// transitions as one partial record), takes an arrival ticket of its group (workgroup b -> counter b % 32: 64 arrivals per counter at
-// 2048 workgroups; every counter on its own 256-byte line — nine counters in ONE line serialised all 2048 arrivals of a
-// 1-step launch: 35 us instead of 17), the last arrival of a group adds the group's partial sums in workgroup order and
-// arrives at the top counter, and the last of those writes the results.  The summation
-// order is a function of the workgroup indices only, never of the arrival order: the same bits on every run.
-// Hand-off between workgroups (MI355X_MICROARCH.md, inter-workgroup visibility): payload as 8-byte agent-scope atomic
-// stores (write-through), s_waitcnt vmcnt(0), then the ticket (agent-scope RMW); the reader loads the payload with
-// agent-scope atomic loads after its own ticket came back.  No L2 write-back / L1 invalidate fences.
-__device__ __forceinline__ void agent_store(double* p, double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double agent_load(const double* p) {
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// scratch: LDS, at least (E * (CN_SUMMARY_FIELDS + 1) + 1) doubles, free after the last barrier of the step loop.
-// Called by every thread of the workgroup (contains barriers); `transitions` / `ep_count` are read on the robot lanes.
-//   extra_env (>= 0, robot lanes): an env that is NOT part of this launch (the 3-of-4 schedule's last sub-launch) whose record
-//   ring this workgroup adds to its sums, so that the statistics the launch leaves behind cover every env of the engine
-__device__ __forceinline__ void rollout_epilogue(const Params& P, const StateView& S, const cn_rollout_io& io, const Lane& L,
-                                                 bool robot, unsigned int transitions, int ep_count, double* scratch,
-                                                 int extra_env = -1) {
-    constexpr int F = CN_SUMMARY_FIELDS + 1;  // the eight sums + this launch's transitions (exact in a double)
-    const int tid = threadIdx.x;
-    const int cap = io.record_capacity;
-    const int held = ep_count < cap ? ep_count : cap;
-    if (robot && io.blocks) {  // cn_rollout_records' block of this env
-        const int K = io.blocks_records;
-        double* blk = io.blocks + (size_t)L.env * (1 + (size_t)K * CN_RECORD_FIELDS);
-        blk[0] = (double)ep_count;
-        for (int j = 0; j < K; ++j) {
-            double* rec = blk + 1 + (size_t)j * CN_RECORD_FIELDS;
-            const bool have = j < held;
-            const size_t k = (size_t)L.env * cap + j;
-            rec[0] = (have && io.ep_outcome) ? (double)io.ep_outcome[k] : 0.0;
-            rec[1] = (have && io.ep_steps) ? (double)io.ep_steps[k] : 0.0;
-            rec[2] = (have && io.ep_return) ? io.ep_return[k] : 0.0;
-            rec[3] = (have && io.ep_time) ? io.ep_time[k] : 0.0;
-            rec[4] = (have && io.ep_danger) ? (double)io.ep_danger[k] : 0.0;
-            rec[5] = (have && io.ep_danger_dmin_sum) ? io.ep_danger_dmin_sum[k] : 0.0;
-        }
-    }
-    if (robot && io.env_transitions) io.env_transitions[L.env] += (uint64_t)transitions;  // (ABI v6) this env's own counter
-    const bool want = io.summary != nullptr;  // uniform over the launch
-    // nothing job-wide asked for: the launch ends here — no partial sums, no arrival tickets, no hand-off between workgroups
-    // (eight dependent memory round trips of the LAST wave, ~9 of the 113 us of a 20-step launch)
-    if (!want && io.transitions == nullptr) return;
-    if (robot) {  // this env's sums over its record ring (cn_records_summary's fields) + its transitions
-        double acc[F] = {};
-        acc[F - 1] = (double)transitions;
-        if (want) {
-            acc[0] = (double)ep_count;
-            acc[1] = (double)held;
-            for (int j = 0; j < held; ++j) {
-                const size_t k = (size_t)L.env * cap + j;
-                const int outcome = io.ep_outcome ? (int)io.ep_outcome[k] : 0;
-                acc[2] += outcome == CN_REACH_GOAL ? 1.0 : 0.0;
-                acc[3] += outcome == CN_COLLISION ? 1.0 : 0.0;
-                acc[4] += outcome == CN_TIMEOUT ? 1.0 : 0.0;
-                acc[5] += (outcome == CN_REACH_GOAL && io.ep_time) ? io.ep_time[k] : 0.0;
-                acc[6] += io.ep_return ? io.ep_return[k] : 0.0;
-                acc[7] += io.ep_danger ? (double)io.ep_danger[k] : 0.0;
-            }
-            if (extra_env >= 0) {
-                const int n2 = io.ep_count[extra_env], held2 = n2 < cap ? n2 : cap;
-                acc[0] += (double)n2;
-                acc[1] += (double)held2;
-                for (int j = 0; j < held2; ++j) {
-                    const size_t k = (size_t)extra_env * cap + j;
-                    const int outcome = io.ep_outcome ? (int)io.ep_outcome[k] : 0;
-                    acc[2] += outcome == CN_REACH_GOAL ? 1.0 : 0.0;
-                    acc[3] += outcome == CN_COLLISION ? 1.0 : 0.0;
-                    acc[4] += outcome == CN_TIMEOUT ? 1.0 : 0.0;
-                    acc[5] += (outcome == CN_REACH_GOAL && io.ep_time) ? io.ep_time[k] : 0.0;
-                    acc[6] += io.ep_return ? io.ep_return[k] : 0.0;
-                    acc[7] += io.ep_danger ? (double)io.ep_danger[k] : 0.0;
-                }
-            }
-        }
-        const int el = L.ebase / P.A;
-#pragma unroll
-        for (int f = 0; f < F; ++f) scratch[el * F + f] = acc[f];
-    }
-    block_sync(P);
-    const int f0 = want ? 0 : F - 1;  // without a summary only the transitions travel
-    if (tid >= f0 && tid < F) {  // the workgroup's envs in env order
-        double t = 0.0;
-        for (int el = 0; el < P.E; ++el)
-            if ((int)blockIdx.x * P.E + el < P.B) t += scratch[el * F + tid];
-        agent_store(S.wg_partial + (size_t)blockIdx.x * F + tid, t);
-    }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "rollout_epilogue orders its payload stores before the ticket with s_waitcnt vmcnt(0): on gfx9 (gfx950) vmcnt counts stores; gfx10+ counts them in vscnt - use release / acquire atomics there"
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this lane's payload has left before the ticket is taken
-    block_sync(P);
-    int* const flag = reinterpret_cast<int*>(scratch + P.E * F);
-    const int n_wg = (int)gridDim.x;
-    const int g = blockIdx.x % kEpilogueGroups;
-    const int members = (n_wg - g + kEpilogueGroups - 1) / kEpilogueGroups;  // workgroups b with b % groups == g
-    if (tid == 0)
-        flag[0] = __hip_atomic_fetch_add(&S.tickets[g * kTicketStride], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                  (unsigned)(members - 1);
-    block_sync(P);
-    if (!flag[0]) return;
-    // last arrival of group g: the group's sums, members in index order (lane l: members l, l + 64, ..; lanes by a fixed tree)
-    if (tid < kWave) {
-        double acc[F] = {};
-        for (int m = tid; m < members; m += kWave) {
-            const double* p = S.wg_partial + (size_t)(g + kEpilogueGroups * m) * F;
-#pragma unroll
-            for (int f = 0; f < F; ++f)
-                if (f >= f0) acc[f] += agent_load(p + f);
-        }
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            if (f < f0) continue;
-            double v = acc[f];
-#pragma unroll
-            for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-            if (tid == 0) agent_store(S.group_partial + g * F + f, v);
-        }
-    }
-    const int groups = n_wg < kEpilogueGroups ? n_wg : kEpilogueGroups;
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        flag[1] = __hip_atomic_fetch_add(&S.tickets[kEpilogueGroups * kTicketStride], 1u, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(groups - 1);
-    }
-    block_sync(P);
-    if (!flag[1]) return;
-    // last arrival of all: results out, counters back to zero for the next launch (ordered by the kernel boundary)
-    if (tid >= f0 && tid < F) {
-        double v = 0.0;
-        for (int gg = 0; gg < groups; ++gg) v += agent_load(S.group_partial + gg * F + tid);
-        if (tid < F - 1) {
-            io.summary[tid] = v;
-        } else if (io.transitions && v != 0.0) {
-            *io.transitions += (uint64_t)v;
-        }
-    }
-    if (tid <= kEpilogueGroups) S.tickets[tid * kTicketStride] = 0u;
-}
-
-// Up to n_steps transitions per running env in one launch; state lives in VGPRs between steps, finished envs
-// take their next scenario from the ring.
-// The shard's kernel (HEADLINE instantiation of rollout_kernel<10>) is compiled for THREE resident waves per SIMD (<= 168
-// VGPRs) and uses the compact LDS layout (carve<.., COMPACT>: 12 workgroups per CU); the generic 10-half-plane instantiations are
-// left to the register allocator (two waves).
-constexpr int kGeom20Waves = 3;
-// DYNAMIC SCHEDULE of the shard's kernel (Params::sched == kSchedDynamic; round 5).  The static 3-of-4 schedule needs every
-// workgroup of a sub-launch resident in ONE round: a single slot held by somebody else — a scenario-generator workgroup of the
-// asynchronous fill that runs for milliseconds — sends a step workgroup to a second round and doubles the sub-launch.  Here the
-// grid is a set of PERSISTENT workgroups (at most the resident slots) that take (env, visit)
-// items from a device queue: a call of n steps is V = Params::dyn_visits visits of n / V steps per env, queued visit-major (all
-// envs' visit 0, then all visit 1, ...), so the chip is busy for V B / G "rounds" of n / V steps whatever G is, with no launch
-// boundary (and no slowest-wave tail) in between; short visits (~56 steps) also even out the envs that sit in a jam.  An env's
-// visits must run in order: a workgroup that takes visit k of an env waits until dyn_queue[1 + env] == k (release / acquire at agent scope around the env's state in HBM).  No deadlock: an
-// item's predecessor was dequeued earlier, i.e. is held by a workgroup that is running.
-constexpr int kSchedDynamic = 100;
-template <int MAXL, bool UNI, bool HEADLINE = false, bool KD = false>
-__global__ __launch_bounds__(kMaxBlock, (MAXL == 10 && HEADLINE ? kGeom20Waves : 1)) void rollout_kernel(Params P_in, const StateView* Sd, const int* ring_filled_in,
-                                                            RolloutView R, int n_steps, const double* ext_action) {
-#include "rollout_body.inc"
-}
-
-// cn_rollout_trace: the generic rollout_kernel<MAXL, false, false, KD> (an ORCA robot is holonomic) with the per-step rows of T
-// written on the way — the same body (rollout_body.inc) with its CN_ROLLOUT_TRACE stores: at the top of a step the state BEFORE
-// the transition (every agent lane of a running env: its eight AgentRegs doubles as four 16-byte stores) and the robot lane's
-// episode ordinal and step index, behind step_core what the transition returned.  Whatever the geometry, a traced call runs
-// this kernel: never the fused one, never the shard's.
-template <int MAXL, bool KD>
-__global__ __launch_bounds__(kMaxBlock, 1) void rollout_trace_kernel(Params P_in, const StateView* Sd, const int* ring_filled_in,
-                                                                     RolloutView R, int n_steps, const cn_trace_out T) {
-    constexpr bool UNI = false, HEADLINE = false;
-    const double* const ext_action = nullptr;
-#define CN_ROLLOUT_TRACE
-#include "rollout_body.inc"
-#undef CN_ROLLOUT_TRACE
-}
-
-// cn_rollout_actions: the generic rollout_kernel<MAXL, UNI, false, KD> of an external robot with the call's action table
-// (double [B][n_steps][2]) in place of the one action block every step of a launch shares — the same body under
-// CN_ROLLOUT_ACTIONS, which moves ext_action to the step's row before step_core reads it.  n_steps cn_rollout_step launches
-// as one.  rollout_actions_trace_kernel is the same with the CN_ROLLOUT_TRACE stores (out != NULL): two kernels rather than
-// one that tests T's pointers, so that an untraced call — a planner's — holds no trace registers across the step loop.
-template <int MAXL, bool UNI, bool KD>
-__global__ __launch_bounds__(kMaxBlock, 1) void rollout_actions_kernel(Params P_in, const StateView* Sd, const int* ring_filled_in,
-                                                                       RolloutView R, int n_steps, const double* action_table) {
-    constexpr bool HEADLINE = false;
-#define CN_ROLLOUT_ACTIONS
-#include "rollout_body.inc"
-#undef CN_ROLLOUT_ACTIONS
-}
-
-template <int MAXL, bool UNI, bool KD>
-__global__ __launch_bounds__(kMaxBlock, 1) void rollout_actions_trace_kernel(Params P_in, const StateView* Sd,
-                                                                             const int* ring_filled_in, RolloutView R, int n_steps,
-                                                                             const double* action_table, const cn_trace_out T) {
-    constexpr bool HEADLINE = false;
-#define CN_ROLLOUT_ACTIONS
-#define CN_ROLLOUT_TRACE
-#include "rollout_body.inc"
-#undef CN_ROLLOUT_TRACE
-#undef CN_ROLLOUT_ACTIONS
-}
-
-#endif  // CN_SARL_TU
-
 }  // namespace cn

@@ -3,7 +3,10 @@ HIP, so tests/fill_plan_check.cpp — a stand-alone program — is compiled with
 decisions on hand-written call sequences (bench.py's two shapes among them) and brute-forces, for ring depths 1, 2, 3 and 48 and
 random call lengths of 1..200, that a launch sees the synchronous rule's fill level wherever that rule fills and at least its
 own length elsewhere, that every ordinal below the level is resident, and that a fill running beside a launch never writes a
-slot the launch may still read — whichever side of the launch's end it reads the env's episode word on."""
+slot the launch may still read — whichever side of the launch's end it reads the env's episode word on.  The model executes
+the hand-over of the two level buffers from the plan's own decisions (a fill beside a launch writes the buffer the launch does
+not read; the next launch reads the one it wrote; once per fill), and every sequence runs twice from one seed, with and without
+settles between the calls: the same decisions and the same levels."""
 import os
 import shutil
 import subprocess

@@ -1,6 +1,6 @@
 """The scenario ring in the regime the long launches of bench.py live in: an env re-uses a ring slot every ring_depth
-episodes (slot = episode ordinal % ring_depth, `rollout_fused.h` / `step_kernels.h: load_from_ring`), the fill kernels
-regenerate exactly the consumed slots (`ring_fill_*_kernel`, the `ring_filled_in / _out` swap in `fill_ring_if_needed`),
+episodes (slot = episode ordinal % ring_depth, `rollout_fused.h` / `scenario_ring.h: load_from_ring`), the fill kernels
+regenerate exactly the consumed slots (`ring_fill_*_kernel`, the `ring_filled_in / _out` swap of `scenario_ring_host.h`),
 an env whose ring ran dry inside a launch pauses and resumes in the next one, and the asynchronous fill publishes slots one
 by one (`ring_claim` / `ring_ready` carry the episode ordinal).  With the default depth of 48 an env wraps the ring after
 ~1 900 steps; CROWDNAV_AMD_RING_DEPTH = 3 (5 for the wave generators) makes it wrap every few dozen steps, and one run
@@ -162,7 +162,7 @@ def test_full_depth_ring_2500_steps(amd, oracle_mod):
     pytest.param(3, [1, 2, 7, 50, 3, 120, 17], 12, 0, id='3-launches2-one_generator_workgroup')])
 def test_asynchronous_fill_with_a_shallow_ring(amd, oracle_mod, monkeypatch, depth, launches, B, generator_wgs):
     """CN_FLAG_ASYNC_SCENARIO_FILL with a ring of 5 / 3 slots: every slot is claimed, generated and published many times
-    over (ring_claim / ring_ready carry episode ordinals; step_kernels.h: ring_fill_scan_kernel claims and lists the slots,
+    over (ring_claim / ring_ready carry episode ordinals; scenario_ring.h: ring_fill_scan_kernel claims and lists the slots,
     ring_fill_jobs_kernel generates and publishes them), fill launches of consecutive rollout calls overlap on the side
     streams.  Timing decides when an env pauses, never what it plays: its finished episodes are the oracle's, in order, bit
     for bit; and the run makes progress (no env starves).
@@ -263,7 +263,7 @@ def test_rollout_step_with_a_shallow_ring(amd, oracle_mod):
 
 @pytest.mark.parametrize('B,H,launches', [(1, 5, [60, 60]), (5, 3, [150]), (300, 5, [100, 20, 1]), (37, 20, [60, 45])])
 def test_launch_epilogue_equals_the_boundary_kernels(amd, B, H, launches):
-    """The rollout kernels' own tail (step_kernels.h: rollout_epilogue; cn_rollout_io.summary / .blocks): record blocks
+    """The rollout kernels' own tail (rollout_kernels.h: rollout_epilogue; cn_rollout_io.summary / .blocks): record blocks
     identical to cn_rollout_records', sums equal to cn_records_summary's (counts exactly, float sums to rounding: the
     summation tree differs), the transitions counter exact — for one workgroup, a partial last wave, several arrival
     groups and the one-env-per-workgroup geometry of 20 humans; and bitwise the same on a second run."""

@@ -1,4 +1,4 @@
-"""The 20-human shard's kernel (BASELINE configs[3]: `rollout_kernel<10, false, true, true>`, step_kernels.h) since round 4:
+"""The 20-human shard's kernel (BASELINE configs[3]: `rollout_kernel<10, false, true, true>`, rollout_kernels.h) since round 4:
 compact LDS layout (12 workgroups per CU), step parameters / episode bookkeeping / per-episode agent constants in LDS instead of
 registers (three resident waves per SIMD), and the 3-of-4 env schedule of `launch_shard` (crowdnav_amd.hip): a call of
 3 q + r steps runs as one launch of r steps over all envs and FOUR launches of q steps over 3 B / 4 workgroups, sub-launch k
@@ -120,7 +120,7 @@ def test_shard_kernel_with_external_robot_actions(amd, oracle_mod):
 @pytest.mark.parametrize('async_fill', [False, True])
 def test_scenario_cache_of_a_small_seed_set_changes_nothing(amd, oracle_mod, monkeypatch, async_fill):
     """Round 5: the wave generators keep the scenarios of a rollout whose episode seeds come from a small set (seed_mod <=
-    4096; step_kernels.h: cached_scenario_wave) — here SEVEN seeds on the reference's 4 m circle, so nearly every auto-reset is
+    4096; scenario_ring.h: cached_scenario_wave) — here SEVEN seeds on the reference's 4 m circle, so nearly every auto-reset is
     a cache copy.  Episodes, records, counters and end states are the oracle's (which generates every scenario afresh), and
     equal bit for bit to a run with the cache switched off (CROWDNAV_AMD_SCENARIO_CACHE=0)."""
     import torch

@@ -1,4 +1,4 @@
-"""The 3-of-4 env schedule of the 20-human shard's kernel as plain arithmetic (crowdnav_amd/csrc/step_kernels.h: rollout_body's
+"""The 3-of-4 env schedule of the 20-human shard's kernel as plain arithmetic (crowdnav_amd/csrc/rollout_kernels.h: rollout_body's
 `env_block` / `extra_env`; crowdnav_amd.hip: launch_shard).  A call of 3 q steps is four launches of q steps over 3 B / 4
 workgroups; workgroup w of sub-launch k plays env 4 (w / 3) + (w % 3) + [w % 3 >= 3 - k].  Checked here for every B that is a
 multiple of four: each sub-launch maps its workgroups onto distinct envs, every env is played in exactly three of the four
@@ -37,7 +37,7 @@ def test_schedule_is_chosen_only_where_it_saves_rounds(B, cus, want):
 
 
 # ------------------------------------------------------------------------------------------------ dynamic schedule (round 5)
-# step_kernels.h: kSchedDynamic — persistent workgroups take (env, visit) items from a device queue, visit-major; visit k of an
+# rollout_kernels.h: kSchedDynamic — persistent workgroups take (env, visit) items from a device queue, visit-major; visit k of an
 # env may start only when the env's k earlier visits are complete.  Emulated as a discrete-event simulation: G workers, item v =
 # (env v % B, visit v // B), arbitrary per-item durations.  Claims checked: no deadlock for any G >= 1 and any durations; every
 # env's visits run in order and never overlap; the split of a call's n steps over its visits adds up; the makespan stays
@@ -89,5 +89,5 @@ def test_visits_per_call_and_their_lengths(n, want):
     visits = min(visits, n)
     assert visits == want
     q, rem = divmod(n, visits)
-    lengths = [q + (1 if k < rem else 0) for k in range(visits)]   # step_kernels.h: n_steps of visit k
+    lengths = [q + (1 if k < rem else 0) for k in range(visits)]   # rollout_body.inc: n_steps of visit k
     assert sum(lengths) == n and max(lengths) - min(lengths) <= 1
