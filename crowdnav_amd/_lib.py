@@ -69,6 +69,14 @@ class CnRolloutIo(C.Structure):
     ]
 
 
+class CnLookaheadOut(C.Structure):
+    """struct cn_lookahead_out (include/crowdnav_amd.h): device pointers; final_state8 and final_theta may be NULL."""
+    _fields_ = [
+        ('ret', C.c_void_p), ('info', C.c_void_p), ('steps', C.c_void_p), ('time', C.c_void_p),
+        ('final_state8', C.c_void_p), ('final_theta', C.c_void_p),
+    ]
+
+
 class CnTraceOut(C.Structure):
     """struct cn_trace_out (include/crowdnav_amd.h): device pointers; reward, info and dmin may be NULL."""
     _fields_ = [
@@ -142,6 +150,8 @@ SYMBOLS = {
     'cn_sarl_network_route': (C.c_int, [_P, C.POINTER(C.c_int)]),
     # n cn_rollout_step calls with a table of actions as one launch (added after v12, no version bump)
     'cn_rollout_actions': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, _P, C.POINTER(CnTraceOut)]),
+    # K candidate action sequences per env scored from the current state, engine untouched (no version bump)
+    'cn_lookahead_actions': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut)]),
 }
 
 _lib = None

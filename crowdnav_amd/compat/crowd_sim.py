@@ -210,11 +210,34 @@ class CrowdSim(_Base):
     def onestep_lookahead(self, action):
         return self.step(action, update=False)
 
-    def step(self, action, update=True):
+    def lookahead(self, sequences):
+        """The n-step sibling of onestep_lookahead: K candidate sequences of n actions each (a list of K lists of n ActionXY /
+        ActionRot), every one played from the CURRENT state by the transitions step() would make, until done or n steps,
+        in one launch and without changing the env.  Returns K tuples (discounted return, info, steps): the return is
+        sum_t gamma^(t * time_step * v_pref) * r_t with t = 0 now and the engine's gamma (0.9 unless its set_gamma was
+        called), info the object of the last transition made — ReachGoal / Collision / Timeout where the sequence ended there,
+        Nothing or Danger (min_dist is not kept: None) where it was still running after n — and steps the transitions made."""
         unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
+        sequences = [list(seq) for seq in sequences]
+        if not sequences or not sequences[0] or any(len(seq) != len(sequences[0]) for seq in sequences):
+            raise ValueError('lookahead: K >= 1 sequences of one length n >= 1 are required')
+        for seq in sequences:
+            for action in seq:
+                self._check_action(action, unicycle)
+        table = np.array([[[list(a) for a in seq] for seq in sequences]], dtype=np.float64)  # [1, K, n, 2]
+        out = self._eng.lookahead(table)
+        ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
+        return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
+
+    @staticmethod
+    def _check_action(action, unicycle):
         if not isinstance(action, tuple) or not hasattr(action, 'v' if unicycle else 'vx'):
             raise TypeError('expected %s for a %s robot' % ('ActionRot' if unicycle else 'ActionXY',
                                                            'unicycle' if unicycle else 'holonomic'))
+
+    def step(self, action, update=True):
+        unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
+        self._check_action(action, unicycle)
         if update:
             self.states.append([self.robot.get_full_state(), [h.get_full_state() for h in self.humans]])
             if hasattr(self.robot.policy, 'action_values'):

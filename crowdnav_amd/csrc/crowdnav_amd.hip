@@ -203,7 +203,7 @@ static int alloc_state(cn_engine* e) {
         (rc = dev_alloc(e, &S.group_partial, (size_t)cn::kEpilogueGroups * (CN_SUMMARY_FIELDS + 1))) ||
         (rc = dev_alloc(e, &S.tickets, (size_t)(cn::kEpilogueGroups + 1) * cn::kTicketStride)) ||
         (rc = dev_alloc(e, &e->io_dev, (size_t)1)) || (rc = dev_alloc(e, &e->C.error, (size_t)1)) ||
-        (rc = dev_alloc(e, &e->S_dev, (size_t)1)))
+        (rc = dev_alloc(e, &e->S_dev, (size_t)1)) || (rc = dev_alloc(e, &e->look_dev, (size_t)1)))
         return rc;
     e->S.error = e->C.error;
     if (hipMemcpy(e->S_dev, &e->S, sizeof(cn::StateView), hipMemcpyHostToDevice) != hipSuccess)
@@ -694,6 +694,52 @@ int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const
         });
         e->launch_counts[CN_COUNT_ROLLOUT_KERNELS] += 1;
     });
+}
+
+// K candidate sequences of n_steps actions per env, scored from the envs' current state in one launch of
+// rollout_lookahead_kernel over B K virtual envs.  Not a rollout call: no io block, no ScenarioRing::around_launch (the ring is
+// neither read nor filled, a pending lagged fill stays pending), no launch counter.  What depends on the arguments alone is
+// refused first, then what depends on the engine; nothing is enqueued before the last check.
+int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out) {
+    if (!actions) return fail(CN_ERR_INVALID, "cn_lookahead_actions: actions is NULL");
+    if (!out) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out is NULL");
+    if (!out->ret) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->ret is NULL");
+    if (!out->info) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->info is NULL");
+    if (!out->steps) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->steps is NULL");
+    if (!out->time) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->time is NULL");
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_steps must be >= 0 (got %d)", n_steps);
+    if (n_candidates < 1) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_candidates must be >= 1 (got %d)", n_candidates);
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_actions: engine is NULL");
+    if (e->P.robot_orca)
+        return fail(CN_ERR_INVALID, "cn_lookahead_actions is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)");
+    // the virtual env index is an int (Lane::env; a workgroup's last lanes may look E - 1 past the end), rows are size_t
+    const uint64_t virtual_envs = (uint64_t)e->P.B * (uint64_t)n_candidates, rows = virtual_envs * (uint64_t)n_steps;
+    if (virtual_envs > (uint64_t)INT32_MAX - cn::kWave)
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates = %llu exceeds the %llu branches a launch "
+                    "indexes", (unsigned long long)virtual_envs, (unsigned long long)((uint64_t)INT32_MAX - cn::kWave));
+    if (rows > ((uint64_t)1 << 59))
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates * n_steps = %llu action rows exceed 2^59",
+                    (unsigned long long)rows);
+    if (!e->discount || e->discount_len <= 0)
+        return fail(CN_ERR_INVALID, "cn_lookahead_actions: the engine has no discount table (cn_set_gamma)");
+    if (n_steps == 0) return CN_OK;
+    int rc = bind(e);
+    if (rc) return rc;
+    if (!e->look_valid || std::memcmp(&e->look_host, out, sizeof(*out)) != 0) {  // (ordered on the engine's stream, as upload_io)
+        e->look_host = *out;
+        CN_HIP(hipMemcpyAsync(e->look_dev, &e->look_host, sizeof(*out), hipMemcpyHostToDevice, e->stream));
+        e->look_valid = true;
+    }
+    cn::Params Pv = e->P;
+    Pv.B = (int)virtual_envs;
+    const cn::RolloutView R{nullptr, e->discount, e->discount_len};
+    pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
+        hipLaunchKernelGGL((cn::rollout_lookahead_kernel<decltype(maxl)::value, decltype(uni)::value, decltype(kd)::value>),
+                           dim3((Pv.B + Pv.E - 1) / Pv.E), dim3(Pv.threads), e->smem, e->stream, Pv, (const cn::StateView*)e->S_dev, R,
+                           n_steps, actions, (const cn_lookahead_out*)e->look_dev, n_candidates);
+    });
+    CN_HIP(hipGetLastError());
+    return CN_OK;
 }
 
 int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {

@@ -89,6 +89,9 @@ struct cn_engine {
     cn_rollout_io io_host{};           // last cn_rollout_io uploaded to io_dev
     cn_rollout_io* io_dev = nullptr;   // device copy the rollout kernels read through
     cn::StateView* S_dev = nullptr;    // device copy of S (the fused rollout kernel re-reads state pointers instead of holding them)
+    cn_lookahead_out look_host{};          // last cn_lookahead_out uploaded to look_dev (look_valid: there is one)
+    cn_lookahead_out* look_dev = nullptr;  // device copy rollout_lookahead_kernel stores through
+    bool look_valid = false;
     ScenarioRing ring;
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one

@@ -2,7 +2,9 @@
 // each: one source, four kernels.
 // In scope where it is included: MAXL, UNI, HEADLINE, KD (compile-time), P_in, Sd, ring_filled_in, R, n_steps, ext_action,
 // and under CN_ROLLOUT_TRACE the caller's cn_trace_out T.  Under CN_ROLLOUT_ACTIONS the call's action table
-// action_table (double [B][n_steps][2]) takes the place of ext_action.
+// action_table (double [B][n_steps][2]) takes the place of ext_action.  Under CN_ROLLOUT_LOOKAHEAD (with CN_ROLLOUT_ACTIONS;
+// rollout_lookahead_kernel) the envs are the B K virtual ones of a cn_lookahead_actions call: P_in.B = B K, n_candidates = K,
+// Od the device copy of the caller's cn_lookahead_out; ring_filled_in and R.io are not in scope / not read.
 // Why an include and not a __device__ __forceinline__ template with a TRACE parameter: with the body behind a call, its
 // arguments passed by value or by reference alike, hipcc gave every existing rollout_kernel instantiation a different
 // instruction stream (a hundred instructions more or fewer each, the 20-human shard's kernel included).  Included text leaves
@@ -96,6 +98,28 @@
     const bool robot = L.valid && L.a == 0;
     double theta = 0.0;  // heading of a unicycle robot (external actions only)
     EpisodeBook ep = {};  // (state = kRetired)
+#ifdef CN_ROLLOUT_LOOKAHEAD
+    // L is the lane of VIRTUAL env v = b K + k (P.B = B K): the action row, the outputs and which lanes exist go by it.  What
+    // the branch starts from is env b = v / K of the engine, read through Lsrc and never written: agents, heading, kd rows,
+    // global time.  Two envs of one workgroup may have different sources (K odd), each lane divides for itself.
+    {
+        const StateView S = *Sd;
+        Lane Lsrc = L;
+        Lsrc.env = L.env / n_candidates;
+        Lsrc.gi = (size_t)Lsrc.env * (size_t)P.A + (size_t)L.a;
+        if (L.valid) load_agent(S, Lsrc.gi, r);
+        if (KD) kd_load(P, S, s, Lsrc);
+        if (robot) {
+            theta = S.theta[Lsrc.env];
+            ep.gtime = S.gtime[Lsrc.env];  // a fresh book: cur_* = 0, the discount index starts at 0
+            ep.state = kRunning;
+            s.flag[L.lane] = 1;
+        }
+    }
+    int look_info = CN_NOTHING;  // (robot lane) info code of the last transition made
+    if (visit_iter == 0) build_pairs<COMPACT>(P, s, dynamic);
+    __syncthreads();
+#else
     {
         const StateView S = *Sd;
         if (L.valid) load_agent(S, L.gi, r);
@@ -122,6 +146,7 @@
         if (KD) kd_new_episode(P, s, L);
         theta = 1.5707963267948966;
     }
+#endif
     // COMPACT: what an agent keeps for a whole episode goes to LDS here and whenever the env loads its next scenario
     const auto stage_constants = [&]() {
         if (L.lane < P.nA) {
@@ -227,14 +252,23 @@
 #endif
                 const double disc = ep.cur_steps < kMaxDiscount ? s.disc[ep.cur_steps] : 0.0;
                 CN_BOOK_TRANSITION(ep, disc, res.reward, res.info, res.dmin);
+#ifdef CN_ROLLOUT_LOOKAHEAD
+                look_info = res.info;
+                if (res.done) next_flag = 0, ep.state = kRetired;  // the branch ends here: its lanes keep what they hold
+#else
                 if (res.done) {  // 0 = the env stops stepping (retired, or waiting for its scenario), 2 + slot = every lane loads it
                     const cn_rollout_io io = *R.io;
                     next_flag = 0;
                     CN_END_EPISODE(P, *Sd, io, L.env, true, P.time_limit, res.info, ep, next_flag = 2 + ep.ep_count % P.ring_mod);
                 }
+#endif
                 s.flag[L.lane] = next_flag;
             }
         }
+#ifdef CN_ROLLOUT_LOOKAHEAD
+        // (no next scenario to load; a workgroup whose branches have all ended has nothing left to step)
+        if (!__syncthreads_or(robot && ep.state == kRunning ? 1 : 0)) break;
+#else
         __syncthreads();
         if (L.valid && s.flag[L.ebase] >= 2) {
             load_from_ring(P, *Sd, L, s.flag[L.ebase] - 2, r);
@@ -242,6 +276,7 @@
             theta = 1.5707963267948966;  // robot.set(..., np.pi / 2)
             if (COMPACT) stage_constants();
         }
+#endif
         CN_TICK(clk, 7);
     }
     if (COMPACT && L.lane < P.nA) {
@@ -256,6 +291,29 @@
     }
 #endif
 
+#ifdef CN_ROLLOUT_LOOKAHEAD
+    // Nothing of the engine is written: no agent state, no book, no kd rows, no epilogue.  A stopped env's lanes were not
+    // stepped again (Ls.valid), so the registers hold the state after each branch's LAST transition, ended or still running:
+    // one store per output here instead of one at the episode end and one behind the loop.  The six pointers come from the
+    // device copy of the caller's block, as the state pointers do: no register of the step loop holds them.
+    {
+        const cn_lookahead_out O = *Od;
+        if (robot) {
+            O.ret[L.env] = ep.cur_return;
+            O.info[L.env] = (uint8_t)look_info;
+            O.steps[L.env] = ep.cur_steps;
+            O.time[L.env] = ep.gtime;
+            if (O.final_theta) O.final_theta[L.env] = theta;
+        }
+        if (L.valid && O.final_state8) {  // cn_get_state's row of virtual env v: [v][a][8]
+            double2* const dst = reinterpret_cast<double2*>(O.final_state8 + L.gi * 8);
+            dst[0] = make_double2(r.px, r.py), dst[1] = make_double2(r.vx, r.vy);
+            dst[2] = make_double2(r.gx, r.gy), dst[3] = make_double2(r.rad, r.vpref);
+        }
+    }
+    (void)transitions, (void)extra_env;
+    }  // visits
+#else
     const StateView S = *Sd;
     if (KD) kd_store(P, S, s, L);
     if (L.valid) CN_STORE_AGENT(S, L.gi, r);
@@ -289,3 +347,4 @@
         const unsigned int dyn_transitions = threadIdx.x == 0 ? reinterpret_cast<EpisodeLds*>(s.disc + 8)->dyn_total : 0u;
         rollout_epilogue(P, *Sd, io, Le, threadIdx.x == 0, dyn_transitions, 0, reinterpret_cast<double*>(s.lines));
     }
+#endif

@@ -325,4 +325,21 @@ __global__ __launch_bounds__(kMaxBlock, 1) void rollout_actions_trace_kernel(Par
 #undef CN_ROLLOUT_ACTIONS
 }
 
+// cn_lookahead_actions: rollout_actions_kernel over B K VIRTUAL envs — branch (b, k) is virtual env v = b K + k, P_in.B = B K,
+// action_table double [B K][n_steps][2] — that start from the state of env v / K as it stands and leave the engine as it was.
+// The same body under CN_ROLLOUT_LOOKAHEAD: every load of the prologue goes through the source env; the book starts fresh;
+// an ended branch stops stepping and nothing takes its place (no ring, no record, no io block: R.io is NULL); the tail stores
+// the branch's outputs through Od, a device copy of the caller's cn_lookahead_out, and nothing else.
+template <int MAXL, bool UNI, bool KD>
+__global__ __launch_bounds__(kMaxBlock, 1) void rollout_lookahead_kernel(Params P_in, const StateView* Sd, RolloutView R, int n_steps,
+                                                                         const double* action_table, const cn_lookahead_out* Od,
+                                                                         int n_candidates) {
+    constexpr bool HEADLINE = false;
+#define CN_ROLLOUT_ACTIONS
+#define CN_ROLLOUT_LOOKAHEAD
+#include "rollout_body.inc"
+#undef CN_ROLLOUT_LOOKAHEAD
+#undef CN_ROLLOUT_ACTIONS
+}
+
 }  // namespace cn

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CnConfig, CnRolloutIo, CnTraceOut, check
+from ._lib import CnConfig, CnLookaheadOut, CnRolloutIo, CnTraceOut, check
 
 # shipped defaults of crowd_nav/configs/env.config + the hard-coded ORCA constants (orca.py:60-66)
 _DEFAULTS = dict(
@@ -306,6 +306,45 @@ class BatchedCrowdSim(object):
             if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
                 self.sync()  # `a` is a temporary copy
         return rows if trace else self._rollout[1]
+
+    def lookahead(self, actions, final_state=False, out=None):
+        """Score K candidate action sequences per env from the CURRENT state, in one launch, leaving the engine as it is
+        (cn_lookahead_actions): the n-step, K-candidate form of step(update=False).  actions: [B, K, n, 2] float64 — (vx, vy), or
+        (v, r) for a unicycle robot; branch (b, k) starts from env b as it stands, applies actions[b, k, t] as step() would
+        and stops after the first transition with done, or after n.  A contiguous float64 tensor on the engine's device is read
+        where it lies (keep it alive until the call has run); anything else is copied and the call synchronises.
+        Returns a dict of device tensors, rows [b, k]:
+            ret   float64  sum_t gamma^(t dt v_pref) r_t, t = 0 at the branch point (set_gamma's table; 0.9 unless set)
+            info  uint8    code of the last transition made (REACH_GOAL / COLLISION / TIMEOUT: the branch ended there)
+            steps int32    transitions made, 1..n
+            time  float64  global_time after the last transition made
+        and with final_state=True final_state8 float64 [B, K, A, 8] (get_state()'s layout) and final_theta float64 [B, K]:
+        the state after that transition.  `out` reuses a previous call's dict (validated).  No state, rollout buffer, ring
+        level or launch counter changes; needs no rollout_begin.  n = 0 is a no-op: the tensors are returned unwritten."""
+        shape = tuple(getattr(actions, 'shape', np.shape(actions)))
+        if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:
+            raise ValueError('lookahead: actions must be [%d, K >= 1, n, 2], got %s' % (self.B, shape))
+        K, n = int(shape[1]), int(shape[2])
+        spec = dict(ret=(torch.float64, (self.B, K)), info=(torch.uint8, (self.B, K)), steps=(torch.int32, (self.B, K)),
+                    time=(torch.float64, (self.B, K)))
+        if final_state:
+            spec.update(final_state8=(torch.float64, (self.B, K, self.A, 8)), final_theta=(torch.float64, (self.B, K)))
+        if out is None:
+            out = {k: self._new(s, dt) for k, (dt, s) in spec.items()}
+        else:
+            for k, (dt, s) in spec.items():
+                t = out.get(k)
+                if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != s
+                        or not t.is_contiguous()):
+                    raise ValueError('lookahead: out[%r] must be a contiguous %s %s tensor on %s' % (k, dt, s, self.device))
+            out = {k: out[k] for k in spec}
+        if n > 0:
+            a = self._dev(actions, torch.float64, (self.B, K, n, 2))
+            lo = CnLookaheadOut(**{k: v.data_ptr() for k, v in out.items()})
+            check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), C.byref(lo)))
+            if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
+                self.sync()  # `a` is a temporary copy
+        return out
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):

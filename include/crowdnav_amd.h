@@ -563,6 +563,39 @@ int cn_rollout_trace(cn_engine* e, const cn_rollout_io* io, int n_steps, const c
  * launch has run. */
 int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const double* actions, const cn_trace_out* out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Multi-step lookahead (no version bump: a new symbol only).  CrowdSim.onestep_lookahead (crowd_sim.py:314-420 with
+ * update=False; here cn_step(update=0)) answers "what if the robot takes action a now"; cn_lookahead_actions answers it for K
+ * candidate SEQUENCES of n actions per env, in one launch, from the envs' current state and without touching it — what a
+ * shooting or CEM planner scores.
+ *   - Branch (b, k) starts from env b as it stands: agents, global time, heading, the humans present under `mixed`, and the
+ *     kd-tree permutations of crowds above 10 humans (which no entry point copies into a second engine).
+ *   - It applies actions[b][k][t] for t = 0, 1, .. exactly as cn_step(update=1) would — the humans react through ORCA — and
+ *     stops after the first transition with done, or after n_steps.  Rows after a branch's end are not read.  Holonomic engines
+ *     read a row as (vx, vy), CN_UNICYCLE engines as (v, r).
+ *   - Nothing of the engine changes: no scenario ring, no auto-reset, no RNG draw, no record, no counter.  State, cn_rollout_io
+ *     arrays, ring levels and cn_launch_counts are not written (the launch is NOT counted: CN_LAUNCH_COUNTERS keeps its length);
+ *     a rollout in progress continues as if the call had not happened, and a pending lagged fill is not settled.
+ *   - ret uses cn_set_gamma's table (cn_create installs gamma = 0.9, as for cn_rollout_begin), index 0 at the branch point;
+ *     an engine without a table (a failed cn_set_gamma) is refused.
+ * All arrays DEVICE memory; arrays of `out` are indexed [b][k]. */
+typedef struct cn_lookahead_out {
+    double*  ret;      /* [B][K] sum_t gamma^(t*dt*v_pref) * r_t, t = 0 at the branch point, left to right            */
+    uint8_t* info;     /* [B][K] CN_* code of the LAST transition made: ReachGoal / Collision / Timeout = it ended there */
+    int32_t* steps;    /* [B][K] transitions made, 1..n                                                                */
+    double*  time;     /* [B][K] the env's global_time after the last transition made                                  */
+    double*  final_state8; /* optional [B][K][A][8] state after the last transition made (cn_get_state layout)         */
+    double*  final_theta;  /* optional [B][K]                                                                          */
+} cn_lookahead_out;
+/* ONE launch of the generic phase kernel's lookahead instantiation over B K virtual envs, on the engine's stream, whatever the
+ * geometry.  Refused, in this order, before anything is enqueued: NULL actions, out, out->ret, out->info, out->steps or
+ * out->time: CN_ERR_INVALID; n_steps < 0 or n_candidates < 1: CN_ERR_INVALID; NULL e: CN_ERR_INVALID; a CN_ROBOT_ORCA engine:
+ * CN_ERR_INVALID; B K beyond a 32-bit env index or B K n beyond 2^59 rows: CN_ERR_UNSUPPORTED.  n_steps == 0: CN_OK, nothing
+ * launched, nothing written.  Asynchronous: `actions` and the arrays of `out` must stay valid until the launch has run; `out`
+ * itself is copied by the call. */
+int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions /* [B][K][n][2] */,
+                         const cn_lookahead_out* out);
+
 #ifdef __cplusplus
 }
 #endif
