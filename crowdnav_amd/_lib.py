@@ -152,6 +152,9 @@ SYMBOLS = {
     'cn_rollout_actions': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, _P, C.POINTER(CnTraceOut)]),
     # K candidate action sequences per env scored from the current state, engine untouched (no version bump)
     'cn_lookahead_actions': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut)]),
+    # V of joint states the caller holds in the env layout, and the lookahead that bootstraps with it (no version bump)
+    'cn_sarl_state_values': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
+    'cn_lookahead_values': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),
 }
 
 _lib = None

@@ -210,13 +210,17 @@ class CrowdSim(_Base):
     def onestep_lookahead(self, action):
         return self.step(action, update=False)
 
-    def lookahead(self, sequences):
+    def lookahead(self, sequences, policy=None):
         """The n-step sibling of onestep_lookahead: K candidate sequences of n actions each (a list of K lists of n ActionXY /
         ActionRot), every one played from the CURRENT state by the transitions step() would make, until done or n steps,
         in one launch and without changing the env.  Returns K tuples (discounted return, info, steps): the return is
         sum_t gamma^(t * time_step * v_pref) * r_t with t = 0 now and the engine's gamma (0.9 unless its set_gamma was
         called), info the object of the last transition made — ReachGoal / Collision / Timeout where the sequence ended there,
-        Nothing or Danger (min_dist is not kept: None) where it was still running after n — and steps the transitions made."""
+        Nothing or Danger (min_dist is not kept: None) where it was still running after n — and steps the transitions made.
+        With a value-network policy (SARL / CADRL / LstmRL, configured and uploaded as for sarl_action) the tuples are (return,
+        info, steps, score): score = return + gamma^(steps * time_step * v_pref) * V(state after the last transition), the n-step
+        return the policy's own decision is the one-step case of; a sequence that ended scores its return alone.  LSTM-RL's rows
+        are ordered as its replay memory holds them (humans by decreasing distance)."""
         unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
         sequences = [list(seq) for seq in sequences]
         if not sequences or not sequences[0] or any(len(seq) != len(sequences[0]) for seq in sequences):
@@ -225,6 +229,11 @@ class CrowdSim(_Base):
             for action in seq:
                 self._check_action(action, unicycle)
         table = np.array([[[list(a) for a in seq] for seq in sequences]], dtype=np.float64)  # [1, K, n, 2]
+        if policy is not None:
+            eng = self._sarl_engine(policy)
+            out = eng.lookahead(table, bootstrap=True, sort_humans=eng.sarl['model'] == 'lstm_rl')
+            ret, info, steps, score = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps', 'score'))
+            return [(float(r), info_from_code(i), int(s), float(v)) for r, i, s, v in zip(ret, info, steps, score)]
         out = self._eng.lookahead(table)
         ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
         return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
@@ -288,9 +297,8 @@ class CrowdSim(_Base):
         v = self._eng.orca().cpu().numpy()[0, 0]
         return float(v[0]), float(v[1])
 
-    def sarl_action(self, policy, want_attention=False):
-        """Greedy SARL decision for the current device state: (best index | -1 stop | -2 invalid, 81 values); with
-        want_attention also the attention weights of the last action's lookahead state over the env's humans."""
+    def _sarl_engine(self, policy):
+        """The engine with `policy`'s value network configured and its current parameters uploaded (sarl_action, lookahead)."""
         eng = self._eng
         if self._rule == 'mixed' and eng.H != 5:
             raise NotImplementedError('value networks under the mixed rule need the 5 human slots the rule can draw')
@@ -304,7 +312,12 @@ class CrowdSim(_Base):
         if getattr(eng, '_sarl_weights_stamp', None) != stamp:
             eng.sarl_set_weights(policy.model.state_dict())
             eng._sarl_weights_stamp = stamp
-        out = eng.sarl_select(want_attention=want_attention)
+        return eng
+
+    def sarl_action(self, policy, want_attention=False):
+        """Greedy SARL decision for the current device state: (best index | -1 stop | -2 invalid, 81 values); with
+        want_attention also the attention weights of the last action's lookahead state over the env's humans."""
+        out = self._sarl_engine(policy).sarl_select(want_attention=want_attention)
         if want_attention:  # env 0's row of action n_actions - 1, H floats (absent humans of a `mixed` episode trimmed)
             att = out['attention'][0, -1, :len(self.humans)].cpu().numpy()
             return int(out['best'].cpu()[0]), out['values'].cpu().numpy()[0].tolist(), att

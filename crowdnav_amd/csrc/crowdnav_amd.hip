@@ -48,6 +48,33 @@ static void pick_fused(const cn_engine* e, int route, F&& f) {
     }
 }
 
+// cn_lookahead_actions' refusals, which cn_lookahead_values (sarl_abi.hip) makes first as well, with these messages: what depends
+// on the arguments alone, then what depends on the engine
+int cn_lookahead_check(const cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out) {
+    if (!actions) return fail(CN_ERR_INVALID, "cn_lookahead_actions: actions is NULL");
+    if (!out) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out is NULL");
+    if (!out->ret) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->ret is NULL");
+    if (!out->info) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->info is NULL");
+    if (!out->steps) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->steps is NULL");
+    if (!out->time) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->time is NULL");
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_steps must be >= 0 (got %d)", n_steps);
+    if (n_candidates < 1) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_candidates must be >= 1 (got %d)", n_candidates);
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_actions: engine is NULL");
+    if (e->P.robot_orca)
+        return fail(CN_ERR_INVALID, "cn_lookahead_actions is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)");
+    // the virtual env index is an int (Lane::env; a workgroup's last lanes may look E - 1 past the end), rows are size_t
+    const uint64_t virtual_envs = (uint64_t)e->P.B * (uint64_t)n_candidates, rows = virtual_envs * (uint64_t)n_steps;
+    if (virtual_envs > (uint64_t)INT32_MAX - cn::kWave)
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates = %llu exceeds the %llu branches a launch "
+                    "indexes", (unsigned long long)virtual_envs, (unsigned long long)((uint64_t)INT32_MAX - cn::kWave));
+    if (rows > ((uint64_t)1 << 59))
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates * n_steps = %llu action rows exceed 2^59",
+                    (unsigned long long)rows);
+    if (!e->discount || e->discount_len <= 0)
+        return fail(CN_ERR_INVALID, "cn_lookahead_actions: the engine has no discount table (cn_set_gamma)");
+    return CN_OK;
+}
+
 extern "C" {
 
 const char* cn_last_error(void) { return cn_g_err; }
@@ -701,30 +728,10 @@ int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const
 // neither read nor filled, a pending lagged fill stays pending), no launch counter.  What depends on the arguments alone is
 // refused first, then what depends on the engine; nothing is enqueued before the last check.
 int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out) {
-    if (!actions) return fail(CN_ERR_INVALID, "cn_lookahead_actions: actions is NULL");
-    if (!out) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out is NULL");
-    if (!out->ret) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->ret is NULL");
-    if (!out->info) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->info is NULL");
-    if (!out->steps) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->steps is NULL");
-    if (!out->time) return fail(CN_ERR_INVALID, "cn_lookahead_actions: out->time is NULL");
-    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_steps must be >= 0 (got %d)", n_steps);
-    if (n_candidates < 1) return fail(CN_ERR_INVALID, "cn_lookahead_actions: n_candidates must be >= 1 (got %d)", n_candidates);
-    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_actions: engine is NULL");
-    if (e->P.robot_orca)
-        return fail(CN_ERR_INVALID, "cn_lookahead_actions is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)");
-    // the virtual env index is an int (Lane::env; a workgroup's last lanes may look E - 1 past the end), rows are size_t
-    const uint64_t virtual_envs = (uint64_t)e->P.B * (uint64_t)n_candidates, rows = virtual_envs * (uint64_t)n_steps;
-    if (virtual_envs > (uint64_t)INT32_MAX - cn::kWave)
-        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates = %llu exceeds the %llu branches a launch "
-                    "indexes", (unsigned long long)virtual_envs, (unsigned long long)((uint64_t)INT32_MAX - cn::kWave));
-    if (rows > ((uint64_t)1 << 59))
-        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_actions: num_envs * n_candidates * n_steps = %llu action rows exceed 2^59",
-                    (unsigned long long)rows);
-    if (!e->discount || e->discount_len <= 0)
-        return fail(CN_ERR_INVALID, "cn_lookahead_actions: the engine has no discount table (cn_set_gamma)");
-    if (n_steps == 0) return CN_OK;
-    int rc = bind(e);
-    if (rc) return rc;
+    int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);
+    if (rc || n_steps == 0) return rc;
+    if ((rc = bind(e))) return rc;
+    const uint64_t virtual_envs = (uint64_t)e->P.B * (uint64_t)n_candidates;
     if (!e->look_valid || std::memcmp(&e->look_host, out, sizeof(*out)) != 0) {  // (ordered on the engine's stream, as upload_io)
         e->look_host = *out;
         CN_HIP(hipMemcpyAsync(e->look_dev, &e->look_host, sizeof(*out), hipMemcpyHostToDevice, e->stream));

@@ -211,3 +211,6 @@ inline int grid_lanes(const cn_engine* e) { return (e->P.B + cn::kWave - 1) / cn
 void cn_sarl_release(cn_engine* e);
 // crowdnav_amd.hip: launches orca_kernel (the kernels of step_kernels.h are instantiated in that translation unit only)
 void cn_launch_orca(cn_engine* e, float* out_vel);
+// crowdnav_amd.hip: cn_lookahead_actions' refusals, in its order and with its messages; CN_OK: the call would launch (or, with
+// n_steps == 0, do nothing)
+int cn_lookahead_check(const cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out);

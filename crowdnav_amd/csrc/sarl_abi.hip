@@ -61,6 +61,7 @@ struct cn_sarl {
     float* f16_bias = nullptr;      // ... and the biases in accumulator order
     int* narrow_counter = nullptr;  // cn_sarl_sample_step: workgroups of sarl_narrow_kernel that have written their V
     double* narrow_value = nullptr; // ... and reward + gamma V per (env, action), each written by the tile that computed V
+    float* state_rows = nullptr;    // cn_sarl_state_values on the narrow tiles: a pass's rows [n_groups][H][13] (allocated by the first call)
     cn::PackJobs pack_jobs = {};    // cn_sarl_set_weights: the layers to repack, run as one launch (sarl_pack_flush)
     int pack_blocks = 0;
 };
@@ -483,9 +484,17 @@ void launch_narrow(cn_engine* e, unsigned tiles, const cn::SarlDecide& D, float*
     e->launch_counts[CN_COUNT_SARL_NARROW] += 1;
 }
 
+// What one launch of the network kernels evaluates: the first n_groups groups of X / hcount / V, on n_tiles tiles of kSarlGroups.
+// A decision is the whole of the engine's buffers (whole_pass); cn_sarl_state_values fills them pass by pass, the last one shorter.
+struct SarlPass {
+    size_t n_groups, n_tiles;
+};
+SarlPass whole_pass(const cn_sarl* s) { return SarlPass{s->n_groups, s->n_tiles}; }
+SarlPass pass_of(size_t groups) { return SarlPass{groups, (groups + cn::kSarlGroups - 1) / cn::kSarlGroups}; }
+
 // the persistent grid of a register-resident kernel: a wave per tile, at most per_cu workgroups (= waves per SIMD) per CU
-dim3 reg_grid(const cn_sarl* s, unsigned per_cu) {
-    const unsigned wgs = (unsigned)((s->n_tiles + cn::kRegWaves - 1) / cn::kRegWaves), resident = (unsigned)s->n_cus * per_cu;
+dim3 reg_grid(const cn_sarl* s, const SarlPass& pass, unsigned per_cu) {
+    const unsigned wgs = (unsigned)((pass.n_tiles + cn::kRegWaves - 1) / cn::kRegWaves), resident = (unsigned)s->n_cus * per_cu;
     return dim3(wgs < resident ? wgs : resident);
 }
 const dim3 kRegBlock(cn::kRegWaves * 64);
@@ -499,18 +508,18 @@ void launch_om_term(cn_engine* e) {  // PRE: the occupancy-map half of mlp1.0, o
                        e->stream, s->om_w, s->om, s->om_term, rows);
 }
 
-int launch_reg_sarl(cn_engine* e, float* att) {
+int launch_reg_sarl(cn_engine* e, const SarlPass& pass, float* att) {
     const cn_sarl* s = e->sarl;
     const int H = s->C.H;
     if (s->pre) launch_om_term(e);
     // waves per SIMD by the kernels' register counts (of 512; scripts/kernel_resources.py): 1 / 2 humans 153 / 215 -> 3 / 2, which
     // also covers the dependent MFMA chain of the 1-human kernel
-    const dim3 grid = reg_grid(s, H == 1 ? 3u : H == 2 ? 2u : 1u);
+    const dim3 grid = reg_grid(s, pass, H == 1 ? 3u : H == 2 ? 2u : 1u);
     const bool ok = pick_int<1, 2, 3, 4, 5>(H, [&](auto nt) {
         pick_bool(s->pre, [&](auto pre) {
             pick_bool(att != nullptr, [&](auto a) {
                 hipLaunchKernelGGL((cn::sarl_reg_kernel<4, decltype(nt)::value, decltype(pre)::value, decltype(a)::value>), grid,
-                                   kRegBlock, 0, e->stream, s->reg_stream, s->X, s->V, (int)s->n_groups, (int)s->n_tiles, s->net.ks_x,
+                                   kRegBlock, 0, e->stream, s->reg_stream, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x,
                                    s->hcount, (const float*)s->om_term, s->C.n_actions, att);
             });
         });
@@ -518,31 +527,31 @@ int launch_reg_sarl(cn_engine* e, float* att) {
     return ok ? CN_OK : bad_humans(H);
 }
 
-int launch_split_f16(cn_engine* e, float* att) {
+int launch_split_f16(cn_engine* e, const SarlPass& pass, float* att) {
     const cn_sarl* s = e->sarl;
     const int H = s->C.H;
-    const dim3 grid = reg_grid(s, 1);  // one wave per SIMD at every crowd size (more than 256 registers; scripts/kernel_resources.py)
+    const dim3 grid = reg_grid(s, pass, 1);  // one wave per SIMD at every crowd size (more than 256 registers; scripts/kernel_resources.py)
     const bool ok = pick_int<1, 2, 3, 4, 5>(H, [&](auto nt) {
         pick_bool(s->net.in_dim != 13, [&](auto wide) {
             pick_bool(att != nullptr, [&](auto a) {
                 hipLaunchKernelGGL((cn::sarl_f16_kernel<cn::f16_key(decltype(wide)::value ? 2 : 1, decltype(nt)::value), decltype(nt)::value, decltype(a)::value>), grid,
                                    kRegBlock, 0, e->stream, (const _Float16*)s->f16_stream, (const float*)s->f16_bias, (const float*)s->X,
-                                   s->V, (int)s->n_groups, (int)s->n_tiles, s->net.ks_x, (const int*)s->hcount, att);
+                                   s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x, (const int*)s->hcount, att);
             });
         });
     });
     return ok ? CN_OK : bad_humans(H);
 }
 
-int launch_reg_sarl_chunk(cn_engine* e, float* att) {
+int launch_reg_sarl_chunk(cn_engine* e, const SarlPass& pass, float* att) {
     const cn_sarl* s = e->sarl;
     if (s->pre) launch_om_term(e);
     const bool ok = pick_int<3, 4>(s->chunk_nt, [&](auto nt) {
         pick_bool(s->pre, [&](auto pre) {
             pick_bool(att != nullptr, [&](auto a) {
                 hipLaunchKernelGGL((cn::sarl_reg_chunk_kernel<decltype(nt)::value, decltype(pre)::value, decltype(a)::value>),
-                                   reg_grid(s, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3, s->reg_stream2, s->X, s->V,
-                                   s->reg_scratch, (int)s->n_groups, (int)s->n_tiles, s->C.H, s->n_chunks, s->net.ks_x, s->hcount,
+                                   reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3, s->reg_stream2, s->X, s->V,
+                                   s->reg_scratch, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->n_chunks, s->net.ks_x, s->hcount,
                                    (const float*)s->om_term, s->C.n_actions, att);
             });
         });
@@ -550,35 +559,36 @@ int launch_reg_sarl_chunk(cn_engine* e, float* att) {
     return ok ? CN_OK : bad_humans(s->C.H);
 }
 
-int launch_reg_cadrl(cn_engine* e) {
+int launch_reg_cadrl(cn_engine* e, const SarlPass& pass) {
     const cn_sarl* s = e->sarl;
     const int NT = s->cadrl_nt;  // (CADRL keeps fewer activations alive than SARL: 4 / 2 waves per SIMD at 1 / 2 humans per chunk)
     const bool ok = pick_int<1, 2, 3, 4, 5>(NT, [&](auto nt) {
-        hipLaunchKernelGGL(cn::cadrl_reg_kernel<decltype(nt)::value>, reg_grid(s, NT == 1 ? 4u : NT == 2 ? 2u : 1u), kRegBlock, 0,
-                           e->stream, s->reg_stream, s->X, s->V, (int)s->n_groups, (int)s->n_tiles, s->net.ks_x, s->hcount, s->C.H,
+        hipLaunchKernelGGL(cn::cadrl_reg_kernel<decltype(nt)::value>, reg_grid(s, pass, NT == 1 ? 4u : NT == 2 ? 2u : 1u), kRegBlock, 0,
+                           e->stream, s->reg_stream, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x, s->hcount, s->C.H,
                            s->cadrl_chunks);
     });
     return ok ? CN_OK : bad_humans(s->C.H);
 }
 
-void launch_reg_lstm(cn_engine* e) {  // RegLstm, RegLstm2: 4 or 16 input k-steps
+void launch_reg_lstm(cn_engine* e, const SarlPass& pass) {  // RegLstm, RegLstm2: 4 or 16 input k-steps
     const cn_sarl* s = e->sarl;
     pick_bool(s->net.in_dim != 13, [&](auto wide) {
         constexpr int KS = decltype(wide)::value ? 16 : 4;
         if (s->route == SarlRoute::RegLstm2)
-            hipLaunchKernelGGL(cn::lstm2_reg_kernel<KS>, reg_grid(s, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3,
-                               s->reg_stream2, s->X, s->V, (int)s->n_groups, (int)s->n_tiles, s->C.H, s->net.ks_x, s->hcount);
+            hipLaunchKernelGGL(cn::lstm2_reg_kernel<KS>, reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3,
+                               s->reg_stream2, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->net.ks_x, s->hcount);
         else
-            hipLaunchKernelGGL(cn::lstm_reg_kernel<KS>, reg_grid(s, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream2, s->X,
-                               s->V, (int)s->n_groups, (int)s->n_tiles, s->C.H, s->net.ks_x, s->hcount);
+            hipLaunchKernelGGL(cn::lstm_reg_kernel<KS>, reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream2, s->X,
+                               s->V, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->net.ks_x, s->hcount);
     });
 }
 
-int launch_lds(cn_engine* e, float* att) {  // LdsTile, LdsChunked
+// LdsTile, LdsChunked — and the one-tile kernel of a configuration whose decisions take the narrow tiles (sarl_state_values)
+int launch_lds(cn_engine* e, const SarlPass& pass, float* att) {
     const cn_sarl* s = e->sarl;
-    const dim3 grid((unsigned)s->n_tiles), block(cn::kSarlThreads);
-    const dim3 pgrid((unsigned)(s->n_tiles < (size_t)s->n_cus ? s->n_tiles : (size_t)s->n_cus));  // persistent: one workgroup per CU
-    const int ng = (int)s->n_groups;
+    const dim3 grid((unsigned)pass.n_tiles), block(cn::kSarlThreads);
+    const dim3 pgrid((unsigned)(pass.n_tiles < (size_t)s->n_cus ? pass.n_tiles : (size_t)s->n_cus));  // persistent: one workgroup per CU
+    const int ng = (int)pass.n_groups;
     const bool cadrl = is_cadrl(s->cfg), lstm = is_lstm(s->cfg), chunked = s->route == SarlRoute::LdsChunked;
     if (chunked && cadrl)
         hipLaunchKernelGGL(cn::cadrl_mlp_chunked_kernel<cn::kSarlChunk>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
@@ -599,10 +609,28 @@ int launch_lds(cn_engine* e, float* att) {  // LdsTile, LdsChunked
         else
             pick_bool(att != nullptr, [&](auto a) {
                 hipLaunchKernelGGL((cn::sarl_mlp_pipe_kernel<H, decltype(a)::value>), pgrid, block, s->lds_bytes, e->stream, s->ref,
-                                   s->X, s->V, ng, (int)s->n_tiles, s->hcount, att);
+                                   s->X, s->V, ng, (int)pass.n_tiles, s->hcount, att);
             });
     });
     return ok ? CN_OK : bad_humans(s->C.H);
+}
+
+// The network on the groups of `pass` as X / hcount hold them, V into s->V: the route's kernel; on a narrow-route engine (whose
+// decisions never put X in HBM) the configuration's LDS one-tile kernel, whose packed layers every configuration uploads.
+int launch_network(cn_engine* e, const SarlPass& pass, float* att) {
+    const cn_sarl* s = e->sarl;
+    switch (s->route) {
+        case SarlRoute::RegSarl: return launch_reg_sarl(e, pass, att);
+        case SarlRoute::RegSarlChunk: return launch_reg_sarl_chunk(e, pass, att);
+        case SarlRoute::SplitF16: return launch_split_f16(e, pass, att);
+        case SarlRoute::RegCadrl: return launch_reg_cadrl(e, pass);
+        case SarlRoute::RegLstm:
+        case SarlRoute::RegLstm2: launch_reg_lstm(e, pass); return CN_OK;
+        case SarlRoute::Narrow:
+        case SarlRoute::LdsChunked:
+        case SarlRoute::LdsTile: return launch_lds(e, pass, att);
+    }
+    return CN_OK;
 }
 
 // cn_sarl_select and cn_sarl_select_attention: att == nullptr launches exactly cn_sarl_select's kernels; otherwise every SARL
@@ -622,26 +650,61 @@ int sarl_select(cn_engine* e, double* values, int32_t* best, double* action, flo
     const bool lookahead = C.with_om || C.sort_lookahead;
     if (lookahead) launch_lookahead(e);
     if (!s->narrow()) launch_features(e, s->pre ? 0 : 1, lookahead ? (const float*)nullptr : (const float*)s->orca_vel);
-    switch (s->route) {
-        case SarlRoute::Narrow: {  // X never leaves the network kernel's LDS
-            cn::SarlDecide D0{};
-            D0.in_dim = s->net.in_dim;
-            launch_narrow(e, (unsigned)s->narrow_tiles, D0, s->V, C.with_om ? s->om : nullptr, att);
-            break;
-        }
-        case SarlRoute::RegSarl: rc = launch_reg_sarl(e, att); break;
-        case SarlRoute::RegSarlChunk: rc = launch_reg_sarl_chunk(e, att); break;
-        case SarlRoute::SplitF16: rc = launch_split_f16(e, att); break;
-        case SarlRoute::RegCadrl: rc = launch_reg_cadrl(e); break;
-        case SarlRoute::RegLstm:
-        case SarlRoute::RegLstm2: launch_reg_lstm(e); break;
-        case SarlRoute::LdsChunked:
-        case SarlRoute::LdsTile: rc = launch_lds(e, att); break;
+    if (s->narrow()) {  // X never leaves the network kernel's LDS
+        cn::SarlDecide D0{};
+        D0.in_dim = s->net.in_dim;
+        launch_narrow(e, (unsigned)s->narrow_tiles, D0, s->V, C.with_om ? s->om : nullptr, att);
+    } else if ((rc = launch_network(e, whole_pass(s), att))) {
+        return rc;
     }
-    if (rc) return rc;
     hipLaunchKernelGGL(cn::sarl_select_kernel, dim3((C.B + 3) / 4), dim3(256), 0, e->stream, C, e->S.pos, e->S.vel, e->S.goal,
                        e->S.rv, e->S.gtime, e->S.theta, s->actions, s->reward, s->V, values, best, action);
     CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// cn_sarl_state_values' conditions on the engine, which cn_lookahead_values shares (`who` speaks): INVALID before UNSUPPORTED
+int state_values_check(const cn_engine* e, const char* who, bool have_theta) {
+    const cn_sarl* s = e->sarl;
+    if (!s || !s->weights_set) return fail(CN_ERR_INVALID, "%s: configure and set weights first", who);
+    if (e->P.robot_unicycle && !have_theta)
+        return fail(CN_ERR_INVALID, "%s: a CN_UNICYCLE engine needs the robot heading of every state (theta / out->final_theta is NULL)", who);
+    if (s->cfg.with_om)
+        return fail(CN_ERR_UNSUPPORTED, "%s: engines with occupancy maps (with_om) are not served: the maps of caller-held states "
+                    "are not built on the device", who);
+    if (e->cfg.scenario_rule == CN_MIXED)
+        return fail(CN_ERR_UNSUPPORTED, "%s: engines under the mixed rule are not served: a caller-held state does not say which "
+                    "humans are absent", who);
+    return CN_OK;
+}
+
+// V of n caller-held joint states (state_values_check has passed): passes of at most n_groups states through the engine's X /
+// hcount / V — or, where the narrow kernel takes caller rows, through state_rows and straight into `value`.
+int state_values_run(cn_engine* e, const double* state8, const double* theta, int64_t n, int sort_humans, float* value) {
+    cn_sarl* s = e->sarl;
+    const int H = s->C.H;
+    const bool rows_mode = s->narrow() && !is_cadrl(s->cfg);  // SarlDecide::x_rows, as cn_sarl_values; CADRL: the one-tile kernel
+    int rc;
+    if (rows_mode && !s->state_rows && (rc = dev_alloc(e, &s->state_rows, s->n_groups * H * 13))) return rc;  // the first call only
+    for (size_t first = 0; first < (size_t)n; first += s->n_groups) {
+        const size_t m = (size_t)n - first < s->n_groups ? (size_t)n - first : s->n_groups;
+        const SarlPass pass = pass_of(m);
+        const size_t lanes = pass.n_tiles * cn::kSarlGroups * H;
+        hipLaunchKernelGGL(cn::sarl_state_feature_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, H,
+                           (int)e->P.robot_unicycle, sort_humans ? 1 : 0, state8, e->P.robot_unicycle ? theta : (const double*)nullptr,
+                           first, m, pass.n_tiles, s->net.ks_x, s->X, s->hcount, rows_mode ? s->state_rows : (float*)nullptr);
+        CN_HIP(hipGetLastError());
+        if (rows_mode) {
+            cn::SarlDecide D{};
+            D.x_rows = s->state_rows, D.ext_groups = (int)m, D.in_dim = s->net.in_dim;
+            const size_t GT = (size_t)(cn::kSarlGroups / H);
+            launch_narrow(e, (unsigned)((m + GT - 1) / GT), D, value + first, nullptr, nullptr);
+        } else {
+            if ((rc = launch_network(e, pass, nullptr))) return rc;
+            CN_HIP(hipMemcpyAsync(value + first, s->V, sizeof(float) * m, hipMemcpyDeviceToDevice, e->stream));
+        }
+        CN_HIP(hipGetLastError());
+    }
     return CN_OK;
 }
 
@@ -884,6 +947,35 @@ int cn_sarl_values(cn_engine* e, const float* states, int64_t n, float* out) {
     D.x_rows = states, D.ext_groups = (int)n, D.in_dim = s->net.in_dim;
     const int GT = cn::kSarlGroups / s->C.H;
     launch_narrow(e, (unsigned)((n + GT - 1) / GT), D, out, nullptr, nullptr);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+int cn_sarl_state_values(cn_engine* e, const double* state8, const double* theta, int64_t n, int sort_humans, float* value) {
+    if (!state8) return fail(CN_ERR_INVALID, "cn_sarl_state_values: state8 is NULL");
+    if (!value) return fail(CN_ERR_INVALID, "cn_sarl_state_values: value is NULL");
+    if (n < 1) return fail(CN_ERR_INVALID, "cn_sarl_state_values: n must be >= 1 (got %lld)", (long long)n);
+    if (!e) return fail(CN_ERR_INVALID, "cn_sarl_state_values: engine is NULL");
+    int rc = state_values_check(e, "cn_sarl_state_values", theta != nullptr);
+    if (rc || (rc = bind(e))) return rc;
+    return state_values_run(e, state8, theta, n, sort_humans, value);
+}
+
+int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out,
+                        int sort_humans, float* value, double* score) {
+    int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);  // cn_lookahead_actions' own checks and messages
+    if (rc) return rc;
+    if (!out->final_state8) return fail(CN_ERR_INVALID, "cn_lookahead_values: out->final_state8 is NULL (the caller owns the branch states)");
+    if (!value) return fail(CN_ERR_INVALID, "cn_lookahead_values: value is NULL");
+    if (!score) return fail(CN_ERR_INVALID, "cn_lookahead_values: score is NULL");
+    if ((rc = state_values_check(e, "cn_lookahead_values", out->final_theta != nullptr))) return rc;
+    if (n_steps == 0) return CN_OK;
+    if ((rc = cn_lookahead_actions(e, n_steps, n_candidates, actions, out))) return rc;
+    const int64_t branches = (int64_t)e->P.B * n_candidates;
+    if ((rc = state_values_run(e, out->final_state8, out->final_theta, branches, sort_humans, value))) return rc;
+    hipLaunchKernelGGL(cn::lookahead_score_kernel, dim3((unsigned)((branches + 255) / 256)), dim3(256), 0, e->stream, (size_t)branches,
+                       (const double*)out->ret, (const uint8_t*)out->info, (const int32_t*)out->steps, (const float*)value,
+                       (const double*)e->discount, e->discount_len, score);
     CN_HIP(hipGetLastError());
     return CN_OK;
 }

@@ -362,10 +362,19 @@ __device__ __forceinline__ bool occupancy_coop_ok(const SarlCfg& C, size_t scrat
 // sorted(..., reverse=True) is stable: equal distances keep their original order).  Returns the human that sits at
 // position p of the sorted joint state: the one whose stable rank equals p.  Distances are numpy's 2-vector norm of
 // (human.position - robot.position).
-__device__ inline int human_by_decreasing_distance(const double2* pos, size_t g0, int H, int p) {
-    double d[kSarlAnyHumans];  // a parked (absent) human sorts behind every present one
-    for (int j = 0; j < H; ++j)
-        d[j] = is_parked(pos[g0 + 1 + j]) ? -1.0 - j : norm2(pos[g0 + 1 + j].x - pos[g0].x, pos[g0 + 1 + j].y - pos[g0].y);
+// THE rule, stated once for every joint state whatever holds it (the engine's arrays, a caller's state8 rows): agent_pos(0) is
+// the robot's position, agent_pos(1 + j) human j's.  human_order_key: what the humans are ranked by; human j comes before
+// human k when its key is larger, or equal with j < k.
+template <class AgentPos>
+__device__ __forceinline__ double human_order_key(AgentPos agent_pos, int j, bool slot_in_use = true) {
+    // a parked (absent) human sorts behind every present one (and so does a slot beyond the crowd, which is not read)
+    const size_t a = (size_t)1 + j;
+    return (slot_in_use && !is_parked(agent_pos(a))) ? norm2(agent_pos(a).x - agent_pos(0).x, agent_pos(a).y - agent_pos(0).y) : -1.0 - j;
+}
+template <class AgentPos>
+__device__ __forceinline__ int human_at_sorted_position(AgentPos agent_pos, int H, int p) {
+    double d[kSarlAnyHumans];
+    for (int j = 0; j < H; ++j) d[j] = human_order_key(agent_pos, j);
     int who = p;
     for (int j = 0; j < H; ++j) {
         int rank = 0;
@@ -373,6 +382,37 @@ __device__ inline int human_by_decreasing_distance(const double2* pos, size_t g0
         who = rank == p ? j : who;
     }
     return who;
+}
+// ... of up to kSarlMaxHumans humans as a permutation in registers: perm[p] = the human at position p (identity beyond H)
+template <class AgentPos>
+__device__ __forceinline__ void humans_sorted_permutation(AgentPos agent_pos, int H, int* perm /*[kSarlMaxHumans]*/) {
+    double d[kSarlMaxHumans];
+#pragma unroll
+    for (int j = 0; j < kSarlMaxHumans; ++j) d[j] = human_order_key(agent_pos, j, j < H);
+#pragma unroll
+    for (int j = 0; j < kSarlMaxHumans; ++j) {
+        int rank = 0;
+#pragma unroll
+        for (int k = 0; k < kSarlMaxHumans; ++k) rank += (k < H && (d[k] > d[j] || (d[k] == d[j] && k < j))) ? 1 : 0;
+#pragma unroll
+        for (int p = 0; p < kSarlMaxHumans; ++p) perm[p] = (j < H && rank == p) ? j : perm[p];
+    }
+}
+// ... the human at position h of a joint state of H humans: the register permutation up to kSarlMaxHumans, ranked on demand above
+template <class AgentPos>
+__device__ __forceinline__ int human_of_sorted_state(AgentPos agent_pos, int H, int h) {
+    if (H > kSarlMaxHumans) return human_at_sorted_position(agent_pos, H, h);
+    int perm[kSarlMaxHumans];
+#pragma unroll
+    for (int p = 0; p < kSarlMaxHumans; ++p) perm[p] = p;
+    humans_sorted_permutation(agent_pos, H, perm);
+    int me = h;
+#pragma unroll
+    for (int p = 0; p < kSarlMaxHumans; ++p) me = (p == h) ? perm[p] : me;
+    return me;
+}
+__device__ inline int human_by_decreasing_distance(const double2* pos, size_t g0, int H, int p) {
+    return human_at_sorted_position([&](size_t a) { return pos[g0 + a]; }, H, p);
 }
 
 // Next observable state of every human (get_next_observable_state, agent.py:63-74) from the ORCA velocities,
@@ -648,21 +688,7 @@ __device__ __forceinline__ void sarl_transform_row(const SarlCfg& C, int in_dim,
     int perm[kSarlMaxHumans];
 #pragma unroll
     for (int p = 0; p < kSarlMaxHumans; ++p) perm[p] = p;
-    if (sort_humans && C.H <= kSarlMaxHumans) {
-        double d[kSarlMaxHumans];
-#pragma unroll
-        for (int j = 0; j < kSarlMaxHumans; ++j)
-            d[j] = (j < C.H && !is_parked(pos[g0 + 1 + j])) ? norm2(pos[g0 + 1 + j].x - pos[g0].x, pos[g0 + 1 + j].y - pos[g0].y)
-                                                            : -1.0 - j;
-#pragma unroll
-        for (int j = 0; j < kSarlMaxHumans; ++j) {
-            int rank = 0;
-#pragma unroll
-            for (int k = 0; k < kSarlMaxHumans; ++k) rank += (k < C.H && (d[k] > d[j] || (d[k] == d[j] && k < j))) ? 1 : 0;
-#pragma unroll
-            for (int p = 0; p < kSarlMaxHumans; ++p) perm[p] = (j < C.H && rank == p) ? j : perm[p];
-        }
-    }
+    if (sort_humans && C.H <= kSarlMaxHumans) humans_sorted_permutation([&](size_t a) { return pos[g0 + a]; }, C.H, perm);
     const bool big = C.H > kSarlMaxHumans;  // the register permutation holds kSarlMaxHumans; larger crowds rank on demand
     int me = h;  // env order unless sorted
     if (sort_humans && !big) {
@@ -701,6 +727,67 @@ __global__ void sarl_transform_kernel(SarlCfg C, int in_dim, int sort_humans, co
     if (idx >= C.B * C.H) return;
     const int b = idx / C.H;
     sarl_transform_row(C, in_dim, sort_humans, pos, vel, goal, rv, theta, out, env_stride, b, idx - b * C.H);
+}
+
+// cn_sarl_state_values: the same transform of joint states the CALLER holds in the env layout — state8 double [n][A][8] = px,
+// py, vx, vy, gx, gy, radius, v_pref per agent (cn_get_state's rows; agent 0 the robot), theta double [n] or nullptr (0) — for
+// states first .. first + count - 1 as the network input of one pass: state first + G is group G of the pass.  Narrowed to
+// float32 where sarl_transform_row narrows, rotated by the same rotate_row, ordered by the same rule.  One lane per (group,
+// human), indexed like sarl_feature_kernel's.  rows == nullptr: X in the MLP tile order, every word of a row written (features
+// 13 .. 4 ks_x - 1 zero), padding groups of the last tile finite zeros, hcount = H throughout (no mixed rule here);
+// otherwise rows [count][H][13] for the narrow kernel's caller-rows mode (SarlDecide::x_rows).
+__global__ void sarl_state_feature_kernel(int H, int unicycle, int sort_humans, const double* state8, const double* theta,
+                                          size_t first, size_t count, size_t n_tiles, int ks_x, float* X, int* hcount, float* rows) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_tiles * H * kSarlGroups) return;
+    const int g = (int)(idx % kSarlGroups);
+    const int h = (int)((idx / kSarlGroups) % H);
+    const size_t tile = idx / ((size_t)kSarlGroups * H);
+    const size_t G = tile * kSarlGroups + g;
+    float* x = X + ((tile * H + h) * ks_x) * 64 + g;
+    if (G >= count) {
+        if (rows != nullptr) return;
+        for (int n = 0; n < ks_x * 4; ++n) x[tile_word(n)] = 0.0f;
+        if (h == 0) hcount[tile * kSarlGroups + g] = H;
+        return;
+    }
+    // an agent's row is four double2: (px, py) (vx, vy) (gx, gy) (radius, v_pref)
+    const double2* agents = reinterpret_cast<const double2*>(state8) + (first + G) * (size_t)(H + 1) * 4;
+    const int me = sort_humans ? human_of_sorted_state([&](size_t a) { return agents[4 * a]; }, H, h) : h;
+    const double2* other = agents + 4 * (size_t)(1 + me);
+    const double2 p0 = agents[0], v0 = agents[1], g0 = agents[2], r0 = agents[3];
+    const double2 p1 = other[0], v1 = other[1], r1 = other[3];
+    const float th = theta != nullptr ? (float)theta[first + G] : 0.0f;
+    float f[13];
+    rotate_row((float)p0.x, (float)p0.y, (float)v0.x, (float)v0.y, (float)r0.x, (float)g0.x, (float)g0.y, (float)r0.y, th, unicycle,
+               (float)p1.x, (float)p1.y, (float)v1.x, (float)v1.y, (float)r1.x, f);
+    if (rows != nullptr) {
+        float* r = rows + (G * H + h) * 13;
+#pragma unroll
+        for (int k = 0; k < 13; ++k) r[k] = f[k];
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 13; ++k) x[tile_word(k)] = f[k];
+    for (int n = 13; n < ks_x * 4; ++n) x[tile_word(n)] = 0.0f;
+    if (h == 0) hcount[tile * kSarlGroups + g] = H;
+}
+
+// cn_lookahead_values: the n-step return of every branch, score = ret + table[steps] * V(final state); a branch that ended
+// (ReachGoal / Collision / Timeout) gets no bootstrap, as the TD target of an episode's last transition is the reward alone
+// (explorer.py:107-113).  One multiply and one add, in that order (the build has -ffp-contract=off).  One lane per branch.
+__global__ void lookahead_score_kernel(size_t n, const double* ret, const uint8_t* info, const int32_t* steps, const float* value,
+                                       const double* table, int len, double* score) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double boot = 0.0;
+    if (info[i] < CN_REACH_GOAL) {
+        int t = steps[i];
+        t = t < len - 1 ? t : len - 1;
+        t = t < 0 ? 0 : t;
+        boot = table[t] * (double)value[i];
+    }
+    score[i] = ret[i] + boot;
 }
 
 // The epsilon-greedy branch of MultiHumanRL.predict (multi_human_rl.py:28-31), on each env's OWN numpy stream — the

@@ -307,7 +307,7 @@ class BatchedCrowdSim(object):
                 self.sync()  # `a` is a temporary copy
         return rows if trace else self._rollout[1]
 
-    def lookahead(self, actions, final_state=False, out=None):
+    def lookahead(self, actions, final_state=False, out=None, bootstrap=False, sort_humans=False):
         """Score K candidate action sequences per env from the CURRENT state, in one launch, leaving the engine as it is
         (cn_lookahead_actions): the n-step, K-candidate form of step(update=False).  actions: [B, K, n, 2] float64 — (vx, vy), or
         (v, r) for a unicycle robot; branch (b, k) starts from env b as it stands, applies actions[b, k, t] as step() would
@@ -320,15 +320,24 @@ class BatchedCrowdSim(object):
             time  float64  global_time after the last transition made
         and with final_state=True final_state8 float64 [B, K, A, 8] (get_state()'s layout) and final_theta float64 [B, K]:
         the state after that transition.  `out` reuses a previous call's dict (validated).  No state, rollout buffer, ring
-        level or launch counter changes; needs no rollout_begin.  n = 0 is a no-op: the tensors are returned unwritten."""
+        level or launch counter changes; needs no rollout_begin.  n = 0 is a no-op: the tensors are returned unwritten.
+        bootstrap=True (cn_lookahead_values; needs sarl_configure + sarl_set_weights, no occupancy maps, not the mixed rule): the
+        dict also holds the final state (as with final_state=True) and
+            value float32  V of that state under the engine's value network, for every branch, ended or not
+            score float64  ret + gamma^(steps dt v_pref) * value — the n-step return; a branch that ended (REACH_GOAL / COLLISION /
+                           TIMEOUT) gets no bootstrap: score = ret
+        sort_humans: the humans of the network's rows by decreasing distance to the robot (LSTM-RL's replay-memory order), as
+        in sarl_transform; False = env order.  The buffers sarl_export reads may be overwritten."""
         shape = tuple(getattr(actions, 'shape', np.shape(actions)))
         if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:
             raise ValueError('lookahead: actions must be [%d, K >= 1, n, 2], got %s' % (self.B, shape))
         K, n = int(shape[1]), int(shape[2])
         spec = dict(ret=(torch.float64, (self.B, K)), info=(torch.uint8, (self.B, K)), steps=(torch.int32, (self.B, K)),
                     time=(torch.float64, (self.B, K)))
-        if final_state:
+        if final_state or bootstrap:
             spec.update(final_state8=(torch.float64, (self.B, K, self.A, 8)), final_theta=(torch.float64, (self.B, K)))
+        if bootstrap:
+            spec.update(value=(torch.float32, (self.B, K)), score=(torch.float64, (self.B, K)))
         if out is None:
             out = {k: self._new(s, dt) for k, (dt, s) in spec.items()}
         else:
@@ -340,8 +349,12 @@ class BatchedCrowdSim(object):
             out = {k: out[k] for k in spec}
         if n > 0:
             a = self._dev(actions, torch.float64, (self.B, K, n, 2))
-            lo = CnLookaheadOut(**{k: v.data_ptr() for k, v in out.items()})
-            check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), C.byref(lo)))
+            lo = CnLookaheadOut(**{k: v.data_ptr() for k, v in out.items() if k not in ('value', 'score')})
+            if bootstrap:
+                check(self._lib.cn_lookahead_values(self._h, n, K, _ptr(a), C.byref(lo), int(bool(sort_humans)),
+                                                    _ptr(out['value']), _ptr(out['score'])))
+            else:
+                check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), C.byref(lo)))
             if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
                 self.sync()  # `a` is a temporary copy
         return out
@@ -617,7 +630,38 @@ def _sarl_values(self, states, out=None):
     return out
 
 
+def _sarl_state_values(self, state8, theta=None, sort_humans=False, out=None):
+    """V(state) of joint states the caller holds in the env layout (cn_sarl_state_values): state8 float64 [n, A, 8] — get_state()'s
+    rows, a rollout trace's, lookahead()'s final_state8; any leading axes [..., A, 8] are flattened — and theta float64 [n] (or the
+    same leading axes), the robot heading, required for a unicycle robot and ignored otherwise -> float32 [n], under the weights
+    of the last sarl_set_weights.  The rows are sarl_transform's (sort_humans as there; False = env order).  Any n >= 1, through
+    the engine's own network kernels in passes of num_envs x n_actions; the engine's env state is not touched, the buffers
+    sarl_export reads may be overwritten.  Contiguous float64 tensors on the engine's device are read in place; anything else is
+    copied and the call synchronises."""
+    shape = tuple(getattr(state8, 'shape', np.shape(state8)))
+    if len(shape) < 3 or shape[-2:] != (self.A, 8):
+        raise ValueError('sarl_state_values: state8 must be [n, %d, 8] (or [..., %d, 8]), got %s' % (self.A, self.A, shape))
+    n = int(np.prod(shape[:-2], dtype=np.int64))
+    if theta is not None:
+        tshape = tuple(getattr(theta, 'shape', np.shape(theta)))
+        if int(np.prod(tshape, dtype=np.int64)) != n or (len(tshape) != 1 and tshape != shape[:-2]):
+            raise ValueError('sarl_state_values: theta must be [%d] or %s, got %s' % (n, shape[:-2], tshape))
+    if out is None:
+        out = self._new((n,), torch.float32)
+    elif (not torch.is_tensor(out) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (n,)
+          or not out.is_contiguous()):
+        raise ValueError('sarl_state_values: out must be a contiguous float32 [%d] tensor on %s' % (n, self.device))
+    s = self._dev(state8, torch.float64, shape)
+    th = None if theta is None else self._dev(theta, torch.float64, tshape)
+    check(self._lib.cn_sarl_state_values(self._h, _ptr(s), _ptr(th), n, int(bool(sort_humans)), _ptr(out)))
+    in_place = torch.is_tensor(state8) and s.data_ptr() == state8.data_ptr()
+    if not in_place or (th is not None and not (torch.is_tensor(theta) and th.data_ptr() == theta.data_ptr())):
+        self.sync()  # a temporary copy
+    return out
+
+
 BatchedCrowdSim.sarl_values = _sarl_values
+BatchedCrowdSim.sarl_state_values = _sarl_state_values
 BatchedCrowdSim.sarl_sampler = _sarl_sampler
 BatchedCrowdSim.sarl_configure = _sarl_configure
 BatchedCrowdSim.sarl_set_weights = _sarl_set_weights

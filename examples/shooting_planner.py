@@ -3,9 +3,13 @@ from the 81-action table of the value-network policies, scores all of them from 
 (cn_lookahead_actions), and takes the first action of its best sequence with rollout_step.
 
     python examples/shooting_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--seed 0]
+    python examples/shooting_planner.py --model-dir DIR [--policy sarl]   # DIR/rl_model.pth (+ DIR/policy.config), as test.py's
 
 The cases run as one batch, one env per case; the line printed at the end is Explorer.run_k_episodes' summary.  A usage
-example and a smoke run, not a tuned planner: a candidate's score is its discounted return over the horizon, nothing else."""
+example and a smoke run, not a tuned planner: without --model-dir a candidate's score is its discounted return over the
+horizon, nothing else.  With a trained value network the same launch sequence bootstraps it (cn_lookahead_values, DESIGN.md
+§3.8.3): score = return + gamma^(steps * time_step * v_pref) * V(state behind the horizon), the n-step return the network's
+TD targets mean; a candidate that ended inside the horizon scores its return alone."""
 import argparse
 import logging
 import os
@@ -21,7 +25,29 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 from crowdnav_amd.compat.sarl import build_action_space  # noqa: E402
 
 
-def plan(cases, candidates, horizon, seed=0, gamma=0.9):
+def load_policy(model_dir, name):
+    """The value-network policy of a reference output directory: [DIR/policy.config, else the shipped defaults] + DIR/rl_model.pth
+    (crowd_nav/test.py:24-40; the conventions of examples/test_policy.py)."""
+    import configparser
+    from crowdnav_amd.compat.sarl import default_policy_config
+    policy = cn.policy_factory[name]()
+    if not policy.trainable:
+        raise SystemExit('--policy %s has no value network' % name)
+    ini = os.path.join(model_dir, 'policy.config')
+    if os.path.exists(ini):
+        cfg = configparser.RawConfigParser()
+        cfg.read(ini)
+    else:
+        cfg = default_policy_config({})
+    policy.configure(cfg)
+    weights = os.path.join(model_dir, 'rl_model.pth')
+    if not os.path.exists(weights):
+        raise SystemExit('cannot read %s' % weights)
+    policy.get_model().load_state_dict(torch.load(weights, map_location='cpu'))
+    return policy
+
+
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -32,6 +58,14 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9):
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
     space, _, _ = build_action_space(robot.v_pref)
+    rank_by, extra = 'ret', {}
+    if policy is not None:  # rank by the bootstrapped n-step return instead
+        if policy.kinematics != robot.kinematics:
+            raise SystemExit('the policy was configured for a %s robot, the env has a %s one' % (policy.kinematics, robot.kinematics))
+        policy.build_action_space(robot.v_pref)
+        policy.configure_engine(eng)
+        eng.sarl_set_weights(policy.get_model().state_dict())
+        rank_by, extra = 'score', dict(bootstrap=True, sort_humans=eng.sarl['model'] == 'lstm_rl')
     table = torch.tensor([list(a) for a in space], dtype=torch.float64, device=eng.device)
     gen = torch.Generator(device=eng.device)
     gen.manual_seed(seed)
@@ -42,8 +76,8 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9):
     for _ in range(int(round(env.time_limit / env.time_step)) + 2):  # every episode has ended by then (Timeout)
         draw = torch.randint(len(space), (cases, candidates, horizon), generator=gen, device=eng.device)
         sequences = table[draw]  # [cases, K, n, 2], contiguous: read where it lies
-        scores = eng.lookahead(sequences, out=scores)
-        best = scores['ret'].argmax(dim=1)
+        scores = eng.lookahead(sequences, out=scores, **extra)
+        best = scores[rank_by].argmax(dim=1)
         eng.rollout_step(sequences[env_ids, best, 0].contiguous())
         if int(bufs['active'].sum().item()) == 0:
             break
@@ -63,8 +97,11 @@ def main():
     ap.add_argument('--candidates', type=int, default=16, help='K: sequences scored per env and step')
     ap.add_argument('--horizon', type=int, default=8, help='n: actions per sequence')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--model-dir', default=None, help="a reference output directory: rl_model.pth and, if present, policy.config")
+    ap.add_argument('--policy', default='sarl', choices=['sarl', 'cadrl', 'lstm_rl'], help='the policy --model-dir was trained with')
     args = ap.parse_args()
-    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed))
+    policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
+    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy))
     return 0
 
 

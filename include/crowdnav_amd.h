@@ -596,6 +596,42 @@ typedef struct cn_lookahead_out {
 int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions /* [B][K][n][2] */,
                          const cn_lookahead_out* out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Value-bootstrapped lookahead (no version bump: new symbols only).  The n-step return a value-network policy means,
+ *   score = sum_{t<n} gamma^(t dt v_pref) r_t + gamma^(n dt v_pref) V(s_n)
+ * (MultiHumanRL.predict, multi_human_rl.py:52, is n = 1; Explorer.update_memory's TD targets train V to mean it), needs V of
+ * states the engine does not hold: a lookahead's branch ends, the rows of a recorded trace, states made up for analysis. */
+/* V(state) of n joint states the CALLER holds in the env layout: state8 double [n][A][8] (cn_get_state's rows),
+ * theta double [n] (robot heading; read only by CN_UNICYCLE engines, where it is required; NULL otherwise allowed).
+ * Rows = MultiHumanRL.transform of each state (rotate of float32 [robot full state | human h], cadrl.py:187-222) —
+ * the rows cn_sarl_transform writes for the engine's own state; sort_humans as in cn_sarl_transform.
+ * value float [n].  The engine's env state is neither read nor written. */
+int cn_sarl_state_values(cn_engine* e, const double* state8, const double* theta, int64_t n, int sort_humans, float* value);
+/* Any n >= 1: the states go through the engine's network buffers in passes of at most num_envs x n_actions, on the kernel family
+ * cn_sarl_configure chose (cn_sarl_network_route; CN_PRECISION_F16X2 engines included) — every model and human count that route
+ * takes; on a narrow-route engine the narrow kernel reads the rows (as for cn_sarl_values), CN_MODEL_CADRL there runs the
+ * configuration's one-tile LDS kernel.  A state's value does not depend on n or on its place among the n.  No allocation after
+ * the first call.  Refused, in this order, before anything is enqueued: NULL state8, NULL value, n < 1, NULL e, not configured or
+ * no weights set, theta == NULL on a CN_UNICYCLE engine: CN_ERR_INVALID; an engine with occupancy maps (with_om: the maps of
+ * arbitrary states are not built on the device), an engine under the `mixed` rule: CN_ERR_UNSUPPORTED.  Side effects: the
+ * buffers cn_sarl_export reads (V, X) may be overwritten — export what a cn_sarl_select left BEFORE calling this; a launch on
+ * the narrow tiles counts under CN_COUNT_SARL_NARROW, one per pass; the humans' ORCA velocities cn_sarl_sample_step keeps are
+ * forgotten, as by every other entry point.  Nothing else of the engine changes.  Asynchronous on the engine's stream. */
+
+/* cn_lookahead_actions(e, n_steps, n_candidates, actions, out) followed by the bootstrap, in one call:
+ *   value float  [B][K]  V of the state after the branch's last transition (every branch, ended or not)
+ *   score double [B][K]  ret + (info is ReachGoal / Collision / Timeout ? 0 : table[steps] * (double)value),
+ *                        table = cn_set_gamma's, the one `ret` uses; one multiply and one add, in that order
+ * out->final_state8 must be non-NULL (and out->final_theta on CN_UNICYCLE engines): the caller owns the branch states. */
+int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out,
+                        int sort_humans, float* value, double* score);
+/* An ended branch gets no bootstrap — the TD target of an episode's last transition is the reward alone (explorer.py:107-113) —
+ * but its value is written, for the caller who wants multi_human_rl.py:52's decision-time form.  Refused before anything is
+ * enqueued: everything cn_lookahead_actions refuses, in its order and with its messages; then NULL out->final_state8, value,
+ * score: CN_ERR_INVALID; then cn_sarl_state_values' conditions on the engine, in its order.  n_steps == 0: CN_OK, nothing
+ * launched, nothing written.  State, rollout io, ring levels and launch counters are left as cn_lookahead_actions leaves them,
+ * apart from CN_COUNT_SARL_NARROW and cn_sarl_export's buffers (above). */
+
 #ifdef __cplusplus
 }
 #endif
