@@ -77,6 +77,24 @@ class CnLookaheadOut(C.Structure):
     ]
 
 
+class CnPlanCfg(C.Structure):
+    """struct cn_plan_cfg (include/crowdnav_amd.h): the CEM planner's settings."""
+    _fields_ = [
+        ('n_steps', C.c_int32), ('n_candidates', C.c_int32), ('n_elites', C.c_int32), ('iterations', C.c_int32),
+        ('bootstrap', C.c_int32), ('sort_humans', C.c_int32),
+        ('init_std', C.c_double), ('min_std', C.c_double), ('smoothing', C.c_double), ('seed', C.c_uint64),
+    ]
+
+
+class CnPlan(C.Structure):
+    """struct cn_plan (include/crowdnav_amd.h): device pointers; order may be NULL, final_state8 / value / score without bootstrap."""
+    _fields_ = [
+        ('mean', C.c_void_p), ('std', C.c_void_p), ('best_actions', C.c_void_p), ('best_score', C.c_void_p),
+        ('action', C.c_void_p), ('candidates', C.c_void_p), ('look', CnLookaheadOut),
+        ('value', C.c_void_p), ('score', C.c_void_p), ('order', C.c_void_p),
+    ]
+
+
 class CnTraceOut(C.Structure):
     """struct cn_trace_out (include/crowdnav_amd.h): device pointers; reward, info and dmin may be NULL."""
     _fields_ = [
@@ -155,6 +173,13 @@ SYMBOLS = {
     # V of joint states the caller holds in the env layout, and the lookahead that bootstraps with it (no version bump)
     'cn_sarl_state_values': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
     'cn_lookahead_values': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),
+    # device CEM planner: draw, score (through the two lookaheads), refit, step, shift (no version bump)
+    'cn_plan_reset': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), _P]),
+    'cn_plan_draw': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_uint32]),
+    'cn_plan_refit': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_int]),
+    'cn_plan_cem': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_uint32]),
+    'cn_plan_shift': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.POINTER(CnPlanCfg), C.POINTER(CnPlan)]),
+    'cn_plan_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_uint32]),
 }
 
 _lib = None

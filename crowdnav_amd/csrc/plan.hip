@@ -1,0 +1,175 @@
+// libcrowdnav_amd.so — the device CEM planner (cn_plan_*): host entry points over the kernels of plan_kernels.h.
+//
+// A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values and real steps
+// made through cn_rollout_step, by their C entry points and therefore with their checks, their scenario-ring fill and their
+// launch counters; this translation unit only adds what runs between them (draw, refit, shift, prior), enqueued on the
+// engine's stream.  Nothing here synchronises, allocates or counts.
+#include "engine_host.h"
+#include "plan_kernels.h"
+
+namespace {
+
+// Refusals 1-5 of the header, in its order; nothing is enqueued (cn_lookahead_values with n_steps == 0 checks and returns).
+int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const char* who) {
+    if (!cfg) return fail(CN_ERR_INVALID, "%s: cfg is NULL", who);
+    if (!plan) return fail(CN_ERR_INVALID, "%s: plan is NULL", who);
+    const bool boot = cfg->bootstrap != 0;
+    const struct {
+        const void* p;
+        const char* name;
+        bool required;
+    } arrays[] = {{plan->mean, "mean", true},
+                  {plan->std, "std", true},
+                  {plan->best_actions, "best_actions", true},
+                  {plan->best_score, "best_score", true},
+                  {plan->action, "action", true},
+                  {plan->candidates, "candidates", true},
+                  {plan->look.ret, "look.ret", true},
+                  {plan->look.info, "look.info", true},
+                  {plan->look.steps, "look.steps", true},
+                  {plan->look.time, "look.time", true},
+                  {plan->look.final_state8, "look.final_state8 (required with bootstrap)", boot},
+                  {plan->value, "value (required with bootstrap)", boot},
+                  {plan->score, "score (required with bootstrap)", boot}};
+    for (const auto& a : arrays)
+        if (a.required && !a.p) return fail(CN_ERR_INVALID, "%s: plan->%s is NULL", who, a.name);
+    if (cfg->n_steps < 1) return fail(CN_ERR_INVALID, "%s: n_steps must be >= 1 (got %d)", who, cfg->n_steps);
+    if (cfg->n_steps > cn::kMaxDiscount)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_steps = %d exceeds the %d steps the discount table covers", who, cfg->n_steps,
+                    cn::kMaxDiscount);
+    if (cfg->n_candidates < 2) return fail(CN_ERR_INVALID, "%s: n_candidates must be >= 2 (got %d)", who, cfg->n_candidates);
+    if (cfg->n_candidates > cn::kPlanMaxCandidates)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_candidates = %d exceeds the %d scores the refit kernel ranks in LDS", who,
+                    cfg->n_candidates, cn::kPlanMaxCandidates);
+    if (cfg->n_elites < 1) return fail(CN_ERR_INVALID, "%s: n_elites must be >= 1 (got %d)", who, cfg->n_elites);
+    if (cfg->n_elites > cn::kPlanMaxElites)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_elites = %d exceeds the %d elites the refit kernel holds", who, cfg->n_elites,
+                    cn::kPlanMaxElites);
+    if (cfg->n_elites > cfg->n_candidates)
+        return fail(CN_ERR_INVALID, "%s: n_elites = %d exceeds n_candidates = %d", who, cfg->n_elites, cfg->n_candidates);
+    if (cfg->iterations < 1) return fail(CN_ERR_INVALID, "%s: iterations must be >= 1 (got %d)", who, cfg->iterations);
+    if (!(cfg->init_std > 0.0) || !std::isfinite(cfg->init_std))
+        return fail(CN_ERR_INVALID, "%s: init_std must be > 0 and finite (got %g)", who, cfg->init_std);
+    if (!(cfg->min_std >= 0.0) || !std::isfinite(cfg->min_std))
+        return fail(CN_ERR_INVALID, "%s: min_std must be >= 0 and finite (got %g)", who, cfg->min_std);
+    if (!(cfg->smoothing >= 0.0 && cfg->smoothing < 1.0))
+        return fail(CN_ERR_INVALID, "%s: smoothing must be in [0, 1) (got %g)", who, cfg->smoothing);
+    if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
+    if (e->P.robot_orca) return fail(CN_ERR_INVALID, "%s is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)", who);
+    if (e->P.robot_unicycle)
+        return fail(CN_ERR_UNSUPPORTED, "%s: CN_UNICYCLE engines are not served: the plan is a Gaussian over (vx, vy) clipped to "
+                    "the speed disc; one over (v, r) needs its own clip rule", who);
+    if (cfg->bootstrap)
+        return cn_lookahead_values(e, 0, cfg->n_candidates, plan->candidates, &plan->look, cfg->sort_humans, plan->value, plan->score);
+    return cn_lookahead_check(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
+}
+
+// ... and refusal 6: what cn_rollout_step refuses for the io block, without enqueuing (cn_rollout_actions of zero steps runs
+// the io checks of every rollout entry point and launches nothing; the renumbering rule is upload_io's)
+int plan_check_io(cn_engine* e, const cn_rollout_io* io, const cn_plan* plan) {
+    const int rc = cn_rollout_actions(e, io, 0, plan->action, nullptr);
+    if (rc) return rc;
+    if (e->rollout_begun && (io->seed_base != e->begin_seed_base || io->seed_mod != e->begin_seed_mod))
+        return fail(CN_ERR_INVALID, "rollout io: seed_base / seed_mod (%u / %u) differ from cn_rollout_begin's (%u / %u); call "
+                    "cn_rollout_begin to renumber the episodes", io->seed_base, io->seed_mod, e->begin_seed_base, e->begin_seed_mod);
+    return CN_OK;
+}
+
+inline unsigned plan_grid(size_t lanes) { return (unsigned)((lanes + cn::kPlanBlock - 1) / cn::kPlanBlock); }
+
+int run_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const uint8_t* mask) {
+    const cn::Params& P = e->P;
+    hipLaunchKernelGGL(cn::plan_reset_kernel, dim3(plan_grid((size_t)P.B * cfg->n_steps)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
+                       cfg->n_steps, P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal, (const double2*)e->S.rv,
+                       mask, (double2*)plan->mean, (double2*)plan->std);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+int run_draw(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
+    const cn::Params& P = e->P;
+    const size_t rows = (size_t)P.B * cfg->n_candidates * cfg->n_steps;  // (below 2^59 and B K within an int: cn_lookahead_check)
+    hipLaunchKernelGGL(cn::plan_draw_kernel, dim3(plan_grid(rows)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A, cfg->n_candidates,
+                       cfg->n_steps, (uint32_t)(cfg->seed & 0xffffffffu), (uint32_t)(cfg->seed >> 32), counter, (const double2*)e->S.rv,
+                       (const double2*)plan->mean, (const double2*)plan->std, (double2*)plan->candidates);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+int run_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int keep_best) {
+    hipLaunchKernelGGL(cn::plan_refit_kernel, dim3(e->P.B), dim3(64), 0, e->stream, cfg->n_candidates, cfg->n_steps, cfg->n_elites,
+                       keep_best ? 1 : 0, cfg->smoothing, cfg->min_std, (const double*)(cfg->bootstrap ? plan->score : plan->look.ret),
+                       (const double2*)plan->candidates, plan->mean, plan->std, (double2*)plan->best_actions, plan->best_score,
+                       (double2*)plan->action, plan->order);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+int run_cem(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
+    for (int i = 0; i < cfg->iterations; ++i) {
+        int rc = run_draw(e, cfg, plan, counter + (uint32_t)i);
+        if (rc) return rc;
+        rc = cfg->bootstrap ? cn_lookahead_values(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look, cfg->sort_humans,
+                                                  plan->value, plan->score)
+                            : cn_lookahead_actions(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
+        if (rc || (rc = run_refit(e, cfg, plan, i > 0))) return rc;
+    }
+    return CN_OK;
+}
+
+int run_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, const cn_plan* plan) {
+    const cn::Params& P = e->P;
+    hipLaunchKernelGGL(cn::plan_shift_kernel, dim3(plan_grid((size_t)2 * P.B)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A, cfg->n_steps,
+                       P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal, (const double2*)e->S.rv,
+                       (const uint8_t*)io->active, (const int32_t*)io->cur_steps, plan->mean, plan->std);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cn_plan_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const uint8_t* mask) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_reset");
+    if (rc || (rc = bind(e))) return rc;
+    return run_reset(e, cfg, plan, mask);
+}
+
+int cn_plan_draw(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_draw");
+    if (rc || (rc = bind(e))) return rc;
+    return run_draw(e, cfg, plan, counter);
+}
+
+int cn_plan_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int keep_best) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_refit");
+    if (rc || (rc = bind(e))) return rc;
+    return run_refit(e, cfg, plan, keep_best);
+}
+
+int cn_plan_cem(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_cem");
+    if (rc || (rc = bind(e))) return rc;
+    return run_cem(e, cfg, plan, counter);
+}
+
+int cn_plan_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, const cn_plan* plan) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_shift");
+    if (rc || (rc = plan_check_io(e, io, plan)) || (rc = bind(e))) return rc;
+    return run_shift(e, io, cfg, plan);
+}
+
+int cn_plan_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                    uint32_t counter) {
+    int rc = plan_check(e, cfg, plan, "cn_plan_rollout");
+    if (rc || (rc = plan_check_io(e, io, plan))) return rc;
+    if (n_real_steps < 0) return fail(CN_ERR_INVALID, "cn_plan_rollout: n_real_steps must be >= 0 (got %d)", n_real_steps);
+    for (int s = 0; s < n_real_steps; ++s) {
+        if ((rc = bind(e)) || (rc = run_cem(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations))) return rc;
+        if ((rc = cn_rollout_step(e, io, plan->action)) || (rc = run_shift(e, io, cfg, plan))) return rc;
+    }
+    return CN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,162 @@
+// Device side of the CEM planner (cn_plan_*, plan.hip): the four kernels between "score K action sequences per env"
+// (cn_lookahead_actions / cn_lookahead_values) and "a robot that plans" — draw the candidates, rank them and refit the sampling
+// distribution, shift the plan behind a real step, seed it with the goal-directed prior.  Holonomic external robots only.
+//
+// The arithmetic is the header's (include/crowdnav_amd.h, "Device CEM planner"), one IEEE operation per product and sum in the
+// order written there (the library is built with -ffp-contract=off), so that tests/plan_reference.py restates it in numpy
+// float64 bit for bit — apart from the draw's log / cos / sin, which are the device libm's.
+//   plan_reset_kernel  lane = (env, t)            the prior: full speed (or what reaches the goal in one step) towards the goal
+//   plan_draw_kernel   lane = (env, k, t)         one Philox4x32-10 block -> one Box-Muller pair -> one clipped 16-byte row
+//   plan_refit_kernel  workgroup = env, one wave  ranks by counting over the scores in LDS; best row; elite mean / std
+//   plan_shift_kernel  lane = (env, component)    walks t upwards in place: row t <- row t + 1, or the prior at an episode start
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace cn {
+
+constexpr int kPlanMaxCandidates = 1024;  // K: the scores of one env in LDS (8 KiB)
+constexpr int kPlanMaxElites = 64;        // E: the elite indices in LDS
+constexpr int kPlanBlock = 256;           // lanes per workgroup of the streaming kernels (reset, draw, shift)
+
+struct PlanWords {
+    uint32_t w[4];
+};
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between rounds
+__host__ __device__ inline PlanWords philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return PlanWords{{c0, c1, c2, c3}};
+}
+
+// the goal-directed prior of env b: robot row `r` = b A of the engine state
+__device__ inline double2 plan_prior(const double2* pos, const double2* goal, const double2* rv, size_t r, double dt) {
+    const double2 p = pos[r], g = goal[r];
+    const double dx = g.x - p.x, dy = g.y - p.y;
+    const double dist = sqrt(dx * dx + dy * dy);
+    const double reach = dist / dt, v_pref = rv[r].y;
+    const double speed = v_pref < reach ? v_pref : reach;
+    if (!(dist > 0.0)) return make_double2(0.0, 0.0);
+    return make_double2((dx / dist) * speed, (dy / dist) * speed);
+}
+
+__global__ __launch_bounds__(kPlanBlock) void plan_reset_kernel(int B, int A, int n, double dt, double init_std, const double2* pos,
+                                                                const double2* goal, const double2* rv, const uint8_t* mask,
+                                                                double2* mean, double2* std) {
+    const size_t i = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
+    if (i >= (size_t)B * n) return;
+    const size_t b = i / n;
+    if (mask && !mask[b]) return;
+    mean[i] = plan_prior(pos, goal, rv, b * A, dt);
+    std[i] = make_double2(init_std, init_std);
+}
+
+// Streaming: consecutive lanes write consecutive 16-byte rows (t fastest).  The counter words are (t, k, b, counter), so a row
+// does not depend on B, K or n.
+__global__ __launch_bounds__(kPlanBlock) void plan_draw_kernel(int B, int A, int K, int n, uint32_t seed_lo, uint32_t seed_hi,
+                                                               uint32_t counter, const double2* rv, const double2* mean,
+                                                               const double2* std, double2* candidates) {
+    const size_t i = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
+    if (i >= (size_t)B * K * n) return;
+    const uint32_t t = (uint32_t)(i % n), k = (uint32_t)((i / n) % K), b = (uint32_t)(i / ((size_t)n * K));
+    const size_t row = (size_t)b * n + t;
+    double2 a = mean[row];
+    if (k > 0) {
+        const PlanWords r4 = philox4x32_10(t, k, b, counter, seed_lo, seed_hi);
+        const double u1 = ((double)(r4.w[0] >> 5) * 67108864.0 + (double)(r4.w[1] >> 6) + 1.0) / 9007199254740992.0;
+        const double u2 = ((double)(r4.w[2] >> 5) * 67108864.0 + (double)(r4.w[3] >> 6)) / 9007199254740992.0;
+        const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
+        const double2 sd = std[row];
+        a.x = a.x + sd.x * (r * cos(ang));
+        a.y = a.y + sd.y * (r * sin(ang));
+    }
+    const double nrm = sqrt(a.x * a.x + a.y * a.y), v_pref = rv[(size_t)b * A].y;
+    if (nrm > v_pref) {
+        const double s = v_pref / nrm;
+        a.x *= s, a.y *= s;
+    }
+    candidates[i] = a;
+}
+
+// One wave per env.  rank(k) = #{j : s_j > s_k, or s_j == s_k and j < k}: a permutation of 0..K-1 for finite scores (NaN is not
+// handled).  LDS holds the env's scores and the elite indices, nothing else.
+__global__ __launch_bounds__(64) void plan_refit_kernel(int K, int n, int E, int keep_best, double smoothing, double min_std,
+                                                        const double* score, const double2* candidates, double* mean, double* std,
+                                                        double2* best_actions, double* best_score, double2* action, int32_t* order) {
+    __shared__ double sc[kPlanMaxCandidates];
+    __shared__ int elite[kPlanMaxElites];
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double held = best_score[b];  // (read by every lane before lane 0 may replace it below)
+    for (int k = lane; k < K; k += 64) sc[k] = score[b * K + k];
+    elite[lane] = 0;  // (NaN scores rank nothing sensibly; the indices read below still address the env's own candidates)
+    __syncthreads();
+    for (int k = lane; k < K; k += 64) {
+        const double sk = sc[k];
+        int rank = 0;
+        for (int j = 0; j < K; ++j) {
+            const double sj = sc[j];
+            rank += (sj > sk || (sj == sk && j < k)) ? 1 : 0;
+        }
+        if (order) order[b * K + rank] = k;
+        if (rank < E) elite[rank] = k;
+    }
+    __syncthreads();
+    const int top = elite[0];
+    const double s_top = sc[top];
+    if (!keep_best || s_top > held) {  // strict: the earliest holder of a score keeps it
+        const double2* src = candidates + (b * K + top) * n;
+        for (int t = lane; t < n; t += 64) best_actions[b * n + t] = src[t];
+        if (lane == 0) {
+            best_score[b] = s_top;
+            action[b] = src[0];
+        }
+    }
+    const double* cand = reinterpret_cast<const double*>(candidates);
+    const double keep = 1.0 - smoothing;
+    for (int c = lane; c < 2 * n; c += 64) {  // component (t, xy) of the plan: sums over the elites in rank order
+        double sum = 0.0;
+        for (int e = 0; e < E; ++e) sum = sum + cand[(b * K + elite[e]) * n * 2 + c];
+        const double m = sum / (double)E;
+        double dev2 = 0.0;
+        for (int e = 0; e < E; ++e) {
+            const double d = cand[(b * K + elite[e]) * n * 2 + c] - m;
+            dev2 = dev2 + d * d;
+        }
+        const double sd = sqrt(dev2 / (double)E);
+        const size_t at = b * n * 2 + c;
+        mean[at] = smoothing * mean[at] + keep * m;
+        const double blended = smoothing * std[at] + keep * sd;
+        std[at] = blended < min_std ? min_std : blended;
+    }
+}
+
+// After a real step.  In place, so one lane owns component c of env b and walks t upwards (row t + 1 is read before it is
+// written).  cur_steps == 0: the env's episode has just ended and its next scenario is loaded — or it is still waiting for one,
+// and gets the prior of its stale state.
+__global__ __launch_bounds__(kPlanBlock) void plan_shift_kernel(int B, int A, int n, double dt, double init_std, const double2* pos,
+                                                                const double2* goal, const double2* rv, const uint8_t* active,
+                                                                const int32_t* cur_steps, double* mean, double* std) {
+    const int i = blockIdx.x * kPlanBlock + threadIdx.x;
+    if (i >= 2 * B) return;
+    const size_t b = (size_t)(i >> 1);
+    const int c = i & 1;
+    if (!active[b]) return;
+    double* m = mean + b * n * 2 + c;
+    double* s = std + b * n * 2 + c;
+    if (cur_steps[b] == 0) {
+        const double2 prior = plan_prior(pos, goal, rv, b * A, dt);
+        const double v = c ? prior.y : prior.x;
+        for (int t = 0; t < n; ++t) m[2 * t] = v;
+    } else {
+        for (int t = 0; t + 1 < n; ++t) m[2 * t] = m[2 * (t + 1)];
+    }
+    for (int t = 0; t < n; ++t) s[2 * t] = init_std;
+}
+
+}  // namespace cn

@@ -39,6 +39,40 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class Plan(object):
+    """What BatchedCrowdSim.plan_begin returns: the device tensors of a CEM planner (struct cn_plan) and its settings (struct
+    cn_plan_cfg).  The tensors are the caller's to read and write between calls; they live as long as the object."""
+
+    def __init__(self, eng, K, n, elites, iterations, init_std, min_std, smoothing, seed, bootstrap, sort_humans):
+        B, dev = eng.B, eng.device
+        self.engine = weakref.ref(eng)
+        self.K, self.n, self.elites, self.iterations, self.bootstrap = K, n, elites, iterations, bootstrap
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        self.mean, self.std, self.best_actions = f64(B, n, 2), f64(B, n, 2).fill_(init_std), f64(B, n, 2)
+        self.best_score, self.action, self.candidates = f64(B), f64(B, 2), f64(B, K, n, 2)
+        self.order = torch.zeros((B, K), dtype=torch.int32, device=dev)
+        self.look = dict(ret=f64(B, K), info=torch.zeros((B, K), dtype=torch.uint8, device=dev),
+                         steps=torch.zeros((B, K), dtype=torch.int32, device=dev), time=f64(B, K))
+        if bootstrap:
+            self.look.update(final_state8=f64(B, K, eng.A, 8), final_theta=f64(B, K),
+                             value=torch.zeros((B, K), dtype=torch.float32, device=dev), score=f64(B, K))
+        self.cfg = _lib.CnPlanCfg(n_steps=n, n_candidates=K, n_elites=elites, iterations=iterations, bootstrap=int(bootstrap),
+                                  sort_humans=int(sort_humans), init_std=init_std, min_std=min_std, smoothing=smoothing,
+                                  seed=seed & 0xffffffffffffffff)
+        look = CnLookaheadOut(**{k: v.data_ptr() for k, v in self.look.items() if k not in ('value', 'score')})
+        self.c = _lib.CnPlan(mean=self.mean.data_ptr(), std=self.std.data_ptr(), best_actions=self.best_actions.data_ptr(),
+                             best_score=self.best_score.data_ptr(), action=self.action.data_ptr(),
+                             candidates=self.candidates.data_ptr(), look=look, order=self.order.data_ptr(),
+                             value=self.look['value'].data_ptr() if bootstrap else None,
+                             score=self.look['score'].data_ptr() if bootstrap else None)
+
+    def tensors(self):
+        """Every tensor of the plan by name (the lookahead rows as look.<name>)."""
+        out = {k: getattr(self, k) for k in ('mean', 'std', 'best_actions', 'best_score', 'action', 'candidates', 'order')}
+        out.update({'look.' + k: v for k, v in self.look.items()})
+        return out
+
+
 class BatchedCrowdSim(object):
     """B crowd-navigation envs resident in HBM.  All tensors returned live on the engine's device."""
 
@@ -358,6 +392,77 @@ class BatchedCrowdSim(object):
             if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
                 self.sync()  # `a` is a temporary copy
         return out
+
+    # ---------------------------------------------------------------- device CEM planner (cn_plan_*)
+    def plan_begin(self, K, n, elites, iterations, init_std, min_std=0.0, smoothing=0.0, seed=0, bootstrap=False,
+                   sort_humans=False):
+        """The tensors and settings of a cross-entropy-method planner over this engine (struct cn_plan / cn_plan_cfg): per env a
+        Gaussian over sequences of n actions, K candidates drawn from it per iteration, refitted to the `elites` best,
+        `iterations` times per planning step.  Returns a Plan whose attributes are device tensors —
+            mean, std, best_actions float64 [B, n, 2]; best_score float64 [B]; action float64 [B, 2]
+            candidates float64 [B, K, n, 2]; order int32 [B, K] (candidate index at rank r)
+            look: the dict lookahead() returns, rows of the last iteration (with bootstrap: final state, value, score too)
+        mean starts at zero and std at init_std: call plan_reset() for the goal-directed prior.  Holonomic ROBOT_EXTERNAL
+        engines; the settings are checked by the first call that uses the plan."""
+        K, n = int(K), int(n)
+        if K < 1 or n < 1:
+            raise ValueError('plan_begin: K and n must be >= 1')
+        return Plan(self, K, n, int(elites), int(iterations), float(init_std), float(min_std), float(smoothing), int(seed),
+                    bool(bootstrap), bool(sort_humans))
+
+    def _plan(self, plan):
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        return C.byref(plan.cfg), C.byref(plan.c)
+
+    def plan_reset(self, plan, mask=None):
+        """The goal-directed prior (cn_plan_reset): mean = full speed — or what reaches the goal in one step — from the robot
+        towards its goal at every t, std = init_std; for the envs of `mask` ([B] bool / uint8, None = all)."""
+        m = None if mask is None else self._dev(mask, torch.uint8, (self.B,))
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_reset(self._h, cfg, c, _ptr(m)))
+        if m is not None and not (torch.is_tensor(mask) and m.data_ptr() == mask.data_ptr()):
+            self.sync()  # `m` is a temporary copy
+        return plan
+
+    def plan_draw(self, plan, counter):
+        """plan.candidates <- K sequences per env from N(mean, std), clipped to the robot's speed; candidate 0 is the mean
+        (cn_plan_draw).  Philox4x32-10 keyed by the plan's seed, counter words (t, k, b, counter)."""
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_draw(self._h, cfg, c, int(counter) & 0xffffffff))
+        return plan.candidates
+
+    def plan_refit(self, plan, keep_best=False):
+        """Rank plan.candidates by plan.look['ret'] (['score'] with bootstrap), write order / best_* / action, refit mean and
+        std to the elites (cn_plan_refit).  keep_best: the best sequence is replaced only by a strictly better one."""
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_refit(self._h, cfg, c, int(bool(keep_best))))
+        return plan
+
+    def plan_cem(self, plan, counter):
+        """One planning step (cn_plan_cem): `iterations` x (draw with counter + i, lookahead, refit), all enqueued by one
+        call; plan.action then holds the first action of the best sequence found.  The engine is left as lookahead() leaves it."""
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_cem(self._h, cfg, c, int(counter) & 0xffffffff))
+        return plan
+
+    def plan_shift(self, plan):
+        """After rollout_step(plan.action) (cn_plan_shift): the plan of a running env moves up by one step (std back to
+        init_std), an env whose episode has just ended gets the prior of its new scenario, a retired env is left alone."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_shift(self._h, C.byref(self._rollout[0]), cfg, c))
+        return plan
+
+    def plan_rollout(self, plan, n_real, counter):
+        """n_real closed-loop steps in ONE call without host work or synchronisation in between (cn_plan_rollout): per step
+        plan_cem(counter + s * iterations), rollout_step(plan.action), plan_shift.  Returns the rollout's bufs."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_rollout(self._h, C.byref(self._rollout[0]), int(n_real), cfg, c, int(counter) & 0xffffffff))
+        return self._rollout[1]
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):

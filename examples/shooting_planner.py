@@ -4,12 +4,17 @@ from the 81-action table of the value-network policies, scores all of them from 
 
     python examples/shooting_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--seed 0]
     python examples/shooting_planner.py --model-dir DIR [--policy sarl]   # DIR/rl_model.pth (+ DIR/policy.config), as test.py's
+    python examples/shooting_planner.py --cem [--elites 4] [--iterations 3] [--init-std 0.5]   # the device CEM planner
 
 The cases run as one batch, one env per case; the line printed at the end is Explorer.run_k_episodes' summary.  A usage
 example and a smoke run, not a tuned planner: without --model-dir a candidate's score is its discounted return over the
 horizon, nothing else.  With a trained value network the same launch sequence bootstraps it (cn_lookahead_values, DESIGN.md
 §3.8.3): score = return + gamma^(steps * time_step * v_pref) * V(state behind the horizon), the n-step return the network's
-TD targets mean; a candidate that ended inside the horizon scores its return alone."""
+TD targets mean; a candidate that ended inside the horizon scores its return alone.
+
+--cem runs the same cases with the device planner instead (cn_plan_rollout): per env a Gaussian over action
+sequences, K candidates drawn, scored and the Gaussian refitted to the best E of them, I times per real step, the plan carried to
+the next step — one plan_rollout call per chunk of steps, with no host work inside a chunk; `active` is read once per chunk."""
 import argparse
 import logging
 import os
@@ -47,7 +52,10 @@ def load_policy(model_dir, name):
     return policy
 
 
-def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None):
+CEM_CHUNK = 16  # real steps per plan_rollout call: how often the host looks whether every case has ended
+
+
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -73,7 +81,17 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None):
                              record_capacity=1)
     env_ids = torch.arange(cases, device=eng.device)
     scores = None
-    for _ in range(int(round(env.time_limit / env.time_step)) + 2):  # every episode has ended by then (Timeout)
+    most = int(round(env.time_limit / env.time_step)) + 2  # every episode has ended by then (Timeout)
+    if cem is not None:
+        planner = eng.plan_begin(candidates, horizon, cem['elites'], cem['iterations'], cem['init_std'] * robot.v_pref, seed=seed,
+                                 bootstrap=policy is not None, sort_humans=extra.get('sort_humans', False))
+        eng.plan_reset(planner)
+        for first in range(0, most, CEM_CHUNK):
+            eng.plan_rollout(planner, CEM_CHUNK, first * cem['iterations'])
+            if int(bufs['active'].sum().item()) == 0:
+                break
+        most = 0
+    for _ in range(most):
         draw = torch.randint(len(space), (cases, candidates, horizon), generator=gen, device=eng.device)
         sequences = table[draw]  # [cases, K, n, 2], contiguous: read where it lies
         scores = eng.lookahead(sequences, out=scores, **extra)
@@ -99,9 +117,14 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--model-dir', default=None, help="a reference output directory: rl_model.pth and, if present, policy.config")
     ap.add_argument('--policy', default='sarl', choices=['sarl', 'cadrl', 'lstm_rl'], help='the policy --model-dir was trained with')
+    ap.add_argument('--cem', action='store_true', help='plan with the device CEM planner (one plan_rollout call per chunk of steps)')
+    ap.add_argument('--elites', type=int, default=4, help='--cem: E, candidates the distribution is refitted to')
+    ap.add_argument('--iterations', type=int, default=3, help='--cem: I, draw / score / refit rounds per real step')
+    ap.add_argument('--init-std', type=float, default=0.5, help='--cem: standard deviation a step starts from, in units of v_pref')
     args = ap.parse_args()
     policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
-    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy))
+    cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std) if args.cem else None
+    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem))
     return 0
 
 

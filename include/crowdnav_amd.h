@@ -632,6 +632,89 @@ int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const doubl
  * launched, nothing written.  State, rollout io, ring levels and launch counters are left as cn_lookahead_actions leaves them,
  * apart from CN_COUNT_SARL_NARROW and cn_sarl_export's buffers (above). */
 
+/* ------------------------------------------------------------------------------------------------------
+ * Device CEM planner (no version bump: new symbols only).  The caller cn_lookahead_actions / cn_lookahead_values were built
+ * for: per env a Gaussian over sequences of n actions (mean, std per step and component), from which K candidates are drawn,
+ * scored by the lookahead, ranked, and the distribution refitted to the E best (cross-entropy method), I times per real step;
+ * the best sequence's first action is taken, and the plan shifted by one step — or re-seeded where an episode ended.  Drawing,
+ * ranking, refitting, shifting and the closed loop run on the device, enqueued on the engine's stream; no call synchronises.
+ * CN_ROBOT_EXTERNAL engines with a holonomic robot only; a CN_UNICYCLE engine is CN_ERR_UNSUPPORTED.  All arrays are DEVICE
+ * memory, caller-owned, and must stay valid until the work has run; cfg and plan themselves are copied by the call.  Action
+ * rows (mean, std, best_actions, action, candidates) are read and written as 16-byte words: align them to 16 bytes.
+ *
+ * The arithmetic below is float64, every product and sum a separate IEEE operation in the order written, so that a host
+ * restatement is bit-exact (the draw's log / cos / sin excepted: they are the device libm's).  v_pref is the robot's, read
+ * from its row of the engine state.  Scores are finite by construction: NaN is NOT handled. */
+typedef struct cn_plan_cfg {
+    int32_t n_steps;      /* n, horizon: 1 .. 256 (kMaxDiscount)                       */
+    int32_t n_candidates; /* K: 2 .. 1024                                              */
+    int32_t n_elites;     /* E: 1 .. min(K, 64)                                        */
+    int32_t iterations;   /* I >= 1 CEM iterations per planning step                   */
+    int32_t bootstrap;    /* 0: rank by look.ret; 1: by cn_lookahead_values' score     */
+    int32_t sort_humans;  /* passed to cn_lookahead_values                             */
+    double  init_std;     /* > 0, finite (velocity units)                              */
+    double  min_std;      /* >= 0, finite                                              */
+    double  smoothing;    /* alpha in [0, 1)                                           */
+    uint64_t seed;
+} cn_plan_cfg;
+
+typedef struct cn_plan {
+    double* mean;          /* [B][n][2] in/out                                          */
+    double* std;           /* [B][n][2] in/out                                          */
+    double* best_actions;  /* [B][n][2] out                                             */
+    double* best_score;    /* [B] out                                                   */
+    double* action;        /* [B][2] out = best_actions[b][0]                           */
+    double* candidates;    /* [B][K][n][2]: after a call, the LAST iteration's          */
+    cn_lookahead_out look; /* [B][K] rows of the last iteration; final_state8 required iff bootstrap */
+    float*  value;         /* [B][K], required iff bootstrap                            */
+    double* score;         /* [B][K], required iff bootstrap                            */
+    int32_t* order;        /* optional [B][K]: candidate index at rank r, last iteration */
+} cn_plan;
+
+/* Every cn_plan_* call refuses, in this order and before anything is enqueued: NULL cfg, plan or a required array (everything
+ * of cn_plan but `order`; look.final_state8, value and score iff cfg->bootstrap): CN_ERR_INVALID with the name; cfg out of the
+ * ranges above: CN_ERR_INVALID — n_candidates > 1024, n_elites > 64 and n_steps > 256: CN_ERR_UNSUPPORTED with the number;
+ * NULL engine or a CN_ROBOT_ORCA engine: CN_ERR_INVALID; a CN_UNICYCLE engine: CN_ERR_UNSUPPORTED; then whatever
+ * cn_lookahead_actions refuses for (n_steps, n_candidates, candidates, look) and, with bootstrap, cn_lookahead_values, with
+ * their messages; cn_plan_shift and cn_plan_rollout then what cn_rollout_step refuses for the io block. */
+
+/* The goal-directed prior, for every env with mask == NULL || mask[b] (mask: DEVICE uint8 [B]): with (px, py), (gx, gy) the
+ * robot's position and goal as the engine state holds them,
+ *   dx = gx - px, dy = gy - py, dist = sqrt(dx dx + dy dy), speed = min(v_pref, dist / time_step)
+ *   mean[b][t] = dist > 0 ? ((dx / dist) speed, (dy / dist) speed) : (0, 0)   for every t;   std[b][t][c] = init_std */
+int cn_plan_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const uint8_t* mask /* [B] or NULL = all */);
+/* candidates[b][k][t], one lane per row, one 16-byte store per row.  k = 0: the mean itself.  k >= 1: mean[b][t] + std[b][t] *
+ * (z0, z1) componentwise, (z0, z1) ONE Box-Muller pair from ONE Philox4x32-10 block with counter words (t, k, b, counter) and
+ * key (seed & 0xffffffff, seed >> 32) — so a row depends on neither B, K nor n.  With w0..w3 the block's words:
+ *   u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 1) / 2^53  in (0, 1],   u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) / 2^53
+ *   r = sqrt(-2 log(u1)),  z0 = r cos(2 pi u2),  z1 = r sin(2 pi u2)
+ * Every row, k = 0 included, is then clipped to the robot's speed: nrm = sqrt(ax ax + ay ay); if nrm > v_pref, s = v_pref /
+ * nrm, ax *= s, ay *= s. */
+int cn_plan_draw(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter);
+/* One 64-lane workgroup per env.  s_k = bootstrap ? score[b][k] : look.ret[b][k];  rank(k) = #{j : s_j > s_k, or s_j == s_k
+ * and j < k};  order[b][rank(k)] = k if order is given.  With k* the rank-0 candidate: if !keep_best || s_k* > best_score[b]
+ * (strict: the earliest holder wins), best_actions[b] = candidates[b][k*], best_score[b] = s_k*, action[b] = best_actions[b][0].
+ * The elites are ranks 0 .. E - 1; per component (t, c), both sums sequential in rank order from 0.0:
+ *   m = (sum_e a_e) / E,  var = (sum_e (a_e - m) (a_e - m)) / E,  sd = sqrt(var)
+ *   mean <- smoothing mean + (1.0 - smoothing) m,   std <- max(min_std, smoothing std + (1.0 - smoothing) sd) */
+int cn_plan_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int keep_best);
+/* One planning step: for i in 0 .. iterations - 1: cn_plan_draw(counter + i); cn_lookahead_actions(e, n_steps, n_candidates,
+ * candidates, &look) — cn_lookahead_values(.., sort_humans, value, score) with bootstrap —; cn_plan_refit(keep_best = i > 0).
+ * The engine is left exactly as those lookahead calls leave it: no state, io, ring or counter changes beyond what
+ * cn_lookahead_values documents; the plan kernels are NOT counted in cn_launch_counts (CN_LAUNCH_COUNTERS keeps its length). */
+int cn_plan_cem(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter);
+/* After a real step (cn_rollout_step) of the rollout `io` describes.  An env with io->active[b] == 0: nothing.  An env with
+ * io->cur_steps[b] == 0 — its episode has just ended and the next scenario is loaded — gets cn_plan_reset's prior from the
+ * state as it now stands; an env still WAITING for a scenario has cur_steps == 0 as well and gets the prior of its stale state.
+ * Every other env: mean[b][t] <- mean[b][t + 1] for t < n - 1, mean[b][n - 1] stays, std <- init_std everywhere.  In place. */
+int cn_plan_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, const cn_plan* plan);
+/* The closed loop, one C call without host work or synchronisation between the steps: for s in 0 .. n_real_steps - 1:
+ * cn_plan_cem(counter + s * iterations); cn_rollout_step(e, io, plan->action); cn_plan_shift — through those functions' own host
+ * paths, so the checks, the scenario-ring fill and the launch counters are exactly as if the caller had made the calls.
+ * n_real_steps < 0: CN_ERR_INVALID; n_real_steps == 0: CN_OK, nothing enqueued. */
+int cn_plan_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                    uint32_t counter);
+
 #ifdef __cplusplus
 }
 #endif

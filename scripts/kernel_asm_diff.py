@@ -1,11 +1,12 @@
 """Per-function comparison of the device assembly of two revisions: which kernels a source change really touched.
 
-    python scripts/kernel_asm_diff.py [--base REV] [--tu env|sarl|train|all] [-v]
+    python scripts/kernel_asm_diff.py [--base REV] [--tu env|sarl|train|plan|all] [-v]
 
 Compiles the translation unit(s) of REV (default HEAD; taken from git into a temporary directory) and of the working tree with the
 Makefile's flags plus --cuda-device-only -S (cross-compiles without a GPU; sarl_abi.hip takes ~1.5 minutes), splits the
 assembly into functions and compares their instruction streams with comments, directives and the function index of local labels
 stripped.  Prints one line per function that differs (instruction count before -> after), a summary, and exits 1 if any differ.
+A translation unit REV does not have yet counts as empty there: all its functions are listed as new.
 -v lists the identical ones as well.  The assembly files stay under build/asm/ (the base revision's are reused by commit hash).
 """
 import os
@@ -15,7 +16,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip', 'train': 'sarl_train.hip'}
+TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip', 'train': 'sarl_train.hip', 'plan': 'plan.hip'}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-fno-slp-vectorize',
          '--cuda-device-only', '-S']
 ASM = os.path.join(ROOT, 'build', 'asm')
@@ -23,6 +24,9 @@ ASM = os.path.join(ROOT, 'build', 'asm')
 
 def compile_tu(tree, tu, out):
     csrc = os.path.join(tree, 'crowdnav_amd', 'csrc')
+    if not os.path.exists(os.path.join(csrc, TUS[tu])):  # a translation unit added since: no functions
+        open(out, 'w').close()
+        return
     r = subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + [TUS[tu], '-o', out], cwd=csrc, stderr=subprocess.PIPE, text=True)
     if r.returncode:  # (warnings of a compile that succeeds are the build's business)
         sys.exit('hipcc failed on %s of %s:\n%s' % (TUS[tu], tree, r.stderr))

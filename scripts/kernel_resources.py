@@ -1,10 +1,10 @@
 """Per-kernel register / spill / LDS table of libcrowdnav_amd.so's code object, from hipcc's own resource report
 (-Rpass-analysis=kernel-resource-usage; cross-compiles without a GPU).
 
-    python scripts/kernel_resources.py [--tu env|sarl|train] [filter-regex] [-D...]      # extra -D flags go to hipcc
+    python scripts/kernel_resources.py [--tu env|sarl|train|plan] [filter-regex] [-D...]      # extra -D flags go to hipcc
 
 --tu names the translation unit: env (default) = crowdnav_amd.hip, sarl = sarl_abi.hip (the value-network kernels),
-train = sarl_train.hip (the device SGD step).
+train = sarl_train.hip (the device SGD step), plan = plan.hip (the CEM planner's kernels).
 """
 import os
 import re
@@ -12,7 +12,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip', 'train': 'sarl_train.hip'}
+TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip', 'train': 'sarl_train.hip', 'plan': 'plan.hip'}
 
 
 def report(extra=(), tu='env'):
