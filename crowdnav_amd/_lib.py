@@ -180,6 +180,11 @@ SYMBOLS = {
     'cn_plan_cem': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_uint32]),
     'cn_plan_shift': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.POINTER(CnPlanCfg), C.POINTER(CnPlan)]),
     'cn_plan_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_uint32]),
+    # device MPPI update beside the refit: softmax-weighted mean, the mean's first row as the action (no version bump)
+    'cn_plan_mppi_update': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_double, C.c_int, C.c_int]),
+    'cn_plan_mppi': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_double, C.c_int, C.c_uint32]),
+    'cn_plan_mppi_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_double,
+                                       C.c_int, C.c_uint32]),
 }
 
 _lib = None

@@ -1,16 +1,23 @@
-// libcrowdnav_amd.so — the device CEM planner (cn_plan_*): host entry points over the kernels of plan_kernels.h.
+// libcrowdnav_amd.so — the device CEM and MPPI planners (cn_plan_*): host entry points over the kernels of plan_kernels.h.
 //
 // A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values and real steps
 // made through cn_rollout_step, by their C entry points and therefore with their checks, their scenario-ring fill and their
-// launch counters; this translation unit only adds what runs between them (draw, refit, shift, prior), enqueued on the
+// launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior), enqueued on the
 // engine's stream.  Nothing here synchronises, allocates or counts.
 #include "engine_host.h"
 #include "plan_kernels.h"
 
 namespace {
 
+// The MPPI update's two arguments; a NULL Mppi* below means the CEM refit.
+struct Mppi {
+    double temperature;
+    int fit_std;
+};
+
 // Refusals 1-5 of the header, in its order; nothing is enqueued (cn_lookahead_values with n_steps == 0 checks and returns).
-int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const char* who) {
+// The cn_plan_mppi_* calls add theirs between the cfg ranges and the engine.
+int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const char* who, const Mppi* mppi = nullptr) {
     if (!cfg) return fail(CN_ERR_INVALID, "%s: cfg is NULL", who);
     if (!plan) return fail(CN_ERR_INVALID, "%s: plan is NULL", who);
     const bool boot = cfg->bootstrap != 0;
@@ -54,6 +61,8 @@ int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const 
         return fail(CN_ERR_INVALID, "%s: min_std must be >= 0 and finite (got %g)", who, cfg->min_std);
     if (!(cfg->smoothing >= 0.0 && cfg->smoothing < 1.0))
         return fail(CN_ERR_INVALID, "%s: smoothing must be in [0, 1) (got %g)", who, cfg->smoothing);
+    if (mppi && (!(mppi->temperature > 0.0) || !std::isfinite(mppi->temperature)))
+        return fail(CN_ERR_INVALID, "%s: temperature must be > 0 and finite (got %g)", who, mppi->temperature);
     if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
     if (e->P.robot_orca) return fail(CN_ERR_INVALID, "%s is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)", who);
     if (e->P.robot_unicycle)
@@ -105,14 +114,25 @@ int run_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int kee
     return CN_OK;
 }
 
-int run_cem(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
+int run_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const Mppi& mppi, int keep_best) {
+    hipLaunchKernelGGL(cn::plan_mppi_kernel, dim3(e->P.B), dim3(64), 0, e->stream, e->P.A, cfg->n_candidates, cfg->n_steps,
+                       mppi.fit_std ? 1 : 0, keep_best ? 1 : 0, mppi.temperature, cfg->smoothing, cfg->min_std,
+                       (const double*)(cfg->bootstrap ? plan->score : plan->look.ret), (const double2*)plan->candidates,
+                       (const double2*)e->S.rv, plan->mean, plan->std, (double2*)plan->best_actions, plan->best_score,
+                       (double2*)plan->action, plan->order);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// One planning step of either planner: draw, score, update, `iterations` times
+int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter, const Mppi* mppi) {
     for (int i = 0; i < cfg->iterations; ++i) {
         int rc = run_draw(e, cfg, plan, counter + (uint32_t)i);
         if (rc) return rc;
         rc = cfg->bootstrap ? cn_lookahead_values(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look, cfg->sort_humans,
                                                   plan->value, plan->score)
                             : cn_lookahead_actions(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
-        if (rc || (rc = run_refit(e, cfg, plan, i > 0))) return rc;
+        if (rc || (rc = mppi ? run_mppi_update(e, cfg, plan, *mppi, i > 0) : run_refit(e, cfg, plan, i > 0))) return rc;
     }
     return CN_OK;
 }
@@ -123,6 +143,19 @@ int run_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, con
                        P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal, (const double2*)e->S.rv,
                        (const uint8_t*)io->active, (const int32_t*)io->cur_steps, plan->mean, plan->std);
     CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// The closed loop of either planner
+int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                uint32_t counter, const char* who, const Mppi* mppi) {
+    int rc = plan_check(e, cfg, plan, who, mppi);
+    if (rc || (rc = plan_check_io(e, io, plan))) return rc;
+    if (n_real_steps < 0) return fail(CN_ERR_INVALID, "%s: n_real_steps must be >= 0 (got %d)", who, n_real_steps);
+    for (int s = 0; s < n_real_steps; ++s) {
+        if ((rc = bind(e)) || (rc = run_plan(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations, mppi))) return rc;
+        if ((rc = cn_rollout_step(e, io, plan->action)) || (rc = run_shift(e, io, cfg, plan))) return rc;
+    }
     return CN_OK;
 }
 
@@ -151,7 +184,7 @@ int cn_plan_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int
 int cn_plan_cem(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
     int rc = plan_check(e, cfg, plan, "cn_plan_cem");
     if (rc || (rc = bind(e))) return rc;
-    return run_cem(e, cfg, plan, counter);
+    return run_plan(e, cfg, plan, counter, nullptr);
 }
 
 int cn_plan_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, const cn_plan* plan) {
@@ -162,14 +195,27 @@ int cn_plan_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg,
 
 int cn_plan_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
                     uint32_t counter) {
-    int rc = plan_check(e, cfg, plan, "cn_plan_rollout");
-    if (rc || (rc = plan_check_io(e, io, plan))) return rc;
-    if (n_real_steps < 0) return fail(CN_ERR_INVALID, "cn_plan_rollout: n_real_steps must be >= 0 (got %d)", n_real_steps);
-    for (int s = 0; s < n_real_steps; ++s) {
-        if ((rc = bind(e)) || (rc = run_cem(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations))) return rc;
-        if ((rc = cn_rollout_step(e, io, plan->action)) || (rc = run_shift(e, io, cfg, plan))) return rc;
-    }
-    return CN_OK;
+    return run_rollout(e, io, n_real_steps, cfg, plan, counter, "cn_plan_rollout", nullptr);
+}
+
+int cn_plan_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, double temperature, int fit_std, int keep_best) {
+    const Mppi mppi{temperature, fit_std};
+    int rc = plan_check(e, cfg, plan, "cn_plan_mppi_update", &mppi);
+    if (rc || (rc = bind(e))) return rc;
+    return run_mppi_update(e, cfg, plan, mppi, keep_best);
+}
+
+int cn_plan_mppi(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, double temperature, int fit_std, uint32_t counter) {
+    const Mppi mppi{temperature, fit_std};
+    int rc = plan_check(e, cfg, plan, "cn_plan_mppi", &mppi);
+    if (rc || (rc = bind(e))) return rc;
+    return run_plan(e, cfg, plan, counter, &mppi);
+}
+
+int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                         double temperature, int fit_std, uint32_t counter) {
+    const Mppi mppi{temperature, fit_std};
+    return run_rollout(e, io, n_real_steps, cfg, plan, counter, "cn_plan_mppi_rollout", &mppi);
 }
 
 }  // extern "C"

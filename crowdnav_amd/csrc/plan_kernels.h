@@ -1,13 +1,16 @@
-// Device side of the CEM planner (cn_plan_*, plan.hip): the four kernels between "score K action sequences per env"
-// (cn_lookahead_actions / cn_lookahead_values) and "a robot that plans" — draw the candidates, rank them and refit the sampling
-// distribution, shift the plan behind a real step, seed it with the goal-directed prior.  Holonomic external robots only.
+// Device side of the shooting planners (cn_plan_*, plan.hip): the kernels between "score K action sequences per env"
+// (cn_lookahead_actions / cn_lookahead_values) and "a robot that plans" — draw the candidates, rank them and update the sampling
+// distribution (CEM: refit to the elites; MPPI: softmax-weighted mean), shift the plan behind a real step, seed it with the
+// goal-directed prior.  Holonomic external robots only.
 //
-// The arithmetic is the header's (include/crowdnav_amd.h, "Device CEM planner"), one IEEE operation per product and sum in the
-// order written there (the library is built with -ffp-contract=off), so that tests/plan_reference.py restates it in numpy
-// float64 bit for bit — apart from the draw's log / cos / sin, which are the device libm's.
+// The arithmetic is the header's (include/crowdnav_amd.h, "Device CEM planner" and "Device MPPI update"), one IEEE operation per
+// product and sum in the order written there (the library is built with -ffp-contract=off), so that tests/plan_reference.py and
+// tests/plan_mppi_reference.py restate it in numpy float64 bit for bit — apart from the draw's log / cos / sin and the MPPI
+// weights' exp, which are the device libm's.
 //   plan_reset_kernel  lane = (env, t)            the prior: full speed (or what reaches the goal in one step) towards the goal
 //   plan_draw_kernel   lane = (env, k, t)         one Philox4x32-10 block -> one Box-Muller pair -> one clipped 16-byte row
 //   plan_refit_kernel  workgroup = env, one wave  ranks by counting over the scores in LDS; best row; elite mean / std
+//   plan_mppi_kernel   workgroup = env, one wave  the same ranks and best row; weights exp((s - s_max) / T) in LDS; weighted mean / std
 //   plan_shift_kernel  lane = (env, component)    walks t upwards in place: row t <- row t + 1, or the prior at an episode start
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,7 +18,7 @@
 
 namespace cn {
 
-constexpr int kPlanMaxCandidates = 1024;  // K: the scores of one env in LDS (8 KiB)
+constexpr int kPlanMaxCandidates = 1024;  // K: the scores of one env in LDS (8 KiB; the MPPI update holds K weights beside them)
 constexpr int kPlanMaxElites = 64;        // E: the elite indices in LDS
 constexpr int kPlanBlock = 256;           // lanes per workgroup of the streaming kernels (reset, draw, shift)
 
@@ -83,8 +86,19 @@ __global__ __launch_bounds__(kPlanBlock) void plan_draw_kernel(int B, int A, int
     candidates[i] = a;
 }
 
-// One wave per env.  rank(k) = #{j : s_j > s_k, or s_j == s_k and j < k}: a permutation of 0..K-1 for finite scores (NaN is not
-// handled).  LDS holds the env's scores and the elite indices, nothing else.
+// rank(k) = #{j : s_j > s_k, or s_j == s_k and j < k} over the env's scores in LDS: a permutation of 0..K-1 for finite scores
+// (NaN is not handled).  The one ranking rule of the refit and of the MPPI update.
+__device__ inline int plan_rank(const double* sc, int K, int k) {
+    const double sk = sc[k];
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+        const double sj = sc[j];
+        rank += (sj > sk || (sj == sk && j < k)) ? 1 : 0;
+    }
+    return rank;
+}
+
+// One wave per env.  LDS holds the env's scores and the elite indices, nothing else.
 __global__ __launch_bounds__(64) void plan_refit_kernel(int K, int n, int E, int keep_best, double smoothing, double min_std,
                                                         const double* score, const double2* candidates, double* mean, double* std,
                                                         double2* best_actions, double* best_score, double2* action, int32_t* order) {
@@ -97,12 +111,7 @@ __global__ __launch_bounds__(64) void plan_refit_kernel(int K, int n, int E, int
     elite[lane] = 0;  // (NaN scores rank nothing sensibly; the indices read below still address the env's own candidates)
     __syncthreads();
     for (int k = lane; k < K; k += 64) {
-        const double sk = sc[k];
-        int rank = 0;
-        for (int j = 0; j < K; ++j) {
-            const double sj = sc[j];
-            rank += (sj > sk || (sj == sk && j < k)) ? 1 : 0;
-        }
+        const int rank = plan_rank(sc, K, k);
         if (order) order[b * K + rank] = k;
         if (rank < E) elite[rank] = k;
     }
@@ -133,6 +142,75 @@ __global__ __launch_bounds__(64) void plan_refit_kernel(int K, int n, int E, int
         mean[at] = smoothing * mean[at] + keep * m;
         const double blended = smoothing * std[at] + keep * sd;
         std[at] = blended < min_std ? min_std : blended;
+    }
+}
+
+// One wave per env: the refit's ranks and best row, then every candidate weighted by exp((s_k - s_max) / temperature).  LDS holds
+// the env's scores, its weights, the rank-0 index and the new first mean row (16 KiB + 24 bytes).  Lane = component (t, xy), the
+// k loops sequential and the same in every lane: candidates[b] is streamed once for the mean and, with fit_std, once more for
+// the deviation, consecutive lanes reading consecutive doubles of one row.  `action` is the updated mean's first row clipped
+// as the draw clips, NOT the best row's.
+__global__ __launch_bounds__(64) void plan_mppi_kernel(int A, int K, int n, int fit_std, int keep_best, double temperature,
+                                                       double smoothing, double min_std, const double* score,
+                                                       const double2* candidates, const double2* rv, double* mean, double* std,
+                                                       double2* best_actions, double* best_score, double2* action, int32_t* order) {
+    __shared__ double sc[kPlanMaxCandidates];
+    __shared__ double wt[kPlanMaxCandidates];
+    __shared__ double first[2];
+    __shared__ int top_k;
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double held = best_score[b];  // (read by every lane before lane 0 may replace it below)
+    for (int k = lane; k < K; k += 64) sc[k] = score[b * K + k];
+    if (lane == 0) top_k = 0;  // (NaN scores rank nothing sensibly; the index read below still addresses the env's own candidates)
+    __syncthreads();
+    for (int k = lane; k < K; k += 64) {
+        const int rank = plan_rank(sc, K, k);
+        if (order) order[b * K + rank] = k;
+        if (rank == 0) top_k = k;
+    }
+    __syncthreads();
+    const int top = top_k;
+    const double s_top = sc[top];
+    if (!keep_best || s_top > held) {  // strict: the earliest holder of a score keeps it
+        const double2* src = candidates + (b * K + top) * n;
+        for (int t = lane; t < n; t += 64) best_actions[b * n + t] = src[t];
+        if (lane == 0) best_score[b] = s_top;
+    }
+    for (int k = lane; k < K; k += 64) wt[k] = exp((sc[k] - s_top) / temperature);
+    __syncthreads();
+    double Z = 0.0;
+    for (int k = 0; k < K; ++k) Z = Z + wt[k];
+    const double* cand = reinterpret_cast<const double*>(candidates) + b * K * n * 2;
+    const double keep = 1.0 - smoothing;
+    for (int c = lane; c < 2 * n; c += 64) {  // component (t, xy) of the plan: sums over all candidates in index order
+        double num = 0.0;
+        for (int k = 0; k < K; ++k) num = num + wt[k] * cand[(size_t)k * n * 2 + c];
+        const double m = num / Z;
+        const size_t at = b * n * 2 + c;
+        const double updated = smoothing * mean[at] + keep * m;
+        mean[at] = updated;
+        if (c < 2) first[c] = updated;
+        if (fit_std) {
+            double dev2 = 0.0;
+            for (int k = 0; k < K; ++k) {
+                const double d = cand[(size_t)k * n * 2 + c] - m;
+                dev2 = dev2 + wt[k] * (d * d);
+            }
+            const double sd = sqrt(dev2 / Z);
+            const double blended = smoothing * std[at] + keep * sd;
+            std[at] = blended < min_std ? min_std : blended;
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double2 a = make_double2(first[0], first[1]);
+        const double nrm = sqrt(a.x * a.x + a.y * a.y), v_pref = rv[b * A].y;
+        if (nrm > v_pref) {
+            const double s = v_pref / nrm;
+            a.x *= s, a.y *= s;
+        }
+        action[b] = a;
     }
 }
 

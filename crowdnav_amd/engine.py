@@ -464,6 +464,33 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_plan_rollout(self._h, C.byref(self._rollout[0]), int(n_real), cfg, c, int(counter) & 0xffffffff))
         return self._rollout[1]
 
+    # ---------------------------------------------------------------- device MPPI update (cn_plan_mppi_*), on the same Plan
+    def plan_mppi_update(self, plan, temperature, fit_std=False, keep_best=False):
+        """The MPPI update in place of plan_refit (cn_plan_mppi_update): the same ranks, order and best_*; every candidate
+        weighted by exp((score - best score) / temperature); mean <- the weighted mean (through smoothing), std <- the weighted
+        deviation only with fit_std; plan.action <- the updated mean's first row, clipped to the robot's speed.  The plan's
+        `elites` is not read."""
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_mppi_update(self._h, cfg, c, float(temperature), int(bool(fit_std)), int(bool(keep_best))))
+        return plan
+
+    def plan_mppi(self, plan, temperature, counter, fit_std=False):
+        """One planning step (cn_plan_mppi): `iterations` x (draw with counter + i, lookahead, MPPI update), all enqueued by
+        one call.  The engine is left as lookahead() leaves it."""
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_mppi(self._h, cfg, c, float(temperature), int(bool(fit_std)), int(counter) & 0xffffffff))
+        return plan
+
+    def plan_mppi_rollout(self, plan, n_real, temperature, counter, fit_std=False):
+        """plan_rollout with the MPPI update (cn_plan_mppi_rollout): per step plan_mppi(counter + s * iterations),
+        rollout_step(plan.action), plan_shift, in ONE call.  Returns the rollout's bufs."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        cfg, c = self._plan(plan)
+        check(self._lib.cn_plan_mppi_rollout(self._h, C.byref(self._rollout[0]), int(n_real), cfg, c, float(temperature),
+                                             int(bool(fit_std)), int(counter) & 0xffffffff))
+        return self._rollout[1]
+
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):
         """The finished episodes of this engine's rollout as ONE self-contained float64 block per env:

@@ -5,6 +5,7 @@ from the 81-action table of the value-network policies, scores all of them from 
     python examples/shooting_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--seed 0]
     python examples/shooting_planner.py --model-dir DIR [--policy sarl]   # DIR/rl_model.pth (+ DIR/policy.config), as test.py's
     python examples/shooting_planner.py --cem [--elites 4] [--iterations 3] [--init-std 0.5]   # the device CEM planner
+    python examples/shooting_planner.py --mppi [--temperature 1.0] [--iterations 3] [--init-std 0.5]   # ... with the MPPI update
 
 The cases run as one batch, one env per case; the line printed at the end is Explorer.run_k_episodes' summary.  A usage
 example and a smoke run, not a tuned planner: without --model-dir a candidate's score is its discounted return over the
@@ -14,7 +15,11 @@ TD targets mean; a candidate that ended inside the horizon scores its return alo
 
 --cem runs the same cases with the device planner instead (cn_plan_rollout): per env a Gaussian over action
 sequences, K candidates drawn, scored and the Gaussian refitted to the best E of them, I times per real step, the plan carried to
-the next step — one plan_rollout call per chunk of steps, with no host work inside a chunk; `active` is read once per chunk."""
+the next step — one plan_rollout call per chunk of steps, with no host work inside a chunk; `active` is read once per chunk.
+
+--mppi is the same loop with the other update (cn_plan_mppi_rollout): every candidate weighted by
+exp((score - best score) / T), the mean moved to the weighted mean and its first row taken as the action; the sampling deviation
+stays at --init-std."""
 import argparse
 import logging
 import os
@@ -87,7 +92,10 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None):
                                  bootstrap=policy is not None, sort_humans=extra.get('sort_humans', False))
         eng.plan_reset(planner)
         for first in range(0, most, CEM_CHUNK):
-            eng.plan_rollout(planner, CEM_CHUNK, first * cem['iterations'])
+            if cem.get('temperature') is None:
+                eng.plan_rollout(planner, CEM_CHUNK, first * cem['iterations'])
+            else:
+                eng.plan_mppi_rollout(planner, CEM_CHUNK, cem['temperature'], first * cem['iterations'])
             if int(bufs['active'].sum().item()) == 0:
                 break
         most = 0
@@ -117,13 +125,19 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--model-dir', default=None, help="a reference output directory: rl_model.pth and, if present, policy.config")
     ap.add_argument('--policy', default='sarl', choices=['sarl', 'cadrl', 'lstm_rl'], help='the policy --model-dir was trained with')
-    ap.add_argument('--cem', action='store_true', help='plan with the device CEM planner (one plan_rollout call per chunk of steps)')
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument('--cem', action='store_true', help='plan with the device CEM planner (one plan_rollout call per chunk of steps)')
+    how.add_argument('--mppi', action='store_true', help='... with the MPPI update instead (one plan_mppi_rollout call per chunk)')
+    ap.add_argument('--temperature', type=float, default=1.0, help='--mppi: T of the weights exp((score - best score) / T)')
     ap.add_argument('--elites', type=int, default=4, help='--cem: E, candidates the distribution is refitted to')
-    ap.add_argument('--iterations', type=int, default=3, help='--cem: I, draw / score / refit rounds per real step')
-    ap.add_argument('--init-std', type=float, default=0.5, help='--cem: standard deviation a step starts from, in units of v_pref')
+    ap.add_argument('--iterations', type=int, default=3, help='--cem / --mppi: I, draw / score / update rounds per real step')
+    ap.add_argument('--init-std', type=float, default=0.5, help='--cem / --mppi: standard deviation a step starts from, in units of v_pref')
     args = ap.parse_args()
     policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
-    cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std) if args.cem else None
+    cem = None
+    if args.cem or args.mppi:
+        cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std,
+                   temperature=args.temperature if args.mppi else None)
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem))
     return 0
 

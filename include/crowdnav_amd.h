@@ -715,6 +715,35 @@ int cn_plan_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg,
 int cn_plan_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
                     uint32_t counter);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Device MPPI update (no version bump: three new symbols, the structs above unchanged).  The other standard update of a
+ * sampling-based planner, beside the CEM refit and over the same cn_plan_cfg / cn_plan: EVERY candidate contributes, weighted by
+ * the softmax of its score at `temperature`, and the action taken is the updated mean's first row, not the best sample's.
+ * n_elites is range-checked as in every cn_plan_* call but not read.  The three calls refuse what every cn_plan_* call
+ * refuses, in that order and with their own names; and, after the cfg ranges and before the engine is looked at, a
+ * temperature that is not finite or <= 0: CN_ERR_INVALID naming `temperature`.
+ *
+ * One 64-lane workgroup per env, float64, every product and sum a separate IEEE operation in the order written (a host
+ * restatement is bit-exact but for exp, which is the device libm's).  s_k, rank(k), order and k* as in cn_plan_refit; if
+ * !keep_best || s_k* > best_score[b] (strict), best_actions[b] = candidates[b][k*] and best_score[b] = s_k*.  With s_max = s_k*:
+ *   w_k = exp((s_k - s_max) / temperature)   (so w_k* = 1),   Z = sum_k w_k   (so Z >= 1)
+ * per component (t, c), with a_k = candidates[b][k][t][c]; Z and both sums sequential in k order from 0.0:
+ *   num = sum_k w_k a_k,  m = num / Z,  var = (sum_k w_k ((a_k - m) (a_k - m))) / Z,  sd = sqrt(var)
+ *   mean <- smoothing mean + (1.0 - smoothing) m
+ *   std  <- max(min_std, smoothing std + (1.0 - smoothing) sd)   only if fit_std; otherwise std is not touched (classic MPPI:
+ *           a fixed sampling deviation, which cn_plan_shift sets back to init_std as for CEM)
+ * action[b] = the updated mean[b][0], clipped by cn_plan_draw's rule with the robot's v_pref — NOT best_actions[b][0].
+ * NaN scores are not handled, as in cn_plan_refit. */
+int cn_plan_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, double temperature, int fit_std, int keep_best);
+/* One planning step: for i in 0 .. iterations - 1: cn_plan_draw(counter + i); cn_lookahead_actions — cn_lookahead_values with
+ * bootstrap —; cn_plan_mppi_update(keep_best = i > 0).  The engine is left exactly as those lookahead calls leave it. */
+int cn_plan_mppi(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, double temperature, int fit_std, uint32_t counter);
+/* cn_plan_rollout with the other update: for s in 0 .. n_real_steps - 1: cn_plan_mppi(counter + s * iterations);
+ * cn_rollout_step(e, io, plan->action); cn_plan_shift — one C call, no host work or synchronisation between the steps.
+ * n_real_steps < 0: CN_ERR_INVALID; n_real_steps == 0: CN_OK, nothing enqueued. */
+int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                         double temperature, int fit_std, uint32_t counter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@
     python scripts/kernel_resources.py [--tu env|sarl|train|plan] [filter-regex] [-D...]      # extra -D flags go to hipcc
 
 --tu names the translation unit: env (default) = crowdnav_amd.hip, sarl = sarl_abi.hip (the value-network kernels),
-train = sarl_train.hip (the device SGD step), plan = plan.hip (the CEM planner's kernels).
+train = sarl_train.hip (the device SGD step), plan = plan.hip (the CEM / MPPI planners' kernels).
 """
 import os
 import re
