@@ -251,7 +251,9 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
         // occupancy maps (multi_human_rl.py:46-49): columns 13.. of a row are its human's map among the humans' NEXT states —
         // the same for every action of the env (sarl_lookahead_kernel or the previous call's sarl_decide_step_kernel wrote
         // them).  Four consecutive cells per thread (one 16-byte load), the row's offset into `om` from its own thread (vbuf)
-        const int extra = D.in_dim - 13, quads = extra >> 2;  // (cells x channels: 16 x 3 at the shipped size)
+        // A row of `om` starts at a multiple of `extra` floats: 16-byte aligned for every row only when the map width is a multiple
+        // of four (16 x 3 at the shipped size).  Any other width takes the scalar loop for the whole row.
+        const int extra = D.in_dim - 13, quads = (extra & 3) == 0 ? extra >> 2 : 0, rest = extra - 4 * quads;
         const int* row_om = reinterpret_cast<const int*>(vbuf);
         for (int i = tid; i < rows * quads; i += kNarrowThreads) {
             const int r = i / quads, q = i - r * quads;
@@ -265,8 +267,8 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
                 }
             }
         }
-        for (int i = tid; i < rows * (extra & 3); i += kNarrowThreads) {  // (a cell count that is not a multiple of four)
-            const int r = i / (extra & 3), k = 4 * quads + i - r * (extra & 3);
+        for (int i = tid; i < rows * rest; i += kNarrowThreads) {  // (a map width that is not a multiple of four)
+            const int r = i / rest, k = 4 * quads + i - r * rest;
             const int base = row_om[r], kk = 13 + k;
             if (base >= 0) xs[tile_word(kk) + xrow(r)] = om[base + k];
         }

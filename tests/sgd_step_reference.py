@@ -23,6 +23,23 @@ def load(fixture, H=5):
     return P, np.ascontiguousarray(S), np.ascontiguousarray(V)
 
 
+OTHER_WIDTHS = (14, 16, 17, 22, 40, 63)  # occupancy-map settings other than the shipped one: 1 x 1 x 1 ... 5 x 5 x 2, the widest below 64
+
+
+def fresh_case(D, H, rows=64):
+    """A freshly initialised ValueNetwork(D, ...) under a fixed torch seed, random float32 rows [rows, H, D] and values [rows]."""
+    from crowdnav_amd.compat.sarl import ValueNetwork
+    torch.manual_seed(400 + D)
+    net = ValueNetwork(D, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
+    P = {k: v.detach().numpy().copy() for k, v in net.state_dict().items()}
+    assert list(P) == NAMES and P['mlp1.0.weight'].shape == (150, D)
+    rs = np.random.RandomState(10 * D + H)
+    S = rs.uniform(-1.0, 1.0, (rows, H, D)).astype(np.float32)
+    S[:, :, 13:] *= rs.uniform(size=(rows, H, D - 13)) < 0.3  # map columns: mostly zeros, as occupancy maps are
+    V = rs.uniform(-0.5, 1.0, rows).astype(np.float32)
+    return P, S, V
+
+
 def network(P, dtype, device='cpu'):
     from crowdnav_amd.compat.sarl import ValueNetwork
     d = P['mlp1.0.weight'].shape[1]

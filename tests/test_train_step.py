@@ -120,6 +120,59 @@ def test_one_step_against_the_reference_arithmetic(fixture, H):
     assert L_k <= max(FACTOR * L_t, FLOOR), (L_t, L_k)
 
 
+@pytest.mark.parametrize('D', ref.OTHER_WIDTHS)
+def test_one_step_at_other_input_widths(D):
+    """train_tile_kernel / train_update_kernel at input widths other than 13 and 61: the same metric, bound and report as
+    test_one_step_against_the_reference_arithmetic, pooled per (D, H) over n in {37, 1}, zero and warm starting buffers."""
+    lr, mom = 0.01, 0.9
+    for H in (2, 5):
+        P, S, V = ref.fresh_case(D, H)
+        K = Kernel(P, S, V)
+        other = np.random.RandomState(999).permutation(len(S))[:40]
+        _, warm, _, _ = ref.torch_steps(P, [(S[other], V[other])], lr, mom, torch.float32, DEV)
+        warm = {k: v.astype(np.float32) for k, v in warm.items()}
+        E_t, E_k, L_t, L_k, absolute = {}, {}, 0.0, 0.0, {}
+        for start in (None, warm):
+            for n in (37, 1):
+                for seed in range(4):
+                    idx = np.random.RandomState(1000 * n + seed).permutation(len(S))[:n]
+                    batch = [(S[idx], V[idx])]
+                    _, b64, l64, g64 = ref.torch_steps(P, batch, lr, mom, torch.float64, 'cpu', start)
+                    _, b32, l32, _ = ref.torch_steps(P, batch, lr, mom, torch.float32, DEV, start)
+                    K.set(bufs=start)
+                    K.run(idx, n, lr, mom)
+                    pk, bk, lk = K.get()
+                    et, G = errors(b32, b64, g64)
+                    ek, _ = errors(bk, b64, g64)
+                    pool(E_t, et)
+                    pool(E_k, ek)
+                    L_t, L_k = max(L_t, abs(l32 - l64) / abs(l64)), max(L_k, abs(lk - l64) / abs(l64))
+                    for k in ref.NAMES:
+                        assert np.array_equal(pk[k], P[k] - np.float32(lr) * bk[k]), (k, n, seed)
+                        if zero_gradient(k, H):
+                            carried = np.float32(mom) * start[k] if start is not None else np.zeros_like(bk[k])
+                            pool(absolute, {k: np.abs(bk[k].astype(np.float64) - carried.astype(np.float64)).max() / G})
+        where = 'fresh D=%d H=%d' % (D, H)
+        table, bad = check_pooled(E_t, E_k, H, where)
+        print('%-28s loss: E_torch %.3e E_kernel %.3e; zero-gradient tensors, largest |change| / G: %s' % (where, L_t, L_k, absolute))
+        ref.report('one_step/' + where, dict(tensors=table, loss=dict(E_torch=L_t, E_kernel=L_k), zero_gradient_change_over_G=absolute))
+        assert not bad, bad
+        assert all(v < FLOOR for v in absolute.values()), absolute
+        assert L_k <= max(FACTOR * L_t, FLOOR), (L_t, L_k)
+        K.step.close()
+
+
+def test_an_input_wider_than_64_is_refused():
+    """cell_num 5 with 3 channels is 88 inputs: cn_trainer_create refuses it by name, it does not truncate."""
+    from crowdnav_amd import CrowdNavAmdError, _lib
+    from crowdnav_amd import train as cn_train
+    with pytest.raises(CrowdNavAmdError) as ei:
+        cn_train.SarlTrainStep(cn_train.sarl_net_config(88, cell_num=5), 5, 128, 0)
+    assert ei.value.status == _lib.CN_ERR_UNSUPPORTED
+    assert 'input width 88' in str(ei.value) and 'exceeds 64' in str(ei.value)
+    cn_train.SarlTrainStep(cn_train.sarl_net_config(63, cell_num=5), 5, 128, 0).close()  # 5 x 5 x 2 is served
+
+
 @pytest.mark.parametrize('fixture', ref.FIXTURES)
 def test_twenty_consecutive_steps(fixture):
     """Momentum 0.9, lr 0.01, a fresh index set per step, H = 5; the same metric on the buffers after the last step, pooled

@@ -107,6 +107,29 @@ def test_float64_emulation_of_the_kernel_formulas_equals_autograd(fixture, n):
             assert np.abs(b[k] - tb[k]).max() <= 1e-9 * max(np.abs(tb[k]).max(), 1e-6 * big), (k, steps)
 
 
+@pytest.mark.parametrize('D', ref.OTHER_WIDTHS)
+def test_float64_emulation_equals_autograd_at_other_input_widths(D, built):
+    """The emulation takes the input width from the data: the same pin at the widths of other occupancy-map settings, H = 2 and 5,
+    and cn_trainer_create serves each of them."""
+    for H in (2, 5):
+        P, S, V = ref.fresh_case(D, H)
+        rng = np.random.RandomState(70 + D)
+        batches = [(S[i], V[i]) for i in (rng.permutation(len(S))[:n] for n in (37, 1, 37))]
+        tp, tb, tl, _ = ref.torch_steps(P, batches, 0.01, 0.9, torch.float64)
+        p = {k: v.astype(np.float64) for k, v in P.items()}
+        b = {k: np.zeros_like(v) for k, v in p.items()}
+        for x, y in batches:
+            p, b, loss = ref.manual_step(p, x, y, 0.01, 0.9, b, np.float64)
+        assert abs(loss - tl) <= 1e-9 * abs(tl)
+        big = max(np.abs(v).max() for v in tb.values())
+        for k in ref.NAMES:
+            assert np.abs(p[k] - tp[k]).max() <= 1e-9 * np.abs(tp[k]).max(), (k, H)
+            assert np.abs(b[k] - tb[k]).max() <= 1e-9 * max(np.abs(tb[k]).max(), 1e-6 * big), (k, H)
+    rc, msg, h = _create(built, input_dim=D)
+    assert rc == built.CN_OK, msg
+    assert built.load().cn_trainer_destroy(h) == built.CN_OK
+
+
 def _cpu_trainer(monkeypatch, switch, P, S, V):
     from crowdnav_amd.compat.trainer import ReplayMemory, Trainer
     monkeypatch.setenv('CROWDNAV_AMD_SGD_KERNEL', switch)
