@@ -39,6 +39,24 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _struct(cls, tensors, **fields):
+    """A ctypes struct of device pointers: every field of cls that `tensors` names holds that tensor's address, the other
+    pointers stay NULL; **fields are set as given."""
+    return cls(**{k: tensors[k].data_ptr() for k, _ in cls._fields_ if k in tensors}, **fields)
+
+
+# the state_dict names of each value network, in the order sarl_set_weights hands the parameters over
+SARL_PARAM_ORDER = tuple('%s.%d.%s' % (m, i, p) for m, idxs in (('mlp1', (0, 2)), ('mlp2', (0, 2)),
+                                                               ('attention', (0, 2, 4)), ('mlp3', (0, 2, 4, 6)))
+                         for i in idxs for p in ('weight', 'bias'))
+
+
+LSTM_PARAM_ORDER = tuple('mlp.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias')) + (
+    'lstm.weight_ih_l0', 'lstm.weight_hh_l0', 'lstm.bias_ih_l0', 'lstm.bias_hh_l0')
+LSTM_PAIRWISE_MLP1_ORDER = tuple('mlp1.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias'))
+CADRL_PARAM_ORDER = tuple('value_network.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias'))
+
+
 class Plan(object):
     """What BatchedCrowdSim.plan_begin returns: the device tensors of a CEM planner (struct cn_plan) and its settings (struct
     cn_plan_cfg).  The tensors are the caller's to read and write between calls; they live as long as the object."""
@@ -59,16 +77,15 @@ class Plan(object):
         self.cfg = _lib.CnPlanCfg(n_steps=n, n_candidates=K, n_elites=elites, iterations=iterations, bootstrap=int(bootstrap),
                                   sort_humans=int(sort_humans), init_std=init_std, min_std=min_std, smoothing=smoothing,
                                   seed=seed & 0xffffffffffffffff)
-        look = CnLookaheadOut(**{k: v.data_ptr() for k, v in self.look.items() if k not in ('value', 'score')})
-        self.c = _lib.CnPlan(mean=self.mean.data_ptr(), std=self.std.data_ptr(), best_actions=self.best_actions.data_ptr(),
-                             best_score=self.best_score.data_ptr(), action=self.action.data_ptr(),
-                             candidates=self.candidates.data_ptr(), look=look, order=self.order.data_ptr(),
-                             value=self.look['value'].data_ptr() if bootstrap else None,
-                             score=self.look['score'].data_ptr() if bootstrap else None)
+        # value and score (bootstrap only) are lookahead rows in Python and fields of cn_plan itself in C
+        self.c = _struct(_lib.CnPlan, dict(self._own(), **self.look), look=_struct(CnLookaheadOut, self.look))
+
+    def _own(self):
+        return {k: getattr(self, k) for k in ('mean', 'std', 'best_actions', 'best_score', 'action', 'candidates', 'order')}
 
     def tensors(self):
         """Every tensor of the plan by name (the lookahead rows as look.<name>)."""
-        out = {k: getattr(self, k) for k in ('mean', 'std', 'best_actions', 'best_score', 'action', 'candidates', 'order')}
+        out = self._own()
         out.update({'look.' + k: v for k, v in self.look.items()})
         return out
 
@@ -113,17 +130,49 @@ class BatchedCrowdSim(object):
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
-    def _dev(self, x, dtype, shape):
+    def _borrow(self, x, dtype, shape):
+        """x as the library reads it, and whether that is a temporary copy: a contiguous tensor of that dtype on the engine's
+        device is read where it lies, anything else is copied there; None passes through.  A call that handed a temporary over
+        ends with _release: torch may otherwise free the copy while a kernel still reads it."""
+        if x is None:
+            return None, False
         t = torch.as_tensor(x, dtype=dtype).to(self.device).contiguous()
         if tuple(t.shape) != tuple(shape):
             raise ValueError('expected shape %s, got %s' % (tuple(shape), tuple(t.shape)))
-        return t
+        return t, not (torch.is_tensor(x) and t.data_ptr() == x.data_ptr())
+
+    def _release(self, *temporary):
+        """Synchronise if any argument of the call just made was a temporary copy (the flags _borrow returned)."""
+        if any(temporary):
+            self.sync()
+
+    def _dense(self, t, dtype, shape, pinned_ok=False):
+        """Whether the library can take t by its address: a contiguous tensor of that dtype and shape on the engine's device
+        (pinned_ok: or in pinned host memory)."""
+        return (torch.is_tensor(t) and (t.device == self.device or (pinned_ok and t.device.type == 'cpu' and t.is_pinned()))
+                and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous())
+
+    def _rows(self, who, spec, out):
+        """The output tensors of a call by name, spec: name -> (dtype, shape).  Fresh tensors, or the caller's `out` validated
+        and restricted to the names of the spec."""
+        if out is None:
+            return {k: self._new(shape, dt) for k, (dt, shape) in spec.items()}
+        for k, (dt, shape) in spec.items():
+            if not self._dense(out.get(k), dt, shape):
+                raise ValueError('%s: out[%r] must be a contiguous %s %s tensor on %s' % (who, k, dt, shape, self.device))
+        return {k: out[k] for k in spec}
+
+    def _roll(self):
+        """(io, bufs) of the rollout in progress: what every rollout-bound method starts with."""
+        if self._rollout is None:
+            raise RuntimeError('call rollout_begin() first')
+        return self._rollout
 
     # ---------------------------------------------------------------- state
     def set_state(self, state8=None, global_time=None):
         """state8: [B, A, 8] float64 (px,py,vx,vy,gx,gy,radius,v_pref); global_time: [B] float64."""
-        s = None if state8 is None else self._dev(state8, torch.float64, (self.B, self.A, 8))
-        g = None if global_time is None else self._dev(global_time, torch.float64, (self.B,))
+        s, _ = self._borrow(state8, torch.float64, (self.B, self.A, 8))
+        g, _ = self._borrow(global_time, torch.float64, (self.B,))
         check(self._lib.cn_set_state(self._h, _ptr(s), _ptr(g)))
         self.sync()  # s/g may be temporaries
 
@@ -135,7 +184,7 @@ class BatchedCrowdSim(object):
 
     def set_theta(self, theta):
         """Robot heading per env, [B] float64 (FullState.theta)."""
-        t = self._dev(theta, torch.float64, (self.B,))
+        t, _ = self._borrow(theta, torch.float64, (self.B,))
         check(self._lib.cn_set_theta(self._h, _ptr(t)))
         self.sync()
 
@@ -168,8 +217,8 @@ class BatchedCrowdSim(object):
         """np.random.seed(seeds[b]) + scenario generation per env; returns the np.random.random() call counts."""
         host = seeds.cpu().numpy() if torch.is_tensor(seeds) else np.asarray(seeds)
         bits = np.ascontiguousarray(host.astype(np.uint32)).view(np.int32)  # torch has no uint32 arithmetic
-        sd = self._dev(torch.from_numpy(bits), torch.int32, (self.B,))
-        m = None if mask is None else self._dev(mask, torch.uint8, (self.B,))
+        sd, _ = self._borrow(torch.from_numpy(bits), torch.int32, (self.B,))
+        m, _ = self._borrow(mask, torch.uint8, (self.B,))
         draws = torch.zeros(self.B, dtype=torch.int64, device=self.device)
         check(self._lib.cn_reset(self._h, _ptr(sd), _ptr(m), _ptr(draws)))
         self.sync()
@@ -187,7 +236,7 @@ class BatchedCrowdSim(object):
 
     def step(self, action=None, update=True, want_obs=True):
         """CrowdSim.step for every env.  action: [B, 2] float64 or None when the robot is ORCA on device."""
-        a = None if action is None else self._dev(action, torch.float64, (self.B, 2))
+        a, temporary = self._borrow(action, torch.float64, (self.B, 2))
         out = dict(
             reward=self._new((self.B,), torch.float64), done=self._new((self.B,), torch.uint8),
             info=self._new((self.B,), torch.uint8), dmin=self._new((self.B,), torch.float64),
@@ -197,8 +246,7 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_step(self._h, _ptr(a), int(bool(update)), _ptr(out['reward']), _ptr(out['done']),
                                 _ptr(out['info']), _ptr(out['dmin']), _ptr(out['action']),
                                 _ptr(out['orca_vel']), _ptr(out['obs'])))
-        if a is not None and not (torch.is_tensor(action) and a.data_ptr() == action.data_ptr()):
-            self.sync()  # `a` is a temporary copy
+        self._release(temporary)
         return out
 
     def step_into(self, action, reward, done, info, dmin, update=True):
@@ -256,10 +304,9 @@ class BatchedCrowdSim(object):
 
     def rollout(self, n_steps):
         """n_steps transitions per active env in one kernel launch (in-kernel auto-reset)."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        check(self._lib.cn_rollout(self._h, C.byref(self._rollout[0]), int(n_steps)))
-        return self._rollout[1]
+        io, bufs = self._roll()
+        check(self._lib.cn_rollout(self._h, C.byref(io), int(n_steps)))
+        return bufs
 
     def rollout_trace(self, n_steps, rewards=False, out=None):
         """rollout(n_steps) that also records every step (cn_rollout_trace): the same transitions, counters and records, plus a
@@ -275,18 +322,16 @@ class BatchedCrowdSim(object):
         chunks, or pass the previous call's dict as `out` to reuse it (validated; episode is refilled with -1).
         One launch of the generic phase kernel whatever the geometry: slower than rollout(), which it may be mixed with freely.
         crowdnav_amd.trace.episodes() splits the result into episodes on the host."""
+        io, _ = self._roll()
         out = self._trace_out('rollout_trace', n_steps, rewards, out)
         if out['episode'].shape[1] == 0:  # a no-op, as rollout(0) is (empty tensors have no address to hand over)
             return out
-        tr = CnTraceOut(**{k: v.data_ptr() for k, v in out.items()})
-        check(self._lib.cn_rollout_trace(self._h, C.byref(self._rollout[0]), int(n_steps), C.byref(tr)))
+        check(self._lib.cn_rollout_trace(self._h, C.byref(io), int(n_steps), C.byref(_struct(CnTraceOut, out))))
         return out
 
     def _trace_out(self, who, n_steps, rewards, out):
         """The dict of per-step rows a traced call of n_steps writes (rollout_trace, rollout_actions): fresh tensors, or the
         caller's `out` validated; episode filled with -1."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
         n = int(n_steps)
         if n < 0:
             raise ValueError('n_steps must be >= 0')
@@ -294,28 +339,18 @@ class BatchedCrowdSim(object):
                     step=(torch.int32, (self.B, n)))
         if rewards:
             spec.update(reward=(torch.float64, (self.B, n)), info=(torch.uint8, (self.B, n)), dmin=(torch.float64, (self.B, n)))
-        if out is None:
-            out = {k: self._new(shape, dt) for k, (dt, shape) in spec.items()}
-        else:
-            for k, (dt, shape) in spec.items():
-                t = out.get(k)
-                if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape
-                        or not t.is_contiguous()):
-                    raise ValueError('%s: out[%r] must be a contiguous %s %s tensor on %s' % (who, k, dt, shape, self.device))
-            out = {k: out[k] for k in spec}
+        out = self._rows(who, spec, out)
         out['episode'].fill_(-1)
         return out
 
     def rollout_step(self, action):
         """One bookkept transition of every running env with caller-supplied actions ([B, 2] float64 device tensor):
         the external-policy counterpart of rollout() (robot_policy == ROBOT_EXTERNAL)."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        a = self._dev(action, torch.float64, (self.B, 2))
-        check(self._lib.cn_rollout_step(self._h, C.byref(self._rollout[0]), _ptr(a)))
-        if not (torch.is_tensor(action) and a.data_ptr() == action.data_ptr()):
-            self.sync()
-        return self._rollout[1]
+        io, bufs = self._roll()
+        a, temporary = self._borrow(action, torch.float64, (self.B, 2))
+        check(self._lib.cn_rollout_step(self._h, C.byref(io), _ptr(a)))
+        self._release(temporary)
+        return bufs
 
     def rollout_actions(self, actions, trace=False, rewards=False, out=None):
         """n bookkept transitions of every running env with the actions known in advance, in ONE launch (cn_rollout_actions):
@@ -326,20 +361,18 @@ class BatchedCrowdSim(object):
         Returns the rollout's bufs; with trace=True the dict rollout_trace returns instead (state8 / episode / step, and with
         rewards=True reward / info / dmin, rows [b, t]; `out` reuses a previous call's dict) — one launch either way.
         crowdnav_amd.trace.episodes() cuts it into episodes."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
+        io, bufs = self._roll()
         shape = tuple(getattr(actions, 'shape', np.shape(actions)))
         if len(shape) != 3 or shape[0] != self.B or shape[2] != 2:
             raise ValueError('rollout_actions: actions must be [%d, n, 2], got %s' % (self.B, shape))
         n = int(shape[1])
         rows = self._trace_out('rollout_actions', n, rewards, out) if trace else None
         if n > 0:
-            a = self._dev(actions, torch.float64, (self.B, n, 2))
-            tr = None if rows is None else C.byref(CnTraceOut(**{k: v.data_ptr() for k, v in rows.items()}))
-            check(self._lib.cn_rollout_actions(self._h, C.byref(self._rollout[0]), n, _ptr(a), tr))
-            if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
-                self.sync()  # `a` is a temporary copy
-        return rows if trace else self._rollout[1]
+            a, temporary = self._borrow(actions, torch.float64, (self.B, n, 2))
+            tr = None if rows is None else C.byref(_struct(CnTraceOut, rows))
+            check(self._lib.cn_rollout_actions(self._h, C.byref(io), n, _ptr(a), tr))
+            self._release(temporary)
+        return rows if trace else bufs
 
     def lookahead(self, actions, final_state=False, out=None, bootstrap=False, sort_humans=False):
         """Score K candidate action sequences per env from the CURRENT state, in one launch, leaving the engine as it is
@@ -372,25 +405,16 @@ class BatchedCrowdSim(object):
             spec.update(final_state8=(torch.float64, (self.B, K, self.A, 8)), final_theta=(torch.float64, (self.B, K)))
         if bootstrap:
             spec.update(value=(torch.float32, (self.B, K)), score=(torch.float64, (self.B, K)))
-        if out is None:
-            out = {k: self._new(s, dt) for k, (dt, s) in spec.items()}
-        else:
-            for k, (dt, s) in spec.items():
-                t = out.get(k)
-                if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != s
-                        or not t.is_contiguous()):
-                    raise ValueError('lookahead: out[%r] must be a contiguous %s %s tensor on %s' % (k, dt, s, self.device))
-            out = {k: out[k] for k in spec}
+        out = self._rows('lookahead', spec, out)
         if n > 0:
-            a = self._dev(actions, torch.float64, (self.B, K, n, 2))
-            lo = CnLookaheadOut(**{k: v.data_ptr() for k, v in out.items() if k not in ('value', 'score')})
+            a, temporary = self._borrow(actions, torch.float64, (self.B, K, n, 2))
+            lo = C.byref(_struct(CnLookaheadOut, out))
             if bootstrap:
-                check(self._lib.cn_lookahead_values(self._h, n, K, _ptr(a), C.byref(lo), int(bool(sort_humans)),
+                check(self._lib.cn_lookahead_values(self._h, n, K, _ptr(a), lo, int(bool(sort_humans)),
                                                     _ptr(out['value']), _ptr(out['score'])))
             else:
-                check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), C.byref(lo)))
-            if not (torch.is_tensor(actions) and a.data_ptr() == actions.data_ptr()):
-                self.sync()  # `a` is a temporary copy
+                check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), lo))
+            self._release(temporary)
         return out
 
     # ---------------------------------------------------------------- device CEM planner (cn_plan_*)
@@ -410,59 +434,54 @@ class BatchedCrowdSim(object):
         return Plan(self, K, n, int(elites), int(iterations), float(init_std), float(min_std), float(smoothing), int(seed),
                     bool(bootstrap), bool(sort_humans))
 
-    def _plan(self, plan):
+    def _plan_call(self, name, plan, *args, rollout=False, n_real=None, counter=None):
+        """check(cn_plan_<name>(engine, [io, [n_real,]] cfg, plan, *args[, counter])), the one way to the planner's entry points.
+        rollout: the call takes the io of the rollout in progress (asked for before the plan is looked at) and its bufs are
+        returned; counter: cut to the uint32 the library takes."""
+        io, bufs = self._roll() if rollout else (None, None)
         if not isinstance(plan, Plan) or plan.engine() is not self:
             raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
-        return C.byref(plan.cfg), C.byref(plan.c)
+        head = [] if not rollout else [C.byref(io)] if n_real is None else [C.byref(io), int(n_real)]
+        tail = [] if counter is None else [int(counter) & 0xffffffff]
+        check(getattr(self._lib, 'cn_plan_' + name)(self._h, *head, C.byref(plan.cfg), C.byref(plan.c), *args, *tail))
+        return bufs
 
     def plan_reset(self, plan, mask=None):
         """The goal-directed prior (cn_plan_reset): mean = full speed — or what reaches the goal in one step — from the robot
         towards its goal at every t, std = init_std; for the envs of `mask` ([B] bool / uint8, None = all)."""
-        m = None if mask is None else self._dev(mask, torch.uint8, (self.B,))
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_reset(self._h, cfg, c, _ptr(m)))
-        if m is not None and not (torch.is_tensor(mask) and m.data_ptr() == mask.data_ptr()):
-            self.sync()  # `m` is a temporary copy
+        m, temporary = self._borrow(mask, torch.uint8, (self.B,))
+        self._plan_call('reset', plan, _ptr(m))
+        self._release(temporary)
         return plan
 
     def plan_draw(self, plan, counter):
         """plan.candidates <- K sequences per env from N(mean, std), clipped to the robot's speed; candidate 0 is the mean
         (cn_plan_draw).  Philox4x32-10 keyed by the plan's seed, counter words (t, k, b, counter)."""
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_draw(self._h, cfg, c, int(counter) & 0xffffffff))
+        self._plan_call('draw', plan, counter=counter)
         return plan.candidates
 
     def plan_refit(self, plan, keep_best=False):
         """Rank plan.candidates by plan.look['ret'] (['score'] with bootstrap), write order / best_* / action, refit mean and
         std to the elites (cn_plan_refit).  keep_best: the best sequence is replaced only by a strictly better one."""
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_refit(self._h, cfg, c, int(bool(keep_best))))
+        self._plan_call('refit', plan, int(bool(keep_best)))
         return plan
 
     def plan_cem(self, plan, counter):
         """One planning step (cn_plan_cem): `iterations` x (draw with counter + i, lookahead, refit), all enqueued by one
         call; plan.action then holds the first action of the best sequence found.  The engine is left as lookahead() leaves it."""
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_cem(self._h, cfg, c, int(counter) & 0xffffffff))
+        self._plan_call('cem', plan, counter=counter)
         return plan
 
     def plan_shift(self, plan):
         """After rollout_step(plan.action) (cn_plan_shift): the plan of a running env moves up by one step (std back to
         init_std), an env whose episode has just ended gets the prior of its new scenario, a retired env is left alone."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_shift(self._h, C.byref(self._rollout[0]), cfg, c))
+        self._plan_call('shift', plan, rollout=True)
         return plan
 
     def plan_rollout(self, plan, n_real, counter):
         """n_real closed-loop steps in ONE call without host work or synchronisation in between (cn_plan_rollout): per step
         plan_cem(counter + s * iterations), rollout_step(plan.action), plan_shift.  Returns the rollout's bufs."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_rollout(self._h, C.byref(self._rollout[0]), int(n_real), cfg, c, int(counter) & 0xffffffff))
-        return self._rollout[1]
+        return self._plan_call('rollout', plan, rollout=True, n_real=n_real, counter=counter)
 
     # ---------------------------------------------------------------- device MPPI update (cn_plan_mppi_*), on the same Plan
     def plan_mppi_update(self, plan, temperature, fit_std=False, keep_best=False):
@@ -470,35 +489,27 @@ class BatchedCrowdSim(object):
         weighted by exp((score - best score) / temperature); mean <- the weighted mean (through smoothing), std <- the weighted
         deviation only with fit_std; plan.action <- the updated mean's first row, clipped to the robot's speed.  The plan's
         `elites` is not read."""
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_mppi_update(self._h, cfg, c, float(temperature), int(bool(fit_std)), int(bool(keep_best))))
+        self._plan_call('mppi_update', plan, float(temperature), int(bool(fit_std)), int(bool(keep_best)))
         return plan
 
     def plan_mppi(self, plan, temperature, counter, fit_std=False):
         """One planning step (cn_plan_mppi): `iterations` x (draw with counter + i, lookahead, MPPI update), all enqueued by
         one call.  The engine is left as lookahead() leaves it."""
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_mppi(self._h, cfg, c, float(temperature), int(bool(fit_std)), int(counter) & 0xffffffff))
+        self._plan_call('mppi', plan, float(temperature), int(bool(fit_std)), counter=counter)
         return plan
 
     def plan_mppi_rollout(self, plan, n_real, temperature, counter, fit_std=False):
         """plan_rollout with the MPPI update (cn_plan_mppi_rollout): per step plan_mppi(counter + s * iterations),
         rollout_step(plan.action), plan_shift, in ONE call.  Returns the rollout's bufs."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        cfg, c = self._plan(plan)
-        check(self._lib.cn_plan_mppi_rollout(self._h, C.byref(self._rollout[0]), int(n_real), cfg, c, float(temperature),
-                                             int(bool(fit_std)), int(counter) & 0xffffffff))
-        return self._rollout[1]
+        return self._plan_call('mppi_rollout', plan, float(temperature), int(bool(fit_std)), rollout=True, n_real=n_real,
+                               counter=counter)
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):
         """The finished episodes of this engine's rollout as ONE self-contained float64 block per env:
         [B, 1 + 6 K] = (episodes finished, K x (outcome, steps, discounted return, nav time, danger steps, danger dmin
         sum)); see distributed.split_blocks.  One kernel (cn_rollout_records)."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
-        io, bufs = self._rollout
+        io, bufs = self._roll()
         K = int(bufs['ep_outcome'].shape[1] if max_records is None else max_records)
         blocks = self._new((self.B, 1 + K * _lib.RECORD_FIELDS), torch.float64)
         check(self._lib.cn_rollout_records(self._h, C.byref(io), K, _ptr(blocks)))
@@ -517,7 +528,7 @@ class BatchedCrowdSim(object):
     def _summary_out(self, out):
         if out is None:
             return self._new((_lib.SUMMARY_FIELDS,), torch.float64)
-        if out.dtype != torch.float64 or out.device != self.device or out.numel() != _lib.SUMMARY_FIELDS or not out.is_contiguous():
+        if not self._dense(out, torch.float64, out.shape) or out.numel() != _lib.SUMMARY_FIELDS:  # 8 numbers in any shape
             raise ValueError('summary output: a contiguous float64 [%d] tensor on %s' % (_lib.SUMMARY_FIELDS, self.device))
         return out
 
@@ -525,10 +536,9 @@ class BatchedCrowdSim(object):
         """records_summary(rollout_records()) of this engine in ONE kernel, straight from its record rings (cn_rollout_summary):
         the statistics of explorer.py:74-90 for a run on one engine.  out: the caller's float64 [8] device tensor (a run that
         asks once per boundary keeps one: no allocation between the last launch and the kernel)."""
-        if self._rollout is None:
-            raise RuntimeError('call rollout_begin() first')
+        io, _ = self._roll()
         out = self._summary_out(out)
-        check(self._lib.cn_rollout_summary(self._h, C.byref(self._rollout[0]), _ptr(out)))
+        check(self._lib.cn_rollout_summary(self._h, C.byref(io), _ptr(out)))
         return out
 
     def gather_records_rccl(self, comm, n_ranks, blocks):
@@ -570,234 +580,198 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_mt_random(self._h, int(seed), int(n), _ptr(out)))
         return out
 
+    # ---------------------------------------------------------------- SARL decision
+    def sarl_configure(self, actions, gamma=0.9, with_om=False, cell_num=4, cell_size=1.0, om_channel_size=3,
+                       with_global_state=True, mlp1_dims=(150, 100), mlp2_dims=(100, 50), attention_dims=(100, 100, 1),
+                       mlp3_dims=(150, 100, 100, 1), model='sarl', interaction_dims=None, query_env=True, precision='f32'):
+        """SARL.configure (or model='cadrl': mlp3_dims = [cadrl] mlp_dims; model='lstm_rl': mlp1_dims[0] = hidden width,
+        mlp3_dims = [lstm_rl] mlp2_dims, interaction_dims = [lstm_rl] mlp1_dims when with_interaction_module) +
+        build_action_space for
+        this engine.  actions: [K, 2] float64 ActionXY table (host).  query_env=False: [action_space] query_env = false, the
+        constant-velocity human model + MultiHumanRL.compute_reward instead of the env's lookahead.
+        precision: 'f32', or 'f16x2' — the split-f16 matrix route (CN_PRECISION_F16X2: sarl.ValueNetwork at the shipped widths, 1..5
+        humans; values within 1e-6 of fp32).  The library refuses what that route does not cover (CrowdNavAmdError, status
+        CN_ERR_UNSUPPORTED, the engine stays unconfigured): it never falls back.  An integer is passed on as the raw CN_PRECISION_*."""
+        acts = np.ascontiguousarray(np.asarray(actions, dtype=np.float64).reshape(-1, 2))
+        cfg = _lib.CnSarlConfig(n_actions=len(acts), with_om=int(bool(with_om)), cell_num=int(cell_num),
+                                om_channel_size=int(om_channel_size), cell_size=float(cell_size), gamma=float(gamma),
+                                with_global_state=int(bool(with_global_state)),
+                                mlp1_dims=(C.c_int32 * 2)(*mlp1_dims), mlp2_dims=(C.c_int32 * 2)(*mlp2_dims),
+                                attention_dims=(C.c_int32 * 3)(*attention_dims), mlp3_dims=(C.c_int32 * 4)(*mlp3_dims),
+                                model={'sarl': 0, 'cadrl': 1, 'lstm_rl': 2}[model],
+                                interaction_dims=(C.c_int32 * 4)(*(interaction_dims or (0, 0, 0, 0))),
+                                constant_velocity_model=0 if query_env else 1,
+                                precision=_lib.PRECISIONS.index(precision) if isinstance(precision, str) else int(precision))
+        check(self._lib.cn_sarl_configure(self._h, C.byref(cfg), acts.ctypes.data_as(C.c_void_p)))
+        self.sarl = dict(n_actions=len(acts), in_dim=13 + (cell_num ** 2 * om_channel_size if with_om else 0),
+                         actions=acts, model=model, pairwise=bool(interaction_dims))
 
-# ---------------------------------------------------------------------------------------- SARL decision
-SARL_PARAM_ORDER = tuple('%s.%d.%s' % (m, i, p) for m, idxs in (('mlp1', (0, 2)), ('mlp2', (0, 2)),
-                                                               ('attention', (0, 2, 4)), ('mlp3', (0, 2, 4, 6)))
-                         for i in idxs for p in ('weight', 'bias'))
+    def sarl_set_weights(self, state_dict):
+        """Hand the value network's parameters (sarl.ValueNetwork.state_dict()) to the device kernels."""
+        order = {'cadrl': CADRL_PARAM_ORDER, 'lstm_rl': LSTM_PARAM_ORDER}.get(self.sarl['model'], SARL_PARAM_ORDER)
+        if self.sarl.get('pairwise'):  # lstm_rl.ValueNetwork2: mlp1 first, as in its state_dict
+            order = LSTM_PAIRWISE_MLP1_ORDER + order
+        # parameters that live on the engine's device as dense float32 are read in place (the RL phase uploads weights once per
+        # sampled episode: 22 conversions and stream records were ~0.1 ms of host time each time); anything else goes through a copy
+        tensors, temporaries = [], []
+        for k in order:
+            t = state_dict[k]
+            if not (t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+                temporaries.append(t)
+            tensors.append(t)
+        ptrs = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        check(self._lib.cn_sarl_set_weights(self._h, ptrs))
+        # the tensors above must outlive the repack kernel: kept until the next call — by then it is long behind on the engine's
+        # stream; no synchronize per call.  The caching allocator is told that the engine's stream reads the TEMPORARIES: were the
+        # caller inside another torch.cuda.stream(...) context, a freed temporary could otherwise be handed out again on THAT stream
+        # while the repack kernel, on the stream captured at construction / use_current_stream(), still reads it.
+        for t in temporaries:
+            t.record_stream(self._stream)
+        self._sarl_weights_keepalive = tensors
 
+    def sarl_select(self, want_values=True, best=None, action=None, want_attention=False):
+        """Greedy SARL action of every env: dict(values [B,K] f64, best [B] i32, action [B,2] f64).  best / action: the caller's
+        device tensors to write into (e.g. row t of an action history) instead of fresh ones.  want_attention (SARL only): also
+        attention [B,K,H] f32, the softmax weights of every lookahead state (cn_sarl_select_attention; 0 for absent humans)."""
+        K = self.sarl['n_actions']
+        if best is None:
+            best = self._new((self.B,), torch.int32)
+        if action is None:
+            action = self._new((self.B, 2), torch.float64)
+        assert best.dtype == torch.int32 and best.is_contiguous() and action.dtype == torch.float64 and action.is_contiguous()
+        out = dict(values=self._new((self.B, K), torch.float64) if want_values else None, best=best, action=action)
+        if want_attention:
+            out['attention'] = self._new((self.B, K, self.H), torch.float32)
+            check(self._lib.cn_sarl_select_attention(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action']),
+                                                     _ptr(out['attention'])))
+        else:
+            check(self._lib.cn_sarl_select(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action'])))
+        return out
 
-LSTM_PARAM_ORDER = tuple('mlp.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias')) + (
-    'lstm.weight_ih_l0', 'lstm.weight_hh_l0', 'lstm.bias_ih_l0', 'lstm.bias_hh_l0')
-LSTM_PAIRWISE_MLP1_ORDER = tuple('mlp1.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias'))
-CADRL_PARAM_ORDER = tuple('value_network.%d.%s' % (i, p) for i in (0, 2, 4, 6) for p in ('weight', 'bias'))
+    def sarl_export(self, name):
+        """Internal buffers of the last sarl_select (tests): reward, V, next_obs, om, X (natural [B,K,H,ld] order)."""
+        K, H = self.sarl['n_actions'], self.H
+        if name == 'reward':
+            t, which = self._new((self.B, K), torch.float64), 0
+        elif name == 'V':
+            t, which = self._new((self.B, K), torch.float32), 1
+        elif name == 'next_obs':
+            t, which = self._new((self.B, H, 5), torch.float64), 2
+        elif name == 'om':
+            t, which = self._new((self.B, H, self.sarl['in_dim'] - 13), torch.float32), 3
+        elif name == 'X':
+            d = self.sarl['in_dim']  # cn::sarl_ks: whole 16-column tiles, at least the k loop's 5-step chunks
+            ks = max((d + 15) // 16 * 4, ((d + 3) // 4 + 4) // 5 * 5)
+            tiles = (self.B * K + 15) // 16
+            t, which = self._new((tiles, H, ks, 4, 16), torch.float32), 4  # MFMA A-fragment order
+        else:
+            raise KeyError(name)
+        check(self._lib.cn_sarl_export(self._h, which, _ptr(t), t.numel() * t.element_size()))
+        if name == 'X':  # [tile][h][k-step][k % 4][g] -> [B, K, H, in_dim]
+            t = t.permute(0, 4, 1, 2, 3).reshape(-1, H, t.shape[2] * 4)[:self.B * K, :, :self.sarl['in_dim']]
+            t = t.reshape(self.B, K, H, -1)
+        return t
 
+    def sarl_explore(self, sel, epsilon, mask=None, want_explored=True):
+        """Epsilon-greedy on top of a sarl_select result (in place): each env draws np.random.random() — and, below
+        epsilon, np.random.choice(K) — from the numpy stream its last reset() seeded (multi_human_rl.py:28-31)."""
+        m, _ = self._borrow(mask, torch.uint8, (self.B,))
+        explored = self._new((self.B,), torch.uint8) if want_explored else None
+        check(self._lib.cn_sarl_explore(self._h, float(epsilon), _ptr(m), _ptr(sel['best']), _ptr(sel['action']),
+                                        _ptr(explored)))
+        sel['explored'] = explored
+        return sel
 
-def _sarl_configure(self, actions, gamma=0.9, with_om=False, cell_num=4, cell_size=1.0, om_channel_size=3,
-                    with_global_state=True, mlp1_dims=(150, 100), mlp2_dims=(100, 50), attention_dims=(100, 100, 1),
-                    mlp3_dims=(150, 100, 100, 1), model='sarl', interaction_dims=None, query_env=True, precision='f32'):
-    """SARL.configure (or model='cadrl': mlp3_dims = [cadrl] mlp_dims; model='lstm_rl': mlp1_dims[0] = hidden width,
-    mlp3_dims = [lstm_rl] mlp2_dims, interaction_dims = [lstm_rl] mlp1_dims when with_interaction_module) +
-    build_action_space for
-    this engine.  actions: [K, 2] float64 ActionXY table (host).  query_env=False: [action_space] query_env = false, the
-    constant-velocity human model + MultiHumanRL.compute_reward instead of the env's lookahead.
-    precision: 'f32', or 'f16x2' — the split-f16 matrix route (CN_PRECISION_F16X2: sarl.ValueNetwork at the shipped widths, 1..5
-    humans; values within 1e-6 of fp32).  The library refuses what that route does not cover (CrowdNavAmdError, status
-    CN_ERR_UNSUPPORTED, the engine stays unconfigured): it never falls back.  An integer is passed on as the raw CN_PRECISION_*."""
-    acts = np.ascontiguousarray(np.asarray(actions, dtype=np.float64).reshape(-1, 2))
-    cfg = _lib.CnSarlConfig(n_actions=len(acts), with_om=int(bool(with_om)), cell_num=int(cell_num),
-                            om_channel_size=int(om_channel_size), cell_size=float(cell_size), gamma=float(gamma),
-                            with_global_state=int(bool(with_global_state)),
-                            mlp1_dims=(C.c_int32 * 2)(*mlp1_dims), mlp2_dims=(C.c_int32 * 2)(*mlp2_dims),
-                            attention_dims=(C.c_int32 * 3)(*attention_dims), mlp3_dims=(C.c_int32 * 4)(*mlp3_dims),
-                            model={'sarl': 0, 'cadrl': 1, 'lstm_rl': 2}[model],
-                            interaction_dims=(C.c_int32 * 4)(*(interaction_dims or (0, 0, 0, 0))),
-                            constant_velocity_model=0 if query_env else 1,
-                            precision=_lib.PRECISIONS.index(precision) if isinstance(precision, str) else int(precision))
-    check(self._lib.cn_sarl_configure(self._h, C.byref(cfg), acts.ctypes.data_as(C.c_void_p)))
-    self.sarl = dict(n_actions=len(acts), in_dim=13 + (cell_num ** 2 * om_channel_size if with_om else 0),
-                     actions=acts, model=model, pairwise=bool(interaction_dims))
+    def sarl_transform(self, out=None, env_stride=0, sort_humans=None):
+        """MultiHumanRL.transform of every env's current joint state: [B, H, in_dim] float32 (replay-memory state).
+        With out (a float32 device tensor) and env_stride (floats between consecutive envs) the rows are written in place,
+        e.g. out = traj[:, t] of a [B, T, H, D] trajectory tensor with env_stride = T * H * D.  sort_humans: LSTM-RL's
+        decreasing-distance order (default for that model: the RL phase); False = env order (imitation learning)."""
+        if out is None:
+            out = self._new((self.B, self.H, self.sarl['in_dim']), torch.float32)
+        assert out.dtype == torch.float32 and out.device.type == self.device.type
+        if sort_humans is None:  # what a train-phase predict() of this model leaves in last_state
+            sort_humans = self.sarl['model'] == 'lstm_rl'
+        check(self._lib.cn_sarl_transform(self._h, C.c_void_p(out.data_ptr()), int(env_stride), int(bool(sort_humans))))
+        return out
 
+    def sarl_sampler(self, traj, rew, info, dmin, act, alive, done, action):
+        """The train-phase decision + step of every env as ONE call per step: step(t, epsilon) is cn_sarl_sample_step —
+        alive &= ~done (the previous step's episode ends; zero `done` before an episode's first step), then cn_sarl_select ->
+        cn_sarl_explore (mask = alive) -> cn_sarl_transform -> cn_step — with row t of the caller's histories (traj [B, T, H, D]
+        float32; rew / dmin [T, B] float64; info [T, B] uint8; act [T, B] int32: the chosen action index) as outputs, addresses
+        precomputed.  For a few envs a streamed loop of these calls is two launches per step (include/crowdnav_amd.h); on that
+        route the kernels skip an env whose episode is over (its rows of the histories are not written any more)."""
+        B, T, H, D = traj.shape
+        if B != self.B or H != self.H:
+            raise ValueError('traj is [%d, T, %d, D]; the engine holds %d envs x %d humans' % (B, H, self.B, self.H))
+        specs = ((traj, torch.float32, (B, T, H, D)), (act, torch.int32, (T, B)), (rew, torch.float64, (T, B)),
+                 (dmin, torch.float64, (T, B)), (info, torch.uint8, (T, B)), (alive, torch.uint8, (B,)), (done, torch.uint8, (B,)),
+                 (action, torch.float64, (B, 2)))
+        for t_, dt, shape in specs:  # raw addresses go to the C ABI below: every tensor on the engine's device, dense, as declared
+            # (info may live in PINNED host memory instead: the kernels only write it — posted stores over the host link — and a
+            # caller that streams steps can watch the episode-end codes arrive without a device synchronisation)
+            # (round 6, later: so may the reward / min-distance / action histories — written before the step's info code on the
+            # two-launch route; on the other routes a kernel READS the action row back: correct over the host link, only slower)
+            if not self._dense(t_, dt, shape, pinned_ok=any(t_ is w for w in (info, rew, dmin, act))):
+                raise ValueError('sarl_sampler: expected a contiguous %s %s tensor on %s, got %s %s on %s (contiguous: %s)'
+                                 % (dt, shape, self.device, t_.dtype, tuple(t_.shape), t_.device, t_.is_contiguous()))
+        # the closure owns the tensors its addresses point into, but only a WEAK reference to the engine: stored on the engine or on
+        # a rollout object it would otherwise form a cycle, and cn_destroy (a stream synchronize + hipFree) would run whenever the
+        # cyclic collector gets to it — e.g. in the middle of somebody's timed region (bench.py closes its engines explicitly)
+        keep = (traj, rew, info, dmin, act, alive, done, action)
+        alive_engine = weakref.ref(self)
+        lib, h, V = self._lib, self._h, C.c_void_p
+        p_traj, p_rew, p_inf, p_dmn, p_act = traj.data_ptr(), rew.data_ptr(), info.data_ptr(), dmin.data_ptr(), act.data_ptr()
+        p_alive, p_done, p_action = V(alive.data_ptr()), V(done.data_ptr()), V(action.data_ptr())
+        sort = int(self.sarl['model'] == 'lstm_rl')
+        stride = T * H * D
 
-def _sarl_set_weights(self, state_dict):
-    """Hand the value network's parameters (sarl.ValueNetwork.state_dict()) to the device kernels."""
-    order = {'cadrl': CADRL_PARAM_ORDER, 'lstm_rl': LSTM_PARAM_ORDER}.get(self.sarl['model'], SARL_PARAM_ORDER)
-    if self.sarl.get('pairwise'):  # lstm_rl.ValueNetwork2: mlp1 first, as in its state_dict
-        order = LSTM_PAIRWISE_MLP1_ORDER + order
-    # parameters that live on the engine's device as dense float32 are read in place (the RL phase uploads weights once per
-    # sampled episode: 22 conversions and stream records were ~0.1 ms of host time each time); anything else goes through a copy
-    tensors, temporaries = [], []
-    for k in order:
-        t = state_dict[k]
-        if not (t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()):
-            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-            temporaries.append(t)
-        tensors.append(t)
-    ptrs = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-    check(self._lib.cn_sarl_set_weights(self._h, ptrs))
-    # the tensors above must outlive the repack kernel: kept until the next call — by then it is long behind on the engine's
-    # stream; no synchronize per call.  The caching allocator is told that the engine's stream reads the TEMPORARIES: were the
-    # caller inside another torch.cuda.stream(...) context, a freed temporary could otherwise be handed out again on THAT stream
-    # while the repack kernel, on the stream captured at construction / use_current_stream(), still reads it.
-    for t in temporaries:
-        t.record_stream(self._stream)
-    self._sarl_weights_keepalive = tensors
+        def step(t, epsilon):
+            eng = alive_engine()
+            if eng is None or eng._h is not h or not h.value:
+                raise RuntimeError('sarl_sampler: the engine has been closed')
+            check(lib.cn_sarl_sample_step(h, epsilon, p_alive, V(p_act + 4 * B * t), p_action, V(p_traj + 4 * H * D * t), stride, sort,
+                                          V(p_rew + 8 * B * t), p_done, V(p_inf + B * t), V(p_dmn + 8 * B * t)))
+        step.keep = keep  # the tensors live as long as the step function does
+        return step
 
+    def sarl_values(self, states, out=None):
+        """V(state) of joint states the caller holds (cn_sarl_values): float32 [n, H, 13] rows as sarl_transform / the sampler
+        write them -> float32 [n], under the weights of the last sarl_set_weights.  One launch on the narrow tiles; the engine's
+        env state is not touched.  What target_model(next_states) is to Explorer.update_memory's TD targets."""
+        n = int(states.shape[0])
+        if not self._dense(states, torch.float32, (n, self.H, 13)):
+            raise ValueError('sarl_values: expected a contiguous float32 [n, %d, 13] tensor on %s' % (self.H, self.device))
+        if out is None:
+            out = self._new((n,), torch.float32)
+        check(self._lib.cn_sarl_values(self._h, _ptr(states), n, _ptr(out)))
+        return out
 
-def _sarl_select(self, want_values=True, best=None, action=None, want_attention=False):
-    """Greedy SARL action of every env: dict(values [B,K] f64, best [B] i32, action [B,2] f64).  best / action: the caller's
-    device tensors to write into (e.g. row t of an action history) instead of fresh ones.  want_attention (SARL only): also
-    attention [B,K,H] f32, the softmax weights of every lookahead state (cn_sarl_select_attention; 0 for absent humans)."""
-    K = self.sarl['n_actions']
-    if best is None:
-        best = self._new((self.B,), torch.int32)
-    if action is None:
-        action = self._new((self.B, 2), torch.float64)
-    assert best.dtype == torch.int32 and best.is_contiguous() and action.dtype == torch.float64 and action.is_contiguous()
-    out = dict(values=self._new((self.B, K), torch.float64) if want_values else None, best=best, action=action)
-    if want_attention:
-        out['attention'] = self._new((self.B, K, self.H), torch.float32)
-        check(self._lib.cn_sarl_select_attention(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action']),
-                                                 _ptr(out['attention'])))
-    else:
-        check(self._lib.cn_sarl_select(self._h, _ptr(out['values']), _ptr(out['best']), _ptr(out['action'])))
-    return out
-
-
-def _sarl_export(self, name):
-    """Internal buffers of the last sarl_select (tests): reward, V, next_obs, om, X (natural [B,K,H,ld] order)."""
-    K, H = self.sarl['n_actions'], self.H
-    if name == 'reward':
-        t, which = self._new((self.B, K), torch.float64), 0
-    elif name == 'V':
-        t, which = self._new((self.B, K), torch.float32), 1
-    elif name == 'next_obs':
-        t, which = self._new((self.B, H, 5), torch.float64), 2
-    elif name == 'om':
-        t, which = self._new((self.B, H, self.sarl['in_dim'] - 13), torch.float32), 3
-    elif name == 'X':
-        d = self.sarl['in_dim']  # cn::sarl_ks: whole 16-column tiles, at least the k loop's 5-step chunks
-        ks = max((d + 15) // 16 * 4, ((d + 3) // 4 + 4) // 5 * 5)
-        tiles = (self.B * K + 15) // 16
-        t, which = self._new((tiles, H, ks, 4, 16), torch.float32), 4  # MFMA A-fragment order
-    else:
-        raise KeyError(name)
-    check(self._lib.cn_sarl_export(self._h, which, _ptr(t), t.numel() * t.element_size()))
-    if name == 'X':  # [tile][h][k-step][k % 4][g] -> [B, K, H, in_dim]
-        t = t.permute(0, 4, 1, 2, 3).reshape(-1, H, t.shape[2] * 4)[:self.B * K, :, :self.sarl['in_dim']]
-        t = t.reshape(self.B, K, H, -1)
-    return t
-
-
-def _sarl_explore(self, sel, epsilon, mask=None, want_explored=True):
-    """Epsilon-greedy on top of a sarl_select result (in place): each env draws np.random.random() — and, below
-    epsilon, np.random.choice(K) — from the numpy stream its last reset() seeded (multi_human_rl.py:28-31)."""
-    m = None if mask is None else self._dev(mask, torch.uint8, (self.B,))
-    explored = self._new((self.B,), torch.uint8) if want_explored else None
-    check(self._lib.cn_sarl_explore(self._h, float(epsilon), _ptr(m), _ptr(sel['best']), _ptr(sel['action']),
-                                    _ptr(explored)))
-    sel['explored'] = explored
-    return sel
-
-
-def _sarl_transform(self, out=None, env_stride=0, sort_humans=None):
-    """MultiHumanRL.transform of every env's current joint state: [B, H, in_dim] float32 (replay-memory state).
-    With out (a float32 device tensor) and env_stride (floats between consecutive envs) the rows are written in place,
-    e.g. out = traj[:, t] of a [B, T, H, D] trajectory tensor with env_stride = T * H * D.  sort_humans: LSTM-RL's
-    decreasing-distance order (default for that model: the RL phase); False = env order (imitation learning)."""
-    if out is None:
-        out = self._new((self.B, self.H, self.sarl['in_dim']), torch.float32)
-    assert out.dtype == torch.float32 and out.device.type == self.device.type
-    if sort_humans is None:  # what a train-phase predict() of this model leaves in last_state
-        sort_humans = self.sarl['model'] == 'lstm_rl'
-    check(self._lib.cn_sarl_transform(self._h, C.c_void_p(out.data_ptr()), int(env_stride), int(bool(sort_humans))))
-    return out
-
-
-def _sarl_sampler(self, traj, rew, info, dmin, act, alive, done, action):
-    """The train-phase decision + step of every env as ONE call per step: step(t, epsilon) is cn_sarl_sample_step —
-    alive &= ~done (the previous step's episode ends; zero `done` before an episode's first step), then cn_sarl_select ->
-    cn_sarl_explore (mask = alive) -> cn_sarl_transform -> cn_step — with row t of the caller's histories (traj [B, T, H, D]
-    float32; rew / dmin [T, B] float64; info [T, B] uint8; act [T, B] int32: the chosen action index) as outputs, addresses
-    precomputed.  For a few envs a streamed loop of these calls is two launches per step (include/crowdnav_amd.h); on that
-    route the kernels skip an env whose episode is over (its rows of the histories are not written any more)."""
-    B, T, H, D = traj.shape
-    if B != self.B or H != self.H:
-        raise ValueError('traj is [%d, T, %d, D]; the engine holds %d envs x %d humans' % (B, H, self.B, self.H))
-    specs = ((traj, torch.float32, (B, T, H, D)), (act, torch.int32, (T, B)), (rew, torch.float64, (T, B)),
-             (dmin, torch.float64, (T, B)), (info, torch.uint8, (T, B)), (alive, torch.uint8, (B,)), (done, torch.uint8, (B,)),
-             (action, torch.float64, (B, 2)))
-    for t_, dt, shape in specs:  # raw addresses go to the C ABI below: every tensor on the engine's device, dense, as declared
-        # (info may live in PINNED host memory instead: the kernels only write it — posted stores over the host link — and a
-        # caller that streams steps can watch the episode-end codes arrive without a device synchronisation)
-        # (round 6, later: so may the reward / min-distance / action histories — written before the step's info code on the
-        # two-launch route; on the other routes a kernel READS the action row back: correct over the host link, only slower)
-        on_device = t_.device == self.device or (any(t_ is w for w in (info, rew, dmin, act)) and t_.device.type == 'cpu'
-                                                 and t_.is_pinned())
-        if not on_device or t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous():
-            raise ValueError('sarl_sampler: expected a contiguous %s %s tensor on %s, got %s %s on %s (contiguous: %s)'
-                             % (dt, shape, self.device, t_.dtype, tuple(t_.shape), t_.device, t_.is_contiguous()))
-    # the closure owns the tensors its addresses point into, but only a WEAK reference to the engine: stored on the engine or on
-    # a rollout object it would otherwise form a cycle, and cn_destroy (a stream synchronize + hipFree) would run whenever the
-    # cyclic collector gets to it — e.g. in the middle of somebody's timed region (bench.py closes its engines explicitly)
-    keep = (traj, rew, info, dmin, act, alive, done, action)
-    alive_engine = weakref.ref(self)
-    lib, h, V = self._lib, self._h, C.c_void_p
-    p_traj, p_rew, p_inf, p_dmn, p_act = traj.data_ptr(), rew.data_ptr(), info.data_ptr(), dmin.data_ptr(), act.data_ptr()
-    p_alive, p_done, p_action = V(alive.data_ptr()), V(done.data_ptr()), V(action.data_ptr())
-    sort = int(self.sarl['model'] == 'lstm_rl')
-    stride = T * H * D
-
-    def step(t, epsilon):
-        eng = alive_engine()
-        if eng is None or eng._h is not h or not h.value:
-            raise RuntimeError('sarl_sampler: the engine has been closed')
-        check(lib.cn_sarl_sample_step(h, epsilon, p_alive, V(p_act + 4 * B * t), p_action, V(p_traj + 4 * H * D * t), stride, sort,
-                                      V(p_rew + 8 * B * t), p_done, V(p_inf + B * t), V(p_dmn + 8 * B * t)))
-    step.keep = keep  # the tensors live as long as the step function does
-    return step
-
-
-def _sarl_values(self, states, out=None):
-    """V(state) of joint states the caller holds (cn_sarl_values): float32 [n, H, 13] rows as sarl_transform / the sampler
-    write them -> float32 [n], under the weights of the last sarl_set_weights.  One launch on the narrow tiles; the engine's
-    env state is not touched.  What target_model(next_states) is to Explorer.update_memory's TD targets."""
-    n = int(states.shape[0])
-    if (states.device != self.device or states.dtype != torch.float32 or tuple(states.shape[1:]) != (self.H, 13)
-            or not states.is_contiguous()):
-        raise ValueError('sarl_values: expected a contiguous float32 [n, %d, 13] tensor on %s' % (self.H, self.device))
-    if out is None:
-        out = self._new((n,), torch.float32)
-    check(self._lib.cn_sarl_values(self._h, _ptr(states), n, _ptr(out)))
-    return out
-
-
-def _sarl_state_values(self, state8, theta=None, sort_humans=False, out=None):
-    """V(state) of joint states the caller holds in the env layout (cn_sarl_state_values): state8 float64 [n, A, 8] — get_state()'s
-    rows, a rollout trace's, lookahead()'s final_state8; any leading axes [..., A, 8] are flattened — and theta float64 [n] (or the
-    same leading axes), the robot heading, required for a unicycle robot and ignored otherwise -> float32 [n], under the weights
-    of the last sarl_set_weights.  The rows are sarl_transform's (sort_humans as there; False = env order).  Any n >= 1, through
-    the engine's own network kernels in passes of num_envs x n_actions; the engine's env state is not touched, the buffers
-    sarl_export reads may be overwritten.  Contiguous float64 tensors on the engine's device are read in place; anything else is
-    copied and the call synchronises."""
-    shape = tuple(getattr(state8, 'shape', np.shape(state8)))
-    if len(shape) < 3 or shape[-2:] != (self.A, 8):
-        raise ValueError('sarl_state_values: state8 must be [n, %d, 8] (or [..., %d, 8]), got %s' % (self.A, self.A, shape))
-    n = int(np.prod(shape[:-2], dtype=np.int64))
-    if theta is not None:
-        tshape = tuple(getattr(theta, 'shape', np.shape(theta)))
-        if int(np.prod(tshape, dtype=np.int64)) != n or (len(tshape) != 1 and tshape != shape[:-2]):
-            raise ValueError('sarl_state_values: theta must be [%d] or %s, got %s' % (n, shape[:-2], tshape))
-    if out is None:
-        out = self._new((n,), torch.float32)
-    elif (not torch.is_tensor(out) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (n,)
-          or not out.is_contiguous()):
-        raise ValueError('sarl_state_values: out must be a contiguous float32 [%d] tensor on %s' % (n, self.device))
-    s = self._dev(state8, torch.float64, shape)
-    th = None if theta is None else self._dev(theta, torch.float64, tshape)
-    check(self._lib.cn_sarl_state_values(self._h, _ptr(s), _ptr(th), n, int(bool(sort_humans)), _ptr(out)))
-    in_place = torch.is_tensor(state8) and s.data_ptr() == state8.data_ptr()
-    if not in_place or (th is not None and not (torch.is_tensor(theta) and th.data_ptr() == theta.data_ptr())):
-        self.sync()  # a temporary copy
-    return out
-
-
-BatchedCrowdSim.sarl_values = _sarl_values
-BatchedCrowdSim.sarl_state_values = _sarl_state_values
-BatchedCrowdSim.sarl_sampler = _sarl_sampler
-BatchedCrowdSim.sarl_configure = _sarl_configure
-BatchedCrowdSim.sarl_set_weights = _sarl_set_weights
-BatchedCrowdSim.sarl_select = _sarl_select
-BatchedCrowdSim.sarl_export = _sarl_export
-BatchedCrowdSim.sarl_explore = _sarl_explore
-BatchedCrowdSim.sarl_transform = _sarl_transform
+    def sarl_state_values(self, state8, theta=None, sort_humans=False, out=None):
+        """V(state) of joint states the caller holds in the env layout (cn_sarl_state_values): state8 float64 [n, A, 8] — get_state()'s
+        rows, a rollout trace's, lookahead()'s final_state8; any leading axes [..., A, 8] are flattened — and theta float64 [n] (or the
+        same leading axes), the robot heading, required for a unicycle robot and ignored otherwise -> float32 [n], under the weights
+        of the last sarl_set_weights.  The rows are sarl_transform's (sort_humans as there; False = env order).  Any n >= 1, through
+        the engine's own network kernels in passes of num_envs x n_actions; the engine's env state is not touched, the buffers
+        sarl_export reads may be overwritten.  Contiguous float64 tensors on the engine's device are read in place; anything else is
+        copied and the call synchronises."""
+        shape = tuple(getattr(state8, 'shape', np.shape(state8)))
+        if len(shape) < 3 or shape[-2:] != (self.A, 8):
+            raise ValueError('sarl_state_values: state8 must be [n, %d, 8] (or [..., %d, 8]), got %s' % (self.A, self.A, shape))
+        n = int(np.prod(shape[:-2], dtype=np.int64))
+        tshape = None
+        if theta is not None:
+            tshape = tuple(getattr(theta, 'shape', np.shape(theta)))
+            if int(np.prod(tshape, dtype=np.int64)) != n or (len(tshape) != 1 and tshape != shape[:-2]):
+                raise ValueError('sarl_state_values: theta must be [%d] or %s, got %s' % (n, shape[:-2], tshape))
+        if out is None:
+            out = self._new((n,), torch.float32)
+        elif not self._dense(out, torch.float32, (n,)):
+            raise ValueError('sarl_state_values: out must be a contiguous float32 [%d] tensor on %s' % (n, self.device))
+        s, temporary_s = self._borrow(state8, torch.float64, shape)
+        th, temporary_th = self._borrow(theta, torch.float64, tshape)
+        check(self._lib.cn_sarl_state_values(self._h, _ptr(s), _ptr(th), n, int(bool(sort_humans)), _ptr(out)))
+        self._release(temporary_s, temporary_th)
+        return out
