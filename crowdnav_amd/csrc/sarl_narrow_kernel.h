@@ -171,6 +171,7 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
     }
     int* hc = reinterpret_cast<int*>(vbuf + kSarlThreads);  // [16] humans present in the tile's groups (H unless the `mixed` rule)
     int* const hl = hc + kSarlGroups;                       // [16] cn_sarl_sample_step: the group's env is still sampling
+    int* const row_om = hl + kSarlGroups;                   // [16] (occupancy maps) where a row's map starts in `om`: wave 0's `wrow`, idle until the softmax
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int H = C.H, GT = kSarlGroups / H, rows = GT * H;
     // cn_sarl_sample_step on the two-launch route: an env whose episode is over (alive[b] && !done[b] is false: the flags as the
@@ -205,7 +206,10 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
     // every word of LDS starts finite (k padding meets zero weights); meanwhile the tile's rows of X in registers
     {
         f32x4* z = reinterpret_cast<f32x4*>(lds);
-        for (int i = tid; i < (int)(vbuf - lds) / 4; i += kNarrowThreads) z[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        // ... vbuf included: narrow_k_loop reads 15 / 20 / 25 / 40 k-steps whatever the layer's kpad, so behind a last buffer (mbuf;
+        // LSTM: kbuf) of fewer k-steps — any network narrower than the shipped ones — it runs on through sbuf into up to 9 k-steps
+        // of vbuf, where words left by whatever held this LDS before would meet the zero weights as NaN
+        for (int i = tid; i < (int)(vbuf + kSarlThreads - lds) / 4; i += kNarrowThreads) z[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     double my_reward = 0.0;
     const bool head_lane = wave == kNarrowWaves - 1 && lane < GT && tile * GT + lane < (size_t)n_groups;
@@ -232,8 +236,8 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
             hc[g] = present;
             hl[g] = (row_valid && (D.x_rows != nullptr || sampling((int)(G / C.n_actions)))) ? 1 : 0;
         }
-        // (occupancy maps) where this row's map starts in `om`; vbuf is not part of the zeroed region
-        if (om != nullptr) reinterpret_cast<int*>(vbuf)[tid] = row_valid ? (int)(((G / C.n_actions) * H + h) * (size_t)(D.in_dim - 13)) : -1;
+        // (occupancy maps) where this row's map starts in `om`
+        if (om != nullptr) row_om[tid] = row_valid ? (int)(((G / C.n_actions) * H + h) * (size_t)(D.in_dim - 13)) : -1;
     }
     lds_barrier();
     CN_SARL_TICK(0);
@@ -250,11 +254,10 @@ __global__ __launch_bounds__(kNarrowThreads) void sarl_narrow_kernel(SarlNetRef 
     if (om != nullptr) {
         // occupancy maps (multi_human_rl.py:46-49): columns 13.. of a row are its human's map among the humans' NEXT states —
         // the same for every action of the env (sarl_lookahead_kernel or the previous call's sarl_decide_step_kernel wrote
-        // them).  Four consecutive cells per thread (one 16-byte load), the row's offset into `om` from its own thread (vbuf)
+        // them).  Four consecutive cells per thread (one 16-byte load), the row's offset into `om` from its own thread (row_om)
         // A row of `om` starts at a multiple of `extra` floats: 16-byte aligned for every row only when the map width is a multiple
         // of four (16 x 3 at the shipped size).  Any other width takes the scalar loop for the whole row.
         const int extra = D.in_dim - 13, quads = (extra & 3) == 0 ? extra >> 2 : 0, rest = extra - 4 * quads;
-        const int* row_om = reinterpret_cast<const int*>(vbuf);
         for (int i = tid; i < rows * quads; i += kNarrowThreads) {
             const int r = i / quads, q = i - r * quads;
             const int base = row_om[r];

@@ -335,7 +335,12 @@ enum { CN_PRECISION_F32 = 0, CN_PRECISION_F16X2 = 1 };
  * group's activations for all humans plus the pipelined side buffer, 4 x 64 x (H (ks_a + ks_b + ks_c + 4) + ks_b + 3 ks_a) bytes,
  * ks = the widest layer of each buffer in 4-column steps — exceeds the 160 KiB of LDS streams the humans through in chunks
  * instead (at 5 humans: a first mlp1 / mlp3 layer wider than 160); under the `mixed` rule, whose one-tile kernel masks absent
- * humans, such a network is CN_ERR_UNSUPPORTED. */
+ * humans, such a network is CN_ERR_UNSUPPORTED.
+ * What "free" ends at, each CN_ERR_UNSUPPORTED with its reason (tests/test_net_widths.py): a layer of more than 1020 inputs or
+ * 4080 outputs (the packed descriptors hold 255 k-steps and 255 column tiles); a network beyond the 16 MiB weight arena; a
+ * network whose STREAMED form — five humans at a time, 4 x (64 x (5 (ks_a + ks_b + ks_c + 4) + ks_b + 2 ks_a + ks_c + 1) + 1024)
+ * bytes — exceeds the 160 KiB as well (mlp1 272,100 in front of the shipped layers does: 202 496 B); CN_MODEL_CADRL, which
+ * streams only beyond 8 humans, when 4 x 64 x H (ks_a + ks_b + 4) does (mlp_dims 272,100,36,1 at 8 humans). */
 int cn_sarl_configure(cn_engine* e, const cn_sarl_config* cfg, const double* actions_host);
 /* replaces model.load_state_dict: params_host_array = HOST array of 22 DEVICE pointers to the float32 tensors of
  * sarl.ValueNetwork.state_dict() in its own order (mlp1.0.weight, mlp1.0.bias, mlp1.2.*, mlp2.0.*, mlp2.2.*,
