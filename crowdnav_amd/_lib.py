@@ -25,6 +25,8 @@ SARL_ROUTES = ('lds_tile', 'lds_chunked', 'narrow', 'reg_sarl', 'reg_sarl_chunk'
                'split_f16')  # CN_SARL_ROUTE_*
 PRECISIONS = ('f32', 'f16x2')  # CN_PRECISION_*
 FLAG_ASYNC_SCENARIO_FILL = 1
+HUMANS_ORCA, HUMANS_CONSTANT_VELOCITY = 0, 1  # CN_HUMANS_*
+HUMAN_MODELS = ('orca', 'constant_velocity')
 
 
 class CrowdNavAmdError(RuntimeError):
@@ -170,6 +172,9 @@ SYMBOLS = {
     'cn_rollout_actions': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, _P, C.POINTER(CnTraceOut)]),
     # K candidate action sequences per env scored from the current state, engine untouched (no version bump)
     'cn_lookahead_actions': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut)]),
+    # how the humans of a lookahead's branches move: ORCA (default) or constant velocity (no version bump)
+    'cn_lookahead_set_human_model': (C.c_int, [_P, C.c_int]),
+    'cn_lookahead_get_human_model': (C.c_int, [_P, C.POINTER(C.c_int)]),
     # V of joint states the caller holds in the env layout, and the lookahead that bootstraps with it (no version bump)
     'cn_sarl_state_values': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
     'cn_lookahead_values': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),

@@ -210,7 +210,7 @@ class CrowdSim(_Base):
     def onestep_lookahead(self, action):
         return self.step(action, update=False)
 
-    def lookahead(self, sequences, policy=None):
+    def lookahead(self, sequences, policy=None, human_model=None):
         """The n-step sibling of onestep_lookahead: K candidate sequences of n actions each (a list of K lists of n ActionXY /
         ActionRot), every one played from the CURRENT state by the transitions step() would make, until done or n steps,
         in one launch and without changing the env.  Returns K tuples (discounted return, info, steps): the return is
@@ -220,7 +220,11 @@ class CrowdSim(_Base):
         With a value-network policy (SARL / CADRL / LstmRL, configured and uploaded as for sarl_action) the tuples are (return,
         info, steps, score): score = return + gamma^(steps * time_step * v_pref) * V(state after the last transition), the n-step
         return the policy's own decision is the one-step case of; a sequence that ended scores its return alone.  LSTM-RL's rows
-        are ordered as its replay memory holds them (humans by decreasing distance)."""
+        are ordered as its replay memory holds them (humans by decreasing distance).
+        human_model: 'orca' or 'constant_velocity' sets the engine's lookahead human model first (and it stays set: see
+        BatchedCrowdSim.set_lookahead_human_model); None leaves the engine's setting alone."""
+        if human_model is not None:
+            self._eng.set_lookahead_human_model(human_model)
         unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
         sequences = [list(seq) for seq in sequences]
         if not sequences or not sequences[0] or any(len(seq) != len(sequences[0]) for seq in sequences):

@@ -16,6 +16,7 @@
 #include "scenario_ring_host.h"
 #include "rollout_fused.h"
 #include "records_kernels.h"
+#include "lookahead_cv_kernel.h"
 
 thread_local char cn_g_err[512] = "";
 
@@ -726,7 +727,8 @@ int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const
 // K candidate sequences of n_steps actions per env, scored from the envs' current state in one launch of
 // rollout_lookahead_kernel over B K virtual envs.  Not a rollout call: no io block, no ScenarioRing::around_launch (the ring is
 // neither read nor filled, a pending lagged fill stays pending), no launch counter.  What depends on the arguments alone is
-// refused first, then what depends on the engine; nothing is enqueued before the last check.
+// refused first, then what depends on the engine; nothing is enqueued before the last check.  Under
+// CN_HUMANS_CONSTANT_VELOCITY (cn_lookahead_set_human_model) the one launch is lookahead_cv_kernel's instead.
 int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out) {
     int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);
     if (rc || n_steps == 0) return rc;
@@ -737,6 +739,23 @@ int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const doub
         CN_HIP(hipMemcpyAsync(e->look_dev, &e->look_host, sizeof(*out), hipMemcpyHostToDevice, e->stream));
         e->look_valid = true;
     }
+    if (e->look_human_model == CN_HUMANS_CONSTANT_VELOCITY) {  // lookahead_cv_kernel.h: lane = branch, no ORCA
+        const cn::Params& P = e->P;
+        cn::CvParams C{};
+        C.B = P.B, C.K = n_candidates, C.A = P.A, C.n_steps = n_steps;
+        C.chunks = (n_candidates + cn::kWave - 1) / cn::kWave;
+        C.discount_len = e->discount_len, C.discount = e->discount;
+        C.dt = P.dt, C.time_limit = P.time_limit, C.success_reward = P.success_reward, C.collision_penalty = P.collision_penalty;
+        C.discomfort_dist = P.discomfort_dist, C.discomfort_factor = P.discomfort_factor;
+        C.pos = e->S.pos, C.vel = e->S.vel, C.goal = e->S.goal, C.rv = e->S.rv, C.gtime = e->S.gtime, C.theta = e->S.theta;
+        // B * chunks <= B * K workgroups: within an int (cn_lookahead_check)
+        pick_bool(P.robot_unicycle, [&](auto uni) {
+            hipLaunchKernelGGL((cn::lookahead_cv_kernel<decltype(uni)::value>), dim3((unsigned)P.B * (unsigned)C.chunks),
+                               dim3(cn::kWave), 0, e->stream, C, actions, (const cn_lookahead_out*)e->look_dev);
+        });
+        CN_HIP(hipGetLastError());
+        return CN_OK;
+    }
     cn::Params Pv = e->P;
     Pv.B = (int)virtual_envs;
     const cn::RolloutView R{nullptr, e->discount, e->discount_len};
@@ -746,6 +765,23 @@ int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const doub
                            n_steps, actions, (const cn_lookahead_out*)e->look_dev, n_candidates);
     });
     CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// how the humans of a lookahead's branches move: a host-side setting of the engine, nothing of the device is touched
+int cn_lookahead_set_human_model(cn_engine* e, int model) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_set_human_model: engine is NULL");
+    if (model != CN_HUMANS_ORCA && model != CN_HUMANS_CONSTANT_VELOCITY)
+        return fail(CN_ERR_INVALID, "cn_lookahead_set_human_model: model %d unknown (CN_HUMANS_ORCA = 0, "
+                    "CN_HUMANS_CONSTANT_VELOCITY = 1)", model);
+    e->look_human_model = model;
+    return CN_OK;
+}
+
+int cn_lookahead_get_human_model(const cn_engine* e, int* model_host) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_get_human_model: engine is NULL");
+    if (!model_host) return fail(CN_ERR_INVALID, "cn_lookahead_get_human_model: model_host is NULL");
+    *model_host = e->look_human_model;
     return CN_OK;
 }
 

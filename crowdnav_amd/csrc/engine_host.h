@@ -92,6 +92,7 @@ struct cn_engine {
     cn_lookahead_out look_host{};          // last cn_lookahead_out uploaded to look_dev (look_valid: there is one)
     cn_lookahead_out* look_dev = nullptr;  // device copy rollout_lookahead_kernel stores through
     bool look_valid = false;
+    int look_human_model = CN_HUMANS_ORCA;  // cn_lookahead_set_human_model: read by cn_lookahead_actions and by nothing else
     ScenarioRing ring;
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one

@@ -394,7 +394,9 @@ class BatchedCrowdSim(object):
             score float64  ret + gamma^(steps dt v_pref) * value — the n-step return; a branch that ended (REACH_GOAL / COLLISION /
                            TIMEOUT) gets no bootstrap: score = ret
         sort_humans: the humans of the network's rows by decreasing distance to the robot (LSTM-RL's replay-memory order), as
-        in sarl_transform; False = env order.  The buffers sarl_export reads may be overwritten."""
+        in sarl_transform; False = env order.  The buffers sarl_export reads may be overwritten.
+        The humans of the branches move by the engine's lookahead_human_model: through ORCA unless set_lookahead_human_model said
+        'constant_velocity'."""
         shape = tuple(getattr(actions, 'shape', np.shape(actions)))
         if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:
             raise ValueError('lookahead: actions must be [%d, K >= 1, n, 2], got %s' % (self.B, shape))
@@ -417,6 +419,22 @@ class BatchedCrowdSim(object):
             self._release(temporary)
         return out
 
+    def set_lookahead_human_model(self, model):
+        """How the humans of a lookahead's branches move (cn_lookahead_set_human_model): 'orca' (the default: they react through
+        ORCA, which knows their goals) or 'constant_velocity' (every human keeps its current velocity — what a planner fed
+        observed positions and velocities can assume; one lane per branch instead of one wave, no ORCA).  Read by lookahead()
+        and the plan_* calls that score through it; step(), the rollout calls and the real step inside plan_rollout stay ORCA."""
+        if model not in _lib.HUMAN_MODELS:
+            raise ValueError('lookahead human model: one of %s, got %r' % (_lib.HUMAN_MODELS, model))
+        check(self._lib.cn_lookahead_set_human_model(self._h, _lib.HUMAN_MODELS.index(model)))
+
+    @property
+    def lookahead_human_model(self):
+        """'orca' or 'constant_velocity' (cn_lookahead_get_human_model)."""
+        model = C.c_int()
+        check(self._lib.cn_lookahead_get_human_model(self._h, C.byref(model)))
+        return _lib.HUMAN_MODELS[model.value]
+
     # ---------------------------------------------------------------- device CEM planner (cn_plan_*)
     def plan_begin(self, K, n, elites, iterations, init_std, min_std=0.0, smoothing=0.0, seed=0, bootstrap=False,
                    sort_humans=False):
@@ -427,7 +445,8 @@ class BatchedCrowdSim(object):
             candidates float64 [B, K, n, 2]; order int32 [B, K] (candidate index at rank r)
             look: the dict lookahead() returns, rows of the last iteration (with bootstrap: final state, value, score too)
         mean starts at zero and std at init_std: call plan_reset() for the goal-directed prior.  Holonomic ROBOT_EXTERNAL
-        engines; the settings are checked by the first call that uses the plan."""
+        engines; the settings are checked by the first call that uses the plan.  The planner's candidates are scored under the
+        engine's lookahead_human_model (set_lookahead_human_model), as it stands when each plan_* call is made."""
         K, n = int(K), int(n)
         if K < 1 or n < 1:
             raise ValueError('plan_begin: K and n must be >= 1')

@@ -19,7 +19,11 @@ the next step — one plan_rollout call per chunk of steps, with no host work in
 
 --mppi is the same loop with the other update (cn_plan_mppi_rollout): every candidate weighted by
 exp((score - best score) / T), the mean moved to the weighted mean and its first row taken as the action; the sampling deviation
-stays at --init-std."""
+stays at --init-std.
+
+--human-model constant_velocity (every mode) scores the candidates with humans that keep their current
+velocity instead of reacting through ORCA (set_lookahead_human_model): what a planner outside the simulator can assume.  The
+real steps stay the simulator's."""
 import argparse
 import logging
 import os
@@ -60,7 +64,7 @@ def load_policy(model_dir, name):
 CEM_CHUNK = 16  # real steps per plan_rollout call: how often the host looks whether every case has ended
 
 
-def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None):
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, human_model='orca'):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -70,6 +74,7 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None):
         robot.kinematics = 'holonomic'
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
+    eng.set_lookahead_human_model(human_model)
     space, _, _ = build_action_space(robot.v_pref)
     rank_by, extra = 'ret', {}
     if policy is not None:  # rank by the bootstrapped n-step return instead
@@ -132,13 +137,15 @@ def main():
     ap.add_argument('--elites', type=int, default=4, help='--cem: E, candidates the distribution is refitted to')
     ap.add_argument('--iterations', type=int, default=3, help='--cem / --mppi: I, draw / score / update rounds per real step')
     ap.add_argument('--init-std', type=float, default=0.5, help='--cem / --mppi: standard deviation a step starts from, in units of v_pref')
+    ap.add_argument('--human-model', default='orca', choices=['orca', 'constant_velocity'],
+                    help="how the humans move in the planner's lookahead (the real steps are always ORCA)")
     args = ap.parse_args()
     policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
     cem = None
     if args.cem or args.mppi:
         cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std,
                    temperature=args.temperature if args.mppi else None)
-    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem))
+    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem, human_model=args.human_model))
     return 0
 
 

@@ -602,6 +602,54 @@ int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const doub
                          const cn_lookahead_out* out);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Lookahead human model (no version bump: two new symbols; CN_LAUNCH_COUNTERS keeps its length).  How the humans of a
+ * lookahead's branches move.  CN_HUMANS_ORCA (what cn_create installs): they react through ORCA, which reads every human's goal
+ * — right inside this simulator, where the humans ARE ORCA.  CN_HUMANS_CONSTANT_VELOCITY: every human keeps the velocity it
+ * has, the standard model of a planner fed observed positions and velocities; the reference's `[action_space] query_env =
+ * false` (multi_human_rl.py:37-41, cadrl.py:104-110) carried from the one-step decision to the n-step lookahead.
+ * A per-engine setting, read by cn_lookahead_actions and by everything that reaches a lookahead through it —
+ * cn_lookahead_values, cn_plan_cem, cn_plan_rollout, cn_plan_mppi, cn_plan_mppi_rollout — and by nothing else: cn_step, every
+ * cn_rollout_* call (the cn_rollout_step inside cn_plan_rollout / cn_plan_mppi_rollout too: the real step of a planner's closed
+ * loop stays ORCA, only its model of the future changes) and cn_sarl_select do not look at it; cn_reset and the rollout calls
+ * do not change it.  cn_lookahead_actions' refusals are the same under either model, in the same order, with the same messages. */
+enum { CN_HUMANS_ORCA = 0, CN_HUMANS_CONSTANT_VELOCITY = 1 };
+/* Refused before anything is touched: NULL e: CN_ERR_INVALID; a model that is neither value: CN_ERR_INVALID naming it. */
+int cn_lookahead_set_human_model(cn_engine* e, int model);
+/* NULL e or model_host: CN_ERR_INVALID. */
+int cn_lookahead_get_human_model(const cn_engine* e, int* model_host);
+/* Under CN_HUMANS_CONSTANT_VELOCITY branch (b, k) is the branch described above — the same start state, action rows, stop at
+ * the first `done`, outputs, and nothing of the engine written — made of cn_step(update=1)'s transition with ONE substitution:
+ * the velocity a human "chooses" is its own current float64 velocity (vx, vy), unrounded (under ORCA: the float32 ORCA result
+ * widened to double).  All float64, every product and sum a separate IEEE operation in the order written, so that a host
+ * restatement is bit-exact (a unicycle's cos / sin excepted: they are the device libm's).  Per step of a running branch, with
+ * (px, py) the robot, dt = time_step, and t the transitions the branch has made:
+ *   robot action   as under ORCA.  Holonomic: (ax, ay) = the row.  CN_UNICYCLE: row (v, r), th = theta + r,
+ *                  (ax, ay) = (v cos(r + theta), v sin(r + theta)) for the collision test; the heading is carried.
+ *   human slots    1 .. A - 1, every one, the parked placeholders of the `mixed` rule included: with (hx, hy), (hvx, hvy), r_h
+ *                  the human's position, velocity and radius,
+ *                    x1 = hx - px, y1 = hy - py, wx = hvx - ax, wy = hvy - ay, x2 = x1 + wx dt, y2 = y1 + wy dt,
+ *                    sx = x2 - x1, sy = y2 - y1, u = clamp(((0 - x1) sx + (0 - y1) sy) / (sx sx + sy sy), 0, 1),
+ *                    (cx, cy) = sx == 0 && sy == 0 ? (0 - x1, 0 - y1) : ((x1 + u sx) - 0, (y1 + u sy) - 0),
+ *                    c = sqrt(fma(cy, cy, cx cx)) - r_h - r_robot        (the one fused operation)
+ *   scan           in slot order: hit = c < 0; dmin = the smallest c seen BEFORE the first hit (infinity if none).
+ *   robot end      holonomic (ex, ey) = (px + ax dt, py + ay dt); unicycle (px + cos(th) v dt, py + sin(th) v dt), products
+ *                  left to right; reaching = sqrt(fma(ey - gy, ey - gy, (ex - gx) (ex - gx))) < r_robot.
+ *   outcome        global_time >= time_limit - 1: Timeout, reward 0; else a hit: Collision, collision_penalty; else reaching:
+ *                  ReachGoal, success_reward; else dmin < discomfort_dist: Danger, (dmin - discomfort_dist) *
+ *                  discomfort_penalty_factor * dt, goes on; else Nothing, 0, goes on.
+ *   book           ret <- ret + table[t] * reward (cn_set_gamma's table; 0 beyond its end), steps <- t + 1,
+ *                  global_time <- global_time + dt.
+ *   moves          robot <- (ex, ey), its velocity (ax, ay) — unicycle: theta <- python's th % (2 pi), velocity
+ *                  (v cos(theta), v sin(theta)).  Human: hx <- hx + hvx dt, hy <- hy + hvy dt, one multiply and one add each,
+ *                  sequential from step to step (never p0 + t dt v); its velocity, goal, radius and v_pref stay.
+ * final_state8 / final_theta: the state after the branch's last transition, as under ORCA.  Neither robot_visible, the safety
+ * spaces, max_neighbors, the kd-tree rows nor the humans' goals are read (the goals are copied into final_state8).
+ * With n = 1 this is NOT cn_sarl_select's constant_velocity_model reward: that one is compute_reward on END positions
+ * (multi_human_rl.py:65-90), this one the environment's SWEPT test — the environment's transition with the humans' policy
+ * replaced, so `ret` means what it means under ORCA.  Humans do not stop at their goals.
+ * One launch of a kernel of its own (lane = branch, the humans of an env shared by its K branches), not counted either. */
+
+/* ------------------------------------------------------------------------------------------------------
  * Value-bootstrapped lookahead (no version bump: new symbols only).  The n-step return a value-network policy means,
  *   score = sum_{t<n} gamma^(t dt v_pref) r_t + gamma^(n dt v_pref) V(s_n)
  * (MultiHumanRL.predict, multi_human_rl.py:52, is n = 1; Explorer.update_memory's TD targets train V to mean it), needs V of
