@@ -190,6 +190,11 @@ SYMBOLS = {
     'cn_plan_mppi': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_double, C.c_int, C.c_uint32]),
     'cn_plan_mppi_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.c_double,
                                        C.c_int, C.c_uint32]),
+    # the lookaheads and the planning steps against caller-predicted human velocities [B][n][A - 1][2] (no version bump)
+    'cn_lookahead_paths': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(CnLookaheadOut)]),
+    'cn_lookahead_paths_values': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),
+    'cn_plan_cem_paths': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), _P, C.c_uint32]),
+    'cn_plan_mppi_paths': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), _P, C.c_double, C.c_int, C.c_uint32]),
 }
 
 _lib = None

@@ -242,6 +242,32 @@ class CrowdSim(_Base):
         ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
         return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
 
+    def lookahead_paths(self, sequences, human_velocities, policy=None):
+        """lookahead() against predicted human motion (BatchedCrowdSim.lookahead_paths): human_velocities[t][h] is the (vx, vy)
+        human h takes during step t of the horizon — n rows of one pair per human, anything np.asarray reads as [n, humans, 2]
+        (crowdnav_amd.predict makes them; the [0] of its result for this env).  The engine's lookahead human model is neither
+        read nor changed.  Returns what lookahead() returns."""
+        unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
+        sequences = [list(seq) for seq in sequences]
+        if not sequences or not sequences[0] or any(len(seq) != len(sequences[0]) for seq in sequences):
+            raise ValueError('lookahead_paths: K >= 1 sequences of one length n >= 1 are required')
+        for seq in sequences:
+            for action in seq:
+                self._check_action(action, unicycle)
+        table = np.array([[[list(a) for a in seq] for seq in sequences]], dtype=np.float64)  # [1, K, n, 2]
+        vel = np.asarray(human_velocities, dtype=np.float64)
+        if vel.shape != (len(sequences[0]), self.human_num, 2):
+            raise ValueError('lookahead_paths: human_velocities must be [n = %d, %d humans, 2], got %s'
+                             % (len(sequences[0]), self.human_num, vel.shape))
+        if policy is not None:
+            eng = self._sarl_engine(policy)
+            out = eng.lookahead_paths(table, vel[None], bootstrap=True, sort_humans=eng.sarl['model'] == 'lstm_rl')
+            ret, info, steps, score = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps', 'score'))
+            return [(float(r), info_from_code(i), int(s), float(v)) for r, i, s, v in zip(ret, info, steps, score)]
+        out = self._eng.lookahead_paths(table, vel[None])
+        ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
+        return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
+
     @staticmethod
     def _check_action(action, unicycle):
         if not isinstance(action, tuple) or not hasattr(action, 'v' if unicycle else 'vx'):

@@ -76,6 +76,30 @@ int cn_lookahead_check(const cn_engine* e, int n_steps, int n_candidates, const 
     return CN_OK;
 }
 
+// the device copy of a lookahead's cn_lookahead_out: uploaded when it differs from the last one (ordered on the engine's
+// stream, as upload_io)
+static int upload_look(cn_engine* e, const cn_lookahead_out* out) {
+    if (!e->look_valid || std::memcmp(&e->look_host, out, sizeof(*out)) != 0) {
+        e->look_host = *out;
+        CN_HIP(hipMemcpyAsync(e->look_dev, &e->look_host, sizeof(*out), hipMemcpyHostToDevice, e->stream));
+        e->look_valid = true;
+    }
+    return CN_OK;
+}
+
+// what lookahead_cv_kernel and lookahead_paths_kernel read of the engine
+static cn::CvParams cv_params(const cn_engine* e, int n_steps, int n_candidates) {
+    const cn::Params& P = e->P;
+    cn::CvParams C{};
+    C.B = P.B, C.K = n_candidates, C.A = P.A, C.n_steps = n_steps;
+    C.chunks = (n_candidates + cn::kWave - 1) / cn::kWave;
+    C.discount_len = e->discount_len, C.discount = e->discount;
+    C.dt = P.dt, C.time_limit = P.time_limit, C.success_reward = P.success_reward, C.collision_penalty = P.collision_penalty;
+    C.discomfort_dist = P.discomfort_dist, C.discomfort_factor = P.discomfort_factor;
+    C.pos = e->S.pos, C.vel = e->S.vel, C.goal = e->S.goal, C.rv = e->S.rv, C.gtime = e->S.gtime, C.theta = e->S.theta;
+    return C;
+}
+
 extern "C" {
 
 const char* cn_last_error(void) { return cn_g_err; }
@@ -732,25 +756,13 @@ int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const
 int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out) {
     int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);
     if (rc || n_steps == 0) return rc;
-    if ((rc = bind(e))) return rc;
+    if ((rc = bind(e)) || (rc = upload_look(e, out))) return rc;
     const uint64_t virtual_envs = (uint64_t)e->P.B * (uint64_t)n_candidates;
-    if (!e->look_valid || std::memcmp(&e->look_host, out, sizeof(*out)) != 0) {  // (ordered on the engine's stream, as upload_io)
-        e->look_host = *out;
-        CN_HIP(hipMemcpyAsync(e->look_dev, &e->look_host, sizeof(*out), hipMemcpyHostToDevice, e->stream));
-        e->look_valid = true;
-    }
     if (e->look_human_model == CN_HUMANS_CONSTANT_VELOCITY) {  // lookahead_cv_kernel.h: lane = branch, no ORCA
-        const cn::Params& P = e->P;
-        cn::CvParams C{};
-        C.B = P.B, C.K = n_candidates, C.A = P.A, C.n_steps = n_steps;
-        C.chunks = (n_candidates + cn::kWave - 1) / cn::kWave;
-        C.discount_len = e->discount_len, C.discount = e->discount;
-        C.dt = P.dt, C.time_limit = P.time_limit, C.success_reward = P.success_reward, C.collision_penalty = P.collision_penalty;
-        C.discomfort_dist = P.discomfort_dist, C.discomfort_factor = P.discomfort_factor;
-        C.pos = e->S.pos, C.vel = e->S.vel, C.goal = e->S.goal, C.rv = e->S.rv, C.gtime = e->S.gtime, C.theta = e->S.theta;
+        const cn::CvParams C = cv_params(e, n_steps, n_candidates);
         // B * chunks <= B * K workgroups: within an int (cn_lookahead_check)
-        pick_bool(P.robot_unicycle, [&](auto uni) {
-            hipLaunchKernelGGL((cn::lookahead_cv_kernel<decltype(uni)::value>), dim3((unsigned)P.B * (unsigned)C.chunks),
+        pick_bool(e->P.robot_unicycle, [&](auto uni) {
+            hipLaunchKernelGGL((cn::lookahead_cv_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
                                dim3(cn::kWave), 0, e->stream, C, actions, (const cn_lookahead_out*)e->look_dev);
         });
         CN_HIP(hipGetLastError());
@@ -763,6 +775,24 @@ int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const doub
         hipLaunchKernelGGL((cn::rollout_lookahead_kernel<decltype(maxl)::value, decltype(uni)::value, decltype(kd)::value>),
                            dim3((Pv.B + Pv.E - 1) / Pv.E), dim3(Pv.threads), e->smem, e->stream, Pv, (const cn::StateView*)e->S_dev, R,
                            n_steps, actions, (const cn_lookahead_out*)e->look_dev, n_candidates);
+    });
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// The lookahead whose humans take the velocities the caller predicts: lookahead_paths_kernel (lookahead_cv_kernel.h), the
+// constant-velocity kernel's lane body with human_vel[b][t][h] as the velocity a human chooses at step t.  cn_lookahead_actions' checks,
+// upload and "nothing of the engine changes"; the engine's human-model setting is neither read nor written.
+int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candidates, const double* actions, const double* human_vel,
+                       const cn_lookahead_out* out) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_lookahead_paths: human_vel is NULL");
+    int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);
+    if (rc || n_steps == 0) return rc;
+    if ((rc = bind(e)) || (rc = upload_look(e, out))) return rc;
+    const cn::CvParams C = cv_params(e, n_steps, n_candidates);
+    pick_bool(e->P.robot_unicycle, [&](auto uni) {
+        hipLaunchKernelGGL((cn::lookahead_paths_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
+                           dim3(cn::kWave), 0, e->stream, C, actions, human_vel, (const cn_lookahead_out*)e->look_dev);
     });
     CN_HIP(hipGetLastError());
     return CN_OK;

@@ -1,6 +1,7 @@
 // libcrowdnav_amd.so — the device CEM and MPPI planners (cn_plan_*): host entry points over the kernels of plan_kernels.h.
 //
-// A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values and real steps
+// A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values (the *_paths
+// calls: cn_lookahead_paths / cn_lookahead_paths_values) and real steps
 // made through cn_rollout_step, by their C entry points and therefore with their checks, their scenario-ring fill and their
 // launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior), enqueued on the
 // engine's stream.  Nothing here synchronises, allocates or counts.
@@ -124,14 +125,21 @@ int run_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, c
     return CN_OK;
 }
 
-// One planning step of either planner: draw, score, update, `iterations` times
-int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter, const Mppi* mppi) {
+// One planning step of either planner: draw, score, update, `iterations` times.  human_vel (optional): the candidates are
+// scored by the paths lookahead against the caller's predicted human motion instead of the engine's human model.
+int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter, const Mppi* mppi,
+             const double* human_vel = nullptr) {
+    const int n = cfg->n_steps, K = cfg->n_candidates;
     for (int i = 0; i < cfg->iterations; ++i) {
         int rc = run_draw(e, cfg, plan, counter + (uint32_t)i);
         if (rc) return rc;
-        rc = cfg->bootstrap ? cn_lookahead_values(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look, cfg->sort_humans,
-                                                  plan->value, plan->score)
-                            : cn_lookahead_actions(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
+        if (human_vel)
+            rc = cfg->bootstrap ? cn_lookahead_paths_values(e, n, K, plan->candidates, human_vel, &plan->look, cfg->sort_humans,
+                                                            plan->value, plan->score)
+                                : cn_lookahead_paths(e, n, K, plan->candidates, human_vel, &plan->look);
+        else
+            rc = cfg->bootstrap ? cn_lookahead_values(e, n, K, plan->candidates, &plan->look, cfg->sort_humans, plan->value, plan->score)
+                                : cn_lookahead_actions(e, n, K, plan->candidates, &plan->look);
         if (rc || (rc = mppi ? run_mppi_update(e, cfg, plan, *mppi, i > 0) : run_refit(e, cfg, plan, i > 0))) return rc;
     }
     return CN_OK;
@@ -210,6 +218,22 @@ int cn_plan_mppi(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, doub
     int rc = plan_check(e, cfg, plan, "cn_plan_mppi", &mppi);
     if (rc || (rc = bind(e))) return rc;
     return run_plan(e, cfg, plan, counter, &mppi);
+}
+
+int cn_plan_cem_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const double* human_vel, uint32_t counter) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_plan_cem_paths: human_vel is NULL");
+    int rc = plan_check(e, cfg, plan, "cn_plan_cem_paths");
+    if (rc || (rc = bind(e))) return rc;
+    return run_plan(e, cfg, plan, counter, nullptr, human_vel);
+}
+
+int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const double* human_vel, double temperature,
+                       int fit_std, uint32_t counter) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_plan_mppi_paths: human_vel is NULL");
+    const Mppi mppi{temperature, fit_std};
+    int rc = plan_check(e, cfg, plan, "cn_plan_mppi_paths", &mppi);
+    if (rc || (rc = bind(e))) return rc;
+    return run_plan(e, cfg, plan, counter, &mppi, human_vel);
 }
 
 int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,

@@ -961,16 +961,20 @@ int cn_sarl_state_values(cn_engine* e, const double* state8, const double* theta
     return state_values_run(e, state8, theta, n, sort_humans, value);
 }
 
-int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out,
-                        int sort_humans, float* value, double* score) {
+// cn_lookahead_values and cn_lookahead_paths_values: the extra checks, the lookahead (human_vel == NULL: cn_lookahead_actions,
+// else cn_lookahead_paths), the values of the branch ends, the score
+static int lookahead_values(cn_engine* e, const char* who, int n_steps, int n_candidates, const double* actions,
+                            const double* human_vel, const cn_lookahead_out* out, int sort_humans, float* value, double* score) {
     int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, out);  // cn_lookahead_actions' own checks and messages
     if (rc) return rc;
-    if (!out->final_state8) return fail(CN_ERR_INVALID, "cn_lookahead_values: out->final_state8 is NULL (the caller owns the branch states)");
-    if (!value) return fail(CN_ERR_INVALID, "cn_lookahead_values: value is NULL");
-    if (!score) return fail(CN_ERR_INVALID, "cn_lookahead_values: score is NULL");
-    if ((rc = state_values_check(e, "cn_lookahead_values", out->final_theta != nullptr))) return rc;
+    if (!out->final_state8) return fail(CN_ERR_INVALID, "%s: out->final_state8 is NULL (the caller owns the branch states)", who);
+    if (!value) return fail(CN_ERR_INVALID, "%s: value is NULL", who);
+    if (!score) return fail(CN_ERR_INVALID, "%s: score is NULL", who);
+    if ((rc = state_values_check(e, who, out->final_theta != nullptr))) return rc;
     if (n_steps == 0) return CN_OK;
-    if ((rc = cn_lookahead_actions(e, n_steps, n_candidates, actions, out))) return rc;
+    if ((rc = human_vel ? cn_lookahead_paths(e, n_steps, n_candidates, actions, human_vel, out)
+                        : cn_lookahead_actions(e, n_steps, n_candidates, actions, out)))
+        return rc;
     const int64_t branches = (int64_t)e->P.B * n_candidates;
     if ((rc = state_values_run(e, out->final_state8, out->final_theta, branches, sort_humans, value))) return rc;
     hipLaunchKernelGGL(cn::lookahead_score_kernel, dim3((unsigned)((branches + 255) / 256)), dim3(256), 0, e->stream, (size_t)branches,
@@ -978,6 +982,17 @@ int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const doubl
                        (const double*)e->discount, e->discount_len, score);
     CN_HIP(hipGetLastError());
     return CN_OK;
+}
+
+int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_lookahead_out* out,
+                        int sort_humans, float* value, double* score) {
+    return lookahead_values(e, "cn_lookahead_values", n_steps, n_candidates, actions, nullptr, out, sort_humans, value, score);
+}
+
+int cn_lookahead_paths_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, const double* human_vel,
+                              const cn_lookahead_out* out, int sort_humans, float* value, double* score) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_lookahead_paths_values: human_vel is NULL");
+    return lookahead_values(e, "cn_lookahead_paths_values", n_steps, n_candidates, actions, human_vel, out, sort_humans, value, score);
 }
 
 int cn_sarl_export(cn_engine* e, int which, void* dst, uint64_t bytes) {

@@ -397,26 +397,49 @@ class BatchedCrowdSim(object):
         in sarl_transform; False = env order.  The buffers sarl_export reads may be overwritten.
         The humans of the branches move by the engine's lookahead_human_model: through ORCA unless set_lookahead_human_model said
         'constant_velocity'."""
+        return self._lookahead('lookahead', actions, None, final_state, out, bootstrap, sort_humans)
+
+    def lookahead_paths(self, actions, human_vel, final_state=False, out=None, bootstrap=False, sort_humans=False):
+        """lookahead() against the human motion the CALLER predicts (cn_lookahead_paths; with bootstrap=True
+        cn_lookahead_paths_values): human_vel [B, n, H, 2] float64 — human_vel[b, t, h] is the velocity human h of env b takes
+        during step t of the horizon, shared by the K branches of env b; zeros for the parked placeholders of the mixed rule.
+        Every branch is the 'constant_velocity' branch with the table as the humans' policy, in step()'s own order: the swept
+        test of step t reads the velocity a human has when the step starts (its state velocity, then human_vel[b, t - 1, h]),
+        the move and final_state8's velocity columns take human_vel[b, t, h].  The table that repeats the state velocity gives
+        the 'constant_velocity' result, velocities recorded from ORCA humans that do not see the robot the 'orca' result, bit
+        for bit; crowdnav_amd.predict builds tables (constant_velocity, to_goal, from_positions).  An argument, not a setting: lookahead_human_model is neither read nor
+        changed.  Everything else — actions, the returned dict, final_state / out / bootstrap / sort_humans, n = 0, what is
+        borrowed and what is copied — as in lookahead().  Non-finite velocities are not checked."""
+        return self._lookahead('lookahead_paths', actions, human_vel, final_state, out, bootstrap, sort_humans)
+
+    def _lookahead(self, who, actions, human_vel, final_state, out, bootstrap, sort_humans):
+        """lookahead() (human_vel None) and lookahead_paths(): shapes, the rows of `out`, the one C call."""
         shape = tuple(getattr(actions, 'shape', np.shape(actions)))
         if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:
-            raise ValueError('lookahead: actions must be [%d, K >= 1, n, 2], got %s' % (self.B, shape))
+            raise ValueError('%s: actions must be [%d, K >= 1, n, 2], got %s' % (who, self.B, shape))
         K, n = int(shape[1]), int(shape[2])
+        if human_vel is not None:
+            vshape = tuple(getattr(human_vel, 'shape', np.shape(human_vel)))
+            if vshape != (self.B, n, self.H, 2):
+                raise ValueError('%s: human_vel must be [%d, n = %d, %d, 2], got %s' % (who, self.B, n, self.H, vshape))
         spec = dict(ret=(torch.float64, (self.B, K)), info=(torch.uint8, (self.B, K)), steps=(torch.int32, (self.B, K)),
                     time=(torch.float64, (self.B, K)))
         if final_state or bootstrap:
             spec.update(final_state8=(torch.float64, (self.B, K, self.A, 8)), final_theta=(torch.float64, (self.B, K)))
         if bootstrap:
             spec.update(value=(torch.float32, (self.B, K)), score=(torch.float64, (self.B, K)))
-        out = self._rows('lookahead', spec, out)
+        out = self._rows(who, spec, out)
         if n > 0:
             a, temporary = self._borrow(actions, torch.float64, (self.B, K, n, 2))
+            v, temporary_v = self._borrow(human_vel, torch.float64, (self.B, n, self.H, 2))
             lo = C.byref(_struct(CnLookaheadOut, out))
+            head = (self._h, n, K, _ptr(a)) + (() if v is None else (_ptr(v),)) + (lo,)
             if bootstrap:
-                check(self._lib.cn_lookahead_values(self._h, n, K, _ptr(a), lo, int(bool(sort_humans)),
-                                                    _ptr(out['value']), _ptr(out['score'])))
+                call = self._lib.cn_lookahead_values if v is None else self._lib.cn_lookahead_paths_values
+                check(call(*head, int(bool(sort_humans)), _ptr(out['value']), _ptr(out['score'])))
             else:
-                check(self._lib.cn_lookahead_actions(self._h, n, K, _ptr(a), lo))
-            self._release(temporary)
+                check((self._lib.cn_lookahead_actions if v is None else self._lib.cn_lookahead_paths)(*head))
+            self._release(temporary, temporary_v)
         return out
 
     def set_lookahead_human_model(self, model):
@@ -516,6 +539,27 @@ class BatchedCrowdSim(object):
         one call.  The engine is left as lookahead() leaves it."""
         self._plan_call('mppi', plan, float(temperature), int(bool(fit_std)), counter=counter)
         return plan
+
+    # ---------------------------------------------------------------- planning against predicted human motion
+    def _plan_paths(self, name, plan, human_vel, *args, counter):
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        v, temporary = self._borrow(human_vel, torch.float64, (self.B, plan.n, self.H, 2))
+        if v is None:
+            raise ValueError('plan_%s: human_vel is required ([%d, %d, %d, 2])' % (name, self.B, plan.n, self.H))
+        self._plan_call(name, plan, _ptr(v), *args, counter=counter)
+        self._release(temporary)
+        return plan
+
+    def plan_cem_paths(self, plan, human_vel, counter):
+        """plan_cem with its candidates scored by lookahead_paths (cn_plan_cem_paths): human_vel [B, n, H, 2] float64, the
+        predicted velocity of every human at every step of the plan's horizon.  There is no rollout form: predict from the state
+        after each real step — plan_cem_paths, rollout_step(plan.action), plan_shift."""
+        return self._plan_paths('cem_paths', plan, human_vel, counter=counter)
+
+    def plan_mppi_paths(self, plan, human_vel, temperature, counter, fit_std=False):
+        """plan_mppi with its candidates scored by lookahead_paths (cn_plan_mppi_paths)."""
+        return self._plan_paths('mppi_paths', plan, human_vel, float(temperature), int(bool(fit_std)), counter=counter)
 
     def plan_mppi_rollout(self, plan, n_real, temperature, counter, fit_std=False):
         """plan_rollout with the MPPI update (cn_plan_mppi_rollout): per step plan_mppi(counter + s * iterations),

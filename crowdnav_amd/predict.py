@@ -1,0 +1,78 @@
+"""Tables of predicted human velocities for BatchedCrowdSim.lookahead_paths / plan_cem_paths / plan_mppi_paths
+(cn_lookahead_paths): human_vel[b, t, h] is the (vx, vy) human h of env b takes during step t of the horizon.
+
+    constant_velocity(state8, n)       every human keeps the velocity it has: the 'constant_velocity' human model as a table
+    to_goal(state8, n, dt)             every human heads straight for its goal at v_pref and stops there
+    from_positions(start_xy, pos, dt)  the velocities that carry the humans through predicted positions
+
+torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
+returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is
+the robot).  Under the `mixed` rule the parked placeholders stand still at their goals with zero velocity, so constant_velocity
+and to_goal give them zeros, as cn_lookahead_paths asks."""
+import numpy as np
+import torch
+
+
+def _f64(x):
+    """(x as a float64 torch tensor, whether the caller gave numpy)."""
+    if torch.is_tensor(x):
+        return x.to(torch.float64), False
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64))), True
+
+
+def _back(t, as_numpy):
+    t = t.contiguous()
+    return t.numpy() if as_numpy else t
+
+
+def _humans(state8):
+    s, as_numpy = _f64(state8)
+    if s.dim() != 3 or s.shape[1] < 2 or s.shape[2] != 8:
+        raise ValueError('state8 must be [B, A >= 2, 8], got %s' % (tuple(s.shape),))
+    return s[:, 1:], as_numpy
+
+
+def constant_velocity(state8, n):
+    """human_vel[b, t, h] = the human's state velocity for every t: lookahead_paths then gives, bit for bit, what lookahead()
+    gives under set_lookahead_human_model('constant_velocity')."""
+    humans, as_numpy = _humans(state8)
+    n = int(n)
+    if n < 0:
+        raise ValueError('n must be >= 0')
+    return _back(humans[:, None, :, 2:4].expand(-1, n, -1, -1).clone(), as_numpy)
+
+
+def to_goal(state8, n, dt):
+    """Every human walks straight towards its goal at its v_pref and stops there.  Per step, with d = goal - p and dist = |d|:
+    dist == 0: (0, 0); dist <= v_pref dt: d / dt, the shortened last step that lands on the goal; else (d / dist) v_pref.  Then
+    p <- p + v dt, as the lookahead moves it."""
+    humans, as_numpy = _humans(state8)
+    n, dt = int(n), float(dt)
+    if n < 0 or not dt > 0.0:
+        raise ValueError('n must be >= 0 and dt > 0')
+    p, goal, v_pref = humans[..., 0:2].clone(), humans[..., 4:6], humans[..., 7:8]
+    out = torch.zeros((humans.shape[0], n, humans.shape[1], 2), dtype=torch.float64, device=humans.device)
+    for t in range(n):
+        d = goal - p
+        dist = torch.sqrt(d[..., 0:1] * d[..., 0:1] + d[..., 1:2] * d[..., 1:2])
+        cruise = d / torch.where(dist > 0.0, dist, torch.ones_like(dist)) * v_pref
+        v = torch.where(dist <= v_pref * dt, d / dt, cruise)
+        v = torch.where(dist > 0.0, v, torch.zeros_like(v))
+        out[:, t] = v
+        p = p + v * dt
+    return _back(out, as_numpy)
+
+
+def from_positions(start_xy, positions, dt):
+    """start_xy [B, H, 2]: where the humans are now (state8[:, 1:, 0:2]); positions [B, n, H, 2]: where the predictor puts them
+    after step 0, 1, .. n - 1.  human_vel[:, t] = (positions[:, t] - the position before it) / dt.  (The lookahead moves a human
+    by p + v dt, which lands within an ulp or so of the predicted position, not always on it.)"""
+    start, as_numpy = _f64(start_xy)
+    pos, _ = _f64(positions)
+    dt = float(dt)
+    if pos.dim() != 4 or pos.shape[3] != 2 or tuple(start.shape) != (pos.shape[0], pos.shape[2], 2):
+        raise ValueError('start_xy must be [B, H, 2] and positions [B, n, H, 2], got %s and %s' % (tuple(start.shape), tuple(pos.shape)))
+    if not dt > 0.0:
+        raise ValueError('dt must be > 0')
+    before = torch.cat([start[:, None].to(pos.device), pos[:, :-1]], dim=1)
+    return _back((pos - before) / dt, as_numpy)

@@ -1,0 +1,85 @@
+"""A planner with a predictor of its own: the test cases driven by the device CEM (or, with --mppi, MPPI) planner whose model
+of the humans is neither ORCA (which reads their goals through the simulator) nor "straight on forever", but a table of
+predicted velocities the CALLER makes from the state after every real step.
+
+    python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
+
+Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
+stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
+`iterations` times), rollout_step(plan.action), plan_shift.  The prediction goes through the host once per step, which is why
+there is no *_rollout form of these calls; the real steps are ORCA, as always.  Prints the success rate, the collision rate
+and the navigation time in the reference's format."""
+import argparse
+import logging
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import crowdnav_amd  # noqa: E402
+import crowdnav_amd.compat as cn  # noqa: E402
+from crowdnav_amd import predict  # noqa: E402
+from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E402
+
+
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
+         predictor='to_goal'):
+    env_cfg = cn.default_env_config()
+    env = cn.CrowdSim()
+    env.configure(env_cfg)
+    robot = cn.Robot(env_cfg, 'robot')
+    env.set_robot(robot)
+    if robot.kinematics is None:  # ([robot] policy = none: the planner's actions are (vx, vy))
+        robot.kinematics = 'holonomic'
+    eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
+    eng.set_gamma(gamma)
+    bufs = eng.rollout_begin(seed_base=env.case_capacity['val'], seed_mod=env.case_size['test'], episode_limit=cases,
+                             record_capacity=1)
+    planner = eng.plan_reset(eng.plan_begin(candidates, horizon, elites, iterations, init_std * robot.v_pref, seed=seed))
+    most = int(round(env.time_limit / env.time_step)) + 2  # every episode has ended by then (Timeout)
+    for step in range(most):
+        state8, _ = eng.get_state()  # what the planner observes: positions and velocities (to_goal also reads the goals)
+        if predictor == 'to_goal':
+            human_vel = predict.to_goal(state8, horizon, env.time_step)
+        else:
+            human_vel = predict.constant_velocity(state8, horizon)
+        if temperature is None:
+            eng.plan_cem_paths(planner, human_vel, step * iterations)
+        else:
+            eng.plan_mppi_paths(planner, human_vel, temperature, step * iterations)
+        eng.rollout_step(planner.action)
+        eng.plan_shift(planner)
+        if int(bufs['active'].sum().item()) == 0:
+            break
+    rec = {k: bufs[k].cpu().numpy()[:, 0] for k in ('ep_outcome', 'ep_time', 'ep_return', 'ep_danger', 'ep_danger_dmin_sum')}
+    eng.close()
+    success, collision, timeout, _, _, _, _, returns = episode_statistics(
+        [int(o) for o in rec['ep_outcome']], [float(t) for t in rec['ep_time']], [float(r) for r in rec['ep_return']],
+        [int(d) for d in rec['ep_danger']], [float(d) for d in rec['ep_danger_dmin_sum']], timeout_time=env.time_limit)
+    assert len(success) + len(collision) + len(timeout) == cases
+    return ('{:<5} has success rate: {:.2f}, collision rate: {:.2f}, nav time: {:.2f}, total reward: {:.4f}'.format(
+        'TEST', len(success) / cases, len(collision) / cases, average(success) if success else env.time_limit, average(returns)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--cases', type=int, default=8, help='test cases 0 .. cases - 1, one env each')
+    ap.add_argument('--candidates', type=int, default=16, help='K: sequences scored per env and iteration')
+    ap.add_argument('--horizon', type=int, default=8, help='n: actions per sequence, and steps the humans are predicted for')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--mppi', action='store_true', help='the MPPI update (plan_mppi_paths) instead of the CEM refit (plan_cem_paths)')
+    ap.add_argument('--temperature', type=float, default=1.0, help='--mppi: T of the weights exp((score - best score) / T)')
+    ap.add_argument('--elites', type=int, default=4, help='CEM: E, candidates the distribution is refitted to')
+    ap.add_argument('--iterations', type=int, default=3, help='I, draw / score / update rounds per real step')
+    ap.add_argument('--init-std', type=float, default=0.5, help='standard deviation a step starts from, in units of v_pref')
+    ap.add_argument('--predictor', default='to_goal', choices=['to_goal', 'constant_velocity'],
+                    help="the planner's model of the humans (the real steps are always ORCA)")
+    args = ap.parse_args()
+    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
+                      iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
+                      predictor=args.predictor))
+    return 0
+
+
+if __name__ == '__main__':
+    logging.basicConfig(level=logging.INFO, format='%(asctime)s, %(levelname)s: %(message)s', datefmt='%Y-%m-%d %H:%M:%S')
+    sys.exit(main())

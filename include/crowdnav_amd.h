@@ -650,6 +650,60 @@ int cn_lookahead_get_human_model(const cn_engine* e, int* model_host);
  * One launch of a kernel of its own (lane = branch, the humans of an env shared by its K branches), not counted either. */
 
 /* ------------------------------------------------------------------------------------------------------
+ * Lookahead under predicted human motion (no version bump: four new symbols; no struct, enum or counter touched).  The two
+ * human models above are the ends of a range: ORCA reads every human's goal, constant velocity extrapolates forever.  A planner
+ * outside the simulator has a predictor of its own — a learned trajectory model, a goal-directed extrapolation, a recorded
+ * track replayed — and cn_lookahead_paths scores action sequences against whatever it says: the caller hands over the velocity
+ * every human takes at every step of the horizon.
+ *   human_vel: DEVICE double [B][n_steps][A - 1][2].  human_vel[b][t][h] is the velocity (vx, vy) human slot h + 1 of env b
+ *   takes during step t of the horizon; all K branches of env b share it.  Read as 16-byte words: align it to 16 bytes.
+ * An ARGUMENT, not an engine setting: cn_lookahead_set_human_model's setting is neither read nor written by the four calls.
+ * Branch (b, k) is exactly the branch of CN_HUMANS_CONSTANT_VELOCITY above with that section's ONE substitution made by the
+ * table: the velocity a human "chooses" at step t is human_vel[b][t][h] (there: its own current velocity; under ORCA: the ORCA
+ * result).  As in cn_step(update=1), a step distinguishes the velocity a human HAS when the step starts — (hvx, hvy) of its
+ * state: the state velocity at t = 0, human_vel[b][t - 1][h] afterwards — from the one it chooses during it:
+ *   the swept test      wx = hvx - ax, wy = hvy - ay with the velocity the human HAS, as crowd_sim.py:331-351 reads human.vx;
+ *   the move            hx <- hx + cvx dt, hy <- hy + cvy dt with the chosen (cvx, cvy) = human_vel[b][t][h]: one multiply and
+ *                       one add each, sequential from step to step; the chosen velocity becomes the one the human has;
+ *   final_state8        the human's velocity columns hold human_vel[b][s][h], s the LAST step the branch made (steps - 1); its
+ *                       position is the one after step s; goal, radius and v_pref are copied through as before.
+ * Under constant velocity the two coincide, which is why that section names one velocity.  Everything else is that section's,
+ * unchanged: the robot action (holonomic or CN_UNICYCLE), the one fused operation, the slot-order scan and the dmin rule, the
+ * outcome priority, the book, theta.  Every slot 1 .. A - 1 takes part, the parked placeholders of the `mixed` rule
+ * included: the caller writes zeros for them.  Rows behind the last step any branch of env b makes are not read.  Non-finite
+ * velocities are NOT checked: a NaN or infinite row that a running branch uses makes its distances NaN, which compare false —
+ * no collision, no danger — from there on.
+ * A caller who holds predicted POSITIONS passes (p[t + 1] - p[t]) / dt; the ABI takes velocities so that two special cases are
+ * bit-exact on every output: human_vel[b][t][h] = the state velocity for every t gives CN_HUMANS_CONSTANT_VELOCITY's result,
+ * and the velocities recorded from ORCA humans that do not see the robot (robot_visible = 0; the state velocity after step t
+ * of an engine whose robot is parked away from them) give CN_HUMANS_ORCA's.
+ * cn_lookahead_paths refuses NULL human_vel first (CN_ERR_INVALID naming it), then everything cn_lookahead_actions refuses, in
+ * its order and with its messages.  n_steps == 0: CN_OK, nothing launched, nothing written.  ONE launch (lane = branch, the
+ * constant-velocity kernel's lane body), NOT counted; state, cn_rollout_io arrays, ring levels and cn_launch_counts are not
+ * written, a rollout in progress continues as if the call had not happened.  Asynchronous: actions, human_vel and the arrays
+ * of `out` must stay valid until the launch has run. */
+int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candidates,
+                       const double* actions   /* [B][K][n][2] */,
+                       const double* human_vel /* [B][n][A-1][2] */,
+                       const cn_lookahead_out* out);
+/* cn_lookahead_values (below) with cn_lookahead_paths as its lookahead: NULL human_vel first, then cn_lookahead_values'
+ * refusals in its order (under this call's name where the message names the call), the same value and score. */
+int cn_lookahead_paths_values(cn_engine* e, int n_steps, int n_candidates, const double* actions,
+                              const double* human_vel, const cn_lookahead_out* out,
+                              int sort_humans, float* value, double* score);
+/* cn_plan_cem and cn_plan_mppi (below, with their structs) scoring through cn_lookahead_paths — cn_lookahead_paths_values with
+ * cfg->bootstrap —: NULL human_vel first, then every refusal of the cn_plan_* calls; the draw, refit and MPPI update are
+ * untouched, human_vel is [B][cfg->n_steps][A - 1][2].  There is deliberately no *_rollout form: a prediction is made from the
+ * state after each real step, so the closed loop goes through the host once per step (cn_plan_cem_paths, cn_rollout_step,
+ * cn_plan_shift). */
+typedef struct cn_plan_cfg cn_plan_cfg;
+typedef struct cn_plan cn_plan;
+int cn_plan_cem_paths (cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan,
+                       const double* human_vel, uint32_t counter);
+int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan,
+                       const double* human_vel, double temperature, int fit_std, uint32_t counter);
+
+/* ------------------------------------------------------------------------------------------------------
  * Value-bootstrapped lookahead (no version bump: new symbols only).  The n-step return a value-network policy means,
  *   score = sum_{t<n} gamma^(t dt v_pref) r_t + gamma^(n dt v_pref) V(s_n)
  * (MultiHumanRL.predict, multi_human_rl.py:52, is n = 1; Explorer.update_memory's TD targets train V to mean it), needs V of
