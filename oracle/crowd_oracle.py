@@ -146,6 +146,10 @@ class CrowdOracle(object):
     def drop_sims(self):
         lib().co_drop_sims(self._h)
 
+    def set_gamma(self, gamma):
+        """The discount table of rollout / rollout_full: gamma^(t * time_step * robot_v_pref) (explorer.py:71-72); 0.9 unless set."""
+        lib().co_set_gamma(self._h, float(gamma))
+
     def reset(self, seeds, mask=None):
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

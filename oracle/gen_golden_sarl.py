@@ -26,14 +26,17 @@ def snapshot(env):
 
 
 def generate(name, with_om, robot_visible, cases, max_steps, policy_name='sarl', kinematics='holonomic', extra=None,
-             human_num=5):
+             human_num=5, env_overrides=None, out_dir=None, first_step=0):
+    """env_overrides: {'section.key': value} on top of env.config (tests/env_setting_cases.py: reference_overrides); they travel
+    in the file as env_overrides_json.  first_step: decisions of every episode made but not recorded (the crowd has met by then)."""
     rh.activate()
     torch.manual_seed(0)
     pcfg = rh.read_config('policy.config', {('sarl', 'with_om'): 'true' if with_om else 'false',
                                             ('lstm_rl', 'with_om'): 'true' if with_om else 'false',
                                             ('action_space', 'kinematics'): kinematics, **(extra or {})})
     env, robot, policy = rh.make_env(robot_visible=robot_visible, policy_name=policy_name, policy_config=pcfg,
-                                     human_num=human_num)
+                                     human_num=human_num,
+                                     overrides={tuple(k.split('.')): v for k, v in (env_overrides or {}).items()})
     policy.set_device(torch.device('cpu'))
     policy.set_phase('test')
     policy.set_env(env)
@@ -44,6 +47,9 @@ def generate(name, with_om, robot_visible, cases, max_steps, policy_name='sarl',
     for case in cases:
         ob = env.reset('test', case)
         done, t = False, 0
+        for _ in range(first_step):
+            if not done:
+                ob, _, done, _ = env.step(robot.act(ob))
         while not done and t < max_steps:
             state8, gt, th = snapshot(env), env.global_time, float(robot.theta)
             action = robot.act(ob)  # MultiHumanRL.predict: fills policy.action_values
@@ -103,13 +109,35 @@ def generate(name, with_om, robot_visible, cases, max_steps, policy_name='sarl',
         out['param_' + k] = v.numpy()
     out['with_om'] = np.array(int(with_om))
     out['robot_visible'] = np.array(int(robot_visible))
-    np.savez_compressed(os.path.join(OUT, name), **out)
+    if env_overrides:
+        import json
+        out['env_overrides_json'] = np.array(json.dumps(env_overrides, sort_keys=True))
+    np.savez_compressed(os.path.join(out_dir or OUT, name), **out)
     print(name, 'decisions', len(rec['best']), 'best', rec['best'][:8], 'value range',
           float(out['values'].min()), float(out['values'].max()))
 
 
+FIRST = 6  # a human passes the robot's start within the next six decisions: discomfort rewards for many actions
+
+
+def settings_fixtures(out_dir=None):
+    """The decision at non-default environment settings (env_setting_cases.py: radii_rewards + dt_inexact, without the robot
+    policy's safety space, which a value-network robot has none of): with the env queried, and with query_env = false, where
+    MultiHumanRL.compute_reward keeps its own constants whatever [reward] says."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'tests'))
+    import env_setting_cases as cases
+    ov = cases.reference_overrides(cases.sarl_env_config())
+    generate('sarl_settings_query.npz', with_om=False, robot_visible=True, cases=[27, 28], max_steps=6, env_overrides=ov,
+             out_dir=out_dir, first_step=FIRST)
+    generate('sarl_settings_noquery.npz', with_om=False, robot_visible=True, cases=[27, 28], max_steps=6, env_overrides=ov,
+             extra={('action_space', 'query_env'): 'false'}, out_dir=out_dir, first_step=FIRST)
+
+
 if __name__ == '__main__':
     assert rh.available()
+    if sys.argv[1:] == ['settings']:
+        settings_fixtures()
+        sys.exit(0)
     generate('sarl_plain.npz', with_om=False, robot_visible=False, cases=[0, 1, 2], max_steps=8)
     generate('sarl_om.npz', with_om=True, robot_visible=True, cases=[3, 4, 5], max_steps=8)
     generate('cadrl_plain.npz', with_om=False, robot_visible=True, cases=[6, 7], max_steps=8, policy_name='cadrl')
@@ -129,3 +157,4 @@ if __name__ == '__main__':
              policy_name='lstm_rl', extra=noq)
     generate('sarl_noquery_unicycle.npz', with_om=False, robot_visible=False, cases=[22, 23], max_steps=10,
              kinematics='unicycle', extra=noq)
+    settings_fixtures()

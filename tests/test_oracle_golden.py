@@ -147,7 +147,7 @@ def test_survey_known_answer_velocities(oracle_mod):
 def test_committed_fixtures_regenerate_bit_for_bit_from_the_unmodified_reference(tmp_path):
     """the fixtures are not a one-off.  With the reference on this machine (/root/reference or oracle/_ref),
     oracle/gen_golden.py — the UNMODIFIED reference Python on the float32 rvo2 restatement — rewrites traj_visible_h5.npz
-    and outcomes_500.npz into a scratch directory in a subprocess; every array must equal the committed file's bit for bit
+    and outcomes_500.npz — and oracle/gen_golden_settings.py settings_dt_inexact.npz — into a scratch directory in a subprocess; every array must equal the committed file's bit for bit
     and the key sets must match (no stale schema)."""
     import os
     import subprocess
@@ -158,11 +158,12 @@ def test_committed_fixtures_regenerate_bit_for_bit_from_the_unmodified_reference
     if not ref_harness.available():
         pytest.skip('the reference is not on this machine')
     code = ("import sys; sys.path.insert(0, %r); import gen_golden as g; g.OUT = %r; "
-            "g.trajectories('traj_visible_h5.npz', list(range(10)), robot_visible=True); g.outcomes_500()"
+            "g.trajectories('traj_visible_h5.npz', list(range(10)), robot_visible=True); g.outcomes_500(); "
+            "import gen_golden_settings as gs; gs.generate('dt_inexact', out_dir=g.OUT)"
             % (os.path.join(root, 'oracle'), str(tmp_path)))
     subprocess.run([sys.executable, '-c', code], check=True, capture_output=True, timeout=300,
                    env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'))
-    for name in ('traj_visible_h5.npz', 'outcomes_500.npz'):
+    for name in ('traj_visible_h5.npz', 'outcomes_500.npz', 'settings_dt_inexact.npz'):
         new, old = dict(np.load(str(tmp_path / name))), dict(load_golden(name))
         assert sorted(new) == sorted(old)
         for k in new:
