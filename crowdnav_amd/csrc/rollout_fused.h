@@ -38,10 +38,11 @@ __device__ __forceinline__ T in_vgpr(T x) {
 }
 
 // What the NEXT step's pair and collide phases read: the float32 view of the agents, float64 position, radii.
+// `kin`: where the view goes — Smem::kin, or the env wave's staging rows of the two-wave kernel (split_orca_wave).
 __device__ __forceinline__ void stage_agent(const Params& P, const Smem& s, const Lane& L, const AgentRegs& r,
-                                            double human_safety) {
+                                            double human_safety, float4* kin) {
     if (L.lane >= P.nA) return;
-    s.kin[L.lane] = make_float4((float)r.px, (float)r.py, (float)r.vx, (float)r.vy);
+    kin[L.lane] = make_float4((float)r.px, (float)r.py, (float)r.vx, (float)r.vy);
     s.posd[L.lane] = make_double2(r.px, r.py);
     s.rad[L.lane] = r.rad;
     s.hview[L.lane] = (float)(r.rad + 0.01 + human_safety);
@@ -78,50 +79,54 @@ __device__ __forceinline__ void preferred_velocity(const AgentRegs& r, float max
 // The one-wave kernel and the two-wave kernel (rollout_fused_split below) run the SAME phase bodies: what differs is which
 // wave runs them and what sits between them.
 
-// A pair lane's row: the kin slots of its agent's candidates (8 bits each).  A pair that does not exist (robot invisible to
-// the humans, env beyond the batch, fewer than 5 candidates) points at slot nA = (+inf, +inf): its squared distance is +inf
-// without a select, so the pair phase has no data-dependent control flow at all.
+// A pair lane's row: the kin slot of its candidate.  A pair that does not exist (robot invisible to the humans, env beyond
+// the batch) points at slot nA = (+inf, +inf): its squared distance is +inf without a select, so the pair phase has no
+// data-dependent control flow at all.  The lanes of an agent's candidates are consecutive — (q, 0) .. (q, NC - 1) —
+// xbase: the byte address (ds_bpermute: lane * 4) of the group's first lane, (q, 0): lane (q, k) is xbase + 4 k.
 struct PairRow {
-    int my_info, my_slot;
-    unsigned long long row_slots;
+    int my_info, my_slot, xbase;
 };
 __device__ __forceinline__ PairRow pair_row_of(const Params& P, const Smem& s, int lane) {
-    PairRow pr{0, P.nA, 0ull};
+    PairRow pr{0, P.nA, 0};
     if (lane < P.pairs) {
         pr.my_info = s.pinfo[lane];
         const int c = (pr.my_info >> 16) & 0xff;
-        for (int k = 0; k < kFusedMaxNC; ++k) {
-            int slot = P.nA;
-            if (k < P.NC) {
-                const int ik = s.pinfo[lane - c + k];
-                slot = ((ik >> 24) & 1) ? ((ik >> 8) & 0xff) : P.nA;
-            }
-            pr.row_slots |= (unsigned long long)slot << (8 * k);
-        }
-        pr.my_slot = (int)((pr.row_slots >> (8 * c)) & 0xffull);
+        pr.xbase = (lane - c) * 4;
+        pr.my_slot = ((pr.my_info >> 24) & 1) ? ((pr.my_info >> 8) & 0xff) : P.nA;
     }
     return pr;
 }
 
+// The pair's combined radius as its agent's simulator holds it: rview is written in the launch prologue, hview by
+// stage_agent — a per-episode constant (the ORCA wave keeps it in a register between episode ends).
+__device__ __forceinline__ float pair_rsum(const Smem& s, const PairRow& pr) {
+    const int q = pr.my_info & 0xff, ol = (pr.my_info >> 8) & 0xff;
+    const float* view = ((pr.my_info >> 25) & 1) ? s.rview : s.hview;
+    return view[q] + view[ol];
+}
+
 // pairs: candidate distances (Appendix A.2), stable rank = RVO2's sorted-insertion slot, half-plane (A.3).  Pair lanes only.
 // `mid` runs between the rank and the stores, in the same basic block (the one-wave kernel's preferred velocity).
+// `me`, `other`: kin[q] and kin[my_slot], requested by the caller — the ORCA wave issues them beside its exchange words.
 template <typename Mid>
-__device__ __forceinline__ void fused_pair_phase(const Params& P, const Smem& s, const PairRow& pr, float range_sq, Mid&& mid) {
-    const int my_info = pr.my_info, my_slot = pr.my_slot;
-    const unsigned long long row_slots = pr.row_slots;
+__device__ __forceinline__ void fused_pair_body(const Params& P, const Smem& s, const PairRow& pr, float range_sq, float rsum,
+                                                const float4 me, const float4 other, Mid&& mid) {
+    const int my_info = pr.my_info;
     const int q = my_info & 0xff, c = (my_info >> 16) & 0xff;
-    const int ol = (my_info >> 8) & 0xff;
-    const bool robot_sim = (my_info >> 25) & 1;
-    // every LDS request of the phase first, none of them behind a condition
-    const float4 me = s.kin[q];
-    const float4 other = s.kin[my_slot];
-    float4 ot[kFusedMaxNC];
-#pragma unroll
-    for (int k = 0; k < kFusedMaxNC; ++k) ot[k] = s.kin[(int)((row_slots >> (8 * k)) & 0xffull)];
-    const float* view = robot_sim ? s.rview : s.hview;
-    const float rsum = view[q] + view[ol];
     const float odx = me.x - other.x, ody = me.y - other.y;
     const float mine = odx * odx + ody * ody;
+    // The agent's five candidate distances are the `mine` of the five lanes of its group, (q, 0) .. (q, NC - 1): the same
+    // subtraction, products and sum on the same kin rows, fetched by a lane exchange (ds_bpermute_b32, the lane's byte address
+    // xbase + 4 k as base + immediate offset) instead of five more kin rows and their arithmetic.  Issued right behind `mine`:
+    // make_half_plane below does not depend on the rank and covers the exchange.  Every pair lane executes it and reads
+    // lanes of its own group only (all pair lanes); a pair that does not exist has my_slot = nA, so its `mine` is +inf as
+    // before; k >= NC (no such lane in the group) is +inf by a select.
+    uint32_t vbk[kFusedMaxNC];
+#pragma unroll
+    for (int k = 0; k < kFusedMaxNC; ++k) {
+        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_bpermute(pr.xbase + 4 * k, (int)__float_as_uint(mine));
+        vbk[k] = k < P.NC ? got : 0x7f800000u;
+    }
     int rank = 0, within = 0;
     {
         // squared distances are +0 .. +inf: their bit patterns order like the floats, so "v < mine, or v == mine and
@@ -132,8 +137,7 @@ __device__ __forceinline__ void fused_pair_phase(const Params& P, const Smem& s,
         uint32_t before = 0u, inside = 0u;
 #pragma unroll
         for (int k = 0; k < kFusedMaxNC; ++k) {
-            const float dx = me.x - ot[k].x, dy = me.y - ot[k].y;
-            const uint32_t vb = __float_as_uint(dx * dx + dy * dy);  // +inf for a pair that does not exist: never in range
+            const uint32_t vb = vbk[k];  // +inf for a pair that does not exist: never in range
             const uint32_t tie = (uint32_t)(k - c) >> 31;           // k < c
             before = __builtin_amdgcn_alignbit(before, vb - mb - tie, 31);
             inside = __builtin_amdgcn_alignbit(inside, vb - rb, 31);
@@ -146,6 +150,14 @@ __device__ __forceinline__ void fused_pair_phase(const Params& P, const Smem& s,
     if (mine < range_sq && rank < P.orca.max_neighbors)
         s.lines[q * kLineStride + rank] =
             make_half_plane(P.orca, me.x, me.y, me.z, me.w, other.x, other.y, other.z, other.w, rsum);
+}
+template <typename Mid>
+__device__ __forceinline__ void fused_pair_phase(const Params& P, const Smem& s, const PairRow& pr, float range_sq, float rsum,
+                                                 Mid&& mid) {
+    // every LDS request of the phase first, none of them behind a condition
+    const float4 me = s.kin[pr.my_info & 0xff];
+    const float4 other = s.kin[pr.my_slot];
+    fused_pair_body(P, s, pr, range_sq, rsum, me, other, mid);
 }
 
 // candidates: lane = (agent, half-plane)
@@ -394,14 +406,17 @@ static __device__ unsigned long long cn_wave_trace[8192 * 6];
 //                               the next float32 view with the same `px + vx * dt` as the env wave
 // The waves meet at two s_barrier per step.  Iteration of the loop, u = the step whose velocities the ORCA wave computes:
 //   barrier 1   both read what the other left: the ORCA wave the "episode ended" word, the env wave the velocities of u - 1
-//     ORCA wave: stage kin(u) from its registers, pairs(u)          env wave: integrate u - 1, publish sol / res of u
+//     ORCA wave: pairs(u) on the kin(u) it staged itself             env wave: integrate u - 1, publish sol / res of u
 //   barrier 2
-//     ORCA wave: candidates, scan (+ fallback) of u, publish vel(u) env wave: swept distance, reduce, bookkeeping of u - 1
+//     ORCA wave: candidates, scan (+ fallback) of u, publish vel(u),  env wave: swept distance, reduce, bookkeeping of u - 1
+//                stage kin(u + 1) = its positions + vel(u) dt
 // Both sides of an iteration ASSUME that step u - 1 ended no episode.  When it did, the env wave (which now holds the state
-// after the episode end: next scenario loaded, env paused or retired) re-stages kin / posd / rad / hview of its lanes and
-// posts the word; at barrier 1 the ORCA wave then drops the velocities it has just published — they touched LDS only —
-// re-reads its positions and computes step u again, while the env wave publishes sol / res of the true state and idles
-// past barrier 2.  One ORCA step is redone per episode end of a workgroup (~1 in 21 wave-steps at the headline shape).
+// after the episode end: next scenario loaded, env paused or retired) re-stages posd / rad / hview of its lanes, leaves the
+// true float32 view in rows of its own (Smem::d2 — kin belongs to the ORCA wave in that window) and posts the word; at
+// barrier 1 the ORCA wave then drops the velocities and the view it has just published — they touched LDS only — copies
+// the true rows into kin, re-reads its positions and its per-episode constants and computes step u again, while the env
+// wave publishes sol / res of the true state and idles past barrier 2.  One ORCA step is redone per episode end of a
+// workgroup (~1 in 21 wave-steps at the headline shape).
 // The step counters, the discount index and every store to global memory live in the env wave.
 // What the waves exchange lives in arrays of the LDS layout that the fused kernels do not otherwise use: Smem::act (the
 // published velocities, as float2), Smem::flag[0] (the word) and, with ASSIST, Smem::flag[1] (the prediction word: an
@@ -496,11 +511,20 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
     double px = 0.0, py = 0.0;
     float rx = 0.0f, ry = 0.0f;
     bool solved = false;
+    // Per-episode constants, refreshed in an iteration with `ended` (the launch's first has it: word = 1).  rsum: rview is
+    // written in the prologue only, hview by stage_agent — prologue and episode end.  solved: sol[].w is the env wave's
+    // `running && (human || robot_orca)`, and ep.state changes in CN_END_EPISODE alone (next scenario, pause, retire: all
+    // under `done`, which sets `ended`); scenario_ready outside of it is the prologue's.
+    float rsum = 0.0f;
+    const int pq = pr.my_info & 0xff;  // (0 / nA beyond the pair lanes: in bounds)
     SPLIT_PROBE_DECL();
     for (int u = 0;;) {
         SPLIT_PROBE_WAIT(0, split_barrier());  // 1
-        const bool ended = __builtin_amdgcn_readfirstlane(s.flag[0]) != 0;
-        const unsigned int pred = ((ASSIST & kAssistHead) || kSplitProbe) ? (unsigned int)__builtin_amdgcn_readfirstlane(s.flag[1]) : 0u;
+        // kin(u) was staged at the end of the previous iteration: the pair rows are requested beside the two words
+        const int2 words = make_int2(s.flag[0], ((ASSIST & kAssistHead) || kSplitProbe) ? s.flag[1] : 0);
+        float4 me = s.kin[pq], other = s.kin[pr.my_slot];
+        const bool ended = __builtin_amdgcn_readfirstlane(words.x) != 0;
+        const unsigned int pred = ((ASSIST & kAssistHead) || kSplitProbe) ? (unsigned int)__builtin_amdgcn_readfirstlane(words.y) : 0u;
         if (!ended) ++u;
         if (u >= n_steps) {  // the env wave finishes step n_steps - 1 alone
             split_barrier();  // 2
@@ -508,27 +532,33 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
         }
         const bool head = (ASSIST & kAssistHead) ? split_has_head<MAXL>(pred, u, n_steps) : false;
         SPLIT_PROBE_AFTER_1(pred, head);
-        if (lane < P.nA) {
-            if (ended) {  // the env wave staged the true state
+        if (ended) {  // the env wave staged the true state (its kin rows in d2: this wave owns kin in window 2): the one extra trip
+            if (lane < P.nA) {
                 const double2 p = s.posd[lane];
                 px = p.x, py = p.y;
-            } else if (solved) {  // Agent.step (agent.py:127-135), as the env wave does it
-                px = px + (double)rx * c_dt;
-                py = py + (double)ry * c_dt;
-                s.kin[lane] = make_float4((float)px, (float)py, rx, ry);
+                s.kin[lane] = reinterpret_cast<const float4*>(s.d2)[lane];
             }
+            CN_FUSED_SYNC();
+            me = s.kin[pq], other = s.kin[pr.my_slot];
         }
-        CN_FUSED_SYNC();
-        if (lane < P.pairs) fused_pair_phase(P, s, pr, range_sq, [] {});
+        if (ended) rsum = pair_rsum(s, pr);
+        if (lane < P.pairs) fused_pair_body(P, s, pr, range_sq, rsum, me, other, [] {});
         SPLIT_PROBE_WAIT(1, split_barrier());  // 2: sol / res of step u
         fused_candidates<MAXL>(P, s, lane);
         CN_FUSED_SYNC();
-        solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
+        if (ended) solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
         const unsigned long long nm = fused_solve<MAXL, kSplitOrcaPrio>(P, s, lane, solved, rx, ry, nullptr, head ? pred : 0u, [&] {
             if (head) SPLIT_PROBE_WAIT(2, split_barrier());  // 3: the env wave's proj / cand3 rows of the agents of pred
         });
         if (lane < P.nA) vel[lane] = make_float2(rx, ry);
         if (((ASSIST & kAssistHead) || kSplitProbe) && lane == 0) s.flag[1] = (int)nm;  // the next iteration's prediction word
+        // the view of step u + 1, ahead of barrier 1: Agent.step (agent.py:127-135), as the env wave does it.  Nobody reads kin
+        // in this window; an episode end found meanwhile drops it (`ended` above)
+        if (solved) {
+            px = px + (double)rx * c_dt;
+            py = py + (double)ry * c_dt;
+            s.kin[lane] = make_float4((float)px, (float)py, rx, ry);
+        }
         SPLIT_PROBE_STEP(ended, nm, head, pred);
     }
     SPLIT_PROBE_FLUSH(lane, 0);
@@ -618,7 +648,10 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     if (L.lane == 0) s.kin[P.nA] = make_float4(std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity(), 0.0f, 0.0f);
     const PairRow pr = pair_row_of(P, s, L.lane);
     const StepConsts K = step_consts(P);
-    stage_agent(P, s, L, r, K.hsafety);
+    // two-wave kernel: the ORCA wave owns kin (it stages the next view itself, ahead of barrier 1); the env wave's true rows of
+    // a (re)started episode go to d2, free in the fused kernels (headline geometry: 60 floats for 12 rows of 16 bytes, 16-byte aligned)
+    float4* const kin_stage = SPLIT ? reinterpret_cast<float4*>(s.d2) : s.kin;
+    stage_agent(P, s, L, r, K.hsafety, kin_stage);
     CN_FUSED_SYNC();
 
 #ifdef CN_PHASE_TIMING
@@ -638,6 +671,22 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
         if (L.lane == 0) s.flag[0] = 1, s.flag[1] = 0;  // "re-read the staged state"; no agent predicted infeasible
         split_barrier();  // prologue staged
         bool skip = true;  // the state of step u is already in registers: nothing to integrate, nothing to book
+        // Mirror lanes: lane 16 + l carries a copy of agent lane l's position and goal (in the same registers: nothing else
+        // reads r beyond the agent lanes) and of "its env runs", so that the two divisions of the preferred velocity are ONE
+        // sequence on two lane groups.  Copied here and after an episode end (the only places where goal, position or the
+        // env's state change other than by Agent.step), integrated by the mirror lanes themselves in between.
+        // (headline geometry: 12 agent lanes, so lanes 16-27 are free)
+        const bool mirror = L.lane >= 16 && L.lane < 16 + P.nA;
+        const int m_lane = L.lane & 15;
+        const int m_ebase = __shfl(L.ebase, m_lane);
+        const bool m_robot = __shfl((int)(L.a == 0), m_lane) != 0;
+        bool m_running = false;
+        const auto copy_to_mirror = [&] {
+            const double px = __shfl(r.px, m_lane), py = __shfl(r.py, m_lane), gx = __shfl(r.gx, m_lane), gy = __shfl(r.gy, m_lane);
+            const int run = __shfl((int)(L.valid && ep.state == kRunning), m_lane);
+            if (mirror) r.px = px, r.py = py, r.gx = gx, r.gy = gy, m_running = run != 0;
+        };
+        copy_to_mirror();
         SPLIT_PROBE_DECL();
         for (int u = 0;;) {
             SPLIT_PROBE_WAIT(0, split_barrier());  // 1: vel(u - 1)
@@ -647,23 +696,35 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             const bool running = L.valid && ep.state == kRunning;
             const AgentRegs r0 = r;  // the agent at the start of step u - 1
             double act_x = 0.0, act_y = 0.0, new_vx = 0.0, new_vy = 0.0;
-            if (!skip && L.lane < P.nA) {
-                const float2 mine = vel[L.lane], robots = vel[L.ebase];
+            // (the mirror lanes integrate their copy with the same statements on the same operands: no instruction more)
+            if (!skip && (L.lane < P.nA || mirror)) {
+                const float2 mine = vel[m_lane], robots = vel[m_ebase];
                 act_x = (double)robots.x, act_y = (double)robots.y;
-                new_vx = (L.a == 0) ? act_x : (double)mine.x;
-                new_vy = (L.a == 0) ? act_y : (double)mine.y;
-                if (running) {  // Agent.step (agent.py:127-135)
+                new_vx = m_robot ? act_x : (double)mine.x;
+                new_vy = m_robot ? act_y : (double)mine.y;
+                if (mirror ? m_running : running) {  // Agent.step (agent.py:127-135)
                     r.px = r.px + new_vx * K.dt;
                     r.py = r.py + new_vy * K.dt;
                     r.vx = new_vx;
                     r.vy = new_vy;
                 }
             }
-            if (u < n_steps && L.lane < P.nA) {
-                float4 sol4, start4;
-                preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, running && (L.a > 0 || P.robot_orca), sol4, start4);
-                s.sol[L.lane] = sol4;
-                s.res[L.lane] = start4;
+            if (u < n_steps && (L.lane < P.nA || mirror)) {
+                // preferred_velocity with ONE float64 division sequence: the agent's lane divides gdx, its mirror lane gdy
+                const double gdx = r.gx - r.px, gdy = r.gy - r.py;
+                const double speed = norm2(gdx, gdy);
+                const double num = mirror ? gdy : gdx;
+                const float pref = (float)(speed > 1.0 ? num / speed : num);
+                // rows of 16 lanes: row 1 of the first operand <-> row 0 of the second, so [1] holds the mirror lanes' value on
+                // the agent lanes
+                const float pref_y = __uint_as_float(__builtin_amdgcn_permlane16_swap(__float_as_uint(pref), __float_as_uint(pref), false, false)[1]);
+                if (L.lane < P.nA) {
+                    const float max_speed = (L.a == 0) ? robot_max_speed : (float)r.vpref;
+                    float sx, sy;
+                    lp_start_point(max_speed, pref, pref_y, sx, sy);
+                    s.sol[L.lane] = make_float4(pref, pref_y, max_speed, (running && (L.a > 0 || P.robot_orca)) ? 1.0f : 0.0f);
+                    s.res[L.lane] = make_float4(sx, sy, 0.0f, 0.0f);
+                }
             }
             SPLIT_PROBE_WAIT(1, split_barrier());  // 2
             if constexpr ((ASSIST & kAssistHead) != 0) {
@@ -703,7 +764,8 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                 ended = __ballot(done) != 0ull;
             }
             // per-episode constants (rad, hview) and the float32 view are staged here and in the prologue only
-            if (ended) stage_agent(P, s, L, r, K.hsafety);
+            if (ended) stage_agent(P, s, L, r, K.hsafety, kin_stage);
+            if (ended) copy_to_mirror();
             if (L.lane == 0) s.flag[0] = ended ? 1 : 0;
             skip = ended;
             if constexpr ((ASSIST & kAssistHead) != 0 && CN_SPLIT_HEAD_TAIL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
@@ -720,7 +782,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
         if (L.lane < P.pairs) {
             // (agent lanes are pair lanes too: their preferred velocity, same block)
             float4 sol4, start4;
-            fused_pair_phase(P, s, pr, range_sq, [&] {
+            fused_pair_phase(P, s, pr, range_sq, pair_rsum(s, pr), [&] {
                 preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, solve, sol4, start4);
             });
             if (L.lane < P.nA) {
@@ -786,7 +848,7 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                                load_from_ring(P, *Sd, L, ep.ep_count % P.ring_mod, r); theta = 1.5707963267948966);
             }
         }
-        stage_agent(P, s, L, r, K.hsafety);
+        stage_agent(P, s, L, r, K.hsafety, kin_stage);
         CN_FUSED_SYNC();
         CN_TICK(clk, 7);
     }
