@@ -27,6 +27,9 @@ PRECISIONS = ('f32', 'f16x2')  # CN_PRECISION_*
 FLAG_ASYNC_SCENARIO_FILL = 1
 HUMANS_ORCA, HUMANS_CONSTANT_VELOCITY = 0, 1  # CN_HUMANS_*
 HUMAN_MODELS = ('orca', 'constant_velocity')
+MODES_MEAN, MODES_MIN = 0, 1  # CN_MODES_*
+MODES_REDUCE = ('mean', 'min')
+MODES_MAX = 8  # cn_path_modes.n_modes
 
 
 class CrowdNavAmdError(RuntimeError):
@@ -76,6 +79,23 @@ class CnLookaheadOut(C.Structure):
     _fields_ = [
         ('ret', C.c_void_p), ('info', C.c_void_p), ('steps', C.c_void_p), ('time', C.c_void_p),
         ('final_state8', C.c_void_p), ('final_theta', C.c_void_p),
+    ]
+
+
+class CnPathModes(C.Structure):
+    """struct cn_path_modes (include/crowdnav_amd.h): M predicted futures and how their returns are reduced; weight may be NULL."""
+    _fields_ = [
+        ('n_modes', C.c_int32), ('reduce', C.c_int32), ('risk_penalty', C.c_double),
+        ('human_vel', C.c_void_p), ('weight', C.c_void_p),
+    ]
+
+
+class CnModesOut(C.Structure):
+    """struct cn_modes_out (include/crowdnav_amd.h): device pointers; everything but score may be NULL."""
+    _fields_ = [
+        ('score', C.c_void_p), ('risk', C.c_void_p), ('worst_mode', C.c_void_p), ('worst_info', C.c_void_p),
+        ('worst_steps', C.c_void_p), ('worst_time', C.c_void_p),
+        ('ret', C.c_void_p), ('info', C.c_void_p), ('steps', C.c_void_p), ('time', C.c_void_p),
     ]
 
 
@@ -195,6 +215,11 @@ SYMBOLS = {
     'cn_lookahead_paths_values': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),
     'cn_plan_cem_paths': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), _P, C.c_uint32]),
     'cn_plan_mppi_paths': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), _P, C.c_double, C.c_int, C.c_uint32]),
+    # the lookahead and the planning steps against M predicted futures [B][M][n][A - 1][2], reduced per branch (no version bump)
+    'cn_lookahead_modes': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnPathModes), C.POINTER(CnModesOut)]),
+    'cn_plan_cem_modes': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.POINTER(CnPathModes), C.c_uint32]),
+    'cn_plan_mppi_modes': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.POINTER(CnPathModes), C.c_double, C.c_int,
+                                     C.c_uint32]),
 }
 
 _lib = None

@@ -268,6 +268,29 @@ class CrowdSim(_Base):
         ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
         return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
 
+    def lookahead_modes(self, sequences, human_velocities, weights=None, reduce='mean', risk_penalty=0.0):
+        """lookahead_paths() against M predicted futures at once (BatchedCrowdSim.lookahead_modes): human_velocities[m] is
+        lookahead_paths' table of mode m — anything np.asarray reads as [M, n, humans, 2]; weights: M numbers or None = 1 / M
+        each, used as given.  Returns K tuples (score, risk, worst_mode, info): score = the weighted mean ('mean') or the
+        minimum ('min') of the modes' returns, less risk_penalty * risk; risk = the summed weight of the modes that end in a
+        collision; worst_mode the first mode with the lowest return and info the object of that mode's last transition."""
+        unicycle = getattr(self.robot, 'kinematics', 'holonomic') == 'unicycle'
+        sequences = [list(seq) for seq in sequences]
+        if not sequences or not sequences[0] or any(len(seq) != len(sequences[0]) for seq in sequences):
+            raise ValueError('lookahead_modes: K >= 1 sequences of one length n >= 1 are required')
+        for seq in sequences:
+            for action in seq:
+                self._check_action(action, unicycle)
+        table = np.array([[[list(a) for a in seq] for seq in sequences]], dtype=np.float64)  # [1, K, n, 2]
+        vel = np.asarray(human_velocities, dtype=np.float64)
+        if vel.ndim != 4 or vel.shape[1:] != (len(sequences[0]), self.human_num, 2):
+            raise ValueError('lookahead_modes: human_velocities must be [M, n = %d, %d humans, 2], got %s'
+                             % (len(sequences[0]), self.human_num, vel.shape))
+        w = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(1, -1)
+        out = self._eng.lookahead_modes(table, vel[None], weights=w, reduce=reduce, risk_penalty=risk_penalty)
+        score, risk, worst, info = (out[k].cpu().numpy()[0] for k in ('score', 'risk', 'worst_mode', 'worst_info'))
+        return [(float(s), float(r), int(m), info_from_code(i)) for s, r, m, i in zip(score, risk, worst, info)]
+
     @staticmethod
     def _check_action(action, unicycle):
         if not isinstance(action, tuple) or not hasattr(action, 'v' if unicycle else 'vx'):

@@ -17,6 +17,7 @@
 #include "rollout_fused.h"
 #include "records_kernels.h"
 #include "lookahead_cv_kernel.h"
+#include "lookahead_modes_kernel.h"
 
 thread_local char cn_g_err[512] = "";
 
@@ -793,6 +794,45 @@ int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candidates, const double
     pick_bool(e->P.robot_unicycle, [&](auto uni) {
         hipLaunchKernelGGL((cn::lookahead_paths_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
                            dim3(cn::kWave), 0, e->stream, C, actions, human_vel, (const cn_lookahead_out*)e->look_dev);
+    });
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// cn_lookahead_paths against M tables at once, reduced per branch: lookahead_modes_kernel (lookahead_modes_kernel.h).  The
+// refusals in the header's order; cn_lookahead_actions' own are made by cn_lookahead_check, which wants a cn_lookahead_out: the
+// one handed to it names out->score in every required place and is only tested for NULL.  `modes` and `out` travel as kernel
+// arguments, so no device copy of either is kept and nothing of the engine is written.
+int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double* actions, const cn_path_modes* modes,
+                       const cn_modes_out* out) {
+    if (!modes) return fail(CN_ERR_INVALID, "cn_lookahead_modes: modes is NULL");
+    if (!modes->human_vel) return fail(CN_ERR_INVALID, "cn_lookahead_modes: modes->human_vel is NULL");
+    if (!out) return fail(CN_ERR_INVALID, "cn_lookahead_modes: out is NULL");
+    if (!out->score) return fail(CN_ERR_INVALID, "cn_lookahead_modes: out->score is NULL");
+    if (modes->n_modes < 1) return fail(CN_ERR_INVALID, "cn_lookahead_modes: n_modes must be >= 1 (got %d)", modes->n_modes);
+    if (modes->n_modes > cn::kModesMax)
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_modes: n_modes = %d exceeds the %d modes a lane keeps in registers",
+                    modes->n_modes, cn::kModesMax);
+    if (modes->reduce != CN_MODES_MEAN && modes->reduce != CN_MODES_MIN)
+        return fail(CN_ERR_INVALID, "cn_lookahead_modes: reduce %d unknown (CN_MODES_MEAN = 0, CN_MODES_MIN = 1)", modes->reduce);
+    if (!(modes->risk_penalty >= 0.0) || !std::isfinite(modes->risk_penalty))
+        return fail(CN_ERR_INVALID, "cn_lookahead_modes: risk_penalty must be >= 0 and finite (got %g)", modes->risk_penalty);
+    const cn_lookahead_out probe{out->score, reinterpret_cast<uint8_t*>(out->score), reinterpret_cast<int32_t*>(out->score),
+                                 out->score, nullptr, nullptr};
+    int rc = cn_lookahead_check(e, n_steps, n_candidates, actions, &probe);
+    if (rc) return rc;
+    const uint64_t mode_rows = (uint64_t)e->P.B * (uint64_t)n_candidates * (uint64_t)modes->n_modes;
+    if (mode_rows > (uint64_t)INT32_MAX)
+        return fail(CN_ERR_UNSUPPORTED, "cn_lookahead_modes: num_envs * n_candidates * n_modes = %llu exceeds the %llu per-mode "
+                    "rows a launch indexes", (unsigned long long)mode_rows, (unsigned long long)INT32_MAX);
+    if (n_steps == 0) return CN_OK;
+    if ((rc = bind(e))) return rc;
+    const cn::CvParams C = cv_params(e, n_steps, n_candidates);
+    const cn::ModesParams Q{modes->n_modes, modes->reduce, modes->risk_penalty, modes->human_vel, modes->weight, *out};
+    const size_t lds = cn::modes_lds_bytes(Q.M, C.A - 1);  // at most 4 * 504 * 16 + 63 * 8 = 32760 bytes
+    pick_bool(e->P.robot_unicycle, [&](auto uni) {
+        hipLaunchKernelGGL((cn::lookahead_modes_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
+                           dim3(cn::kWave), lds, e->stream, C, actions, Q);
     });
     CN_HIP(hipGetLastError());
     return CN_OK;

@@ -1,7 +1,7 @@
 // libcrowdnav_amd.so — the device CEM and MPPI planners (cn_plan_*): host entry points over the kernels of plan_kernels.h.
 //
 // A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values (the *_paths
-// calls: cn_lookahead_paths / cn_lookahead_paths_values) and real steps
+// calls: cn_lookahead_paths / cn_lookahead_paths_values; the *_modes calls: cn_lookahead_modes) and real steps
 // made through cn_rollout_step, by their C entry points and therefore with their checks, their scenario-ring fill and their
 // launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior), enqueued on the
 // engine's stream.  Nothing here synchronises, allocates or counts.
@@ -74,6 +74,15 @@ int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const 
     return cn_lookahead_check(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
 }
 
+// the *_modes planners, behind plan_check: no bootstrap form (the branch-end states are per mode), then cn_lookahead_modes' own
+// refusals without enqueuing (zero steps: it checks and returns)
+int plan_check_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, const char* who) {
+    if (cfg->bootstrap)
+        return fail(CN_ERR_UNSUPPORTED, "%s: bootstrap is not served: the branch-end states are per mode and not kept", who);
+    const cn_modes_out out{plan->look.ret, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return cn_lookahead_modes(e, 0, cfg->n_candidates, plan->candidates, modes, &out);
+}
+
 // ... and refusal 6: what cn_rollout_step refuses for the io block, without enqueuing (cn_rollout_actions of zero steps runs
 // the io checks of every rollout entry point and launches nothing; the renumbering rule is upload_io's)
 int plan_check_io(cn_engine* e, const cn_rollout_io* io, const cn_plan* plan) {
@@ -126,14 +135,20 @@ int run_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, c
 }
 
 // One planning step of either planner: draw, score, update, `iterations` times.  human_vel (optional): the candidates are
-// scored by the paths lookahead against the caller's predicted human motion instead of the engine's human model.
+// scored by the paths lookahead against the caller's predicted human motion instead of the engine's human model.  modes
+// (optional, never with human_vel or bootstrap): by cn_lookahead_modes against the caller's M futures — look.ret receives the
+// reduced score, which the updates rank, and look.info / steps / time the worst mode's rows.
 int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter, const Mppi* mppi,
-             const double* human_vel = nullptr) {
+             const double* human_vel = nullptr, const cn_path_modes* modes = nullptr) {
     const int n = cfg->n_steps, K = cfg->n_candidates;
+    const cn_modes_out worst{plan->look.ret, nullptr, nullptr, plan->look.info, plan->look.steps, plan->look.time,
+                             nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < cfg->iterations; ++i) {
         int rc = run_draw(e, cfg, plan, counter + (uint32_t)i);
         if (rc) return rc;
-        if (human_vel)
+        if (modes)
+            rc = cn_lookahead_modes(e, n, K, plan->candidates, modes, &worst);
+        else if (human_vel)
             rc = cfg->bootstrap ? cn_lookahead_paths_values(e, n, K, plan->candidates, human_vel, &plan->look, cfg->sort_humans,
                                                             plan->value, plan->score)
                                 : cn_lookahead_paths(e, n, K, plan->candidates, human_vel, &plan->look);
@@ -234,6 +249,22 @@ int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan
     int rc = plan_check(e, cfg, plan, "cn_plan_mppi_paths", &mppi);
     if (rc || (rc = bind(e))) return rc;
     return run_plan(e, cfg, plan, counter, &mppi, human_vel);
+}
+
+int cn_plan_cem_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, uint32_t counter) {
+    if (!modes) return fail(CN_ERR_INVALID, "cn_plan_cem_modes: modes is NULL");
+    int rc = plan_check(e, cfg, plan, "cn_plan_cem_modes");
+    if (rc || (rc = plan_check_modes(e, cfg, plan, modes, "cn_plan_cem_modes")) || (rc = bind(e))) return rc;
+    return run_plan(e, cfg, plan, counter, nullptr, nullptr, modes);
+}
+
+int cn_plan_mppi_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, double temperature,
+                       int fit_std, uint32_t counter) {
+    if (!modes) return fail(CN_ERR_INVALID, "cn_plan_mppi_modes: modes is NULL");
+    const Mppi mppi{temperature, fit_std};
+    int rc = plan_check(e, cfg, plan, "cn_plan_mppi_modes", &mppi);
+    if (rc || (rc = plan_check_modes(e, cfg, plan, modes, "cn_plan_mppi_modes")) || (rc = bind(e))) return rc;
+    return run_plan(e, cfg, plan, counter, &mppi, nullptr, modes);
 }
 
 int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,

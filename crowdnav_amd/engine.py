@@ -561,6 +561,82 @@ class BatchedCrowdSim(object):
         """plan_mppi with its candidates scored by lookahead_paths (cn_plan_mppi_paths)."""
         return self._plan_paths('mppi_paths', plan, human_vel, float(temperature), int(bool(fit_std)), counter=counter)
 
+    # ---------------------------------------------------------------- several predicted futures at once (cn_*_modes)
+    def _path_modes(self, who, n, human_vel, weights, reduce, risk_penalty):
+        """(struct cn_path_modes, M, what was borrowed) of a *_modes call: the shapes and `reduce` are checked before the
+        library or the device is asked."""
+        vshape = tuple(getattr(human_vel, 'shape', np.shape(human_vel)))
+        if len(vshape) != 5 or vshape[:1] + vshape[2:] != (self.B, n, self.H, 2) or not 1 <= vshape[1] <= _lib.MODES_MAX:
+            raise ValueError('%s: human_vel must be [%d, M in 1..%d, n = %d, %d, 2], got %s'
+                             % (who, self.B, _lib.MODES_MAX, n, self.H, vshape))
+        M = int(vshape[1])
+        if reduce not in _lib.MODES_REDUCE:
+            raise ValueError('%s: reduce must be one of %s, got %r' % (who, _lib.MODES_REDUCE, reduce))
+        if weights is not None:
+            wshape = tuple(getattr(weights, 'shape', np.shape(weights)))
+            if wshape != (self.B, M):
+                raise ValueError('%s: weights must be [%d, M = %d], got %s' % (who, self.B, M, wshape))
+        v, temporary_v = self._borrow(human_vel, torch.float64, (self.B, M, n, self.H, 2))
+        w, temporary_w = self._borrow(weights, torch.float64, (self.B, M))
+        modes = _lib.CnPathModes(n_modes=M, reduce=_lib.MODES_REDUCE.index(reduce), risk_penalty=float(risk_penalty),
+                                 human_vel=v.data_ptr(), weight=None if w is None else w.data_ptr())
+        return modes, M, (v, w), (temporary_v, temporary_w)
+
+    def lookahead_modes(self, actions, human_vel, weights=None, reduce='mean', risk_penalty=0.0, per_mode=False, out=None):
+        """lookahead_paths() against M predicted futures at once, reduced per branch (cn_lookahead_modes): human_vel
+        [B, M, n, H, 2] float64 — human_vel[b, m] is lookahead_paths' table of env b under mode m (predict.stack_modes builds it);
+        weights [B, M] float64 or None = 1 / M each, used as given (not normalised).  The robot of a branch is moved once and
+        tested against the M sets of humans: the action table is read once.  Mode m of branch (b, k) is lookahead_paths' branch
+        with table human_vel[:, m], bit for bit; each mode ends at its own first done.  Returns a dict of device tensors, rows
+        [b, k]:
+            score       float64  r - risk_penalty * risk; r = sum_m w_m ret_m ('mean') or min_m ret_m ('min', weights not read)
+            risk        float64  sum_m w_m [mode m ended in COLLISION]
+            worst_mode  int32    the smallest m with the lowest ret_m; worst_info uint8, worst_steps int32, worst_time float64:
+                                 that mode's info, steps and time
+        and with per_mode=True ret float64, info uint8, steps int32, time float64 [B, K, M].  There is no final state and no
+        bootstrap.  actions, `out`, n = 0, what is borrowed and what is copied: as in lookahead().  No state, rollout buffer,
+        ring level, launch counter or lookahead_human_model changes."""
+        who = 'lookahead_modes'
+        shape = tuple(getattr(actions, 'shape', np.shape(actions)))
+        if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:
+            raise ValueError('%s: actions must be [%d, K >= 1, n, 2], got %s' % (who, self.B, shape))
+        K, n = int(shape[1]), int(shape[2])
+        modes, M, keep, temporary = self._path_modes(who, n, human_vel, weights, reduce, risk_penalty)
+        spec = dict(score=(torch.float64, (self.B, K)), risk=(torch.float64, (self.B, K)), worst_mode=(torch.int32, (self.B, K)),
+                    worst_info=(torch.uint8, (self.B, K)), worst_steps=(torch.int32, (self.B, K)),
+                    worst_time=(torch.float64, (self.B, K)))
+        if per_mode:
+            spec.update(ret=(torch.float64, (self.B, K, M)), info=(torch.uint8, (self.B, K, M)),
+                        steps=(torch.int32, (self.B, K, M)), time=(torch.float64, (self.B, K, M)))
+        out = self._rows(who, spec, out)
+        if n > 0:
+            a, temporary_a = self._borrow(actions, torch.float64, (self.B, K, n, 2))
+            check(self._lib.cn_lookahead_modes(self._h, n, K, _ptr(a), C.byref(modes), C.byref(_struct(_lib.CnModesOut, out))))
+            self._release(temporary_a, *temporary)
+        del keep
+        return out
+
+    def _plan_modes(self, name, plan, human_vel, weights, reduce, risk_penalty, *args, counter):
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        modes, _, keep, temporary = self._path_modes('plan_' + name, plan.n, human_vel, weights, reduce, risk_penalty)
+        self._plan_call(name, plan, C.byref(modes), *args, counter=counter)
+        self._release(*temporary)
+        del keep
+        return plan
+
+    def plan_cem_modes(self, plan, human_vel, counter, weights=None, reduce='mean', risk_penalty=0.0):
+        """plan_cem with its candidates scored by lookahead_modes (cn_plan_cem_modes): human_vel [B, M, n, H, 2], weights, reduce
+        and risk_penalty as there.  plan.look['ret'] receives the reduced score — which the refit ranks — and look['info'] /
+        ['steps'] / ['time'] the worst mode's rows.  A plan with bootstrap=True is refused.  No rollout form, as for
+        plan_cem_paths."""
+        return self._plan_modes('cem_modes', plan, human_vel, weights, reduce, risk_penalty, counter=counter)
+
+    def plan_mppi_modes(self, plan, human_vel, temperature, counter, weights=None, reduce='mean', risk_penalty=0.0, fit_std=False):
+        """plan_mppi with its candidates scored by lookahead_modes (cn_plan_mppi_modes)."""
+        return self._plan_modes('mppi_modes', plan, human_vel, weights, reduce, risk_penalty, float(temperature),
+                                int(bool(fit_std)), counter=counter)
+
     def plan_mppi_rollout(self, plan, n_real, temperature, counter, fit_std=False):
         """plan_rollout with the MPPI update (cn_plan_mppi_rollout): per step plan_mppi(counter + s * iterations),
         rollout_step(plan.action), plan_shift, in ONE call.  Returns the rollout's bufs."""

@@ -4,6 +4,7 @@
     constant_velocity(state8, n)       every human keeps the velocity it has: the 'constant_velocity' human model as a table
     to_goal(state8, n, dt)             every human heads straight for its goal at v_pref and stops there
     from_positions(start_xy, pos, dt)  the velocities that carry the humans through predicted positions
+    stack_modes(*tables)               M such tables as the [B, M, n, H, 2] of lookahead_modes / plan_*_modes
 
 torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
 returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is
@@ -76,3 +77,17 @@ def from_positions(start_xy, positions, dt):
         raise ValueError('dt must be > 0')
     before = torch.cat([start[:, None].to(pos.device), pos[:, :-1]], dim=1)
     return _back((pos - before) / dt, as_numpy)
+
+
+def stack_modes(*tables):
+    """M tables [B, n, H, 2] of one shape -> [B, M, n, H, 2] float64, the human_vel of lookahead_modes / plan_cem_modes /
+    plan_mppi_modes (cn_lookahead_modes): mode m is tables[m].  numpy unless every table is a torch tensor; then torch, on the
+    first table's device."""
+    if not tables:
+        raise ValueError('stack_modes: at least one table')
+    as_numpy = not all(torch.is_tensor(t) for t in tables)
+    ts = [_f64(t.cpu() if as_numpy and torch.is_tensor(t) else t)[0] for t in tables]
+    for t in ts:
+        if t.dim() != 4 or t.shape[3] != 2 or t.shape != ts[0].shape:
+            raise ValueError('stack_modes: tables must share one shape [B, n, H, 2], got %s' % ([tuple(t.shape) for t in ts],))
+    return _back(torch.stack([t.to(ts[0].device) for t in ts], dim=1), as_numpy)

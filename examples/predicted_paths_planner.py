@@ -3,12 +3,16 @@ of the humans is neither ORCA (which reads their goals through the simulator) no
 predicted velocities the CALLER makes from the state after every real step.
 
     python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
+                                               [--futures cv,to_goal [--reduce min] [--risk-penalty 0.5]]
 
 Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
 stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
 `iterations` times), rollout_step(plan.action), plan_shift.  The prediction goes through the host once per step, which is why
 there is no *_rollout form of these calls; the real steps are ORCA, as always.  Prints the success rate, the collision rate
-and the navigation time in the reference's format."""
+and the navigation time in the reference's format.
+--futures plans against several predictors AT ONCE: one plan_cem_modes / plan_mppi_modes call scores every
+candidate against each listed future (cv = constant_velocity, to_goal), equally weighted, and ranks the mean of the returns
+(--reduce min: the worst one) less --risk-penalty times the share of futures that end in a collision."""
 import argparse
 import logging
 import os
@@ -22,7 +26,7 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
-         predictor='to_goal'):
+         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -38,13 +42,19 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
     most = int(round(env.time_limit / env.time_step)) + 2  # every episode has ended by then (Timeout)
     for step in range(most):
         state8, _ = eng.get_state()  # what the planner observes: positions and velocities (to_goal also reads the goals)
-        if predictor == 'to_goal':
-            human_vel = predict.to_goal(state8, horizon, env.time_step)
-        else:
-            human_vel = predict.constant_velocity(state8, horizon)
-        if temperature is None:
+        tables = {'to_goal': lambda: predict.to_goal(state8, horizon, env.time_step),
+                  'constant_velocity': lambda: predict.constant_velocity(state8, horizon)}
+        if futures:  # several futures side by side, one call
+            human_vel = predict.stack_modes(*(tables[name]() for name in futures))
+            if temperature is None:
+                eng.plan_cem_modes(planner, human_vel, step * iterations, reduce=reduce, risk_penalty=risk_penalty)
+            else:
+                eng.plan_mppi_modes(planner, human_vel, temperature, step * iterations, reduce=reduce, risk_penalty=risk_penalty)
+        elif temperature is None:
+            human_vel = tables[predictor]()
             eng.plan_cem_paths(planner, human_vel, step * iterations)
         else:
+            human_vel = tables[predictor]()
             eng.plan_mppi_paths(planner, human_vel, temperature, step * iterations)
         eng.rollout_step(planner.action)
         eng.plan_shift(planner)
@@ -73,10 +83,20 @@ def main():
     ap.add_argument('--init-std', type=float, default=0.5, help='standard deviation a step starts from, in units of v_pref')
     ap.add_argument('--predictor', default='to_goal', choices=['to_goal', 'constant_velocity'],
                     help="the planner's model of the humans (the real steps are always ORCA)")
+    ap.add_argument('--futures', default=None, help='comma-separated predictors (cv, to_goal) to plan against at once, e.g. cv,to_goal')
+    ap.add_argument('--reduce', default='mean', choices=['mean', 'min'], help='--futures: rank the mean or the worst of the returns')
+    ap.add_argument('--risk-penalty', type=float, default=0.0, help='--futures: subtracted per unit of collision probability')
     args = ap.parse_args()
+    names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal'}
+    futures = None
+    if args.futures:
+        unknown = [f for f in args.futures.split(',') if f not in names]
+        if unknown:
+            ap.error('--futures: unknown predictor(s) %s (cv, to_goal)' % ', '.join(unknown))
+        futures = [names[f] for f in args.futures.split(',')]
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
-                      predictor=args.predictor))
+                      predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty))
     return 0
 
 

@@ -704,6 +704,70 @@ int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan
                        const double* human_vel, double temperature, int fit_std, uint32_t counter);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Lookahead under several predicted futures (no version bump: three new symbols, two new structs, one new enum; no existing
+ * struct, enum or counter touched).  A predictor seldom returns one future: a learned trajectory model returns M weighted
+ * modes, a cautious planner holds "keeps walking" beside "heads for its goal".  cn_lookahead_modes scores every branch (b, k)
+ * against M tables at once and reduces the M returns to the number such a planner optimises: the expected return, the worst
+ * case, either one less a penalty on the probability of a collision.  The robot of a branch does not depend on the humans (its
+ * actions are open-loop), so ONE launch moves it once and tests it against the M sets of humans: the action table is read once,
+ * where M cn_lookahead_paths calls read it M times.
+ *   human_vel: DEVICE double [B][M][n_steps][A - 1][2]: human_vel[b][m] is cn_lookahead_paths' table of env b under mode m.  Read
+ *              as 16-byte words: align it to 16 bytes.
+ *   weight:    DEVICE double [B][M], or NULL = every weight 1.0 / (double)M.  Used as given: not normalised, not validated.
+ * Per-mode branch.  Mode m of branch (b, k) is exactly cn_lookahead_paths' branch (b, k) with the table human_vel[b][m], bit
+ * for bit on ret, info, steps and time: the section above holds unchanged — holonomic and CN_UNICYCLE engines, the parked
+ * slots of the `mixed` rule, the velocity a human HAS against the one it chooses, non-finite velocities NOT checked.  Each mode
+ * ends at its own first `done`; Timeout and ReachGoal depend on the robot alone and so end every mode still running at that
+ * step.  Action rows behind the step at which a branch's last mode ends are not read, nor are table rows behind the last step
+ * any branch of env b makes.
+ * Reduction, per branch, float64, every product and sum a separate IEEE operation, sequential in m from 0.0; w_m = weight[b][m]:
+ *   r          CN_MODES_MEAN: sum_m w_m * ret_m.   CN_MODES_MIN: min_m ret_m (weights are not read for it).
+ *   risk       sum_m w_m * (info_m == Collision ? 1.0 : 0.0)
+ *   score      r - risk_penalty * risk
+ *   worst_mode the smallest m that holds the lowest ret_m; worst_info, worst_steps, worst_time: that mode's values.
+ * There is no final_state8, no final_theta and no bootstrap form: they belong to the per-(branch, mode) state, M times the
+ * largest array of cn_lookahead_paths. */
+enum { CN_MODES_MEAN = 0, CN_MODES_MIN = 1 };
+typedef struct cn_path_modes {
+    int32_t n_modes;          /* M: 1 .. 8                                                  */
+    int32_t reduce;           /* CN_MODES_MEAN | CN_MODES_MIN                               */
+    double  risk_penalty;     /* finite, >= 0                                               */
+    const double* human_vel;  /* DEVICE [B][M][n_steps][A-1][2], 16-byte aligned            */
+    const double* weight;     /* DEVICE [B][M], or NULL = every weight 1.0 / (double)M      */
+} cn_path_modes;
+typedef struct cn_modes_out { /* all DEVICE memory                                          */
+    double*  score;       /* [B][K]    required                                             */
+    double*  risk;        /* [B][K]    optional                                             */
+    int32_t* worst_mode;  /* [B][K]    optional                                             */
+    uint8_t* worst_info;  /* [B][K]    optional                                             */
+    int32_t* worst_steps; /* [B][K]    optional                                             */
+    double*  worst_time;  /* [B][K]    optional                                             */
+    double*  ret;         /* [B][K][M] optional per-mode rows: cn_lookahead_out's, per mode */
+    uint8_t* info;        /* [B][K][M] optional                                             */
+    int32_t* steps;       /* [B][K][M] optional                                             */
+    double*  time;        /* [B][K][M] optional                                             */
+} cn_modes_out;
+/* Refused, in this order, before anything is enqueued: NULL modes, modes->human_vel, out or out->score: CN_ERR_INVALID naming
+ * it; n_modes < 1: CN_ERR_INVALID, n_modes > 8: CN_ERR_UNSUPPORTED with the number; a reduce that is neither value:
+ * CN_ERR_INVALID naming it; a risk_penalty that is negative or not finite: CN_ERR_INVALID; everything cn_lookahead_actions
+ * refuses for (n_steps, n_candidates, actions), in its order and with its messages; B K M beyond an int: CN_ERR_UNSUPPORTED.
+ * n_steps == 0: CN_OK, nothing launched, nothing written.  ONE launch of a kernel of its own (lane = branch, the M H humans of an
+ * env shared by its K branches), NOT counted in cn_launch_counts; state, cn_rollout_io arrays, ring levels and the human-model
+ * setting are neither read nor written, a rollout in progress continues as if the call had not happened.  Asynchronous on the
+ * engine's stream: actions, human_vel, weight and the arrays of `out` must stay valid until the launch has run; `modes` and
+ * `out` themselves are copied by the call. */
+int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double* actions /* [B][K][n][2] */,
+                       const cn_path_modes* modes, const cn_modes_out* out);
+/* cn_plan_cem and cn_plan_mppi (below) scoring through cn_lookahead_modes: plan->look.ret receives `score`, plan->look.info,
+ * look.steps and look.time the worst mode's rows; the draw, refit, MPPI update and cn_plan_shift are untouched and rank
+ * look.ret.  human_vel is [B][M][cfg->n_steps][A - 1][2].  Refused: NULL modes first; then every refusal of the cn_plan_* calls;
+ * then cfg->bootstrap != 0: CN_ERR_UNSUPPORTED naming bootstrap; then cn_lookahead_modes' refusals.  No *_rollout form, for the
+ * reason given above; a CN_UNICYCLE engine stays refused as by every cn_plan_* call (cn_lookahead_modes itself serves it). */
+int cn_plan_cem_modes (cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, uint32_t counter);
+int cn_plan_mppi_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes,
+                       double temperature, int fit_std, uint32_t counter);
+
+/* ------------------------------------------------------------------------------------------------------
  * Value-bootstrapped lookahead (no version bump: new symbols only).  The n-step return a value-network policy means,
  *   score = sum_{t<n} gamma^(t dt v_pref) r_t + gamma^(n dt v_pref) V(s_n)
  * (MultiHumanRL.predict, multi_human_rl.py:52, is n = 1; Explorer.update_memory's TD targets train V to mean it), needs V of
