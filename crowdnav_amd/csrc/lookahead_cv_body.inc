@@ -1,8 +1,8 @@
-// The lane body of lookahead_cv_kernel and lookahead_paths_kernel (lookahead_cv_kernel.h) — the transition is stated here and
-// nowhere else.  Included text, not a __device__ function, for rollout_body.inc's reason: as a __forceinline__ function taking
-// the parameter block by reference or by value hipcc gave both instantiations of lookahead_cv_kernel another instruction stream
-// (profiles/lookahead_paths_kernels.txt); as text they keep the parent's.  In scope where it is included: UNI, PATHS (constexpr
-// bool), P (CvParams), action_table, human_vel (nullptr without PATHS), Od.
+// The lane body of lookahead_cv_kernel and lookahead_paths_kernel (lookahead_cv_kernel.h): the loads, the barrier and the book
+// around the transition, whose arithmetic is transition.h's.  Included text, not a __device__ function, for rollout_body.inc's
+// reason: as a __forceinline__ function taking the parameter block by reference or by value hipcc gave both instantiations of
+// lookahead_cv_kernel another instruction stream (profiles/lookahead_paths_kernels.txt).  In scope where it is included: UNI,
+// PATHS (constexpr bool), P (CvParams), action_table, human_vel (nullptr without PATHS), Od.
 // PATHS = false: the velocity a human chooses is the one it has.  PATHS = true: the velocity human h chooses at step t is
 // human_vel[b][t][h] (include/crowdnav_amd.h, "Lookahead under predicted human motion") — step_core's transition with the
 // humans' policy replaced by the table: the swept test of step t reads the velocity the human HAS when the step starts (its
@@ -65,67 +65,31 @@
         }
         if (running) {
             const double2 a = row[t];
-            // the robot's action (step_core: holonomic (vx, vy); unicycle (v, r) with v (cos, sin)(r + theta))
-            double new_vx = a.x, new_vy = a.y, th = 0.0;
-            if (UNI) {
-                th = theta + a.y;
-                new_vx = a.x * cos(a.y + theta);
-                new_vy = a.x * sin(a.y + theta);
-            }
-            // slot order scan over the swept robot-human distances: point_to_segment_dist(px, py, ex, ey, 0, 0) - r_h - r_robot
-            // with the human's CURRENT velocity against the robot's NEW action; the scan stops counting at the first collision
+            // the transition (transition.h): the robot's step, the slot order scan over the swept distances — the human's CURRENT
+            // velocity against the robot's NEW action — and the outcome
+            const RobotStep rs = robot_step(UNI, px, py, a.x, a.y, theta, P.dt);
             double dmin = std::numeric_limits<double>::infinity();
             bool collision = false;
             for (int i = 0; i < H; ++i) {
                 const double2 hp = cur[i], hv = h_vel[vi][i];
-                const double x1 = hp.x - px, y1 = hp.y - py;
-                const double wx = hv.x - new_vx, wy = hv.y - new_vy;
-                const double x2 = x1 + wx * P.dt, y2 = y1 + wy * P.dt;
-                const double sx = x2 - x1, sy = y2 - y1;
-                double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-                u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-                const bool degenerate = (sx == 0.0 && sy == 0.0);
-                const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
-                const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
-                const double c = norm2(cx, cy) - h_rv[i].x - rad;
-                const bool hit = c < 0.0;
-                dmin = (!collision && !hit && c < dmin) ? c : dmin;
-                collision = collision || hit;
+                const double2 cp = closest_point(hp.x - px, hp.y - py, hv.x - rs.vx, hv.y - rs.vy, P.dt);
+                const double c = norm2(cp.x, cp.y) - h_rv[i].x - rad;
+                dmin = scan_dmin(dmin, collision, c);
+                collision = scan_collision(collision, c);
             }
-            double endx = px + new_vx * P.dt, endy = py + new_vy * P.dt;
-            if (UNI) {
-                endx = px + cos(th) * a.x * P.dt;
-                endy = py + sin(th) * a.x * P.dt;
-            }
-            const bool reaching = norm2(endx - gx, endy - gy) < rad;
-            double reward = 0.0;
-            if (gtime >= P.time_limit - 1.0) {
-                reward = 0.0, ends = true, info = CN_TIMEOUT;
-            } else if (collision) {
-                reward = P.collision_penalty, ends = true, info = CN_COLLISION;
-            } else if (reaching) {
-                reward = P.success_reward, ends = true, info = CN_REACH_GOAL;
-            } else if (dmin < P.discomfort_dist) {
-                reward = (dmin - P.discomfort_dist) * P.discomfort_factor * P.dt;
-                info = CN_DANGER;
-            } else {
-                info = CN_NOTHING;
-            }
+            const bool reaching = norm2(rs.ex - gx, rs.ey - gy) < rad;
+            const Outcome o = outcome_of(gtime >= P.time_limit - 1.0, collision, reaching, dmin, P.success_reward, P.collision_penalty,
+                                         P.discomfort_dist, P.discomfort_factor, P.dt);
+            info = o.info, ends = o.done;
             // the book (CN_BOOK_TRANSITION; a running branch has made t transitions) and the clock
             const double disc = (t < kMaxDiscount && t < P.discount_len) ? P.discount[t] : 0.0;
-            cur_return = cur_return + disc * reward;
+            cur_return = cur_return + disc * o.reward;
             ++cur_steps;
             gtime += P.dt;
             // Agent.step
-            px = endx, py = endy;
-            if (UNI) {
-                const double theta1 = python_fmod(th, 2 * 3.141592653589793);
-                vx = a.x * cos(theta1);
-                vy = a.x * sin(theta1);
-                theta = theta1;
-            } else {
-                vx = new_vx, vy = new_vy;
-            }
+            px = rs.ex, py = rs.ey;
+            const RobotAfter ra = robot_after(UNI, a.x, rs.th, rs.vx, rs.vy, theta);
+            vx = ra.vx, vy = ra.vy, theta = ra.theta;
             ends = ends || t == P.n_steps - 1;
         }
         // the humans' move of this step, by the lane that owns each: one multiply and one add per coordinate

@@ -33,7 +33,7 @@ struct CvParams {
 
 constexpr int kCvHumans = 63;  // check_config: num_humans <= 63
 
-// Both kernels' body is lookahead_cv_body.inc: the decomposition above and the transition, stated once, with the compile-time
+// Both kernels' body is lookahead_cv_body.inc: the decomposition above around transition.h's functions, with the compile-time
 // flag PATHS choosing where a human's velocity comes from.
 template <bool UNI>
 __global__ __launch_bounds__(kWave) void lookahead_cv_kernel(CvParams P, const double* action_table, const cn_lookahead_out* Od) {

@@ -10,10 +10,10 @@
 //     the mode's book: a running bit, return, info, steps, end time.  The books live in registers: every
 //     loop over modes below is fully unrolled over the compile-time cap kModesMax with `m < M` as a uniform guard, so nothing is
 //     indexed dynamically and nothing lives in scratch.
-// The transition itself is lookahead_cv_body.inc's with PATHS = true, restated here line for line (that file is included text
-// whose two kernels must keep their instruction streams, so it is not parametrised further); tests/test_lookahead_modes.py pins
-// the restatement: every mode's ret, info, steps and time are bit-equal to cn_lookahead_paths with that mode's table.  Timeout
-// and ReachGoal depend on the robot alone and so end every mode still running at that step; a Collision ends its own mode.
+// The transition is transition.h's, called in lookahead_cv_body.inc's order with PATHS = true (that file is included text whose
+// two kernels are not parametrised further); tests/test_lookahead_modes.py pins it: every mode's ret, info, steps and time are
+// bit-equal to cn_lookahead_paths with that mode's table.  Timeout and ReachGoal depend on the robot alone and so end every
+// mode still running at that step; a Collision ends its own mode.
 //
 // Humans.  Row r = m H + h of the workgroup is human slot h + 1 under mode m: M H rows, up to 8 x 63 = 504, more than the 64
 // lanes.  Row r is owned by lane r % 64: an owner loops over r = lane, lane + 64, ...  Positions and velocities are
@@ -100,19 +100,8 @@ __global__ __launch_bounds__(kWave) void lookahead_modes_kernel(CvParams P, cons
         if (lane < MH) v0 = vel_rows[off0 + (size_t)t * (size_t)H];  // the velocity this lane's first human chooses at step t
         if (running) {
             const double2 a = row[t];
-            // the robot's action (step_core: holonomic (vx, vy); unicycle (v, r) with v (cos, sin)(r + theta))
-            double new_vx = a.x, new_vy = a.y, th = 0.0;
-            if (UNI) {
-                th = theta + a.y;
-                new_vx = a.x * cos(a.y + theta);
-                new_vy = a.x * sin(a.y + theta);
-            }
-            double endx = px + new_vx * P.dt, endy = py + new_vy * P.dt;
-            if (UNI) {
-                endx = px + cos(th) * a.x * P.dt;
-                endy = py + sin(th) * a.x * P.dt;
-            }
-            const bool reaching = norm2(endx - gx, endy - gy) < rad;
+            const RobotStep rs = robot_step(UNI, px, py, a.x, a.y, theta, P.dt);  // once per lane and step (transition.h)
+            const bool reaching = norm2(rs.ex - gx, rs.ey - gy) < rad;
             const bool timeout = gtime >= P.time_limit - 1.0;
             const double disc = (t < kMaxDiscount && t < P.discount_len) ? P.discount[t] : 0.0;
             gtime += P.dt;  // the clock after this step, which a mode ending here reports
@@ -120,52 +109,31 @@ __global__ __launch_bounds__(kWave) void lookahead_modes_kernel(CvParams P, cons
 #pragma unroll
             for (int m = 0; m < kModesMax; ++m) {
                 if (m < M && (running >> m & 1u)) {
-                    // slot order scan over the swept robot-human distances of mode m (lookahead_cv_body.inc): the human's
-                    // CURRENT velocity against the robot's NEW action; the scan stops counting at the first collision
+                    // slot order scan over the swept distances of mode m and its outcome (transition.h)
                     const double2* const mp = cur + m * H;
                     const double2* const mv = vcur + m * H;
                     double dmin = std::numeric_limits<double>::infinity();
                     bool collision = false;
                     for (int i = 0; i < H; ++i) {
                         const double2 hp = mp[i], hv = mv[i];
-                        const double x1 = hp.x - px, y1 = hp.y - py;
-                        const double wx = hv.x - new_vx, wy = hv.y - new_vy;
-                        const double x2 = x1 + wx * P.dt, y2 = y1 + wy * P.dt;
-                        const double sx = x2 - x1, sy = y2 - y1;
-                        double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-                        u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-                        const bool degenerate = (sx == 0.0 && sy == 0.0);
-                        const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
-                        const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
-                        const double c = norm2(cx, cy) - h_rad[i] - rad;
-                        const bool hit = c < 0.0;
-                        dmin = (!collision && !hit && c < dmin) ? c : dmin;
-                        collision = collision || hit;
+                        const double2 cp = closest_point(hp.x - px, hp.y - py, hv.x - rs.vx, hv.y - rs.vy, P.dt);
+                        const double c = norm2(cp.x, cp.y) - h_rad[i] - rad;
+                        dmin = scan_dmin(dmin, collision, c);
+                        collision = scan_collision(collision, c);
                     }
-                    double reward = 0.0;
-                    int info = CN_NOTHING;
-                    bool ends = last;
-                    if (timeout) {
-                        reward = 0.0, ends = true, info = CN_TIMEOUT;
-                    } else if (collision) {
-                        reward = P.collision_penalty, ends = true, info = CN_COLLISION;
-                    } else if (reaching) {
-                        reward = P.success_reward, ends = true, info = CN_REACH_GOAL;
-                    } else if (dmin < P.discomfort_dist) {
-                        reward = (dmin - P.discomfort_dist) * P.discomfort_factor * P.dt;
-                        info = CN_DANGER;
-                    }
+                    const Outcome o = outcome_of(timeout, collision, reaching, dmin, P.success_reward, P.collision_penalty,
+                                                 P.discomfort_dist, P.discomfort_factor, P.dt);
                     // the mode's book (CN_BOOK_TRANSITION; a running mode has made t transitions)
-                    m_ret[m] = m_ret[m] + disc * reward;
-                    m_info[m] = info;
+                    m_ret[m] = m_ret[m] + disc * o.reward;
+                    m_info[m] = o.info;
                     m_steps[m] = t + 1;
                     m_time[m] = gtime;
-                    if (ends) running &= ~(1u << m);
+                    if (o.done || last) running &= ~(1u << m);
                 }
             }
             // Agent.step
-            px = endx, py = endy;
-            if (UNI) theta = python_fmod(th, 2 * 3.141592653589793);
+            px = rs.ex, py = rs.ey;
+            theta = robot_after(UNI, a.x, rs.th, rs.vx, rs.vy, theta).theta;
         }
         // the humans' move of this step, by the lane that owns each row: one multiply and one add per coordinate
         if (lane < MH) {

@@ -339,19 +339,14 @@ __device__ __forceinline__ double swept_distance(const AgentRegs& r, bool human,
                                                  double new_vx, double new_vy, double dt, double robot_rad) {
     const double x1 = r.px - rp.x, y1 = r.py - rp.y;
     const double wx = r.vx - act_x, wy = r.vy - act_y;
-    const double x2 = x1 + wx * dt, y2 = y1 + wy * dt;
-    const double sx = x2 - x1, sy = y2 - y1;
-    double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-    u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-    const bool degenerate = (sx == 0.0 && sy == 0.0);  // utils.py:11-13
-    const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
-    const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
+    const double2 cp = closest_point(x1, y1, wx, wy, dt);
     const double endx = r.px + new_vx * dt, endy = r.py + new_vy * dt;
-    const double d = norm2(human ? cx : endx - r.gx, human ? cy : endy - r.gy);
+    const double d = norm2(human ? cp.x : endx - r.gx, human ? cp.y : endy - r.gy);
     return human ? d - r.rad - robot_rad : d;
 }
 
 // reduce (every lane of the env, identically): the env's distances (Smem::closest) to reward / done / info.
+// (transition.h states the rule — scan_dmin / scan_collision / outcome_of; this is its branch-free form, kept as text)
 struct StepOutcome {
     double reward, dmin;
     int info;

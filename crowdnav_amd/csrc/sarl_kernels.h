@@ -31,6 +31,7 @@
 
 #include "orca_device.h"     // wave_lds_sync
 #include "scenario_device.h"  // norm2
+#include "transition.h"
 
 namespace cn {
 
@@ -499,18 +500,8 @@ __device__ inline double sarl_reward_of(const SarlCfg& C, const double2* pos, co
     }
     for (int i = 1; i < A; ++i) {
         const double2 hp = pos[g0 + i], hv = vel[g0 + i];
-        const double x1 = hp.x - rp.x, y1 = hp.y - rp.y;
-        const double wx = hv.x - ax, wy = hv.y - ay;
-        const double x2 = x1 + wx * C.dt, y2 = y1 + wy * C.dt;
-        const double sx = x2 - x1, sy = y2 - y1;
-        double d;
-        if (sx == 0.0 && sy == 0.0) {
-            d = norm2(0.0 - x1, 0.0 - y1);
-        } else {
-            double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-            u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-            d = norm2((x1 + u * sx) - 0.0, (y1 + u * sy) - 0.0);
-        }
+        const double2 cp = closest_point(hp.x - rp.x, hp.y - rp.y, hv.x - ax, hv.y - ay, C.dt);  // (transition.h)
+        const double d = norm2(cp.x, cp.y);
         const double c = d - rv[g0 + i].x - rrad;
         if (c < 0.0) {
             collision = true;

@@ -23,6 +23,7 @@
 #include "kd_order.h"
 #include "scenario_device.h"
 #include "scenario_wave.h"
+#include "transition.h"
 
 namespace cn {
 
@@ -969,12 +970,6 @@ struct StepResult {  // meaningful on the robot lane
 // One transition for the lane's agent (crowd_sim.py:317-420).  `r` is updated in place when update != 0.
 // new_vx/new_vy: the velocity this lane's agent chose (float32 for ORCA agents, the action for the robot).
 // Must be called by all 64 lanes (contains workgroup barriers).
-__device__ __forceinline__ double python_fmod(double x, double y) {  // python's float %: result takes the sign of y
-    double m = fmod(x, y);
-    if (m != 0.0 && ((m < 0.0) != (y < 0.0))) m += y;
-    return m;
-}
-
 // UNI (compile time): the robot may be a unicycle.  The holonomic instantiation carries none of that code — it sits
 // inside the fused rollout loop, where 20 extra VGPRs and a few dead branches cost 7 % (712 -> 665 M env-steps/s).
 template <int MAXL, bool UNI, bool KD, bool COMPACT = false>
@@ -1035,13 +1030,7 @@ __device__ __forceinline__ void step_core(const Params& P, const Smem& s, const 
         const double x1 = r.px - rp.x, y1 = r.py - rp.y;
         const double wx = r.vx - act.x, wy = r.vy - act.y;
         const double c_dt = step_param<COMPACT>(P, s, kParDt);
-        const double x2 = x1 + wx * c_dt, y2 = y1 + wy * c_dt;
-        const double sx = x2 - x1, sy = y2 - y1;
-        double u = ((0.0 - x1) * sx + (0.0 - y1) * sy) / (sx * sx + sy * sy);
-        u = (u > 1.0) ? 1.0 : ((u < 0.0) ? 0.0 : u);
-        const bool degenerate = (sx == 0.0 && sy == 0.0);  // utils.py:11-13
-        const double cx = degenerate ? 0.0 - x1 : (x1 + u * sx) - 0.0;
-        const double cy = degenerate ? 0.0 - y1 : (y1 + u * sy) - 0.0;
+        const double2 cp = closest_point(x1, y1, wx, wy, c_dt);
         double endx = r.px + new_vx * c_dt, endy = r.py + new_vy * c_dt;
         if (unicycle) {
             const double th = theta0 + rot_r;
@@ -1049,7 +1038,7 @@ __device__ __forceinline__ void step_core(const Params& P, const Smem& s, const 
             endy = r.py + sin(th) * rot_v * c_dt;
         }
         const double2 goal = COMPACT ? s.goal2[L.lane] : make_double2(r.gx, r.gy);
-        const double d = norm2(human ? cx : endx - goal.x, human ? cy : endy - goal.y);
+        const double d = norm2(human ? cp.x : endx - goal.x, human ? cp.y : endy - goal.y);
         if (human) {
             s.closest[L.lane] = d - (COMPACT ? s.rad[L.lane] : r.rad) - s.rad[L.ebase];
         } else {
