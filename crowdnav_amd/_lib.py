@@ -30,6 +30,9 @@ HUMAN_MODELS = ('orca', 'constant_velocity')
 MODES_MEAN, MODES_MIN = 0, 1  # CN_MODES_*
 MODES_REDUCE = ('mean', 'min')
 MODES_MAX = 8  # cn_path_modes.n_modes
+PREDICT_CONSTANT_VELOCITY, PREDICT_TO_GOAL = 0, 1  # CN_PREDICT_*
+PREDICT_MODELS = ('constant_velocity', 'to_goal')
+PREDICT_ALIASES = {'cv': 'constant_velocity'}
 
 
 class CrowdNavAmdError(RuntimeError):
@@ -86,6 +89,15 @@ class CnPathModes(C.Structure):
     """struct cn_path_modes (include/crowdnav_amd.h): M predicted futures and how their returns are reduced; weight may be NULL."""
     _fields_ = [
         ('n_modes', C.c_int32), ('reduce', C.c_int32), ('risk_penalty', C.c_double),
+        ('human_vel', C.c_void_p), ('weight', C.c_void_p),
+    ]
+
+
+class CnPredictors(C.Structure):
+    """struct cn_predictors (include/crowdnav_amd.h): the device predictors of M futures, the scratch table they fill and how the
+    planner reduces the M returns; weight may be NULL."""
+    _fields_ = [
+        ('n_modes', C.c_int32), ('model', C.c_int32 * 8), ('reduce', C.c_int32), ('risk_penalty', C.c_double),
         ('human_vel', C.c_void_p), ('weight', C.c_void_p),
     ]
 
@@ -220,6 +232,12 @@ SYMBOLS = {
     'cn_plan_cem_modes': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.POINTER(CnPathModes), C.c_uint32]),
     'cn_plan_mppi_modes': (C.c_int, [_P, C.POINTER(CnPlanCfg), C.POINTER(CnPlan), C.POINTER(CnPathModes), C.c_double, C.c_int,
                                      C.c_uint32]),
+    # the shipped predictors on the device, and the closed loop that predicts, plans, steps and shifts in one call (no version bump)
+    'cn_predict': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), _P]),
+    'cn_plan_cem_predict_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
+                                              C.POINTER(CnPredictors), C.c_uint32]),
+    'cn_plan_mppi_predict_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
+                                               C.POINTER(CnPredictors), C.c_double, C.c_int, C.c_uint32]),
 }
 
 _lib = None

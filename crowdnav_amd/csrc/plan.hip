@@ -3,7 +3,8 @@
 // A planner is a CALLER of the engine: candidates are scored through cn_lookahead_actions / cn_lookahead_values (the *_paths
 // calls: cn_lookahead_paths / cn_lookahead_paths_values; the *_modes calls: cn_lookahead_modes) and real steps
 // made through cn_rollout_step, by their C entry points and therefore with their checks, their scenario-ring fill and their
-// launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior), enqueued on the
+// launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior, and the
+// shipped predictors' table: cn_predict, in front of every planning step of the cn_plan_*_predict_rollout calls), enqueued on the
 // engine's stream.  Nothing here synchronises, allocates or counts.
 #include "engine_host.h"
 #include "plan_kernels.h"
@@ -169,17 +170,78 @@ int run_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, con
     return CN_OK;
 }
 
-// The closed loop of either planner
+// The device predictors of a call, checked: M and the CN_PREDICT_* values of its modes as predict_kernel's argument word
+struct Predict {
+    int n_modes = 0;
+    uint32_t models = 0;
+};
+
+// n_modes and the models, in the header's order; nothing else of the call is looked at
+int predict_check_models(int n_modes, const int32_t* model, const char* who, Predict* out) {
+    if (n_modes < 1) return fail(CN_ERR_INVALID, "%s: n_modes must be >= 1 (got %d)", who, n_modes);
+    if (n_modes > cn::kPredictMaxModes)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_modes = %d exceeds the %d modes of a table", who, n_modes, cn::kPredictMaxModes);
+    out->n_modes = n_modes, out->models = 0;
+    for (int m = 0; m < n_modes; ++m) {
+        if (model[m] != CN_PREDICT_CONSTANT_VELOCITY && model[m] != CN_PREDICT_TO_GOAL)
+            return fail(CN_ERR_INVALID, "%s: model[%d] = %d unknown (CN_PREDICT_CONSTANT_VELOCITY = 0, CN_PREDICT_TO_GOAL = 1)", who, m,
+                        model[m]);
+        out->models |= cn::predict_model_bits(m, (uint32_t)model[m]);
+    }
+    return CN_OK;
+}
+
+// ... and the table's size: predict_kernel indexes rows with size_t, the grid counts workgroups in an unsigned
+int predict_check_size(const cn_engine* e, int n_steps, int n_modes, const char* who) {
+    const uint64_t lanes = (uint64_t)e->P.B * (uint64_t)n_modes * (uint64_t)(e->P.A - 1);
+    if (lanes > (uint64_t)INT32_MAX || (lanes > 0 && (uint64_t)n_steps > (uint64_t)INT32_MAX / lanes))
+        return fail(CN_ERR_UNSUPPORTED, "%s: num_envs * n_modes * n_steps * num_humans = %llu * %d rows exceed the %llu a launch "
+                    "indexes", who, (unsigned long long)lanes, n_steps, (unsigned long long)INT32_MAX);
+    return CN_OK;
+}
+
+int run_predict(cn_engine* e, int n_steps, const Predict& pred, double* human_vel) {
+    const cn::Params& P = e->P;
+    hipLaunchKernelGGL(cn::predict_kernel, dim3(plan_grid((size_t)P.B * pred.n_modes * (P.A - 1))), dim3(cn::kPlanBlock), 0, e->stream,
+                       P.B, P.A, pred.n_modes, n_steps, P.dt, pred.models, (const double2*)e->S.pos, (const double2*)e->S.vel,
+                       (const double2*)e->S.goal, (const double2*)e->S.rv, (double2*)human_vel);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
+// The closed loop of either planner.  pred (the *_predict_rollout calls, whose checks of it precede this): every planning step
+// scores against the table the device predictors make from the state as it then stands.
 int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
-                uint32_t counter, const char* who, const Mppi* mppi) {
+                uint32_t counter, const char* who, const Mppi* mppi, const cn_predictors* pred = nullptr,
+                const Predict& models = Predict{}) {
     int rc = plan_check(e, cfg, plan, who, mppi);
     if (rc || (rc = plan_check_io(e, io, plan))) return rc;
     if (n_real_steps < 0) return fail(CN_ERR_INVALID, "%s: n_real_steps must be >= 0 (got %d)", who, n_real_steps);
+    // M == 1: the *_paths planner (bootstrap served); M > 1: the *_modes planner
+    const bool many = pred && pred->n_modes > 1;
+    const cn_path_modes modes{many ? pred->n_modes : 0, many ? pred->reduce : 0, many ? pred->risk_penalty : 0.0,
+                              pred ? pred->human_vel : nullptr, many ? pred->weight : nullptr};
+    if (many && (rc = plan_check_modes(e, cfg, plan, &modes, who))) return rc;
+    if (pred && (rc = predict_check_size(e, cfg->n_steps, pred->n_modes, who))) return rc;
     for (int s = 0; s < n_real_steps; ++s) {
-        if ((rc = bind(e)) || (rc = run_plan(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations, mppi))) return rc;
+        if ((rc = bind(e)) || (pred && (rc = run_predict(e, cfg->n_steps, models, pred->human_vel)))) return rc;
+        if ((rc = run_plan(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations, mppi, pred && !many ? pred->human_vel : nullptr,
+                           many ? &modes : nullptr)))
+            return rc;
         if ((rc = cn_rollout_step(e, io, plan->action)) || (rc = run_shift(e, io, cfg, plan))) return rc;
     }
     return CN_OK;
+}
+
+// the checks of `pred` that come before everything else of a *_predict_rollout call
+int predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                    const cn_predictors* pred, uint32_t counter, const char* who, const Mppi* mppi) {
+    if (!pred) return fail(CN_ERR_INVALID, "%s: pred is NULL", who);
+    if (!pred->human_vel) return fail(CN_ERR_INVALID, "%s: pred->human_vel is NULL", who);
+    Predict models;
+    const int rc = predict_check_models(pred->n_modes, pred->model, who, &models);
+    if (rc) return rc;
+    return run_rollout(e, io, n_real_steps, cfg, plan, counter, who, mppi, pred, models);
 }
 
 }  // namespace
@@ -271,6 +333,30 @@ int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps
                          double temperature, int fit_std, uint32_t counter) {
     const Mppi mppi{temperature, fit_std};
     return run_rollout(e, io, n_real_steps, cfg, plan, counter, "cn_plan_mppi_rollout", &mppi);
+}
+
+int cn_predict(cn_engine* e, int n_steps, int n_modes, const int32_t* models, double* human_vel) {
+    if (!models) return fail(CN_ERR_INVALID, "cn_predict: models is NULL");
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_predict: human_vel is NULL");
+    Predict pred;
+    int rc = predict_check_models(n_modes, models, "cn_predict", &pred);
+    if (rc) return rc;
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_predict: n_steps must be >= 0 (got %d)", n_steps);
+    if (!e) return fail(CN_ERR_INVALID, "cn_predict: engine is NULL");
+    if ((rc = predict_check_size(e, n_steps, n_modes, "cn_predict")) || n_steps == 0) return rc;
+    if ((rc = bind(e))) return rc;
+    return run_predict(e, n_steps, pred, human_vel);
+}
+
+int cn_plan_cem_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                                const cn_predictors* pred, uint32_t counter) {
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_cem_predict_rollout", nullptr);
+}
+
+int cn_plan_mppi_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
+                                 const cn_predictors* pred, double temperature, int fit_std, uint32_t counter) {
+    const Mppi mppi{temperature, fit_std};
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_rollout", &mppi);
 }
 
 }  // extern "C"

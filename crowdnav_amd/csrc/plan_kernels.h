@@ -12,6 +12,7 @@
 //   plan_refit_kernel  workgroup = env, one wave  ranks by counting over the scores in LDS; best row; elite mean / std
 //   plan_mppi_kernel   workgroup = env, one wave  the same ranks and best row; weights exp((s - s_max) / T) in LDS; weighted mean / std
 //   plan_shift_kernel  lane = (env, component)    walks t upwards in place: row t <- row t + 1, or the prior at an episode start
+//   predict_kernel     lane = (env, mode, human)  the table of predicted human velocities the *_paths / *_modes planners score against
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -235,6 +236,48 @@ __global__ __launch_bounds__(kPlanBlock) void plan_shift_kernel(int B, int A, in
         for (int t = 0; t + 1 < n; ++t) m[2 * t] = m[2 * (t + 1)];
     }
     for (int t = 0; t < n; ++t) s[2 * t] = init_std;
+}
+
+// The shipped predictors (cn_predict; crowdnav_amd/predict.py restates them on a host copy of the state bit for bit):
+// human_vel[b][m][t][h] from the engine's state as it stands.  Lane = (env, mode, human), h fastest, so the lanes of one
+// (env, mode) store consecutive 16-byte rows of step t; the lane reads its human once and walks t sequentially (to_goal is a
+// recurrence in the position).  No LDS, no barrier, nothing of the engine written.  `models` holds the CN_PREDICT_* value of
+// mode m in bits 4 m .. 4 m + 3: the M <= 8 models travel by value in one argument word, so no lane indexes an argument array.
+constexpr int kPredictMaxModes = 8;
+__host__ __device__ inline uint32_t predict_model_bits(int m, uint32_t model) { return model << (4 * m); }
+
+__global__ __launch_bounds__(kPlanBlock) void predict_kernel(int B, int A, int M, int n, double dt, uint32_t models,
+                                                             const double2* pos, const double2* vel, const double2* goal,
+                                                             const double2* rv, double2* human_vel) {
+    const size_t i = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
+    const size_t H = (size_t)(A - 1);
+    if (i >= (size_t)B * M * H) return;
+    const size_t h = i % H, bm = i / H, b = bm / M;
+    const uint32_t model = (models >> (4 * (uint32_t)(bm % M))) & 0xfu;
+    const size_t agent = b * A + h + 1;
+    double2* out = human_vel + bm * n * H + h;
+    if (model == 0u) {  // CN_PREDICT_CONSTANT_VELOCITY: the velocity the human has, at every step
+        const double2 v = vel[agent];
+        for (int t = 0; t < n; ++t) out[(size_t)t * H] = v;
+        return;
+    }
+    // CN_PREDICT_TO_GOAL, predict.to_goal line for line: straight for the goal at v_pref, the last step shortened to land on it
+    double2 p = pos[agent];
+    const double2 g = goal[agent];
+    const double v_pref = rv[agent].y;
+    const double reach = v_pref * dt;
+    for (int t = 0; t < n; ++t) {
+        const double dx = g.x - p.x, dy = g.y - p.y;
+        const double dist = sqrt(dx * dx + dy * dy);
+        double2 v = make_double2(0.0, 0.0);
+        if (dist > 0.0) {
+            if (dist <= reach) v = make_double2(dx / dt, dy / dt);
+            else v = make_double2((dx / dist) * v_pref, (dy / dist) * v_pref);
+        }
+        out[(size_t)t * H] = v;
+        p.x = p.x + v.x * dt;
+        p.y = p.y + v.y * dt;
+    }
 }
 
 }  // namespace cn

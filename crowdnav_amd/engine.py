@@ -90,6 +90,38 @@ class Plan(object):
         return out
 
 
+def _predict_models(who, models):
+    """(CN_PREDICT_* values, whether `models` was a single name) of a predictor argument: a name or a sequence of 1 ..
+    MODES_MAX names, 'cv' standing for 'constant_velocity'.  Checked before the library is asked."""
+    single = isinstance(models, str)
+    names = [models] if single else list(models) if isinstance(models, (list, tuple)) else None
+    if names is None or not 1 <= len(names) <= _lib.MODES_MAX:
+        raise ValueError('%s: models must be a name or a sequence of 1 .. %d names, got %r' % (who, _lib.MODES_MAX, models))
+    codes = []
+    for name in names:
+        name = _lib.PREDICT_ALIASES.get(name, name) if isinstance(name, str) else name
+        if name not in _lib.PREDICT_MODELS:
+            raise ValueError("%s: unknown predictor %r (one of %s, or 'cv')" % (who, name, _lib.PREDICT_MODELS))
+        codes.append(_lib.PREDICT_MODELS.index(name))
+    return codes, single
+
+
+class Predictors(object):
+    """What BatchedCrowdSim.plan_predict_begin returns: the device predictors of M futures for one Plan (struct cn_predictors).
+    human_vel float64 [B, M, plan.n, H, 2] is the scratch table plan_predict_rollout fills before every planning step — after
+    a call it holds the prediction the LAST planning step scored against; weights float64 [B, M] or None."""
+
+    def __init__(self, eng, plan, codes, weights, reduce, risk_penalty):
+        self.engine, self.plan = weakref.ref(eng), weakref.ref(plan)
+        self.models = tuple(_lib.PREDICT_MODELS[c] for c in codes)
+        M = len(codes)
+        self.human_vel = torch.zeros((eng.B, M, plan.n, eng.H, 2), dtype=torch.float64, device=eng.device)
+        self.weights = None if weights is None else torch.as_tensor(weights, dtype=torch.float64).to(eng.device).contiguous().clone()
+        self.c = _lib.CnPredictors(n_modes=M, model=(C.c_int32 * 8)(*codes), reduce=_lib.MODES_REDUCE.index(reduce),
+                                   risk_penalty=float(risk_penalty), human_vel=self.human_vel.data_ptr(),
+                                   weight=None if self.weights is None else self.weights.data_ptr())
+
+
 class BatchedCrowdSim(object):
     """B crowd-navigation envs resident in HBM.  All tensors returned live on the engine's device."""
 
@@ -642,6 +674,60 @@ class BatchedCrowdSim(object):
         rollout_step(plan.action), plan_shift, in ONE call.  Returns the rollout's bufs."""
         return self._plan_call('mppi_rollout', plan, float(temperature), int(bool(fit_std)), rollout=True, n_real=n_real,
                                counter=counter)
+
+    # ---------------------------------------------------------------- the shipped predictors on the device (cn_predict)
+    def predict(self, n, models='to_goal', out=None):
+        """The table of predicted human velocities crowdnav_amd.predict makes from get_state(), made on the device from the
+        state as it stands, in one launch (cn_predict): bit for bit predict.constant_velocity(state8, n) or
+        predict.to_goal(state8, n, time_step).  models: 'constant_velocity' (alias 'cv') or 'to_goal' returns float64
+        [B, n, H, 2], lookahead_paths' table; a sequence of 1 .. 8 such names [B, M, n, H, 2], lookahead_modes' (mode m by
+        models[m]).  `out` reuses a contiguous float64 device tensor of that shape.  Any engine, ORCA-robot and unicycle ones
+        included: only the humans are read, and nothing of the engine — state, rollout buffers, ring levels,
+        lookahead_human_model, launch counters — is written.  n = 0 is a no-op: the empty tensor is returned."""
+        codes, single = _predict_models('predict', models)
+        n = int(n)
+        if n < 0:
+            raise ValueError('predict: n must be >= 0')
+        shape = (self.B, n, self.H, 2) if single else (self.B, len(codes), n, self.H, 2)
+        if out is None:
+            out = self._new(shape, torch.float64)
+        elif not self._dense(out, torch.float64, shape):
+            raise ValueError('predict: out must be a contiguous %s %s tensor on %s' % (torch.float64, shape, self.device))
+        if n > 0:
+            check(self._lib.cn_predict(self._h, n, len(codes), (C.c_int32 * len(codes))(*codes), _ptr(out)))
+        return out
+
+    def plan_predict_begin(self, plan, models, weights=None, reduce='mean', risk_penalty=0.0):
+        """The device predictors a closed loop plans against (struct cn_predictors), for plan_predict_rollout: models as in
+        predict() — one name: the plan_*_paths planners; a sequence of M names: the plan_*_modes planners with weights
+        ([B, M] float64 or None = 1 / M each; copied), reduce ('mean' | 'min') and risk_penalty as in lookahead_modes (a
+        sequence of ONE name is the paths planner too: M = 1 reads neither).  Returns a Predictors holder that owns the scratch
+        table .human_vel [B, M, plan.n, H, 2] the predictions are written to."""
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        codes, _ = _predict_models('plan_predict_begin', models)
+        if reduce not in _lib.MODES_REDUCE:
+            raise ValueError('plan_predict_begin: reduce must be one of %s, got %r' % (_lib.MODES_REDUCE, reduce))
+        if weights is not None:
+            wshape = tuple(getattr(weights, 'shape', np.shape(weights)))
+            if wshape != (self.B, len(codes)):
+                raise ValueError('plan_predict_begin: weights must be [%d, M = %d], got %s' % (self.B, len(codes), wshape))
+        return Predictors(self, plan, codes, weights, reduce, risk_penalty)
+
+    def plan_predict_rollout(self, plan, pred, n_real, counter, temperature=None, fit_std=False):
+        """n_real closed-loop steps against the device predictors in ONE call, nothing on the host in between
+        (cn_plan_cem_predict_rollout; with a temperature cn_plan_mppi_predict_rollout): per step predict() from the state as
+        it stands into pred.human_vel, plan_cem_paths / plan_mppi_paths (M > 1: plan_cem_modes / plan_mppi_modes) with
+        counter + s * iterations, rollout_step(plan.action), plan_shift — bit for bit what those calls give with
+        crowdnav_amd.predict's tables of get_state().  Returns the rollout's bufs."""
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        if not isinstance(pred, Predictors) or pred.engine() is not self or pred.plan() is not plan:
+            raise ValueError('pred: the Predictors made by this engine\'s plan_predict_begin() for this plan')
+        if temperature is None:
+            return self._plan_call('cem_predict_rollout', plan, C.byref(pred.c), rollout=True, n_real=n_real, counter=counter)
+        return self._plan_call('mppi_predict_rollout', plan, C.byref(pred.c), float(temperature), int(bool(fit_std)), rollout=True,
+                               n_real=n_real, counter=counter)
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):

@@ -6,6 +6,11 @@
     from_positions(start_xy, pos, dt)  the velocities that carry the humans through predicted positions
     stack_modes(*tables)               M such tables as the [B, M, n, H, 2] of lookahead_modes / plan_*_modes
 
+constant_velocity and to_goal also exist on the device: BatchedCrowdSim.predict (cn_predict) makes the same tables from the
+engine's own state in one launch, bit for bit what these functions give on get_state() — they are its oracle — and
+plan_predict_rollout runs the whole closed loop on them without the host.  A predictor of the caller's own goes through the
+functions here and the per-step calls.
+
 torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
 returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is
 the robot).  Under the `mixed` rule the parked placeholders stand still at their goals with zero velocity, so constant_velocity
@@ -24,6 +29,13 @@ def _f64(x):
 def _back(t, as_numpy):
     t = t.contiguous()
     return t.numpy() if as_numpy else t
+
+
+def _sqrt(x):
+    """The correctly rounded square root.  torch's float64 sqrt on the CPU goes through a vector math library that is within an
+    ulp but not always correctly rounded (about 1 % of arguments differ); numpy's is the IEEE one, as is torch's on the device.
+    cn_predict restates to_goal bit for bit, so every operation here has to be the IEEE one."""
+    return torch.from_numpy(np.sqrt(x.numpy())) if x.device.type == 'cpu' else torch.sqrt(x)
 
 
 def _humans(state8):
@@ -55,7 +67,7 @@ def to_goal(state8, n, dt):
     out = torch.zeros((humans.shape[0], n, humans.shape[1], 2), dtype=torch.float64, device=humans.device)
     for t in range(n):
         d = goal - p
-        dist = torch.sqrt(d[..., 0:1] * d[..., 0:1] + d[..., 1:2] * d[..., 1:2])
+        dist = _sqrt(d[..., 0:1] * d[..., 0:1] + d[..., 1:2] * d[..., 1:2])
         cruise = d / torch.where(dist > 0.0, dist, torch.ones_like(dist)) * v_pref
         v = torch.where(dist <= v_pref * dt, d / dt, cruise)
         v = torch.where(dist > 0.0, v, torch.zeros_like(v))

@@ -4,6 +4,7 @@ predicted velocities the CALLER makes from the state after every real step (DESI
 
     python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
                                                [--futures cv,to_goal [--reduce min] [--risk-penalty 0.5]]
+                                               [--device-loop [--chunk 8]]
 
 Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
 stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
@@ -12,7 +13,11 @@ there is no *_rollout form of these calls; the real steps are ORCA, as always.  
 and the navigation time in the reference's format.
 --futures plans against several predictors AT ONCE: one plan_cem_modes / plan_mppi_modes call scores every
 candidate against each listed future (cv = constant_velocity, to_goal), equally weighted, and ranks the mean of the returns
-(--reduce min: the worst one) less --risk-penalty times the share of futures that end in a collision."""
+(--reduce min: the worst one) less --risk-penalty times the share of futures that end in a collision.
+--device-loop: the two predictors above also exist on the device (BatchedCrowdSim.predict), so the loop
+need not come back to the host: ONE plan_predict_rollout call makes --chunk real steps — predict, plan, step, shift each —
+and the host only looks at the rollout between chunks.  The predictor is bit-exact and the counters are the same
+(step * iterations), so the line printed is the one the per-step loop prints."""
 import argparse
 import logging
 import os
@@ -26,7 +31,7 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
-         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0):
+         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -40,7 +45,13 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
                              record_capacity=1)
     planner = eng.plan_reset(eng.plan_begin(candidates, horizon, elites, iterations, init_std * robot.v_pref, seed=seed))
     most = int(round(env.time_limit / env.time_step)) + 2  # every episode has ended by then (Timeout)
-    for step in range(most):
+    if device_loop:  # the closed loop on the device, `chunk` real steps per call; the host looks at the rollout between calls
+        pred = eng.plan_predict_begin(planner, futures or predictor, reduce=reduce, risk_penalty=risk_penalty)
+        for first in range(0, most, chunk):
+            eng.plan_predict_rollout(planner, pred, min(chunk, most - first), first * iterations, temperature=temperature)
+            if int(bufs['active'].sum().item()) == 0:
+                break
+    for step in range(0 if device_loop else most):  # the per-step loop through the host (not entered with --device-loop)
         state8, _ = eng.get_state()  # what the planner observes: positions and velocities (to_goal also reads the goals)
         tables = {'to_goal': lambda: predict.to_goal(state8, horizon, env.time_step),
                   'constant_velocity': lambda: predict.constant_velocity(state8, horizon)}
@@ -86,6 +97,8 @@ def main():
     ap.add_argument('--futures', default=None, help='comma-separated predictors (cv, to_goal) to plan against at once, e.g. cv,to_goal')
     ap.add_argument('--reduce', default='mean', choices=['mean', 'min'], help='--futures: rank the mean or the worst of the returns')
     ap.add_argument('--risk-penalty', type=float, default=0.0, help='--futures: subtracted per unit of collision probability')
+    ap.add_argument('--device-loop', action='store_true', help='predict on the device too: one plan_predict_rollout call per chunk')
+    ap.add_argument('--chunk', type=int, default=8, help='--device-loop: real steps per call')
     args = ap.parse_args()
     names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal'}
     futures = None
@@ -94,9 +107,14 @@ def main():
         if unknown:
             ap.error('--futures: unknown predictor(s) %s (cv, to_goal)' % ', '.join(unknown))
         futures = [names[f] for f in args.futures.split(',')]
+    if args.device_loop and futures and len(futures) < 2:
+        ap.error('--device-loop: --futures takes two or more predictors (one predictor: --predictor)')
+    if args.chunk < 1:
+        ap.error('--chunk must be >= 1')
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
-                      predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty))
+                      predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty,
+                      device_loop=args.device_loop, chunk=args.chunk))
     return 0
 
 

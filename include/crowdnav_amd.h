@@ -702,6 +702,8 @@ int cn_plan_cem_paths (cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan
                        const double* human_vel, uint32_t counter);
 int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan,
                        const double* human_vel, double temperature, int fit_std, uint32_t counter);
+/* (That holds for a predictor of the CALLER's.  For the two predictors the library ships on the device — cn_predict, at the end
+ * of this header — the closed loop is one call: cn_plan_cem_predict_rollout / cn_plan_mppi_predict_rollout.) */
 
 /* ------------------------------------------------------------------------------------------------------
  * Lookahead under several predicted futures (no version bump: three new symbols, two new structs, one new enum; no existing
@@ -766,6 +768,7 @@ int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double
 int cn_plan_cem_modes (cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, uint32_t counter);
 int cn_plan_mppi_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes,
                        double temperature, int fit_std, uint32_t counter);
+/* (Several futures made by the device predictors: cn_predictors with n_modes > 1, cn_plan_*_predict_rollout below.) */
 
 /* ------------------------------------------------------------------------------------------------------
  * Value-bootstrapped lookahead (no version bump: new symbols only).  The n-step return a value-network policy means,
@@ -914,6 +917,65 @@ int cn_plan_mppi(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, doub
  * n_real_steps < 0: CN_ERR_INVALID; n_real_steps == 0: CN_OK, nothing enqueued. */
 int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
                          double temperature, int fit_std, uint32_t counter);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Device predictors and the closed loop on predicted futures (no version bump: three new symbols, one new struct, one new enum;
+ * no existing struct, enum or counter touched).  cn_lookahead_paths / cn_lookahead_modes take the humans' predicted velocities
+ * from the caller, and a caller with a predictor of their own keeps the per-step calls above.  The two predictors the project
+ * ships (crowdnav_amd/predict.py: constant_velocity, to_goal) are a few float64 operations per human and step; cn_predict makes
+ * their tables on the device from the engine's state as it stands, which is what lets the whole closed loop — predict, plan,
+ * real step, shift — run without the host.
+ *   human_vel: DEVICE double [B][M][n_steps][A - 1][2], written as 16-byte words (align it to 16 bytes).  M = 1: exactly
+ *   cn_lookahead_paths' table; M > 1: cn_lookahead_modes', mode m made by models[m].
+ * One lane per (b, m, h): it reads position, velocity, goal and v_pref of human slot h + 1 of env b once and walks t = 0 ..
+ * n_steps - 1.  Float64, every product, quotient and sum a separate IEEE operation in the order written, sqrt correctly rounded, so
+ * that predict.py on a host copy of the state (cn_get_state) restates the table bit for bit:
+ *   CN_PREDICT_CONSTANT_VELOCITY  human_vel[b][m][t][h] = the human's state velocity, for every t.
+ *   CN_PREDICT_TO_GOAL            with (px, py) the human's position at first, dt the engine's time_step, per step t:
+ *                                   dx = gx - px, dy = gy - py, dist = sqrt(dx dx + dy dy)
+ *                                   v = (0, 0)                                    if !(dist > 0)
+ *                                       (dx / dt, dy / dt)                        else if dist <= v_pref dt  (lands on the goal)
+ *                                       ((dx / dist) v_pref, (dy / dist) v_pref)  otherwise
+ *                                   human_vel[b][m][t][h] = v;  px <- px + vx dt, py <- py + vy dt
+ * The parked placeholders of the `mixed` rule stand at their goals with zero velocity: both models give them zeros.
+ * cn_predict serves ANY engine (CN_ROBOT_ORCA and CN_UNICYCLE included: only the humans are read).  ONE launch on the engine's
+ * stream, NOT counted in cn_launch_counts; state, cn_rollout_io arrays, ring levels and the human-model setting are not
+ * written, a rollout in progress continues as if the call had not happened.  Refused, in this order, before anything is
+ * enqueued: NULL models, NULL human_vel: CN_ERR_INVALID naming it; n_modes < 1: CN_ERR_INVALID, n_modes > 8: CN_ERR_UNSUPPORTED
+ * with the number; a model that is neither value: CN_ERR_INVALID naming its index and the value; n_steps < 0: CN_ERR_INVALID;
+ * NULL engine: CN_ERR_INVALID; B M n_steps (A - 1) rows beyond an int: CN_ERR_UNSUPPORTED.  n_steps == 0: CN_OK, nothing
+ * launched, nothing written.  Asynchronous: human_vel must stay valid until the launch has run; `models` is copied by the call. */
+enum { CN_PREDICT_CONSTANT_VELOCITY = 0, CN_PREDICT_TO_GOAL = 1 };
+int cn_predict(cn_engine* e, int n_steps, int n_modes,
+               const int32_t* models /* HOST [n_modes] */,
+               double* human_vel     /* DEVICE [B][M][n][A-1][2], 16-byte aligned */);
+
+typedef struct cn_predictors {      /* 64 bytes */
+    int32_t n_modes;        /* M: 1 .. 8                                    offset 0  */
+    int32_t model[8];       /* CN_PREDICT_* of mode m; entries >= M not read       4  */
+    int32_t reduce;         /* CN_MODES_MEAN | CN_MODES_MIN; read when M > 1      36  */
+    double  risk_penalty;   /* finite, >= 0; read when M > 1                      40  */
+    double* human_vel;      /* DEVICE scratch [B][M][cfg->n_steps][A-1][2]        48  */
+    const double* weight;   /* DEVICE [B][M] or NULL = 1/M each; read when M > 1  56  */
+} cn_predictors;
+/* cn_plan_rollout / cn_plan_mppi_rollout against the device predictors: for s in 0 .. n_real_steps - 1:
+ *   cn_predict(e, cfg->n_steps, M, pred->model, pred->human_vel);
+ *   M == 1: cn_plan_cem_paths / cn_plan_mppi_paths(.., pred->human_vel, counter + s * iterations) — cfg->bootstrap is served,
+ *           through cn_lookahead_paths_values;
+ *   M > 1:  cn_plan_cem_modes / cn_plan_mppi_modes with {M, reduce, risk_penalty, human_vel, weight} and that counter;
+ *   cn_rollout_step(e, io, plan->action); cn_plan_shift
+ * — one C call, no host work or synchronisation between the steps, bit for bit what those calls give.  An env whose episode
+ * has just ended is predicted from its new scenario; one still waiting for a scenario from its stale state, as cn_plan_shift
+ * seeds its prior from it.  After the call pred->human_vel holds the table the LAST planning step scored against.  Refused, in
+ * this order, before anything is enqueued: NULL pred, NULL pred->human_vel: CN_ERR_INVALID naming it; n_modes and the models as
+ * by cn_predict; everything cn_plan_rollout / cn_plan_mppi_rollout refuses, in their order (CN_ROBOT_ORCA and CN_UNICYCLE
+ * engines stay refused, as by every cn_plan_* call); for M > 1 cfg->bootstrap != 0: CN_ERR_UNSUPPORTED naming bootstrap, then
+ * cn_lookahead_modes' refusals; the table's rows beyond an int: CN_ERR_UNSUPPORTED.  n_real_steps == 0: CN_OK, nothing enqueued. */
+int cn_plan_cem_predict_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                 const cn_plan* plan, const cn_predictors* pred, uint32_t counter);
+int cn_plan_mppi_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                 const cn_plan* plan, const cn_predictors* pred, double temperature, int fit_std,
+                                 uint32_t counter);
 
 #ifdef __cplusplus
 }
