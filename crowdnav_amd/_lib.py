@@ -238,6 +238,12 @@ SYMBOLS = {
                                               C.POINTER(CnPredictors), C.c_uint32]),
     'cn_plan_mppi_predict_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
                                                C.POINTER(CnPredictors), C.c_double, C.c_int, C.c_uint32]),
+    # ORCA among the humans, the robot unseen, as one slot of such a table; the closed loop with that slot (no version bump)
+    'cn_predict_orca': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    'cn_plan_cem_predict_orca_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
+                                                   C.POINTER(CnPredictors), C.c_int, C.c_uint32]),
+    'cn_plan_mppi_predict_orca_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
+                                                    C.POINTER(CnPredictors), C.c_int, C.c_double, C.c_int, C.c_uint32]),
 }
 
 _lib = None

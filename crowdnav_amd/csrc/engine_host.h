@@ -210,7 +210,8 @@ inline int grid_lanes(const cn_engine* e) { return (e->P.B + cn::kWave - 1) / cn
 
 // sarl_abi.hip: frees the host part of the SARL state (device buffers are the engine's slabs)
 void cn_sarl_release(cn_engine* e);
-// crowdnav_amd.hip: launches orca_kernel (the kernels of step_kernels.h are instantiated in that translation unit only)
+// crowdnav_amd.hip: launches orca_kernel (the kernels of step_kernels.h are instantiated in that translation unit only; plan.hip
+// builds its own predict_orca_kernel from the same device functions)
 void cn_launch_orca(cn_engine* e, float* out_vel);
 // crowdnav_amd.hip: cn_lookahead_actions' refusals, in its order and with its messages; CN_OK: the call would launch (or, with
 // n_steps == 0, do nothing)

@@ -6,8 +6,11 @@
 // launch counters; this translation unit only adds what runs between them (draw, refit or MPPI update, shift, prior, and the
 // shipped predictors' table: cn_predict, in front of every planning step of the cn_plan_*_predict_rollout calls), enqueued on the
 // engine's stream.  Nothing here synchronises, allocates or counts.
+// cn_predict_orca (predict_orca_kernel.h) is instantiated here as well: the step kernels' workgroup stepping the humans alone, the
+// third predictor beside cn_predict's two, and the *_predict_orca_rollout calls that write it over one slot of cn_predict's table.
 #include "engine_host.h"
 #include "plan_kernels.h"
+#include "predict_orca_kernel.h"
 
 namespace {
 
@@ -209,11 +212,27 @@ int run_predict(cn_engine* e, int n_steps, const Predict& pred, double* human_ve
     return CN_OK;
 }
 
+// cn_predict_orca's launch: step_kernel's grid, workgroup and LDS under the engine's Params with the robot out of the humans'
+// sight and no ORCA robot (predict_orca_kernel.h); slot `mode` of the table
+int run_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel) {
+    cn::Params Pk = e->P;
+    Pk.robot_visible = 0, Pk.robot_orca = 0;
+    pick_maxl(e, [&](auto maxl) {
+        pick_bool(Pk.kd != 0, [&](auto kd) {
+            hipLaunchKernelGGL((cn::predict_orca_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)),
+                               dim3(Pk.threads), e->smem, e->stream, Pk, e->S, n_steps, n_modes, mode, (double2*)human_vel);
+        });
+    });
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
 // The closed loop of either planner.  pred (the *_predict_rollout calls, whose checks of it precede this): every planning step
-// scores against the table the device predictors make from the state as it then stands.
+// scores against the table the device predictors make from the state as it then stands; orca_mode >= 0 (the
+// *_predict_orca_rollout calls): slot orca_mode of that table is then overwritten by cn_predict_orca's.
 int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
                 uint32_t counter, const char* who, const Mppi* mppi, const cn_predictors* pred = nullptr,
-                const Predict& models = Predict{}) {
+                const Predict& models = Predict{}, int orca_mode = -1) {
     int rc = plan_check(e, cfg, plan, who, mppi);
     if (rc || (rc = plan_check_io(e, io, plan))) return rc;
     if (n_real_steps < 0) return fail(CN_ERR_INVALID, "%s: n_real_steps must be >= 0 (got %d)", who, n_real_steps);
@@ -225,6 +244,7 @@ int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const c
     if (pred && (rc = predict_check_size(e, cfg->n_steps, pred->n_modes, who))) return rc;
     for (int s = 0; s < n_real_steps; ++s) {
         if ((rc = bind(e)) || (pred && (rc = run_predict(e, cfg->n_steps, models, pred->human_vel)))) return rc;
+        if (orca_mode >= 0 && (rc = run_predict_orca(e, cfg->n_steps, pred->n_modes, orca_mode, pred->human_vel))) return rc;
         if ((rc = run_plan(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations, mppi, pred && !many ? pred->human_vel : nullptr,
                            many ? &modes : nullptr)))
             return rc;
@@ -234,14 +254,17 @@ int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const c
 }
 
 // the checks of `pred` that come before everything else of a *_predict_rollout call
+// (orca_mode: the *_predict_orca_rollout calls' argument, checked behind the models; NULL: the call has none)
 int predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
-                    const cn_predictors* pred, uint32_t counter, const char* who, const Mppi* mppi) {
+                    const cn_predictors* pred, uint32_t counter, const char* who, const Mppi* mppi, const int* orca_mode = nullptr) {
     if (!pred) return fail(CN_ERR_INVALID, "%s: pred is NULL", who);
     if (!pred->human_vel) return fail(CN_ERR_INVALID, "%s: pred->human_vel is NULL", who);
     Predict models;
     const int rc = predict_check_models(pred->n_modes, pred->model, who, &models);
     if (rc) return rc;
-    return run_rollout(e, io, n_real_steps, cfg, plan, counter, who, mppi, pred, models);
+    if (orca_mode && (*orca_mode < 0 || *orca_mode >= pred->n_modes))
+        return fail(CN_ERR_INVALID, "%s: orca_mode = %d is outside 0 .. n_modes - 1 = %d", who, *orca_mode, pred->n_modes - 1);
+    return run_rollout(e, io, n_real_steps, cfg, plan, counter, who, mppi, pred, models, orca_mode ? *orca_mode : -1);
 }
 
 }  // namespace
@@ -357,6 +380,33 @@ int cn_plan_mppi_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_re
                                  const cn_predictors* pred, double temperature, int fit_std, uint32_t counter) {
     const Mppi mppi{temperature, fit_std};
     return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_rollout", &mppi);
+}
+
+int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "cn_predict_orca: human_vel is NULL");
+    if (n_modes < 1) return fail(CN_ERR_INVALID, "cn_predict_orca: n_modes must be >= 1 (got %d)", n_modes);
+    if (n_modes > cn::kPredictMaxModes)
+        return fail(CN_ERR_UNSUPPORTED, "cn_predict_orca: n_modes = %d exceeds the %d modes of a table", n_modes, cn::kPredictMaxModes);
+    if (mode < 0 || mode >= n_modes)
+        return fail(CN_ERR_INVALID, "cn_predict_orca: mode = %d is outside 0 .. n_modes - 1 = %d", mode, n_modes - 1);
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_predict_orca: n_steps must be >= 0 (got %d)", n_steps);
+    if (!e) return fail(CN_ERR_INVALID, "cn_predict_orca: engine is NULL");
+    int rc = predict_check_size(e, n_steps, n_modes, "cn_predict_orca");
+    if (rc || n_steps == 0) return rc;
+    if ((rc = bind(e))) return rc;
+    return run_predict_orca(e, n_steps, n_modes, mode, human_vel);
+}
+
+int cn_plan_cem_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                     const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter) {
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_cem_predict_orca_rollout", nullptr, &orca_mode);
+}
+
+int cn_plan_mppi_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                      const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature, int fit_std,
+                                      uint32_t counter) {
+    const Mppi mppi{temperature, fit_std};
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_orca_rollout", &mppi, &orca_mode);
 }
 
 }  // extern "C"

@@ -729,6 +729,60 @@ class BatchedCrowdSim(object):
         return self._plan_call('mppi_predict_rollout', plan, C.byref(pred.c), float(temperature), int(bool(fit_std)), rollout=True,
                                n_real=n_real, counter=counter)
 
+    # ---------------------------------------------------------------- the ORCA predictor: the robot unseen (cn_predict_orca)
+    def predict_orca(self, n, out=None, mode=None):
+        """The table of human velocities ORCA among the humans gives when they do not see the robot, n steps from the state as
+        it stands, in one launch (cn_predict_orca): what step() reports in orca_vel[:, 1:] on an engine with robot_visible = 0
+        and freshly built simulators (drop_sims), step after step, as float64 — the humans' own policy, so on such an engine
+        lookahead_paths(actions, predict_orca(n)) is lookahead(actions) under 'orca'.  mode=None returns float64 [B, n, H, 2],
+        lookahead_paths' table (`out` reuses a contiguous float64 device tensor of that shape).  With `out` a contiguous
+        float64 [B, M, n, H, 2] device tensor (M in 1 .. 8) and mode=m, slot m of it — one future of a lookahead_modes table
+        whose other slots predict() or the caller made — is filled, no other slot is touched, and `out` is returned.  Any
+        engine, ORCA-robot, unicycle and robot_visible = 1 ones included; nothing of the engine — state, rollout buffers, ring
+        levels, simulators, lookahead_human_model, launch counters — is written.  n = 0 is a no-op."""
+        n = int(n)
+        if n < 0:
+            raise ValueError('predict_orca: n must be >= 0')
+        if mode is None:
+            M, m, shape = 1, 0, (self.B, n, self.H, 2)
+            if out is None:
+                out = self._new(shape, torch.float64)
+        else:
+            if out is None:
+                raise ValueError('predict_orca: mode needs out, the [%d, M, %d, %d, 2] table whose slot is filled' % (self.B, n, self.H))
+            oshape = tuple(getattr(out, 'shape', ()))
+            M = int(oshape[1]) if len(oshape) == 5 else 0
+            if not 1 <= M <= _lib.MODES_MAX:
+                raise ValueError('predict_orca: out must be [%d, M in 1..%d, n = %d, %d, 2], got %s'
+                                 % (self.B, _lib.MODES_MAX, n, self.H, oshape))
+            if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or not 0 <= mode < M:
+                raise ValueError('predict_orca: mode must be an int in 0 .. M - 1 = %d, got %r' % (M - 1, mode))
+            m, shape = int(mode), (self.B, M, n, self.H, 2)
+        if not self._dense(out, torch.float64, shape):
+            raise ValueError('predict_orca: out must be a contiguous %s %s tensor on %s' % (torch.float64, shape, self.device))
+        if n > 0:
+            check(self._lib.cn_predict_orca(self._h, n, M, m, _ptr(out)))
+        return out
+
+    def plan_predict_orca_rollout(self, plan, pred, n_real, counter, orca_mode=0, temperature=None, fit_std=False):
+        """plan_predict_rollout with future `orca_mode` of pred made by predict_orca (cn_plan_cem_predict_orca_rollout; with a
+        temperature cn_plan_mppi_predict_orca_rollout): per step predict() into pred.human_vel, predict_orca(plan.n,
+        out=pred.human_vel, mode=orca_mode) over that slot, the paths (M = 1) or modes planner, rollout_step(plan.action),
+        plan_shift — ONE call, bit for bit what those calls give.  pred: plan_predict_begin's, whose name for slot orca_mode is
+        computed and overwritten.  Returns the rollout's bufs."""
+        if not isinstance(plan, Plan) or plan.engine() is not self:
+            raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
+        if not isinstance(pred, Predictors) or pred.engine() is not self or pred.plan() is not plan:
+            raise ValueError('pred: the Predictors made by this engine\'s plan_predict_begin() for this plan')
+        if isinstance(orca_mode, bool) or not isinstance(orca_mode, (int, np.integer)) or not 0 <= orca_mode < pred.c.n_modes:
+            raise ValueError('plan_predict_orca_rollout: orca_mode must be an int in 0 .. M - 1 = %d, got %r'
+                             % (pred.c.n_modes - 1, orca_mode))
+        if temperature is None:
+            return self._plan_call('cem_predict_orca_rollout', plan, C.byref(pred.c), int(orca_mode), rollout=True, n_real=n_real,
+                                   counter=counter)
+        return self._plan_call('mppi_predict_orca_rollout', plan, C.byref(pred.c), int(orca_mode), float(temperature),
+                               int(bool(fit_std)), rollout=True, n_real=n_real, counter=counter)
+
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):
         """The finished episodes of this engine's rollout as ONE self-contained float64 block per env:

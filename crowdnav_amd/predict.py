@@ -11,6 +11,11 @@ engine's own state in one launch, bit for bit what these functions give on get_s
 plan_predict_rollout runs the whole closed loop on them without the host.  A predictor of the caller's own goes through the
 functions here and the per-step calls.
 
+A third predictor exists on the device only: BatchedCrowdSim.predict_orca (cn_predict_orca) steps the humans with the engine's
+own ORCA code, the robot unseen — humans that avoid each other, between to_goal (straight through every other human) and the
+full 'orca' lookahead (humans that react to each candidate robot path) — and plan_predict_orca_rollout plans on it in closed
+loop.  It has no host form here: its oracle is the environment itself, stepped with robot_visible = 0.
+
 torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
 returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is
 the robot).  Under the `mixed` rule the parked placeholders stand still at their goals with zero velocity, so constant_velocity

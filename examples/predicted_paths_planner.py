@@ -17,7 +17,10 @@ candidate against each listed future (cv = constant_velocity, to_goal), equally 
 --device-loop: the two predictors above also exist on the device (BatchedCrowdSim.predict), so the loop
 need not come back to the host: ONE plan_predict_rollout call makes --chunk real steps — predict, plan, step, shift each —
 and the host only looks at the rollout between chunks.  The predictor is bit-exact and the counters are the same
-(step * iterations), so the line printed is the one the per-step loop prints."""
+(step * iterations), so the line printed is the one the per-step loop prints.
+--futures also takes `orca` (once), beside cv and to_goal: the humans avoid EACH OTHER by the engine's own ORCA code but do not
+see the robot (BatchedCrowdSim.predict_orca, DESIGN.md §3.8.11) — a table made on the device in one launch per real step;
+with --device-loop the one call is plan_predict_orca_rollout, which writes that future over its slot of the table."""
 import argparse
 import logging
 import os
@@ -45,16 +48,24 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
                              record_capacity=1)
     planner = eng.plan_reset(eng.plan_begin(candidates, horizon, elites, iterations, init_std * robot.v_pref, seed=seed))
     most = int(round(env.time_limit / env.time_step)) + 2  # every episode has ended by then (Timeout)
+    orca_mode = futures.index('orca') if futures and 'orca' in futures else None
     if device_loop:  # the closed loop on the device, `chunk` real steps per call; the host looks at the rollout between calls
-        pred = eng.plan_predict_begin(planner, futures or predictor, reduce=reduce, risk_penalty=risk_penalty)
+        # (the ORCA future's slot is first made by a predictor cn_predict knows, then overwritten)
+        models = [('to_goal' if name == 'orca' else name) for name in futures] if futures else predictor
+        pred = eng.plan_predict_begin(planner, models, reduce=reduce, risk_penalty=risk_penalty)
         for first in range(0, most, chunk):
-            eng.plan_predict_rollout(planner, pred, min(chunk, most - first), first * iterations, temperature=temperature)
+            if orca_mode is None:
+                eng.plan_predict_rollout(planner, pred, min(chunk, most - first), first * iterations, temperature=temperature)
+            else:
+                eng.plan_predict_orca_rollout(planner, pred, min(chunk, most - first), first * iterations, orca_mode=orca_mode,
+                                              temperature=temperature)
             if int(bufs['active'].sum().item()) == 0:
                 break
     for step in range(0 if device_loop else most):  # the per-step loop through the host (not entered with --device-loop)
         state8, _ = eng.get_state()  # what the planner observes: positions and velocities (to_goal also reads the goals)
         tables = {'to_goal': lambda: predict.to_goal(state8, horizon, env.time_step),
-                  'constant_velocity': lambda: predict.constant_velocity(state8, horizon)}
+                  'constant_velocity': lambda: predict.constant_velocity(state8, horizon),
+                  'orca': lambda: eng.predict_orca(horizon)}
         if futures:  # several futures side by side, one call
             human_vel = predict.stack_modes(*(tables[name]() for name in futures))
             if temperature is None:
@@ -94,19 +105,21 @@ def main():
     ap.add_argument('--init-std', type=float, default=0.5, help='standard deviation a step starts from, in units of v_pref')
     ap.add_argument('--predictor', default='to_goal', choices=['to_goal', 'constant_velocity'],
                     help="the planner's model of the humans (the real steps are always ORCA)")
-    ap.add_argument('--futures', default=None, help='comma-separated predictors (cv, to_goal) to plan against at once, e.g. cv,to_goal')
+    ap.add_argument('--futures', default=None, help='comma-separated predictors (cv, to_goal, orca) to plan against at once, e.g. cv,to_goal')
     ap.add_argument('--reduce', default='mean', choices=['mean', 'min'], help='--futures: rank the mean or the worst of the returns')
     ap.add_argument('--risk-penalty', type=float, default=0.0, help='--futures: subtracted per unit of collision probability')
     ap.add_argument('--device-loop', action='store_true', help='predict on the device too: one plan_predict_rollout call per chunk')
     ap.add_argument('--chunk', type=int, default=8, help='--device-loop: real steps per call')
     args = ap.parse_args()
-    names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal'}
+    names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal', 'orca': 'orca'}
     futures = None
     if args.futures:
         unknown = [f for f in args.futures.split(',') if f not in names]
         if unknown:
-            ap.error('--futures: unknown predictor(s) %s (cv, to_goal)' % ', '.join(unknown))
+            ap.error('--futures: unknown predictor(s) %s (cv, to_goal, orca)' % ', '.join(unknown))
         futures = [names[f] for f in args.futures.split(',')]
+        if futures.count('orca') > 1:
+            ap.error('--futures: orca may be listed once (the closed loop overwrites one slot of the table)')
     if args.device_loop and futures and len(futures) < 2:
         ap.error('--device-loop: --futures takes two or more predictors (one predictor: --predictor)')
     if args.chunk < 1:

@@ -977,6 +977,51 @@ int cn_plan_mppi_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_re
                                  const cn_plan* plan, const cn_predictors* pred, double temperature, int fit_std,
                                  uint32_t counter);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The ORCA predictor: humans that avoid each other, the robot unseen (no version bump: three new symbols; no existing struct,
+ * enum or counter touched — it is not a CN_PREDICT_* value, because its kernel is of another kind: a workgroup per env, not a
+ * lane per human).  It sits between the two predictors above, whose humans walk through each other, and cn_lookahead_actions
+ * under CN_HUMANS_ORCA, whose humans react to each of the K candidate robot paths: its result does not depend on the robot's
+ * candidate, so it is made once per env and every *_paths / *_modes call can use it.
+ *   cn_predict_orca writes slot `mode` of a table laid out as cn_predict's — human_vel [B][n_modes][n_steps][A - 1][2] — and no
+ *   other slot: n_modes = 1, mode = 0 is cn_lookahead_paths' table; with n_modes > 1 it fills one future of a cn_lookahead_modes
+ *   table whose other slots cn_predict or the caller made.
+ * What the table means: from the engine's state as it stands the humans are stepped n_steps times exactly as cn_step steps them
+ * on an engine with robot_visible = 0 and freshly made simulators (cn_drop_sims): every human solves ORCA against the other
+ * humans only, with the engine's own ORCA parameters, max_neighbors, time_step and radii; human_vel[b][mode][t][h] is the float32
+ * velocity human h + 1 chooses at step t — what cn_step reports in orca_vel — widened to double; the human then moves by
+ * p + v dt in float64 (product and sum separate operations) and keeps that velocity as its current one for the next solve.
+ * The robot is not stepped, tested or read; there are no rewards and no episode end: all n_steps rows are always written.  On
+ * the kd route (A > 10) the simulators' visiting order starts as a fresh simulator's and is carried through the n steps inside
+ * the kernel; the engine's own kd rows are neither read nor written.  The parked placeholders of the `mixed` rule get what
+ * cn_step's orca_vel gives them.  It is the humans' policy itself: on an engine whose humans do not see the robot,
+ * cn_lookahead_paths with this table is cn_lookahead_actions under CN_HUMANS_ORCA, bit for bit (fresh simulators on both sides).
+ * cn_predict_orca serves ANY engine (CN_ROBOT_ORCA, CN_UNICYCLE and robot_visible = 1 included).  ONE launch on the engine's
+ * stream — step_kernel's workgroup per E envs, under the engine's Params with robot_visible = 0 and robot_orca = 0 — NOT counted
+ * in cn_launch_counts; state, cn_rollout_io arrays, ring levels, the human-model setting, the robot's captured simulator and the
+ * kd rows are not written, a rollout in progress continues as if the call had not happened.  Refused, in this order, before
+ * anything is enqueued: NULL human_vel: CN_ERR_INVALID; n_modes < 1: CN_ERR_INVALID, n_modes > 8: CN_ERR_UNSUPPORTED with the
+ * number; mode outside 0 .. n_modes - 1: CN_ERR_INVALID with both numbers; n_steps < 0: CN_ERR_INVALID; NULL engine:
+ * CN_ERR_INVALID; B n_modes n_steps (A - 1) rows beyond an int: CN_ERR_UNSUPPORTED.  n_steps == 0: CN_OK, nothing launched,
+ * nothing written.  Asynchronous: human_vel must stay valid until the launch has run. */
+int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode,
+                    double* human_vel /* DEVICE [B][n_modes][n_steps][A-1][2], 16-byte aligned */);
+/* cn_plan_*_predict_rollout with one future made by cn_predict_orca: per real step exactly their sequence, and after cn_predict
+ * has written the table
+ *   cn_predict_orca(e, cfg->n_steps, M, orca_mode, pred->human_vel)
+ * overwrites slot orca_mode; then the paths planner (M == 1) or the modes planner (M > 1), cn_rollout_step and cn_plan_shift —
+ * one C call, no host work or synchronisation between the steps, bit for bit what those calls give.  pred->model[orca_mode]
+ * must still be a valid CN_PREDICT_* value: it is computed and overwritten (a launch of a few microseconds); struct
+ * cn_predictors and its checks are as above.  Refused, before anything is enqueued: everything cn_plan_*_predict_rollout
+ * refuses, in their order and with this call's name, and — after the models, before the engine is looked at — orca_mode
+ * outside 0 .. M - 1: CN_ERR_INVALID with both numbers.  CN_ROBOT_ORCA and CN_UNICYCLE engines stay refused, as by every
+ * cn_plan_* call, and so does M > 1 with cfg->bootstrap. */
+int cn_plan_cem_predict_orca_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                      const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter);
+int cn_plan_mppi_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                      const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
+                                      int fit_std, uint32_t counter);
+
 #ifdef __cplusplus
 }
 #endif
