@@ -244,6 +244,13 @@ SYMBOLS = {
                                                    C.POINTER(CnPredictors), C.c_int, C.c_uint32]),
     'cn_plan_mppi_predict_orca_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg), C.POINTER(CnPlan),
                                                     C.POINTER(CnPredictors), C.c_int, C.c_double, C.c_int, C.c_uint32]),
+    # the ORCA predictor with the robot in sight on a table of actions; the closed loop on the plan's nominal sequence (no version bump)
+    'cn_predict_orca_robot': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    'cn_plan_cem_predict_orca_nominal_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg),
+                                                           C.POINTER(CnPlan), C.POINTER(CnPredictors), C.c_int, C.c_uint32]),
+    'cn_plan_mppi_predict_orca_nominal_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg),
+                                                            C.POINTER(CnPlan), C.POINTER(CnPredictors), C.c_int, C.c_double, C.c_int,
+                                                            C.c_uint32]),
 }
 
 _lib = None

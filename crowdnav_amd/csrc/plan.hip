@@ -8,6 +8,8 @@
 // engine's stream.  Nothing here synchronises, allocates or counts.
 // cn_predict_orca (predict_orca_kernel.h) is instantiated here as well: the step kernels' workgroup stepping the humans alone, the
 // third predictor beside cn_predict's two, and the *_predict_orca_rollout calls that write it over one slot of cn_predict's table.
+// cn_predict_orca_robot is the same launch with the robot in the humans' sight on a table of actions; the *_nominal_rollout calls
+// give it the plan's clipped mean, candidate 0 of the planning step's first draw.
 #include "engine_host.h"
 #include "plan_kernels.h"
 #include "predict_orca_kernel.h"
@@ -142,13 +144,14 @@ int run_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, c
 // scored by the paths lookahead against the caller's predicted human motion instead of the engine's human model.  modes
 // (optional, never with human_vel or bootstrap): by cn_lookahead_modes against the caller's M futures — look.ret receives the
 // reduced score, which the updates rank, and look.info / steps / time the worst mode's rows.
+// drawn: the caller has made iteration 0's draw already (run_rollout's nominal form), with that counter.
 int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter, const Mppi* mppi,
-             const double* human_vel = nullptr, const cn_path_modes* modes = nullptr) {
+             const double* human_vel = nullptr, const cn_path_modes* modes = nullptr, bool drawn = false) {
     const int n = cfg->n_steps, K = cfg->n_candidates;
     const cn_modes_out worst{plan->look.ret, nullptr, nullptr, plan->look.info, plan->look.steps, plan->look.time,
                              nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < cfg->iterations; ++i) {
-        int rc = run_draw(e, cfg, plan, counter + (uint32_t)i);
+        int rc = (drawn && i == 0) ? CN_OK : run_draw(e, cfg, plan, counter + (uint32_t)i);
         if (rc) return rc;
         if (modes)
             rc = cn_lookahead_modes(e, n, K, plan->candidates, modes, &worst);
@@ -213,14 +216,28 @@ int run_predict(cn_engine* e, int n_steps, const Predict& pred, double* human_ve
 }
 
 // cn_predict_orca's launch: step_kernel's grid, workgroup and LDS under the engine's Params with the robot out of the humans'
-// sight and no ORCA robot (predict_orca_kernel.h); slot `mode` of the table
-int run_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel) {
+// sight and no ORCA robot (predict_orca_kernel.h); slot `mode` of the table.  robot_actions (cn_predict_orca_robot): the robot
+// in their sight instead, whatever the engine's own setting — nothing of the workgroup's LDS, of the kd layout or of the
+// geometry is sized by robot_visible — following rows env_stride apart; a unicycle's rows where the engine's step kernels
+// would read them as such.
+int run_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel, const double* robot_actions = nullptr,
+                     int64_t env_stride = 0) {
     cn::Params Pk = e->P;
-    Pk.robot_visible = 0, Pk.robot_orca = 0;
+    Pk.robot_visible = robot_actions ? 1 : 0, Pk.robot_orca = 0;
     pick_maxl(e, [&](auto maxl) {
         pick_bool(Pk.kd != 0, [&](auto kd) {
-            hipLaunchKernelGGL((cn::predict_orca_kernel<decltype(maxl)::value, decltype(kd)::value>), dim3(grid_envs(e)),
-                               dim3(Pk.threads), e->smem, e->stream, Pk, e->S, n_steps, n_modes, mode, (double2*)human_vel);
+            constexpr int kMaxl = decltype(maxl)::value;
+            constexpr bool kKd = decltype(kd)::value;
+            if (!robot_actions) {
+                hipLaunchKernelGGL((cn::predict_orca_kernel<kMaxl, kKd>), dim3(grid_envs(e)), dim3(Pk.threads), e->smem, e->stream, Pk,
+                                   e->S, n_steps, n_modes, mode, (double2*)human_vel);
+                return;
+            }
+            pick_bool(e->P.robot_unicycle && !e->P.robot_orca, [&](auto uni) {
+                hipLaunchKernelGGL((cn::predict_orca_robot_kernel<kMaxl, kKd, decltype(uni)::value>), dim3(grid_envs(e)),
+                                   dim3(Pk.threads), e->smem, e->stream, Pk, e->S, n_steps, n_modes, mode, (double2*)human_vel,
+                                   robot_actions, (long long)(env_stride ? env_stride : n_steps));
+            });
         });
     });
     CN_HIP(hipGetLastError());
@@ -229,10 +246,12 @@ int run_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* h
 
 // The closed loop of either planner.  pred (the *_predict_rollout calls, whose checks of it precede this): every planning step
 // scores against the table the device predictors make from the state as it then stands; orca_mode >= 0 (the
-// *_predict_orca_rollout calls): slot orca_mode of that table is then overwritten by cn_predict_orca's.
+// *_predict_orca_rollout calls): slot orca_mode of that table is then overwritten by cn_predict_orca's.  nominal (the
+// *_nominal_rollout calls): by cn_predict_orca_robot's instead, the robot on candidate 0 of the planning step's first draw — the
+// plan's mean under the draw's clip rule; that draw is made ahead of the prediction and not again by run_plan.
 int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
                 uint32_t counter, const char* who, const Mppi* mppi, const cn_predictors* pred = nullptr,
-                const Predict& models = Predict{}, int orca_mode = -1) {
+                const Predict& models = Predict{}, int orca_mode = -1, bool nominal = false) {
     int rc = plan_check(e, cfg, plan, who, mppi);
     if (rc || (rc = plan_check_io(e, io, plan))) return rc;
     if (n_real_steps < 0) return fail(CN_ERR_INVALID, "%s: n_real_steps must be >= 0 (got %d)", who, n_real_steps);
@@ -244,9 +263,13 @@ int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const c
     if (pred && (rc = predict_check_size(e, cfg->n_steps, pred->n_modes, who))) return rc;
     for (int s = 0; s < n_real_steps; ++s) {
         if ((rc = bind(e)) || (pred && (rc = run_predict(e, cfg->n_steps, models, pred->human_vel)))) return rc;
-        if (orca_mode >= 0 && (rc = run_predict_orca(e, cfg->n_steps, pred->n_modes, orca_mode, pred->human_vel))) return rc;
-        if ((rc = run_plan(e, cfg, plan, counter + (uint32_t)s * (uint32_t)cfg->iterations, mppi, pred && !many ? pred->human_vel : nullptr,
-                           many ? &modes : nullptr)))
+        const uint32_t c = counter + (uint32_t)s * (uint32_t)cfg->iterations;
+        if (nominal && (rc = run_draw(e, cfg, plan, c))) return rc;
+        if (orca_mode >= 0 &&
+            (rc = run_predict_orca(e, cfg->n_steps, pred->n_modes, orca_mode, pred->human_vel, nominal ? plan->candidates : nullptr,
+                                   (int64_t)cfg->n_candidates * cfg->n_steps)))
+            return rc;
+        if ((rc = run_plan(e, cfg, plan, c, mppi, pred && !many ? pred->human_vel : nullptr, many ? &modes : nullptr, nominal)))
             return rc;
         if ((rc = cn_rollout_step(e, io, plan->action)) || (rc = run_shift(e, io, cfg, plan))) return rc;
     }
@@ -256,7 +279,8 @@ int run_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const c
 // the checks of `pred` that come before everything else of a *_predict_rollout call
 // (orca_mode: the *_predict_orca_rollout calls' argument, checked behind the models; NULL: the call has none)
 int predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg, const cn_plan* plan,
-                    const cn_predictors* pred, uint32_t counter, const char* who, const Mppi* mppi, const int* orca_mode = nullptr) {
+                    const cn_predictors* pred, uint32_t counter, const char* who, const Mppi* mppi, const int* orca_mode = nullptr,
+                    bool nominal = false) {
     if (!pred) return fail(CN_ERR_INVALID, "%s: pred is NULL", who);
     if (!pred->human_vel) return fail(CN_ERR_INVALID, "%s: pred->human_vel is NULL", who);
     Predict models;
@@ -264,7 +288,24 @@ int predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, con
     if (rc) return rc;
     if (orca_mode && (*orca_mode < 0 || *orca_mode >= pred->n_modes))
         return fail(CN_ERR_INVALID, "%s: orca_mode = %d is outside 0 .. n_modes - 1 = %d", who, *orca_mode, pred->n_modes - 1);
-    return run_rollout(e, io, n_real_steps, cfg, plan, counter, who, mppi, pred, models, orca_mode ? *orca_mode : -1);
+    return run_rollout(e, io, n_real_steps, cfg, plan, counter, who, mppi, pred, models, orca_mode ? *orca_mode : -1, nominal);
+}
+
+// cn_predict_orca's checks, in the header's order, and the launch; robot_actions: cn_predict_orca_robot's, whose own checks came first
+int predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel, const char* who,
+                 const double* robot_actions = nullptr, int64_t env_stride = 0) {
+    if (!human_vel) return fail(CN_ERR_INVALID, "%s: human_vel is NULL", who);
+    if (n_modes < 1) return fail(CN_ERR_INVALID, "%s: n_modes must be >= 1 (got %d)", who, n_modes);
+    if (n_modes > cn::kPredictMaxModes)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_modes = %d exceeds the %d modes of a table", who, n_modes, cn::kPredictMaxModes);
+    if (mode < 0 || mode >= n_modes)
+        return fail(CN_ERR_INVALID, "%s: mode = %d is outside 0 .. n_modes - 1 = %d", who, mode, n_modes - 1);
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "%s: n_steps must be >= 0 (got %d)", who, n_steps);
+    if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
+    int rc = predict_check_size(e, n_steps, n_modes, who);
+    if (rc || n_steps == 0) return rc;
+    if ((rc = bind(e))) return rc;
+    return run_predict_orca(e, n_steps, n_modes, mode, human_vel, robot_actions, env_stride);
 }
 
 }  // namespace
@@ -383,18 +424,18 @@ int cn_plan_mppi_predict_rollout(cn_engine* e, const cn_rollout_io* io, int n_re
 }
 
 int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human_vel) {
-    if (!human_vel) return fail(CN_ERR_INVALID, "cn_predict_orca: human_vel is NULL");
-    if (n_modes < 1) return fail(CN_ERR_INVALID, "cn_predict_orca: n_modes must be >= 1 (got %d)", n_modes);
-    if (n_modes > cn::kPredictMaxModes)
-        return fail(CN_ERR_UNSUPPORTED, "cn_predict_orca: n_modes = %d exceeds the %d modes of a table", n_modes, cn::kPredictMaxModes);
-    if (mode < 0 || mode >= n_modes)
-        return fail(CN_ERR_INVALID, "cn_predict_orca: mode = %d is outside 0 .. n_modes - 1 = %d", mode, n_modes - 1);
-    if (n_steps < 0) return fail(CN_ERR_INVALID, "cn_predict_orca: n_steps must be >= 0 (got %d)", n_steps);
-    if (!e) return fail(CN_ERR_INVALID, "cn_predict_orca: engine is NULL");
-    int rc = predict_check_size(e, n_steps, n_modes, "cn_predict_orca");
-    if (rc || n_steps == 0) return rc;
-    if ((rc = bind(e))) return rc;
-    return run_predict_orca(e, n_steps, n_modes, mode, human_vel);
+    return predict_orca(e, n_steps, n_modes, mode, human_vel, "cn_predict_orca");
+}
+
+int cn_predict_orca_robot(cn_engine* e, int n_steps, int n_modes, int mode, const double* robot_actions, int64_t env_stride,
+                          double* human_vel) {
+    const char* who = "cn_predict_orca_robot";
+    if (!human_vel) return fail(CN_ERR_INVALID, "%s: human_vel is NULL", who);
+    if (!robot_actions) return fail(CN_ERR_INVALID, "%s: robot_actions is NULL", who);
+    if (env_stride < 0 || (env_stride > 0 && env_stride < (int64_t)n_steps))
+        return fail(CN_ERR_INVALID, "%s: env_stride = %lld rows must be 0 (= n_steps) or >= n_steps = %d", who, (long long)env_stride,
+                    n_steps);
+    return predict_orca(e, n_steps, n_modes, mode, human_vel, who, robot_actions, env_stride);
 }
 
 int cn_plan_cem_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
@@ -407,6 +448,20 @@ int cn_plan_mppi_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int
                                       uint32_t counter) {
     const Mppi mppi{temperature, fit_std};
     return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_orca_rollout", &mppi, &orca_mode);
+}
+
+int cn_plan_cem_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                             const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter) {
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_cem_predict_orca_nominal_rollout", nullptr, &orca_mode,
+                           true);
+}
+
+int cn_plan_mppi_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                              const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
+                                              int fit_std, uint32_t counter) {
+    const Mppi mppi{temperature, fit_std};
+    return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_orca_nominal_rollout", &mppi, &orca_mode,
+                           true);
 }
 
 }  // extern "C"

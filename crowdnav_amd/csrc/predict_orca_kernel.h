@@ -11,6 +11,18 @@
 // The simulators are fresh ones (cn_drop_sims): on the kd route the visiting order starts as kd_identity_row's and is carried
 // in LDS through the n steps; the engine's kd_order / kd_valid rows are neither read nor written, and nothing else of the
 // engine is written either.
+//
+// cn_predict_orca_robot (ROBOT = true): the same steps with the robot in the humans' sight, following a table of actions the
+// caller gives — the host's copy of Params has robot_visible = 1 (robot_orca = 0 as before), so candidate lists, pair
+// descriptors and the kd identity rows hold the robot exactly as step_kernel has them on a robot_visible = 1 CN_ROBOT_EXTERNAL
+// engine.  Order of events within step t, CrowdSim.step's: the humans solve against the robot where it stands and with the
+// velocity it has (orca_phases stages every agent lane's registers, the robot's among them, as float32(radius + 0.01 +
+// human_safety) like any other agent of a human's simulator); the humans move; the robot lane takes row t of its table through
+// robot_step / robot_after (transition.h).  The robot has no swept test, reward, done or time: all n rows are followed.  The
+// row is requested before orca_phases, so its latency hides behind the solve, and there is no further barrier: the robot lane
+// only rewrites its own registers, which the next step's stage phase publishes behind the loop's one block_sync.
+// The flag lives on the shared body text (predict_orca_body.inc), not on predict_orca_kernel's template list: a third template
+// argument would rename the robot-unseen kernels, and with ROBOT = false the body is the text above and nothing else.
 #pragma once
 #include "step_kernels.h"
 
@@ -28,30 +40,20 @@ __device__ __forceinline__ void kd_fresh(const Params& P, const Smem& s, const L
 template <int MAXL, bool KD>
 __global__ __launch_bounds__(kMaxBlock) void predict_orca_kernel(Params P, StateView S, int n_steps, int n_modes, int mode,
                                                                  double2* human_vel) {
-    const Smem s = carve<MAXL>(P);
-    const Lane L = lane_of(P);
-    AgentRegs r = {};
-    if (L.valid) load_agent(S, L.gi, r);
-    // the robot's simulator is never solved; its pairs (build_pairs gives the robot lane every human) read finite radii
-    if (L.lane < P.nA) s.rview[L.lane] = (float)(r.rad + 0.01 + P.robot_safety);
-    build_pairs(P, s);
-    if (KD) kd_fresh(P, s, L);
-    const bool human = L.valid && L.a > 0;
-    // row (b, mode, t, h): B n_modes n_steps (A - 1) is within an int (the host checks), the index is formed in size_t
-    double2* row = human_vel + (((size_t)(human ? L.env : 0) * n_modes + mode) * n_steps) * P.NC + (human ? L.a - 1 : 0);
-    for (int t = 0; t < n_steps; ++t) {
-        float vx, vy;
-        orca_phases<MAXL, KD>(P, s, L, r, 0.0f, human, vx, vy);
-        if (human) {
-            const double nvx = vx, nvy = vy;
-            r.px = r.px + nvx * P.dt;
-            r.py = r.py + nvy * P.dt;
-            r.vx = nvx;
-            r.vy = nvy;
-            row[(size_t)t * P.NC] = make_double2(nvx, nvy);
-        }
-        block_sync(P);  // the solve's last LDS reads, before the next step's stage phase writes
-    }
+    constexpr bool ROBOT = false, UNI = false;
+    constexpr const double* robot_actions = nullptr;
+    constexpr long long env_stride = 0;
+#include "predict_orca_body.inc"
+}
+
+// ... with the robot in sight: robot_actions row (b, t) at robot_actions + 2 (b env_stride + t); UNI: the rows are
+// ActionRot(v, r), the heading S.theta's
+template <int MAXL, bool KD, bool UNI>
+__global__ __launch_bounds__(kMaxBlock) void predict_orca_robot_kernel(Params P, StateView S, int n_steps, int n_modes, int mode,
+                                                                       double2* human_vel, const double* robot_actions,
+                                                                       long long env_stride) {
+    constexpr bool ROBOT = true;
+#include "predict_orca_body.inc"
 }
 
 }  // namespace cn

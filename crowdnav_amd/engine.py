@@ -729,7 +729,7 @@ class BatchedCrowdSim(object):
         return self._plan_call('mppi_predict_rollout', plan, C.byref(pred.c), float(temperature), int(bool(fit_std)), rollout=True,
                                n_real=n_real, counter=counter)
 
-    # ---------------------------------------------------------------- the ORCA predictor: the robot unseen (cn_predict_orca)
+    # ---------------------------------------------------------------- the ORCA predictor: the robot unseen (cn_predict_orca) ...
     def predict_orca(self, n, out=None, mode=None):
         """The table of human velocities ORCA among the humans gives when they do not see the robot, n steps from the state as
         it stands, in one launch (cn_predict_orca): what step() reports in orca_vel[:, 1:] on an engine with robot_visible = 0
@@ -740,29 +740,78 @@ class BatchedCrowdSim(object):
         whose other slots predict() or the caller made — is filled, no other slot is touched, and `out` is returned.  Any
         engine, ORCA-robot, unicycle and robot_visible = 1 ones included; nothing of the engine — state, rollout buffers, ring
         levels, simulators, lookahead_human_model, launch counters — is written.  n = 0 is a no-op."""
+        return self._predict_orca('predict_orca', n, out, mode, None)
+
+    def _predict_orca(self, who, n, out, mode, robot_actions):
         n = int(n)
         if n < 0:
-            raise ValueError('predict_orca: n must be >= 0')
+            raise ValueError('%s: n must be >= 0' % who)
+        rows = None if robot_actions is None else self._action_rows(who, robot_actions, n)
         if mode is None:
             M, m, shape = 1, 0, (self.B, n, self.H, 2)
             if out is None:
                 out = self._new(shape, torch.float64)
         else:
             if out is None:
-                raise ValueError('predict_orca: mode needs out, the [%d, M, %d, %d, 2] table whose slot is filled' % (self.B, n, self.H))
+                raise ValueError('%s: mode needs out, the [%d, M, %d, %d, 2] table whose slot is filled' % (who, self.B, n, self.H))
             oshape = tuple(getattr(out, 'shape', ()))
             M = int(oshape[1]) if len(oshape) == 5 else 0
             if not 1 <= M <= _lib.MODES_MAX:
-                raise ValueError('predict_orca: out must be [%d, M in 1..%d, n = %d, %d, 2], got %s'
-                                 % (self.B, _lib.MODES_MAX, n, self.H, oshape))
+                raise ValueError('%s: out must be [%d, M in 1..%d, n = %d, %d, 2], got %s'
+                                 % (who, self.B, _lib.MODES_MAX, n, self.H, oshape))
             if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or not 0 <= mode < M:
-                raise ValueError('predict_orca: mode must be an int in 0 .. M - 1 = %d, got %r' % (M - 1, mode))
+                raise ValueError('%s: mode must be an int in 0 .. M - 1 = %d, got %r' % (who, M - 1, mode))
             m, shape = int(mode), (self.B, M, n, self.H, 2)
         if not self._dense(out, torch.float64, shape):
-            raise ValueError('predict_orca: out must be a contiguous %s %s tensor on %s' % (torch.float64, shape, self.device))
-        if n > 0:
+            raise ValueError('%s: out must be a contiguous %s %s tensor on %s' % (who, torch.float64, shape, self.device))
+        if n > 0 and rows is None:
             check(self._lib.cn_predict_orca(self._h, n, M, m, _ptr(out)))
+        elif n > 0:
+            a, stride, temporary = rows
+            check(self._lib.cn_predict_orca_robot(self._h, n, M, m, _ptr(a), stride, _ptr(out)))
+            self._release(temporary)
         return out
+
+    def _action_rows(self, who, robot_actions, n):
+        """(tensor, rows between envs, whether it is a temporary copy) of a [B, n, 2] table of robot actions: a float64 tensor on
+        the engine's device whose last two dimensions are contiguous is read where it lies, whatever lies between its envs —
+        plan.candidates[:, 0] as it is; anything else is copied to a dense table there."""
+        shape = tuple(getattr(robot_actions, 'shape', np.shape(robot_actions)))
+        if shape != (self.B, n, 2):
+            raise ValueError('%s: robot_actions must be [%d, n = %d, 2], got %s' % (who, self.B, n, shape))
+        t = robot_actions
+        if not (torch.is_tensor(t) and t.device == self.device and t.dtype == torch.float64):
+            t, temporary = self._borrow(t, torch.float64, shape)
+            return t, n, temporary
+        if n == 0:
+            return t, 0, False
+        between, row, last = t.stride()
+        if last != 1 or (n > 1 and row != 2):
+            raise ValueError('%s: robot_actions: the last two dimensions must be contiguous (strides %s)' % (who, (between, row, last)))
+        if self.B == 1:
+            return t, n, False
+        if between % 2 or between < 2 * n:
+            raise ValueError('%s: robot_actions: %d elements between envs are not a whole number of rows >= n = %d'
+                             % (who, between, n))
+        return t, between // 2, False
+
+    # ---------------------------------------------------------------- ... the robot in sight, on its nominal plan (cn_predict_orca_robot)
+    def predict_orca_robot(self, n, robot_actions, out=None, mode=None):
+        """predict_orca's table with the robot in the humans' sight, following robot_actions [B, n, 2] float64
+        (cn_predict_orca_robot): what step(robot_actions[:, t]) reports in orca_vel[:, 1:], t = 0 .. n - 1, on an external-robot
+        engine with robot_visible = 1 and fresh simulators started from this engine's state.  Within a step the humans solve
+        against the robot where it stands and with the velocity it has, move, and then the robot takes its row: (vx, vy) used as
+        given, not clipped; ActionRot (v, r) on a unicycle engine, from get_theta()'s heading.  The robot has no collision test
+        and no episode end: all n rows are followed.  For the sequence itself lookahead_paths on this table is lookahead() under
+        'orca' on a robot_visible = 1 engine with fresh simulators; for any other candidate the humans avoid the nominal robot,
+        not that candidate.  robot_actions: a float64 tensor on the engine's device whose last two dimensions are contiguous is
+        read where it lies — plan.candidates[:, 0], the plan's clipped mean after plan_draw, as it is (ValueError if what lies
+        between its envs is not whole rows); a numpy array or CPU tensor is copied to the device.  out, mode, n = 0 and what
+        the call leaves alone: as predict_orca.  Any engine, robot_visible = 0 ones included: the humans of this call see the
+        robot all the same."""
+        if robot_actions is None:
+            raise ValueError('predict_orca_robot: robot_actions is required ([%d, n, 2]); predict_orca(n) leaves the robot out' % self.B)
+        return self._predict_orca('predict_orca_robot', n, out, mode, robot_actions)
 
     def plan_predict_orca_rollout(self, plan, pred, n_real, counter, orca_mode=0, temperature=None, fit_std=False):
         """plan_predict_rollout with future `orca_mode` of pred made by predict_orca (cn_plan_cem_predict_orca_rollout; with a
@@ -770,18 +819,29 @@ class BatchedCrowdSim(object):
         out=pred.human_vel, mode=orca_mode) over that slot, the paths (M = 1) or modes planner, rollout_step(plan.action),
         plan_shift — ONE call, bit for bit what those calls give.  pred: plan_predict_begin's, whose name for slot orca_mode is
         computed and overwritten.  Returns the rollout's bufs."""
+        return self._orca_rollout('plan_predict_orca_rollout', 'predict_orca_rollout', plan, pred, n_real, counter, orca_mode,
+                                  temperature, fit_std)
+
+    def plan_predict_orca_nominal_rollout(self, plan, pred, n_real, counter, orca_mode=0, temperature=None, fit_std=False):
+        """plan_predict_orca_rollout whose ORCA future sees the robot on the plan's nominal sequence
+        (cn_plan_cem_predict_orca_nominal_rollout; with a temperature the mppi one): per step plan_draw(plan, c) with
+        c = counter + s * iterations, predict() into pred.human_vel, predict_orca_robot(plan.n, plan.candidates[:, 0],
+        out=pred.human_vel, mode=orca_mode), the paths or modes planner with c, rollout_step(plan.action), plan_shift — ONE
+        call, bit for bit what those calls give.  One prediction per planning step, not per iteration."""
+        return self._orca_rollout('plan_predict_orca_nominal_rollout', 'predict_orca_nominal_rollout', plan, pred, n_real, counter,
+                                  orca_mode, temperature, fit_std)
+
+    def _orca_rollout(self, who, name, plan, pred, n_real, counter, orca_mode, temperature, fit_std):
         if not isinstance(plan, Plan) or plan.engine() is not self:
             raise ValueError('plan: a Plan made by this engine\'s plan_begin()')
         if not isinstance(pred, Predictors) or pred.engine() is not self or pred.plan() is not plan:
             raise ValueError('pred: the Predictors made by this engine\'s plan_predict_begin() for this plan')
         if isinstance(orca_mode, bool) or not isinstance(orca_mode, (int, np.integer)) or not 0 <= orca_mode < pred.c.n_modes:
-            raise ValueError('plan_predict_orca_rollout: orca_mode must be an int in 0 .. M - 1 = %d, got %r'
-                             % (pred.c.n_modes - 1, orca_mode))
+            raise ValueError('%s: orca_mode must be an int in 0 .. M - 1 = %d, got %r' % (who, pred.c.n_modes - 1, orca_mode))
         if temperature is None:
-            return self._plan_call('cem_predict_orca_rollout', plan, C.byref(pred.c), int(orca_mode), rollout=True, n_real=n_real,
-                                   counter=counter)
-        return self._plan_call('mppi_predict_orca_rollout', plan, C.byref(pred.c), int(orca_mode), float(temperature),
-                               int(bool(fit_std)), rollout=True, n_real=n_real, counter=counter)
+            return self._plan_call('cem_' + name, plan, C.byref(pred.c), int(orca_mode), rollout=True, n_real=n_real, counter=counter)
+        return self._plan_call('mppi_' + name, plan, C.byref(pred.c), int(orca_mode), float(temperature), int(bool(fit_std)),
+                               rollout=True, n_real=n_real, counter=counter)
 
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):

@@ -15,6 +15,8 @@ A third predictor exists on the device only: BatchedCrowdSim.predict_orca (cn_pr
 own ORCA code, the robot unseen — humans that avoid each other, between to_goal (straight through every other human) and the
 full 'orca' lookahead (humans that react to each candidate robot path) — and plan_predict_orca_rollout plans on it in closed
 loop.  It has no host form here: its oracle is the environment itself, stepped with robot_visible = 0.
+BatchedCrowdSim.predict_orca_robot (cn_predict_orca_robot) is the same with the robot in the humans' sight on a sequence of
+actions the caller names — the plan's mean, say: plan_predict_orca_nominal_rollout — one prediction per planning step.
 
 torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
 returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is

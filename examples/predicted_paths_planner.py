@@ -4,7 +4,7 @@ predicted velocities the CALLER makes from the state after every real step (DESI
 
     python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
                                                [--futures cv,to_goal [--reduce min] [--risk-penalty 0.5]]
-                                               [--device-loop [--chunk 8]]
+                                               [--device-loop [--chunk 8]] [--orca-sees-plan]
 
 Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
 stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
@@ -20,7 +20,10 @@ and the host only looks at the rollout between chunks.  The predictor is bit-exa
 (step * iterations), so the line printed is the one the per-step loop prints.
 --futures also takes `orca` (once), beside cv and to_goal: the humans avoid EACH OTHER by the engine's own ORCA code but do not
 see the robot (BatchedCrowdSim.predict_orca, DESIGN.md §3.8.11) — a table made on the device in one launch per real step;
-with --device-loop the one call is plan_predict_orca_rollout, which writes that future over its slot of the table."""
+with --device-loop the one call is plan_predict_orca_rollout, which writes that future over its slot of the table.
+--orca-sees-plan (with --futures ...,orca): the humans of that future DO see the robot, on the plan's nominal sequence — per
+real step plan_draw, then BatchedCrowdSim.predict_orca_robot on candidate 0, the clipped mean; with
+--device-loop the one call is plan_predict_orca_nominal_rollout."""
 import argparse
 import logging
 import os
@@ -34,7 +37,7 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
-         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8):
+         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8, orca_sees_plan=False):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -57,15 +60,18 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
             if orca_mode is None:
                 eng.plan_predict_rollout(planner, pred, min(chunk, most - first), first * iterations, temperature=temperature)
             else:
-                eng.plan_predict_orca_rollout(planner, pred, min(chunk, most - first), first * iterations, orca_mode=orca_mode,
-                                              temperature=temperature)
+                loop = eng.plan_predict_orca_nominal_rollout if orca_sees_plan else eng.plan_predict_orca_rollout
+                loop(planner, pred, min(chunk, most - first), first * iterations, orca_mode=orca_mode, temperature=temperature)
             if int(bufs['active'].sum().item()) == 0:
                 break
     for step in range(0 if device_loop else most):  # the per-step loop through the host (not entered with --device-loop)
         state8, _ = eng.get_state()  # what the planner observes: positions and velocities (to_goal also reads the goals)
+        if orca_sees_plan:  # the nominal sequence: candidate 0 of this step's first draw, the mean under the clip rule
+            eng.plan_draw(planner, step * iterations)
         tables = {'to_goal': lambda: predict.to_goal(state8, horizon, env.time_step),
                   'constant_velocity': lambda: predict.constant_velocity(state8, horizon),
-                  'orca': lambda: eng.predict_orca(horizon)}
+                  'orca': lambda: (eng.predict_orca_robot(horizon, planner.candidates[:, 0]) if orca_sees_plan
+                                   else eng.predict_orca(horizon))}
         if futures:  # several futures side by side, one call
             human_vel = predict.stack_modes(*(tables[name]() for name in futures))
             if temperature is None:
@@ -110,6 +116,8 @@ def main():
     ap.add_argument('--risk-penalty', type=float, default=0.0, help='--futures: subtracted per unit of collision probability')
     ap.add_argument('--device-loop', action='store_true', help='predict on the device too: one plan_predict_rollout call per chunk')
     ap.add_argument('--chunk', type=int, default=8, help='--device-loop: real steps per call')
+    ap.add_argument('--orca-sees-plan', action='store_true',
+                    help="--futures ...,orca: that future's humans see the robot on the plan's nominal sequence")
     args = ap.parse_args()
     names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal', 'orca': 'orca'}
     futures = None
@@ -124,10 +132,12 @@ def main():
         ap.error('--device-loop: --futures takes two or more predictors (one predictor: --predictor)')
     if args.chunk < 1:
         ap.error('--chunk must be >= 1')
+    if args.orca_sees_plan and not (futures and 'orca' in futures):
+        ap.error('--orca-sees-plan needs --futures with orca in it')
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
                       predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty,
-                      device_loop=args.device_loop, chunk=args.chunk))
+                      device_loop=args.device_loop, chunk=args.chunk, orca_sees_plan=args.orca_sees_plan))
     return 0
 
 

@@ -1022,6 +1022,52 @@ int cn_plan_mppi_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int
                                       const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
                                       int fit_std, uint32_t counter);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The ORCA predictor with the robot in sight, on its nominal plan (no version bump: three new symbols; no existing struct, enum
+ * or counter touched).  cn_predict_orca's humans behave as if the robot were not there; cn_lookahead_actions under
+ * CN_HUMANS_ORCA solves ORCA for every one of the K candidates.  In between: the humans react to ONE robot trajectory the
+ * caller names — the plan's mean, say — and the table is made once per planning step.
+ *   cn_predict_orca_robot writes slot `mode` of cn_predict_orca's table, from the engine's state as it stands, the humans
+ *   stepped n_steps times exactly as cn_step steps them on a CN_ROBOT_EXTERNAL engine with robot_visible = 1 and freshly made
+ *   simulators (cn_drop_sims) whose robot takes row t of robot_actions at step t.  Row (b, t) is the two doubles at
+ *   robot_actions + 2 (b env_stride + t); env_stride counts rows between envs, 0 means n_steps (a dense [B][n_steps][2]
+ *   table).  With env_stride = K n, plan->candidates is candidate 0 of every env — the plan's mean under the draw's clip rule.
+ * Order of events within step t, CrowdSim.step's: (1) every human solves ORCA against the other humans and the robot WHERE IT
+ * STANDS and WITH THE VELOCITY IT HAS (the observation is built before the robot moves; the robot's radius in a human's
+ * simulator is float32(radius + 0.01 + human_safety), as any other agent's); (2) the humans move by p + v dt and row t is
+ * stored; (3) the robot takes row t: holonomic (vx, vy), used as given and NOT clipped (as cn_rollout_actions and
+ * cn_lookahead_actions take theirs), p + v dt; on a CN_UNICYCLE engine ActionRot(v, r): the end point px + cos(theta + r) v dt,
+ * theta <- (theta + r) mod 2 pi with python's %, the velocity v (cos, sin)(theta).  The robot starts from the engine's state —
+ * position, velocity, radius, cn_get_theta's heading.  It has no swept test, reward, done or time: all n_steps rows are
+ * followed and written, as the environment's humans keep stepping behind a `done`.  So for the sequence itself
+ * cn_lookahead_paths on this table is cn_lookahead_actions under CN_HUMANS_ORCA on a robot_visible = 1 engine with fresh
+ * simulators, bit for bit; for any other candidate scored against it the humans avoid the nominal robot, not that candidate.
+ * ANY engine is served — CN_ROBOT_ORCA (its rows are (vx, vy)), CN_UNICYCLE and robot_visible = 0 ones: the humans of THIS
+ * call see the robot all the same (nothing of the workgroup is sized by the engine's setting).  ONE launch on the engine's
+ * stream, NOT counted in cn_launch_counts; nothing of the engine is written.  Refused, in this order, before anything is
+ * enqueued: NULL human_vel: CN_ERR_INVALID; NULL robot_actions: CN_ERR_INVALID naming it; env_stride < 0 or 0 < env_stride <
+ * n_steps: CN_ERR_INVALID with both numbers; then cn_predict_orca's refusals, in its order, under this call's name.
+ * n_steps == 0: CN_OK, nothing launched, nothing written.  Asynchronous: both arrays must stay valid until the launch has run.
+ * Out of scope: clipping or validating the rows; re-predicting between the iterations of one planning step. */
+int cn_predict_orca_robot(cn_engine* e, int n_steps, int n_modes, int mode,
+                          const double* robot_actions /* DEVICE; row (b, t) at robot_actions + 2 (b env_stride + t) */,
+                          int64_t env_stride          /* rows between envs; 0 means n_steps */,
+                          double* human_vel           /* DEVICE [B][n_modes][n_steps][A-1][2], 16-byte aligned */);
+/* cn_plan_*_predict_orca_rollout with slot orca_mode made by cn_predict_orca_robot on the plan's nominal sequence.  Per real
+ * step s, with c = counter + s * iterations:
+ *   cn_predict(..); cn_plan_draw(e, cfg, plan, c);
+ *   cn_predict_orca_robot(e, cfg->n_steps, M, orca_mode, plan->candidates, K n, pred->human_vel)
+ *       — candidates[b][0] of that draw: the mean as it stands after the previous step's shift, under the draw's clip rule;
+ *   the paths (M == 1) or modes planner with counter c — its iteration 0 draws with c again, the same bits, so the call does
+ *   not launch that draw a second time; cn_rollout_step; cn_plan_shift.
+ * ONE prediction per planning step, not one per CEM / MPPI iteration.  Arguments, checks and their order: those of the
+ * cn_plan_*_predict_orca_rollout calls, under these names; CN_ROBOT_ORCA and CN_UNICYCLE engines stay refused. */
+int cn_plan_cem_predict_orca_nominal_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                              const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter);
+int cn_plan_mppi_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
+                                              const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
+                                              int fit_std, uint32_t counter);
+
 #ifdef __cplusplus
 }
 #endif
