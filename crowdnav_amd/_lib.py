@@ -188,6 +188,9 @@ SYMBOLS = {
     'cn_launch_counts': (C.c_int, [_P, _P]),
     'cn_lagged_fills': (C.c_int, [_P, _P]),
     'cn_mt_random': (C.c_int, [_P, C.c_uint32, C.c_int, _P]),
+    # two-wave rollout: first steps solved at fill time — counters, and a ring slot as the last fill left it (no version bump)
+    'cn_fresh_starts': (C.c_int, [_P, _P]),
+    'cn_ring_slot': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int)]),
     # device SGD step (added after v12, no version bump)
     'cn_trainer_create': (C.c_int, [C.POINTER(CnSarlConfig), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     'cn_trainer_destroy': (C.c_int, [_P]),

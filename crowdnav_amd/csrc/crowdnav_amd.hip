@@ -199,6 +199,8 @@ static void pick_geometry(cn_engine* e) {
     e->smem = cn::smem_bytes(P.nA, P.pairs, e->maxl, P.A, P.E);
 }
 
+static int rollout_route(const cn_engine* e, const double* action);
+
 // The run-time switches and what they are weighed against: the device's size.  The scenario ring reads its own.
 static void read_knobs(cn_engine* e) {
     const cn_config* c = &e->cfg;
@@ -232,6 +234,8 @@ static void read_knobs(cn_engine* e) {
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, e->smem) == hipSuccess)
                 e->split_slots = per_cu * prop.multiProcessorCount;
         });
+    // the engines whose cn_rollout runs the two-wave kernel solve every ring scenario's first step when the slot is filled
+    e->ring.first_step = rollout_route(e, nullptr) == CN_ROUTE_FUSED_SPLIT;
 }
 
 // every device buffer of the engine — the scenario ring allocates its own — and the device copy of the state view (the caller
@@ -355,7 +359,7 @@ __global__ void unpack_state_kernel(int n, double* state8, cn::StateView S) {
 
 int cn_set_state(cn_engine* e, const double* state8, const double* global_time) {
     int rc = bind(e);
-    if (rc || (rc = e->ring.settle(e))) return rc;
+    if (rc || (rc = e->ring.settle(e)) || (rc = e->ring.forget_first_steps(e))) return rc;
     const int n = e->P.B * e->P.A;
     if (state8) hipLaunchKernelGGL(pack_state_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, state8, e->S);
     if (global_time)
@@ -426,6 +430,9 @@ int cn_set_robot_sim(cn_engine* e, const float* radii_host, float max_speed) {
     int rc = bind(e);
     if (rc) return rc;
     if (!radii_host) return fail(CN_ERR_INVALID, "cn_set_robot_sim: NULL");
+    // (a fill beside the previous launch may be solving first steps with the simulator as it was)
+    if ((rc = e->ring.settle(e)) || (rc = e->ring.forget_first_steps(e))) return rc;
+    e->ring.robot_sim_known = true;
     float* staged = reinterpret_cast<float*>(e->probe_key);  // 624 words of scratch, A <= 64
     CN_HIP(hipMemcpyAsync(staged, radii_host, sizeof(float) * e->P.A, hipMemcpyHostToDevice, e->stream));
     CN_HIP(hipStreamSynchronize(e->stream));  // radii_host may be a temporary
@@ -437,7 +444,8 @@ int cn_set_robot_sim(cn_engine* e, const float* radii_host, float max_speed) {
 
 int cn_drop_robot_sim(cn_engine* e) {
     int rc = bind(e);
-    if (rc) return rc;
+    if (rc || (rc = e->ring.settle(e)) || (rc = e->ring.forget_first_steps(e))) return rc;
+    e->ring.robot_sim_known = false;
     CN_HIP(hipMemsetAsync(e->S.rsim_valid, 0, (size_t)e->P.B, e->stream));
     if (e->P.kd)  // ... and its simulator's kd-tree order: byte 0 of every env's A flags
         CN_HIP(hipMemset2DAsync(e->S.kd_valid, (size_t)e->P.A, 0, 1, (size_t)e->P.B, e->stream));
@@ -455,6 +463,7 @@ int cn_reset(cn_engine* e, const uint32_t* seeds, const uint8_t* mask, uint64_t*
     int rc = bind(e);
     if (rc || (rc = e->ring.settle(e))) return rc;
     if (!seeds) return fail(CN_ERR_INVALID, "cn_reset: seeds is NULL");
+    if ((rc = e->ring.forget_first_steps(e))) return rc;
     if (e->ring.gen_wave)
         hipLaunchKernelGGL(cn::reset_wave_kernel, dim3(e->P.B), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, seeds, mask,
                            draws);
@@ -545,6 +554,7 @@ int cn_rollout_begin(cn_engine* e, const cn_rollout_io* io) {
     e->rollout_begun = false;
     if ((rc = upload_io(e, io))) return rc;
     e->rollout_begun = true, e->begin_seed_base = io->seed_base, e->begin_seed_mod = io->seed_mod;
+    if ((rc = e->ring.forget_first_steps(e))) return rc;
     return e->ring.begin(e, io->seed_mod);
 }
 
@@ -865,6 +875,45 @@ int cn_rollout_route(cn_engine* e, int n_steps, int* route_host) {
 int cn_lagged_fills(cn_engine* e, uint64_t* count_host) {
     if (!e || !count_host) return fail(CN_ERR_INVALID, "cn_lagged_fills: NULL argument");
     *count_host = e->ring.lagged_fills;
+    return CN_OK;
+}
+
+int cn_fresh_starts(cn_engine* e, uint64_t* counts_host) {
+    int rc = bind(e);
+    if (rc) return rc;
+    if (!counts_host) return fail(CN_ERR_INVALID, "cn_fresh_starts: counts_host is NULL");
+    unsigned int dev[2] = {0u, 0u};
+    CN_HIP(hipMemcpyAsync(dev, e->S.fresh_counts, sizeof(dev), hipMemcpyDeviceToHost, e->stream));
+    CN_HIP(hipStreamSynchronize(e->stream));
+    counts_host[0] = dev[0], counts_host[1] = dev[1], counts_host[2] = e->ring.first_step_kernels;
+    return CN_OK;
+}
+
+int cn_ring_slot(cn_engine* e, int env, int slot, double* state8_host, float* vel0_host, int* ok_host) {
+    int rc = bind(e);
+    if (rc || (rc = e->ring.settle(e))) return rc;
+    if (!state8_host || !vel0_host || !ok_host) return fail(CN_ERR_INVALID, "cn_ring_slot: NULL argument");
+    if (env < 0 || env >= e->P.B || slot < 0 || slot >= e->P.ring_mod)
+        return fail(CN_ERR_INVALID, "cn_ring_slot: (env, slot) = (%d, %d) outside %d envs x %d slots", env, slot, e->P.B, e->P.ring_mod);
+    const int A = e->P.A;
+    const size_t idx = (size_t)env * e->P.ring_mod + slot;
+    std::vector<double2> pos((size_t)A), goal((size_t)A), rv((size_t)A);
+    std::vector<float2> vel((size_t)A, make_float2(0.0f, 0.0f));
+    uint8_t ok = 0;
+    CN_HIP(hipStreamSynchronize(e->stream));
+    CN_HIP(hipMemcpy(pos.data(), e->S.ring_pos + idx * A, sizeof(double2) * A, hipMemcpyDeviceToHost));
+    CN_HIP(hipMemcpy(goal.data(), e->S.ring_goal + idx * A, sizeof(double2) * A, hipMemcpyDeviceToHost));
+    CN_HIP(hipMemcpy(rv.data(), e->S.ring_rv + idx * A, sizeof(double2) * A, hipMemcpyDeviceToHost));
+    if (e->ring.first_step) {
+        CN_HIP(hipMemcpy(vel.data(), e->S.ring_vel0 + idx * A, sizeof(float2) * A, hipMemcpyDeviceToHost));
+        CN_HIP(hipMemcpy(&ok, e->S.ring_vel0_ok + idx, 1, hipMemcpyDeviceToHost));
+    }
+    for (int a = 0; a < A; ++a) {
+        double* s = state8_host + 8 * (size_t)a;
+        s[0] = pos[a].x, s[1] = pos[a].y, s[2] = 0.0, s[3] = 0.0, s[4] = goal[a].x, s[5] = goal[a].y, s[6] = rv[a].x, s[7] = rv[a].y;
+        vel0_host[2 * a] = vel[a].x, vel0_host[2 * a + 1] = vel[a].y;
+    }
+    *ok_host = ok;
     return CN_OK;
 }
 

@@ -69,6 +69,13 @@ struct ScenarioRing {
     int fill_queue_wgs = 1;      // persistent generator workgroups of a WorkList fill launch (CROWDNAV_AMD_FILL_QUEUE_WGS, at least 1)
     int* ep_snap = nullptr;      // [B] the Beside fill's copy of StateView::ep_word (ring_fill_begin_kernel)
     uint64_t lagged_fills = 0;   // cn_lagged_fills: fills enqueued beside a launch (counted in CN_COUNT_RING_FILLS too)
+    // First step of every scenario solved at fill time (rollout_fused.h: ring_first_step_kernel).
+    bool first_step = false;     // the engine's cn_rollout runs the two-wave kernel (read_knobs): its fills clear ring_vel0_ok, list
+                                 // their slots and are followed by the kernel
+    bool robot_sim_known = false;  // every env's rsim_* is captured and complete in stream order behind whatever the engine's stream
+                                   // holds now: a rollout launch was enqueued, or cn_set_robot_sim, and no drop since.  Only then may
+                                   // the kernel run BESIDE a launch — that launch's prologue might otherwise be the one that captures
+    uint64_t first_step_kernels = 0;  // ring_first_step_kernel launches enqueued (cn_fresh_starts)
 
     void configure(cn_engine* e, int compute_units);
     int create(cn_engine* e);
@@ -78,6 +85,7 @@ struct ScenarioRing {
     int around_launch(cn_engine* e, int n_steps, Launch&& launch);
     int settle(cn_engine* e);
     int drain(cn_engine* e);
+    int forget_first_steps(cn_engine* e);
 };
 
 struct cn_engine {

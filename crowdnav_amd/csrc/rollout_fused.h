@@ -411,7 +411,14 @@ static __device__ unsigned long long cn_wave_trace[8192 * 6];
 // barrier 1 the ORCA wave then drops the velocities and the view it has just published — they touched LDS only — copies
 // the true rows into kin, re-reads its positions and its per-episode constants and computes step u again, while the env
 // wave publishes sol / res of the true state and idles past barrier 2.  One ORCA step is redone per episode end of a
-// workgroup (~1 in 21 wave-steps at the headline shape).
+// workgroup that is NOT FRESH (~1 in 21 wave-steps at the headline shape when none is).
+// Fresh: every env that ended goes on with a ring scenario whose first step was solved when the slot was filled
+// (ring_first_step_kernel at the end of this file; StateView::ring_vel0, loaded with the scenario) and the launch has a step left.
+// Then step u of the new episode IS solved: the env wave stages the state behind it for the restarted envs' lanes (posd = p0 +
+// v0 dt, the d2 row with v0), keeps v0 in a row of its own and posts the envs' bits (bit 1 + el, bit 0 clear).  The ORCA wave
+// adopts positions and kin rows of those lanes — the same extra trip — and goes on with step u + 1; the env wave integrates
+// step u of those lanes from its v0 row, of the other env from vel as ever.  No iteration is redone, the other env is not
+// disturbed, and both waves still count u from the same word.
 // The step counters, the discount index and every store to global memory live in the env wave.
 // What the waves exchange lives in arrays of the LDS layout that the fused kernels do not otherwise use: Smem::act (the
 // published velocities, as float2), Smem::flag[0] (the word) and, with ASSIST, Smem::flag[1] (the prediction word: an
@@ -506,7 +513,7 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
     double px = 0.0, py = 0.0;
     float rx = 0.0f, ry = 0.0f;
     bool solved = false;
-    // Per-episode constants, refreshed in an iteration with `ended` (the launch's first has it: word = 1).  rsum: rview is
+    // Per-episode constants, refreshed in an iteration with `staged` (redo or adopt; the launch's first has it: word = 1).  rsum: rview is
     // written in the prologue only, hview by stage_agent — prologue and episode end.  solved: sol[].w is the env wave's
     // `running && (human || robot_orca)`, and ep.state changes in CN_END_EPISODE alone (next scenario, pause, retire: all
     // under `done`, which sets `ended`); scenario_ready outside of it is the prologue's.
@@ -518,7 +525,10 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
         // kin(u) was staged at the end of the previous iteration: the pair rows are requested beside the two words
         const int2 words = make_int2(s.flag[0], ((ASSIST & kAssistHead) || kSplitProbe) ? s.flag[1] : 0);
         float4 me = s.kin[pq], other = s.kin[pr.my_slot];
-        const bool ended = __builtin_amdgcn_readfirstlane(words.x) != 0;
+        // the word: bit 0 = redo (below); otherwise bit 1 + el = env el of the workgroup starts its episode from a first step
+        // solved at fill time: its lanes ADOPT the state behind that step and nothing is dropped
+        const int word = __builtin_amdgcn_readfirstlane(words.x);
+        const bool ended = (word & 1) != 0;
         const unsigned int pred = ((ASSIST & kAssistHead) || kSplitProbe) ? (unsigned int)__builtin_amdgcn_readfirstlane(words.y) : 0u;
         if (!ended) ++u;
         if (u >= n_steps) {  // the env wave finishes step n_steps - 1 alone
@@ -527,8 +537,10 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
         }
         const bool head = (ASSIST & kAssistHead) ? split_has_head<MAXL>(pred, u, n_steps) : false;
         SPLIT_PROBE_AFTER_1(pred, head);
-        if (ended) {  // the env wave staged the true state (its kin rows in d2: this wave owns kin in window 2): the one extra trip
-            if (lane < P.nA) {
+        const bool staged = word != 0;  // (wave-uniform)
+        if (staged) {  // the env wave staged the true state (its kin rows in d2: this wave owns kin in window 2): the one extra trip
+            // redo: every lane; adopt: the lanes of the adopting envs — the other env's rows and positions are this wave's own
+            if (lane < P.nA && (ended || ((word >> (1 + lane / P.A)) & 1) != 0)) {
                 const double2 p = s.posd[lane];
                 px = p.x, py = p.y;
                 s.kin[lane] = reinterpret_cast<const float4*>(s.d2)[lane];
@@ -536,12 +548,12 @@ __device__ __forceinline__ void split_orca_wave(const Params& P, const Smem& s, 
             CN_FUSED_SYNC();
             me = s.kin[pq], other = s.kin[pr.my_slot];
         }
-        if (ended) rsum = pair_rsum(s, pr);
+        if (staged) rsum = pair_rsum(s, pr);
         if (lane < P.pairs) fused_pair_body(P, s, pr, range_sq, rsum, me, other, [] {});
         SPLIT_PROBE_WAIT(1, split_barrier());  // 2: sol / res of step u
         fused_candidates<MAXL>(P, s, lane);
         CN_FUSED_SYNC();
-        if (ended) solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
+        if (staged) solved = lane < P.nA && s.sol[lane < P.nA ? lane : 0].w != 0.0f;
         const unsigned long long nm = fused_solve<MAXL, kSplitOrcaPrio>(P, s, lane, solved, rx, ry, nullptr, head ? pred : 0u, [&] {
             if (head) SPLIT_PROBE_WAIT(2, split_barrier());  // 3: the env wave's proj / cand3 rows of the agents of pred
         });
@@ -663,7 +675,8 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
 #endif
     if constexpr (SPLIT) {
         float2* const vel = reinterpret_cast<float2*>(s.act);
-        if (L.lane == 0) s.flag[0] = 1, s.flag[1] = 0;  // "re-read the staged state"; no agent predicted infeasible
+        // "re-read the staged state"; no agent predicted infeasible; [2], [3]: episode starts adopted, iterations redone
+        if (L.lane == 0) s.flag[0] = 1, s.flag[1] = 0, s.flag[2] = 0, s.flag[3] = 0;
         split_barrier();  // prologue staged
         bool skip = true;  // the state of step u is already in registers: nothing to integrate, nothing to book
         // Mirror lanes: lane 16 + l carries a copy of agent lane l's position and goal (in the same registers: nothing else
@@ -682,6 +695,12 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             if (mirror) r.px = px, r.py = py, r.gx = gx, r.gy = gy, m_running = run != 0;
         };
         copy_to_mirror();
+        // Fresh start: an episode that starts from a ring slot whose first step was solved when the slot was filled
+        // (ring_first_step_kernel, StateView::ring_vel0) costs the workgroup no redone iteration.  The env wave leaves those
+        // velocities in a row of its own — the upper half of Smem::act, behind the ORCA wave's vel — and the lanes of such an
+        // env (and their mirror lanes) integrate the episode's first step from that row: v0_off is the row's offset for them in
+        // that one iteration, 0 otherwise.  vel holds the dead episode's solve then; the other env reads it as ever.
+        int v0_off = 0;
         SPLIT_PROBE_DECL();
         for (int u = 0;;) {
             SPLIT_PROBE_WAIT(0, split_barrier());  // 1: vel(u - 1)
@@ -693,7 +712,8 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
             double act_x = 0.0, act_y = 0.0, new_vx = 0.0, new_vy = 0.0;
             // (the mirror lanes integrate their copy with the same statements on the same operands: no instruction more)
             if (!skip && (L.lane < P.nA || mirror)) {
-                const float2 mine = vel[m_lane], robots = vel[m_ebase];
+                const float2 mine = vel[v0_off + m_lane], robots = vel[v0_off + m_ebase];
+                v0_off = 0;
                 act_x = (double)robots.x, act_y = (double)robots.y;
                 new_vx = m_robot ? act_x : (double)mine.x;
                 new_vy = m_robot ? act_y : (double)mine.y;
@@ -732,12 +752,14 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                 }
             }
             bool ended = false;
+            unsigned int adopt = 0u;
+            bool done = false, v0_ok = false;  // v0_ok: the env went on with a scenario whose first step is solved (v0)
+            float2 v0 = make_float2(0.0f, 0.0f);
             if (!skip) {
                 // the robot's position at the start of the step: from its lane's registers (posd holds re-staged states only)
                 const double2 rp = make_double2(__shfl(r0.px, L.ebase), __shfl(r0.py, L.ebase));
                 if (L.valid) s.closest[L.lane] = swept_distance(r0, L.a > 0, rp, act_x, act_y, new_vx, new_vy, K.dt, s.rad[L.ebase]);
                 CN_FUSED_SYNC();
-                bool done = false;
                 if (running) {
                     const double disc_t = s.disc[ep.cur_steps < kMaxDiscount ? ep.cur_steps : kMaxDiscount - 1];
                     const StepOutcome o = reduce_env(P, s, L.ebase, ep.gtime, K);
@@ -746,23 +768,51 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
                     ++transitions;
                     CN_BOOK_TRANSITION(ep, ep.cur_steps < kMaxDiscount ? disc_t : 0.0, o.reward, o.info, o.dmin);
                     if (done) {  // explorer.py:50-72: record, then the env's next episode
-                        // every load of the episode end first (the io block, the state pointers, the next scenario — in
-                        // bounds whether or not it is taken), then the record stores: one memory round trip in the shadow
-                        // of the ORCA wave's step
+                        // every load of the episode end first (the io block, the state pointers, the next scenario and its solved
+                        // first step — in bounds whether or not it is taken; an engine that runs this kernel has the ring_vel0
+                        // arrays: ScenarioRing::first_step), then the record stores: one memory round trip in the shadow of the
+                        // ORCA wave's step
                         const cn_rollout_io io = *iop;
                         const StateView S = *Sd;
                         AgentRegs next = r;
-                        load_from_ring(P, S, L, (ep.ep_count + 1) % P.ring_mod, next);
-                        CN_END_EPISODE(P, S, io, L.env, L.a == 0, K.limit, o.info, ep, r = next; theta = 1.5707963267948966);
+                        const int next_slot = (ep.ep_count + 1) % P.ring_mod;
+                        load_from_ring(P, S, L, next_slot, next);
+                        const size_t next_idx = (size_t)L.env * P.ring_mod + next_slot;
+                        const float2 v0_next = S.ring_vel0[next_idx * P.A + L.a];
+                        const bool ok_next = S.ring_vel0_ok[next_idx] != 0;
+                        CN_END_EPISODE(P, S, io, L.env, L.a == 0, K.limit, o.info, ep,
+                                       r = next; theta = 1.5707963267948966; v0 = v0_next; v0_ok = ok_next);
                     }
                 }
-                ended = __ballot(done) != 0ull;
+                const unsigned long long ended_lanes = __ballot(done);
+                ended = ended_lanes != 0ull;
+                // fresh (wave-uniform): every env that ended goes on, from a solved first step, and the launch has a step left for
+                // it.  Then nothing is redone: bit 1 + el of the word tells the ORCA wave that env el adopts what is staged below
+                if (ended && u < n_steps && __ballot(done && v0_ok) == ended_lanes)
+                    for (int el = 0; el < P.E; ++el) adopt |= (unsigned int)((ended_lanes >> (el * P.A)) & 1ull) << (1 + el);
             }
-            // per-episode constants (rad, hview) and the float32 view are staged here and in the prologue only
-            if (ended) stage_agent(P, s, L, r, K.hsafety, kin_stage);
-            if (ended) copy_to_mirror();
-            if (L.lane == 0) s.flag[0] = ended ? 1 : 0;
-            skip = ended;
+            // per-episode constants (rad, hview) and the float32 view are staged here and in the prologue only.  Not fresh: the
+            // true state of step u.  Fresh: the restarted envs' lanes stage the state BEHIND the solved step — the ORCA wave's own
+            // staging expression; the integration of the next iteration yields the same bits — and keep the velocities for it;
+            // what the other env's lanes stage nobody reads.
+            if (ended) {
+                AgentRegs st = r;
+                if (adopt != 0u && done) {
+                    st.px = r.px + (double)v0.x * K.dt;
+                    st.py = r.py + (double)v0.y * K.dt;
+                    st.vx = (double)v0.x, st.vy = (double)v0.y;
+                    vel[P.nA + L.lane] = v0;
+                }
+                stage_agent(P, s, L, st, K.hsafety, kin_stage);
+                copy_to_mirror();
+                if (adopt != 0u) v0_off = ((adopt >> (1 + m_ebase / P.A)) & 1u) != 0u ? P.nA : 0;
+                // counted in two LDS words of the env wave's own and added to StateView::fresh_counts behind the loop: a global
+                // atomic here — the pointer's load, then the atomic — was a dependent memory round trip in front of barrier 1
+                // (the last step of a launch: its end costs no iteration either way)
+                if (L.lane == 0 && u < n_steps) s.flag[adopt != 0u ? 2 : 3] += adopt != 0u ? __popc(adopt) : 1;
+            }
+            if (L.lane == 0) s.flag[0] = ended ? (adopt != 0u ? (int)adopt : 1) : 0;
+            skip = ended && adopt == 0u;
             if constexpr ((ASSIST & kAssistHead) != 0 && CN_SPLIT_HEAD_TAIL_PRIO != 0) __builtin_amdgcn_s_setprio(0);
             if (u >= n_steps) break;
         }
@@ -864,6 +914,13 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
     const unsigned long long wt_exit = __builtin_amdgcn_s_memrealtime();
 #endif
     const StateView S = *Sd;
+    if constexpr (SPLIT) {
+        if (L.lane == 0) {
+            const int adopted = s.flag[2], redone = s.flag[3];
+            if (adopted != 0) atomicAdd(&S.fresh_counts[0], (unsigned int)adopted);
+            if (redone != 0) atomicAdd(&S.fresh_counts[1], (unsigned int)redone);
+        }
+    }
     if (L.valid) CN_STORE_AGENT(S, L.gi, r);
     const cn_rollout_io io = *iop;
     if (robot) CN_STORE_EPISODE(P, S, io, L.env, ep, theta);
@@ -878,6 +935,74 @@ __global__ __launch_bounds__((SPLIT ? 2 : 1) * kWave, (SPLIT ? 4 : HEADLINE ? 3 
         w[4] = wt_fallbacks | (wt_ends << 32), w[5] = hw;
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------- first steps, at fill time
+// The first ORCA step of a ring scenario is a pure function of the scenario (velocities zero), the engine's parameters and the
+// robot's captured simulator: solved HERE, once, behind the fill that generated the scenario (ScenarioRing::around_launch, on the
+// fill's stream), so that the two-wave kernel above starts the episode without redoing that step.  The one-wave headline layout
+// — one wave per workgroup, two jobs (ring slots of StateView::first_list) per wave, 12 agent lanes, 60 pair lanes — and the
+// one-wave kernel's own phase bodies, once each; no swept distance, no integration, no bookkeeping.  A fixed grid strides over the
+// list (a plain bounded loop, as ring_redo_kernel's).  The robot's view follows load_robot_view's rule on the data the next
+// launch's prologue will find: captured radii and top speed where rsim_valid says so, else what that prologue will capture from
+// the env's current state.  The host enqueues the kernel only where that data cannot change under it.
+constexpr int kFirstStepWgs = 2048;
+__global__ __launch_bounds__(kWave) void ring_first_step_kernel(Params P_in, StateView S) {
+    constexpr int MAXL = 5;
+    Params P = P_in;
+    P.A = 6, P.NC = 5, P.E = 2, P.nA = 12, P.pairs = 60, P.threads = 64;
+    const Smem s = carve<MAXL>(P);
+    const int lane = threadIdx.x;
+    const int el = lane / P.A;
+    const bool agent = lane < P.nA;
+    build_pairs(P, s, true);
+    if (lane == 0) s.kin[P.nA] = make_float4(std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity(), 0.0f, 0.0f);
+    CN_FUSED_SYNC();
+    const PairRow pr = pair_row_of(P, s, lane);
+    const float range_sq = P.orca.neighbor_dist * P.orca.neighbor_dist;
+    const int slots = P.B * P.ring_mod;
+    const int listed = __builtin_amdgcn_readfirstlane(S.redo_count[1]);
+    const int n = listed < slots ? listed : slots;
+    for (int k = 2 * (int)blockIdx.x; k < n; k += 2 * kFirstStepWgs) {
+        // the wave's second env is job k + 1, or job k once more where the list ends (computed, not stored)
+        const bool both = k + 1 < n;
+        const int listed_idx = S.first_list[k + ((el == 1 && both) ? 1 : 0)];
+        const int ring_idx = listed_idx < 0 ? 0 : (listed_idx < slots ? listed_idx : slots - 1);
+        Lane L;
+        L.lane = lane, L.a = lane - el * P.A, L.ebase = el * P.A, L.env = ring_idx / P.ring_mod, L.valid = agent;
+        L.gi = (size_t)L.env * P.A + (agent ? L.a : 0);
+        const size_t ri = (size_t)ring_idx * P.A + (agent ? L.a : 0);
+        // every load of the job in one batch, unconditional on in-bounds indices
+        const double2 p = S.ring_pos[ri], g = S.ring_goal[ri], q = S.ring_rv[ri], cur = S.rv[L.gi];
+        const bool have = S.rsim_valid[L.env] != 0;
+        const float rr_kept = S.rsim_radius[L.gi], ms_kept = S.rsim_max_speed[L.env];
+        AgentRegs r;  // (load_from_ring's)
+        r.px = p.x, r.py = p.y, r.vx = 0.0, r.vy = 0.0, r.gx = g.x, r.gy = g.y, r.rad = q.x, r.vpref = q.y;
+        const float robot_max_speed = have ? ms_kept : (float)cur.y;
+        if (agent) s.rview[lane] = have ? rr_kept : (float)(cur.x + 0.01 + P.robot_safety);
+        stage_agent(P, s, L, r, P.human_safety, s.kin);
+        CN_FUSED_SYNC();
+        if (lane < P.pairs) {
+            float4 sol4, start4;
+            fused_pair_phase(P, s, pr, range_sq, pair_rsum(s, pr), [&] {
+                preferred_velocity(r, (L.a == 0) ? robot_max_speed : (float)r.vpref, agent, sol4, start4);
+            });
+            if (agent) {
+                s.sol[lane] = sol4;
+                s.res[lane] = start4;
+            }
+        }
+        CN_FUSED_SYNC();
+        fused_candidates<MAXL>(P, s, lane);
+        CN_FUSED_SYNC();
+        float rx, ry;
+        fused_solve<MAXL>(P, s, lane, agent, rx, ry, nullptr);
+        if (agent && (el == 0 || both)) {
+            S.ring_vel0[ri] = make_float2(rx, ry);
+            if (L.a == 0) S.ring_vel0_ok[ring_idx] = 1;
+        }
+        CN_FUSED_SYNC();
+    }
 }
 
 }  // namespace cn

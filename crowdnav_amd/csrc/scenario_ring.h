@@ -139,10 +139,14 @@ constexpr int kRedoLanes = 4096;
 // for all its lanes, whether that env's workgroup of the running launch had stored the word yet or not.
 __global__ __launch_bounds__(kWave) void ring_fill_begin_kernel(int B, const int* ep_word, int* ep_snap, int* redo_count) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0) *redo_count = 0;
+    if (b == 0) redo_count[0] = 0, redo_count[1] = 0;
     if (b < B) ep_snap[b] = __hip_atomic_load(&ep_word[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R, const int* ep_snap) {
+// first_step != 0 (engines whose cn_rollout runs the two-wave kernel): the slot's solved first step (StateView::ring_vel0) dies with
+// the scenario it belonged to, and the slot joins the job list of ring_first_step_kernel (rollout_fused.h), which follows on the
+// same stream — one atomic per wave, as ring_fill_scan_kernel appends.
+__global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg C, StateView S, RolloutView R, const int* ep_snap,
+                                                         int first_step) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int D = P.ring_mod;  // slots per env; the fill tops up to next + D and publishes that level
     if (idx >= P.B * D) return;
@@ -164,6 +168,15 @@ __global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg 
     if (past_episode_limit(*io, c)) return;
     const uint32_t seed = episode_seed(*io, c);
     const int ring_idx = b * D + ordinal % D;
+    if (first_step) {  // (the lanes that are still here: every one of them generates)
+        S.ring_vel0_ok[ring_idx] = 0;
+        const unsigned long long m = __ballot(1);
+        const int lane = threadIdx.x & (kWave - 1), leader = __ffsll((long long)m) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(&S.redo_count[1], __popcll(m));
+        base = __shfl(base, leader);
+        S.first_list[base + __popcll(m & ((1ull << lane) - 1ull))] = ring_idx;
+    }
     Mt19937Head head;
     generate_scenario(C, head, seed, (size_t)ring_idx * P.A, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
     if (head.dead()) S.redo_list[atomicAdd(S.redo_count, 1)] = make_int2(ring_idx, (int)seed);
@@ -171,11 +184,12 @@ __global__ __launch_bounds__(kWave) void ring_fill_kernel(Params P, ScenarioCfg 
 
 // The scenarios ring_fill_kernel queued: a fixed grid of kRedoLanes lanes strides over the list, each lane with
 // its own column of the word-major generator pool.
-__global__ __launch_bounds__(kWave) void ring_redo_kernel(Params P, ScenarioCfg C, StateView S) {
+__global__ __launch_bounds__(kWave) void ring_redo_kernel(Params P, ScenarioCfg C, StateView S, int first_step) {
     const int lane = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = *S.redo_count;
     for (int k = lane; k < n; k += kRedoLanes) {
         const int2 job = S.redo_list[k];
+        if (first_step) S.ring_vel0_ok[job.x] = 0;  // (already on ring_fill_kernel's job list)
         Mt19937 rng{S.ring_mt_key + lane, kRedoLanes, 0};
         generate_scenario(C, rng, (uint32_t)job.y, (size_t)job.x * P.A, S.ring_pos, nullptr, S.ring_goal, S.ring_rv);
     }

@@ -5,7 +5,7 @@
 // are still out.  WHEN a fill runs, and when the two level buffers change hands, is fill_plan.h's rule; this file executes it.
 #pragma once
 #include "engine_host.h"
-#include "scenario_ring.h"
+#include "rollout_fused.h"  // (ring_first_step_kernel runs the fused kernels' phase bodies; scenario_ring.h comes with it)
 
 // The launch reads StateView::ring_filled_in; a fill reads it too and writes ring_filled_out.  Once per fill the two change
 // hands: at once for a fill in front of the launch, when FillPlan says so (Decision::take_levels, settle()) for one beside it.
@@ -53,7 +53,11 @@ inline int ScenarioRing::create(cn_engine* e) {
         (rc = dev_alloc(e, &S.ring_mt_key, gen_wave ? (size_t)64 : (size_t)624 * cn::kRedoLanes)) ||
         (rc = dev_alloc(e, &S.redo_list, gen_wave ? (size_t)1 : (size_t)P.B * P.ring_mod)) ||
         (rc = dev_alloc(e, &ep_snap, mode == Fill::Beside ? (size_t)P.B : (size_t)1)) ||
-        (rc = dev_alloc(e, &S.redo_count, (size_t)1)) ||
+        (rc = dev_alloc(e, &S.redo_count, (size_t)2)) ||
+        (rc = dev_alloc(e, &S.ring_vel0, first_step ? n * P.ring_mod : (size_t)1)) ||
+        (rc = dev_alloc(e, &S.ring_vel0_ok, first_step ? (size_t)P.B * P.ring_mod : (size_t)1)) ||
+        (rc = dev_alloc(e, &S.first_list, first_step ? (size_t)P.B * P.ring_mod : (size_t)1)) ||
+        (rc = dev_alloc(e, &S.fresh_counts, (size_t)2)) ||
         (rc = dev_alloc(e, &S.ring_filled_in, (size_t)P.B)) || (rc = dev_alloc(e, &S.ring_filled_out, (size_t)P.B)) ||
         (rc = dev_alloc(e, &S.ring_ready, work_list ? slots : (size_t)1)) ||
         (rc = dev_alloc(e, &S.ring_claim, work_list ? slots : (size_t)1)) ||
@@ -118,6 +122,16 @@ inline int ScenarioRing::drain(cn_engine* e) {
 // still be running.  Nothing to wait for unless one is out.  (The rollout entry points do not: around_launch takes the levels.)
 inline int ScenarioRing::settle(cn_engine* e) { return plan.pending ? drain(e) : CN_OK; }
 
+// Who must forget: every entry point that changes what a solved first step was computed from other than the slot's own scenario —
+// the robot's captured simulator (cn_set_robot_sim, cn_drop_robot_sim, cn_drop_sims) or the env state it would be captured from
+// (cn_set_state, cn_reset), and cn_rollout_begin — behind its settle, on the engine's stream.  The slots stay unsolved until a
+// fill generates into them again: an episode that starts from one redoes its first step as before.
+inline int ScenarioRing::forget_first_steps(cn_engine* e) {
+    if (!first_step) return CN_OK;
+    CN_HIP(hipMemsetAsync(e->S.ring_vel0_ok, 0, (size_t)e->P.B * e->P.ring_mod, e->stream));
+    return CN_OK;
+}
+
 // cn_rollout_begin, behind its drain and its upload of the io block: an empty scenario cache, every env's first scenario,
 // nothing known about the ring.
 inline int ScenarioRing::begin(cn_engine* e, uint32_t seed_mod) {
@@ -170,6 +184,14 @@ int ScenarioRing::around_launch(cn_engine* e, int n_steps, Launch&& launch) {
     }
     const int fill_lanes = e->P.B * e->P.ring_mod;
     const dim3 fill_grid((fill_lanes + cn::kWave - 1) / cn::kWave), redo_grid(cn::kRedoLanes / cn::kWave);
+    const int fs_flag = first_step ? 1 : 0;
+    // behind ring_redo_kernel, in front of whatever waits for the fill.  In front of the launch the robot's simulator is what the
+    // launch's prologue will find or capture (the kernel follows load_robot_view's rule on the same data); beside a launch only
+    // once it is known to be captured — else that launch may be the one that captures, and the slots stay unsolved
+    const auto solve_first_steps = [&](hipStream_t on) {
+        hipLaunchKernelGGL(cn::ring_first_step_kernel, dim3(cn::kFirstStepWgs), dim3(cn::kWave), e->smem, on, e->P, e->S);
+        first_step_kernels += 1;
+    };
     if (plan_says.take_levels) {  // the fill that ran beside the previous launch: this launch waits for it and takes its levels
         CN_HIP(hipStreamWaitEvent(e->stream, fill_done, 0));
         swap_levels(e->S);
@@ -178,9 +200,10 @@ int ScenarioRing::around_launch(cn_engine* e, int n_steps, Launch&& launch) {
         if (gen_wave) {
             hipLaunchKernelGGL(cn::ring_fill_wave_kernel, dim3(fill_lanes), dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R);
         } else {
-            CN_HIP(hipMemsetAsync(e->S.redo_count, 0, sizeof(int), e->stream));
-            hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R, nullptr);
-            hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S);
+            CN_HIP(hipMemsetAsync(e->S.redo_count, 0, 2 * sizeof(int), e->stream));
+            hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, R, nullptr, fs_flag);
+            hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, e->stream, e->P, e->C, e->S, fs_flag);
+            if (first_step) solve_first_steps(e->stream);
         }
         swap_levels(e->S);
         e->launch_counts[CN_COUNT_RING_FILLS] += 1;
@@ -188,8 +211,10 @@ int ScenarioRing::around_launch(cn_engine* e, int n_steps, Launch&& launch) {
     // a fill beside the launch is ordered behind everything in front of it (the previous launch's episode words, the levels a
     // fill in front just wrote) and enqueued behind it
     if (plan_says.lagged_fill) CN_HIP(hipEventRecord(rollout_done, e->stream));
+    const bool sim_known_before = robot_sim_known;
     launch(R, (const int*)e->S.ring_filled_in);
     CN_HIP(hipGetLastError());
+    if (e->P.robot_orca) robot_sim_known = true;  // (CN_STORE_EPISODE: every launch of an ORCA robot leaves every env's simulator captured)
     if (plan_says.lagged_fill) {
         // it reads ring_filled_in, as the launch does, and writes ring_filled_out and ring slots of ordinals >= the level the
         // launch was given
@@ -197,8 +222,9 @@ int ScenarioRing::around_launch(cn_engine* e, int n_steps, Launch&& launch) {
         CN_HIP(hipStreamWaitEvent(fs, rollout_done, 0));
         hipLaunchKernelGGL(cn::ring_fill_begin_kernel, dim3(grid_lanes(e)), dim3(cn::kWave), 0, fs, e->P.B, e->S.ep_word, ep_snap,
                            e->S.redo_count);
-        hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, (const int*)ep_snap);
-        hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, fs, e->P, e->C, e->S);
+        hipLaunchKernelGGL(cn::ring_fill_kernel, fill_grid, dim3(cn::kWave), 0, fs, e->P, e->C, e->S, R, (const int*)ep_snap, fs_flag);
+        hipLaunchKernelGGL(cn::ring_redo_kernel, redo_grid, dim3(cn::kWave), 0, fs, e->P, e->C, e->S, fs_flag);
+        if (first_step && sim_known_before) solve_first_steps(fs);
         CN_HIP(hipEventRecord(fill_done, fs));
         e->launch_counts[CN_COUNT_RING_FILLS] += 1;
         lagged_fills += 1;

@@ -72,8 +72,8 @@ struct StateView {
     uint8_t* rsim_valid;    // [B]
     uint32_t* mt_key;       // [624][B]   generator state of the env's own stream
     uint32_t* ring_mt_key;  // [624][kRedoLanes] HBM generator scratch of ring_redo_kernel (scenarios the head generator gave up on)
-    int2* redo_list;        // [B*C] (ring index, seed) of those scenarios; redo_count [1] = how many (zeroed before a fill)
-    int* redo_count;
+    int2* redo_list;        // [B*C] (ring index, seed) of those scenarios; redo_count [0] = how many (zeroed before a fill)
+    int* redo_count;        // [2] ... and [1] = entries of first_list (below), zeroed with it
     int* mt_pos;            // [B]
     // scenario ring: the next ring_depth episodes of every env, generated ahead of the rollout
     double2* ring_pos;      // [B][C][A]
@@ -101,6 +101,12 @@ struct StateView {
     double* group_partial;  // [kEpilogueGroups][CN_SUMMARY_FIELDS + 1]
     unsigned* tickets;      // [(kEpilogueGroups + 1) * kTicketStride] arrivals per group, then of the group leaders, one
                             // counter per 256-byte line; zero between launches
+    // First step of every ring scenario, solved when its slot is filled (rollout_fused.h: ring_first_step_kernel) for the engines
+    // whose cn_rollout runs the two-wave kernel; 1-element placeholders elsewhere.  Last, so that every field above keeps its offset.
+    float2* ring_vel0;          // [B][C][A] the velocity every agent's ORCA solve yields for the scenario's first step
+    uint8_t* ring_vel0_ok;      // [B*C] 1: ring_vel0 of the slot belongs to the scenario it holds and to the robot's simulator as it is
+    int* first_list;            // [B*C] ring indices a fill generated into (ring_fill_kernel); how many: redo_count[1]
+    unsigned int* fresh_counts; // [2] two-wave kernel: episode starts that adopted ring_vel0; iterations redone (cn_fresh_starts)
 };
 
 constexpr int kEpilogueGroups = 32;  // workgroup b arrives at counter b % 32: 64 arrivals per counter at 2048 workgroups

@@ -898,6 +898,24 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_lagged_fills(self._h, C.byref(lagged)))
         return dict(zip(_lib.LAUNCH_COUNTERS, (int(v) for v in out)), lagged_fills=int(lagged.value))
 
+    def fresh_starts(self):
+        """Two-wave rollout kernel, since the engine was created (cn_fresh_starts): 'adopted' episode starts that took the first
+        step solved when their ring slot was filled, 'redone' iterations a workgroup computed again because one could not, and
+        'kernels', the launches of the solving kernel.  Waits for the engine's stream."""
+        out = (C.c_uint64 * 3)()
+        check(self._lib.cn_fresh_starts(self._h, out))
+        return dict(adopted=int(out[0]), redone=int(out[1]), kernels=int(out[2]))
+
+    def ring_slot(self, env, slot):
+        """Ring slot `slot` of env `env` as the last fill left it (cn_ring_slot): (state8 float64 [A, 8] in get_state's layout,
+        vel0 float32 [A, 2], ok) as numpy arrays and a bool — vel0 is the slot's solved first step where ok."""
+        state8 = np.zeros((self.A, 8), np.float64)
+        vel0 = np.zeros((self.A, 2), np.float32)
+        ok = C.c_int(0)
+        check(self._lib.cn_ring_slot(self._h, int(env), int(slot), state8.ctypes.data_as(C.c_void_p),
+                                     vel0.ctypes.data_as(C.c_void_p), C.byref(ok)))
+        return state8, vel0, bool(ok.value)
+
     def rollout_route(self, n_steps):
         """Which transition kernel rollout(n_steps) would launch now (cn_rollout_route): one of _lib.ROLLOUT_ROUTES — 'generic',
         'fused' (one wave per workgroup), 'fused_split' (an ORCA wave and an env wave per workgroup) or 'shard'.  Host-side,

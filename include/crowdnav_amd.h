@@ -256,6 +256,18 @@ int cn_launch_counts(cn_engine* e, uint64_t* counts_host);
  * CROWDNAV_AMD_LAGGED_FILL=0 (read by cn_create) keeps D slots and fills in front of the launch only. */
 int cn_lagged_fills(cn_engine* e, uint64_t* count_host);
 
+/* (no ABI bump: new symbols only) Engines whose cn_rollout runs the two-wave kernel (CN_ROUTE_FUSED_SPLIT) solve the first ORCA
+ * step of every ring scenario when its slot is filled; an episode that starts inside a launch then adopts those velocities and
+ * the workgroup does not compute that step a second time.  Results are bit-identical either way.
+ * cn_fresh_starts — counts_host: HOST uint64 [3], since cn_create: [0] episode starts that adopted solved velocities, [1]
+ * iterations a workgroup computed again because an episode start could not (slot unsolved, env paused or retired), [2] launches
+ * of the solving kernel.  Waits for the engine's stream.
+ * cn_ring_slot — ring slot `slot` (0 .. slots per env - 1; ordinal o lives in slot o % slots) of env `env` as the last fill left
+ * it: state8_host HOST double [A][8] (get_state's layout, velocities 0), vel0_host HOST float [A][2] and *ok_host (1: vel0_host
+ * is the slot's solved first step; always 0 on other engines).  Waits for the fills that are out and the engine's stream. */
+int cn_fresh_starts(cn_engine* e, uint64_t* counts_host);
+int cn_ring_slot(cn_engine* e, int env, int slot, double* state8_host, float* vel0_host, int* ok_host);
+
 /* (no ABI bump: a new symbol only) which transition kernel cn_rollout(e, io, n_steps) would launch NOW — route_host: HOST int,
  * one of CN_ROUTE_*.  Host-only: launches nothing, counts nothing.  The fused two-wave kernel (rollout_fused.h) takes the
  * headline geometry — 5 humans + ORCA robot, 2 envs per workgroup — when every workgroup of the launch is resident at once

@@ -34,6 +34,7 @@ for n in (N, N, 20):
     it, redo, fb, head, hit, miss, alarm = [int(out[k]) for k in range(7)]
     wg = (B + 1) // 2
     print('%5d steps: %d iterations of %d workgroups, redone %.4f per workgroup-step' % (n, it, wg, redo / (wg * n)))
+    print('      since the engine was created (fresh_starts): %s' % eng.fresh_starts())
     print('      per iteration: fallback %.4f   third barrier %.4f   hit %.4f   miss %.4f   false alarm %.4f'
           % tuple(x / it for x in (fb, head, hit, miss, alarm)))
     print('      ticks in barriers per iteration:  ORCA wave 1: %.0f  2: %.0f  3: %.0f (per third barrier: %.0f)   '
