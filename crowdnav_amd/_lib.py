@@ -210,6 +210,8 @@ SYMBOLS = {
     # how the humans of a lookahead's branches move: ORCA (default) or constant velocity (no version bump)
     'cn_lookahead_set_human_model': (C.c_int, [_P, C.c_int]),
     'cn_lookahead_get_human_model': (C.c_int, [_P, C.POINTER(C.c_int)]),
+    'cn_lookahead_set_goal_weight': (C.c_int, [_P, C.c_double]),
+    'cn_lookahead_get_goal_weight': (C.c_int, [_P, C.POINTER(C.c_double)]),
     # V of joint states the caller holds in the env layout, and the lookahead that bootstraps with it (no version bump)
     'cn_sarl_state_values': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
     'cn_lookahead_values': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(CnLookaheadOut), C.c_int, _P, _P]),

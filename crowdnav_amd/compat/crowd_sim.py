@@ -242,6 +242,18 @@ class CrowdSim(_Base):
         ret, info, steps = (out[k].cpu().numpy()[0] for k in ('ret', 'info', 'steps'))
         return [(float(r), info_from_code(i), int(s)) for r, i, s in zip(ret, info, steps)]
 
+    def set_lookahead_goal_weight(self, w):
+        """The weight of the goal-progress term in what lookahead(), lookahead_paths() and lookahead_modes() return
+        (BatchedCrowdSim.set_lookahead_goal_weight): every return becomes return + w * (the robot's distance to its goal now
+        less the distance after the sequence's last transition), and the scores follow.  Set on the engine of the current
+        episode, where it stays set, as human_model does; 0.0 is the lookahead without the term."""
+        self._eng.set_lookahead_goal_weight(w)
+
+    @property
+    def lookahead_goal_weight(self):
+        """The weight the current episode's engine holds (0.0 unless set)."""
+        return self._eng.lookahead_goal_weight
+
     def lookahead_paths(self, sequences, human_velocities, policy=None):
         """lookahead() against predicted human motion (BatchedCrowdSim.lookahead_paths): human_velocities[t][h] is the (vx, vy)
         human h takes during step t of the horizon — n rows of one pair per human, anything np.asarray reads as [n, humans, 2]

@@ -88,6 +88,16 @@ static int upload_look(cn_engine* e, const cn_lookahead_out* out) {
     return CN_OK;
 }
 
+// ... and the engine's goal weight behind it, where rollout_lookahead_goal_kernel reads it: uploaded by the launch that needs it
+// when it differs from the last one, likewise (the setter itself touches nothing on the device)
+static int upload_look_goal(cn_engine* e) {
+    if (e->look_goal_dev != e->look_goal_weight) {
+        e->look_goal_dev = e->look_goal_weight;
+        CN_HIP(hipMemcpyAsync(e->look_dev + 1, &e->look_goal_dev, sizeof(double), hipMemcpyHostToDevice, e->stream));
+    }
+    return CN_OK;
+}
+
 // what lookahead_cv_kernel and lookahead_paths_kernel read of the engine
 static cn::CvParams cv_params(const cn_engine* e, int n_steps, int n_candidates) {
     const cn::Params& P = e->P;
@@ -260,7 +270,7 @@ static int alloc_state(cn_engine* e) {
         (rc = dev_alloc(e, &S.group_partial, (size_t)cn::kEpilogueGroups * (CN_SUMMARY_FIELDS + 1))) ||
         (rc = dev_alloc(e, &S.tickets, (size_t)(cn::kEpilogueGroups + 1) * cn::kTicketStride)) ||
         (rc = dev_alloc(e, &e->io_dev, (size_t)1)) || (rc = dev_alloc(e, &e->C.error, (size_t)1)) ||
-        (rc = dev_alloc(e, &e->S_dev, (size_t)1)) || (rc = dev_alloc(e, &e->look_dev, (size_t)1)))
+        (rc = dev_alloc(e, &e->S_dev, (size_t)1)) || (rc = dev_alloc(e, &e->look_dev, (size_t)2)))
         return rc;
     e->S.error = e->C.error;
     if (hipMemcpy(e->S_dev, &e->S, sizeof(cn::StateView), hipMemcpyHostToDevice) != hipSuccess)
@@ -772,20 +782,36 @@ int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const doub
     if (e->look_human_model == CN_HUMANS_CONSTANT_VELOCITY) {  // lookahead_cv_kernel.h: lane = branch, no ORCA
         const cn::CvParams C = cv_params(e, n_steps, n_candidates);
         // B * chunks <= B * K workgroups: within an int (cn_lookahead_check)
-        pick_bool(e->P.robot_unicycle, [&](auto uni) {
-            hipLaunchKernelGGL((cn::lookahead_cv_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
-                               dim3(cn::kWave), 0, e->stream, C, actions, (const cn_lookahead_out*)e->look_dev);
+        pick_uni_goal(e, [&](auto uni, auto goal) {
+            const dim3 grid((unsigned)C.B * (unsigned)C.chunks);
+            if constexpr (decltype(goal)::value)
+                hipLaunchKernelGGL((cn::lookahead_cv_goal_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), 0, e->stream, C, actions,
+                                   (const cn_lookahead_out*)e->look_dev, e->look_goal_weight);
+            else
+                hipLaunchKernelGGL((cn::lookahead_cv_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), 0, e->stream, C, actions,
+                                   (const cn_lookahead_out*)e->look_dev);
         });
         CN_HIP(hipGetLastError());
         return CN_OK;
     }
+    if (look_goal(e) && (rc = upload_look_goal(e))) return rc;
     cn::Params Pv = e->P;
     Pv.B = (int)virtual_envs;
     const cn::RolloutView R{nullptr, e->discount, e->discount_len};
     pick_maxl_uni_kd(e, [&](auto maxl, auto uni, auto kd) {
-        hipLaunchKernelGGL((cn::rollout_lookahead_kernel<decltype(maxl)::value, decltype(uni)::value, decltype(kd)::value>),
-                           dim3((Pv.B + Pv.E - 1) / Pv.E), dim3(Pv.threads), e->smem, e->stream, Pv, (const cn::StateView*)e->S_dev, R,
-                           n_steps, actions, (const cn_lookahead_out*)e->look_dev, n_candidates);
+        constexpr int kMaxl = decltype(maxl)::value;
+        constexpr bool kUni = decltype(uni)::value, kKd = decltype(kd)::value;
+        const dim3 grid((Pv.B + Pv.E - 1) / Pv.E);
+        pick_bool(look_goal(e), [&](auto goal) {
+            if constexpr (decltype(goal)::value)
+                hipLaunchKernelGGL((cn::rollout_lookahead_goal_kernel<kMaxl, kUni, kKd>), grid, dim3(Pv.threads), e->smem, e->stream, Pv,
+                                   (const cn::StateView*)e->S_dev, R, n_steps, actions, (const cn_lookahead_out*)e->look_dev,
+                                   n_candidates);
+            else
+                hipLaunchKernelGGL((cn::rollout_lookahead_kernel<kMaxl, kUni, kKd>), grid, dim3(Pv.threads), e->smem, e->stream, Pv,
+                                   (const cn::StateView*)e->S_dev, R, n_steps, actions, (const cn_lookahead_out*)e->look_dev,
+                                   n_candidates);
+        });
     });
     CN_HIP(hipGetLastError());
     return CN_OK;
@@ -801,9 +827,14 @@ int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candidates, const double
     if (rc || n_steps == 0) return rc;
     if ((rc = bind(e)) || (rc = upload_look(e, out))) return rc;
     const cn::CvParams C = cv_params(e, n_steps, n_candidates);
-    pick_bool(e->P.robot_unicycle, [&](auto uni) {
-        hipLaunchKernelGGL((cn::lookahead_paths_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
-                           dim3(cn::kWave), 0, e->stream, C, actions, human_vel, (const cn_lookahead_out*)e->look_dev);
+    pick_uni_goal(e, [&](auto uni, auto goal) {
+        const dim3 grid((unsigned)C.B * (unsigned)C.chunks);
+        if constexpr (decltype(goal)::value)
+            hipLaunchKernelGGL((cn::lookahead_paths_goal_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), 0, e->stream, C, actions,
+                               human_vel, (const cn_lookahead_out*)e->look_dev, e->look_goal_weight);
+        else
+            hipLaunchKernelGGL((cn::lookahead_paths_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), 0, e->stream, C, actions,
+                               human_vel, (const cn_lookahead_out*)e->look_dev);
     });
     CN_HIP(hipGetLastError());
     return CN_OK;
@@ -840,9 +871,13 @@ int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double
     const cn::CvParams C = cv_params(e, n_steps, n_candidates);
     const cn::ModesParams Q{modes->n_modes, modes->reduce, modes->risk_penalty, modes->human_vel, modes->weight, *out};
     const size_t lds = cn::modes_lds_bytes(Q.M, C.A - 1);  // at most 4 * 504 * 16 + 63 * 8 = 32760 bytes
-    pick_bool(e->P.robot_unicycle, [&](auto uni) {
-        hipLaunchKernelGGL((cn::lookahead_modes_kernel<decltype(uni)::value>), dim3((unsigned)C.B * (unsigned)C.chunks),
-                           dim3(cn::kWave), lds, e->stream, C, actions, Q);
+    pick_uni_goal(e, [&](auto uni, auto goal) {
+        const dim3 grid((unsigned)C.B * (unsigned)C.chunks);
+        if constexpr (decltype(goal)::value)
+            hipLaunchKernelGGL((cn::lookahead_modes_goal_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), lds, e->stream, C, actions,
+                               Q, e->look_goal_weight);
+        else
+            hipLaunchKernelGGL((cn::lookahead_modes_kernel<decltype(uni)::value>), grid, dim3(cn::kWave), lds, e->stream, C, actions, Q);
     });
     CN_HIP(hipGetLastError());
     return CN_OK;
@@ -862,6 +897,24 @@ int cn_lookahead_get_human_model(const cn_engine* e, int* model_host) {
     if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_get_human_model: engine is NULL");
     if (!model_host) return fail(CN_ERR_INVALID, "cn_lookahead_get_human_model: model_host is NULL");
     *model_host = e->look_human_model;
+    return CN_OK;
+}
+
+// the goal-progress term of every lookahead's return: a host-side setting of the engine, nothing of the device is touched.
+// What depends on the argument alone is refused first.  -0.0 is not negative (IEEE: -0.0 < 0.0 is false): it is accepted and
+// means 0.0, the plain kernels.
+int cn_lookahead_set_goal_weight(cn_engine* e, double weight) {
+    if (!std::isfinite(weight) || weight < 0.0)
+        return fail(CN_ERR_INVALID, "cn_lookahead_set_goal_weight: weight must be >= 0 and finite (got %g)", weight);
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_set_goal_weight: engine is NULL");
+    e->look_goal_weight = weight;
+    return CN_OK;
+}
+
+int cn_lookahead_get_goal_weight(const cn_engine* e, double* weight_host) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_lookahead_get_goal_weight: engine is NULL");
+    if (!weight_host) return fail(CN_ERR_INVALID, "cn_lookahead_get_goal_weight: weight_host is NULL");
+    *weight_host = e->look_goal_weight;
     return CN_OK;
 }
 

@@ -98,9 +98,12 @@ struct cn_engine {
     cn_rollout_io* io_dev = nullptr;   // device copy the rollout kernels read through
     cn::StateView* S_dev = nullptr;    // device copy of S (the fused rollout kernel re-reads state pointers instead of holding them)
     cn_lookahead_out look_host{};          // last cn_lookahead_out uploaded to look_dev (look_valid: there is one)
-    cn_lookahead_out* look_dev = nullptr;  // device copy rollout_lookahead_kernel stores through
+    cn_lookahead_out* look_dev = nullptr;  // device copy rollout_lookahead_kernel stores through; room for two: the double at
+                                           // look_dev + 1 is the weight rollout_lookahead_goal_kernel reads (look_goal_dev)
     bool look_valid = false;
     int look_human_model = CN_HUMANS_ORCA;  // cn_lookahead_set_human_model: read by cn_lookahead_actions and by nothing else
+    double look_goal_weight = 0.0;  // cn_lookahead_set_goal_weight: != 0 launches the goal forms of the four lookahead kernels
+    double look_goal_dev = 0.0;     // the weight last uploaded behind look_dev (the slab is zeroed: 0.0 until one is)
     ScenarioRing ring;
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one
@@ -205,6 +208,15 @@ inline void pick_maxl_uni_kd(const cn_engine* e, F&& f) {
     pick_maxl(e, [&](auto maxl) {
         pick_bool(e->P.robot_unicycle, [&](auto uni) { pick_bool(e->P.kd, [&](auto kd) { f(maxl, uni, kd); }); });
     });
+}
+
+// Goal form or plain form of a lookahead kernel (cn_lookahead_set_goal_weight): the one place that decides it, for the four
+// lookahead launch sites.  A weight of exactly 0.0 (-0.0 included) launches the kernels that know nothing of the term.
+inline bool look_goal(const cn_engine* e) { return e->look_goal_weight != 0.0; }
+// ... beside the robot kinematics: f(uni, goal)
+template <class F>
+inline void pick_uni_goal(const cn_engine* e, F&& f) {
+    pick_bool(e->P.robot_unicycle, [&](auto uni) { pick_bool(look_goal(e), [&](auto goal) { f(uni, goal); }); });
 }
 
 [[maybe_unused]] int env_int(const char* name, int fallback) {

@@ -2,7 +2,7 @@
 // around the transition, whose arithmetic is transition.h's.  Included text, not a __device__ function, for rollout_body.inc's
 // reason: as a __forceinline__ function taking the parameter block by reference or by value hipcc gave both instantiations of
 // lookahead_cv_kernel another instruction stream (profiles/lookahead_paths_kernels.txt).  In scope where it is included: UNI,
-// PATHS (constexpr bool), P (CvParams), action_table, human_vel (nullptr without PATHS), Od.
+// PATHS, GOAL (constexpr bool), P (CvParams), action_table, human_vel (nullptr without PATHS), goal_weight (0.0 without GOAL), Od.
 // PATHS = false: the velocity a human chooses is the one it has.  PATHS = true: the velocity human h chooses at step t is
 // human_vel[b][t][h] (include/crowdnav_amd.h, "Lookahead under predicted human motion") — step_core's transition with the
 // humans' policy replaced by the table: the swept test of step t reads the velocity the human HAS when the step starts (its
@@ -19,6 +19,11 @@
 // after its last step and the velocity of that step; those buffers are written again only in iteration t + 2, behind the
 // barrier of iteration t + 1, which the ending lane reaches after its stores.  One barrier per step; the argument does not lean
 // on the workgroup being a single wave.
+//
+// GOAL = true (include/crowdnav_amd.h, "Lookahead goal-progress term"): the lane keeps d0, the robot's distance to its goal as
+// the engine holds it, from where the robot row is loaded, and stores ret + goal_weight * (d0 - d1) with d1 the distance
+// after the branch's last transition — the position final_state8 reports.  One subtraction, one multiply, one add, after the
+// last reward.  GOAL = false compiles to the instructions the kernels had (profiles/lookahead_goal_kernels.txt).
     __shared__ double2 h_pos[2][kCvHumans];  // position before the step in [t & 1], after it in [(t + 1) & 1]
     __shared__ double2 h_vel[PATHS ? 2 : 1][kCvHumans], h_goal[kCvHumans], h_rv[kCvHumans];
     const int lane = threadIdx.x;
@@ -41,11 +46,13 @@
     bool running = k < P.K;
     const size_t v_env = (size_t)b * (size_t)P.K + (size_t)(running ? k : 0);  // (a tail lane forms no address of its own)
     double px = 0.0, py = 0.0, vx = 0.0, vy = 0.0, gx = 0.0, gy = 0.0, rad = 0.0, vpref = 0.0, theta = 0.0, gtime = 0.0;
+    double d0 = 0.0;  // GOAL: the distance to the goal the branch starts from
     if (running) {
         const double2 p = P.pos[g0], v = P.vel[g0], g = P.goal[g0], rv = P.rv[g0];
         px = p.x, py = p.y, vx = v.x, vy = v.y, gx = g.x, gy = g.y, rad = rv.x, vpref = rv.y;
         gtime = P.gtime[b];
         theta = P.theta[b];  // (carried by UNI engines only, reported by all)
+        if (GOAL) d0 = norm2(px - gx, py - gy);
     }
     const bool mine = running;
     double cur_return = 0.0;
@@ -113,7 +120,7 @@
         if (!any_running) break;
     }
     if (mine) {
-        O.ret[v_env] = cur_return;
+        O.ret[v_env] = GOAL ? cur_return + goal_weight * (d0 - norm2(px - gx, py - gy)) : cur_return;
         O.info[v_env] = (uint8_t)info;
         O.steps[v_env] = cur_steps;
         O.time[v_env] = gtime;

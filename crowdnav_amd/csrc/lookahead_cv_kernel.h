@@ -34,11 +34,12 @@ struct CvParams {
 constexpr int kCvHumans = 63;  // check_config: num_humans <= 63
 
 // Both kernels' body is lookahead_cv_body.inc: the decomposition above around transition.h's functions, with the compile-time
-// flag PATHS choosing where a human's velocity comes from.
+// flag PATHS choosing where a human's velocity comes from and GOAL whether ret carries the goal-progress term.
 template <bool UNI>
 __global__ __launch_bounds__(kWave) void lookahead_cv_kernel(CvParams P, const double* action_table, const cn_lookahead_out* Od) {
-    constexpr bool PATHS = false;
+    constexpr bool PATHS = false, GOAL = false;
     const double* const human_vel = nullptr;
+    const double goal_weight = 0.0;
 #include "lookahead_cv_body.inc"
 }
 
@@ -47,7 +48,26 @@ __global__ __launch_bounds__(kWave) void lookahead_cv_kernel(CvParams P, const d
 template <bool UNI>
 __global__ __launch_bounds__(kWave) void lookahead_paths_kernel(CvParams P, const double* action_table, const double* human_vel,
                                                                 const cn_lookahead_out* Od) {
-    constexpr bool PATHS = true;
+    constexpr bool PATHS = true, GOAL = false;
+    const double goal_weight = 0.0;
+#include "lookahead_cv_body.inc"
+}
+
+// The goal forms of the two (cn_lookahead_set_goal_weight with a weight != 0): the same lane body under GOAL = true, the
+// engine's weight as one more kernel argument.  Kernels of their own, so that the two above keep their instructions and a
+// weight of 0.0 launches what it always launched.
+template <bool UNI>
+__global__ __launch_bounds__(kWave) void lookahead_cv_goal_kernel(CvParams P, const double* action_table, const cn_lookahead_out* Od,
+                                                                  double goal_weight) {
+    constexpr bool PATHS = false, GOAL = true;
+    const double* const human_vel = nullptr;
+#include "lookahead_cv_body.inc"
+}
+
+template <bool UNI>
+__global__ __launch_bounds__(kWave) void lookahead_paths_goal_kernel(CvParams P, const double* action_table, const double* human_vel,
+                                                                     const cn_lookahead_out* Od, double goal_weight) {
+    constexpr bool PATHS = true, GOAL = true;
 #include "lookahead_cv_body.inc"
 }
 

@@ -4,7 +4,8 @@
 // and under CN_ROLLOUT_TRACE the caller's cn_trace_out T.  Under CN_ROLLOUT_ACTIONS the call's action table
 // action_table (double [B][n_steps][2]) takes the place of ext_action.  Under CN_ROLLOUT_LOOKAHEAD (with CN_ROLLOUT_ACTIONS;
 // rollout_lookahead_kernel) the envs are the B K virtual ones of a cn_lookahead_actions call: P_in.B = B K, n_candidates = K,
-// Od the device copy of the caller's cn_lookahead_out; ring_filled_in and R.io are not in scope / not read.
+// Od the device copy of the caller's cn_lookahead_out; ring_filled_in and R.io are not in scope / not read; GOAL (constexpr bool)
+// says whether ret carries the goal-progress term, whose weight then lies behind *Od.
 // Why an include and not a __device__ __forceinline__ template with a TRACE parameter: with the body behind a call, its
 // arguments passed by value or by reference alike, hipcc gave every existing rollout_kernel instantiation a different
 // instruction stream (a hundred instructions more or fewer each, the 20-human shard's kernel included).  Included text leaves
@@ -299,7 +300,20 @@
     {
         const cn_lookahead_out O = *Od;
         if (robot) {
-            O.ret[L.env] = ep.cur_return;
+            double ret = ep.cur_return;
+            if (GOAL) {
+                // rollout_lookahead_goal_kernel (include/crowdnav_amd.h, "Lookahead goal-progress term").  Nothing of the term is
+                // held across the step loop: as a kernel argument the weight — or d0 in two registers — sent the kd
+                // instantiations to scratch where their plain forms have none (profiles/lookahead_goal_kernels.txt).  So the
+                // weight is read here from behind the device copy of the caller's block, whose pointer the tail needs anyway
+                // (upload_look_goal puts it there), and d0 from the robot's start row, read AGAIN from the source env the
+                // prologue read it from and nothing has written.  d1: r.px, r.py are the position final_state8 reports
+                // below.  One subtraction, one multiply, one add.
+                const double goal_weight = *reinterpret_cast<const double*>(Od + 1);
+                const double2 p0 = Sd->pos[(size_t)(L.env / n_candidates) * (size_t)P.A];
+                ret = ret + goal_weight * (norm2(p0.x - r.gx, p0.y - r.gy) - norm2(r.px - r.gx, r.py - r.gy));
+            }
+            O.ret[L.env] = ret;
             O.info[L.env] = (uint8_t)look_info;
             O.steps[L.env] = ep.cur_steps;
             O.time[L.env] = ep.gtime;

@@ -334,7 +334,22 @@ template <int MAXL, bool UNI, bool KD>
 __global__ __launch_bounds__(kMaxBlock, 1) void rollout_lookahead_kernel(Params P_in, const StateView* Sd, RolloutView R, int n_steps,
                                                                          const double* action_table, const cn_lookahead_out* Od,
                                                                          int n_candidates) {
-    constexpr bool HEADLINE = false;
+    constexpr bool HEADLINE = false, GOAL = false;
+#define CN_ROLLOUT_ACTIONS
+#define CN_ROLLOUT_LOOKAHEAD
+#include "rollout_body.inc"
+#undef CN_ROLLOUT_LOOKAHEAD
+#undef CN_ROLLOUT_ACTIONS
+}
+
+// Its goal form (cn_lookahead_set_goal_weight with a weight != 0): the same body under GOAL = true.  A kernel of its own, so
+// that the one above keeps its instructions; the same arguments, with the engine's weight as one double behind *Od (the tail
+// reads it there: rollout_body.inc says why it is not an argument here as it is for the lane-per-branch kernels).
+template <int MAXL, bool UNI, bool KD>
+__global__ __launch_bounds__(kMaxBlock, 1) void rollout_lookahead_goal_kernel(Params P_in, const StateView* Sd, RolloutView R,
+                                                                              int n_steps, const double* action_table,
+                                                                              const cn_lookahead_out* Od, int n_candidates) {
+    constexpr bool HEADLINE = false, GOAL = true;
 #define CN_ROLLOUT_ACTIONS
 #define CN_ROLLOUT_LOOKAHEAD
 #include "rollout_body.inc"

@@ -428,7 +428,7 @@ class BatchedCrowdSim(object):
         sort_humans: the humans of the network's rows by decreasing distance to the robot (LSTM-RL's replay-memory order), as
         in sarl_transform; False = env order.  The buffers sarl_export reads may be overwritten.
         The humans of the branches move by the engine's lookahead_human_model: through ORCA unless set_lookahead_human_model said
-        'constant_velocity'."""
+        'constant_velocity'.  With set_lookahead_goal_weight(w != 0), ret and score include w * (progress towards the goal)."""
         return self._lookahead('lookahead', actions, None, final_state, out, bootstrap, sort_humans)
 
     def lookahead_paths(self, actions, human_vel, final_state=False, out=None, bootstrap=False, sort_humans=False):
@@ -441,7 +441,8 @@ class BatchedCrowdSim(object):
         the 'constant_velocity' result, velocities recorded from ORCA humans that do not see the robot the 'orca' result, bit
         for bit; crowdnav_amd.predict builds tables (constant_velocity, to_goal, from_positions).  An argument, not a setting: lookahead_human_model is neither read nor
         changed.  Everything else — actions, the returned dict, final_state / out / bootstrap / sort_humans, n = 0, what is
-        borrowed and what is copied — as in lookahead().  Non-finite velocities are not checked."""
+        borrowed and what is copied — as in lookahead().  Non-finite velocities are not checked.  With
+        set_lookahead_goal_weight(w != 0), ret and score include w * (progress towards the goal)."""
         return self._lookahead('lookahead_paths', actions, human_vel, final_state, out, bootstrap, sort_humans)
 
     def _lookahead(self, who, actions, human_vel, final_state, out, bootstrap, sort_humans):
@@ -490,6 +491,22 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_lookahead_get_human_model(self._h, C.byref(model)))
         return _lib.HUMAN_MODELS[model.value]
 
+    def set_lookahead_goal_weight(self, w):
+        """The weight of the goal-progress term in every lookahead's return (cn_lookahead_set_goal_weight): with d0 the robot's
+        distance to its goal now and d1 the distance after a branch's last transition, ret becomes ret + w * (d0 - d1) — added
+        once, undiscounted, whatever way the branch ended — in lookahead(), lookahead_paths(), every mode of lookahead_modes()
+        before the reduction, their bootstrap scores, and so in whatever the plan_* calls rank.  info, steps, time, the final
+        state, step(), the rollout calls and the real steps inside the plan_*rollout loops do not change.  w >= 0 and finite;
+        0.0 (the default) is the lookahead without the term, bit for bit.  Stays set across reset()."""
+        check(self._lib.cn_lookahead_set_goal_weight(self._h, float(w)))
+
+    @property
+    def lookahead_goal_weight(self):
+        """The weight set_lookahead_goal_weight set; 0.0 unless set (cn_lookahead_get_goal_weight)."""
+        w = C.c_double()
+        check(self._lib.cn_lookahead_get_goal_weight(self._h, C.byref(w)))
+        return w.value
+
     # ---------------------------------------------------------------- device CEM planner (cn_plan_*)
     def plan_begin(self, K, n, elites, iterations, init_std, min_std=0.0, smoothing=0.0, seed=0, bootstrap=False,
                    sort_humans=False):
@@ -501,7 +518,8 @@ class BatchedCrowdSim(object):
             look: the dict lookahead() returns, rows of the last iteration (with bootstrap: final state, value, score too)
         mean starts at zero and std at init_std: call plan_reset() for the goal-directed prior.  Holonomic ROBOT_EXTERNAL
         engines; the settings are checked by the first call that uses the plan.  The planner's candidates are scored under the
-        engine's lookahead_human_model (set_lookahead_human_model), as it stands when each plan_* call is made."""
+        engine's lookahead_human_model (set_lookahead_human_model), as it stands when each plan_* call is made.  With
+        set_lookahead_goal_weight(w != 0), the ret and score the planner ranks include w * (progress towards the goal)."""
         K, n = int(K), int(n)
         if K < 1 or n < 1:
             raise ValueError('plan_begin: K and n must be >= 1')
@@ -627,7 +645,8 @@ class BatchedCrowdSim(object):
                                  that mode's info, steps and time
         and with per_mode=True ret float64, info uint8, steps int32, time float64 [B, K, M].  There is no final state and no
         bootstrap.  actions, `out`, n = 0, what is borrowed and what is copied: as in lookahead().  No state, rollout buffer,
-        ring level, launch counter or lookahead_human_model changes."""
+        ring level, launch counter or lookahead_human_model changes.  With set_lookahead_goal_weight(w != 0), every mode's ret —
+        and so score, worst_mode and the worst rows — includes w * (progress towards the goal at that mode's last step)."""
         who = 'lookahead_modes'
         shape = tuple(getattr(actions, 'shape', np.shape(actions)))
         if len(shape) != 4 or shape[0] != self.B or shape[1] < 1 or shape[3] != 2:

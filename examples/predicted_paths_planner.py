@@ -4,7 +4,7 @@ predicted velocities the CALLER makes from the state after every real step (DESI
 
     python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
                                                [--futures cv,to_goal [--reduce min] [--risk-penalty 0.5]]
-                                               [--device-loop [--chunk 8]] [--orca-sees-plan]
+                                               [--device-loop [--chunk 8]] [--orca-sees-plan] [--goal-weight W]
 
 Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
 stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
@@ -23,7 +23,9 @@ see the robot (BatchedCrowdSim.predict_orca) — a table mad
 with --device-loop the one call is plan_predict_orca_rollout, which writes that future over its slot of the table.
 --orca-sees-plan (with --futures ...,orca): the humans of that future DO see the robot, on the plan's nominal sequence — per
 real step plan_draw, then BatchedCrowdSim.predict_orca_robot on candidate 0, the clipped mean; with
---device-loop the one call is plan_predict_orca_nominal_rollout."""
+--device-loop the one call is plan_predict_orca_nominal_rollout.
+--goal-weight W (every mode above, --device-loop included) adds W * (metres of progress towards the goal over
+the sequence) to every candidate's return under every future (set_lookahead_goal_weight); 0 (the default) is the run without it."""
 import argparse
 import logging
 import os
@@ -37,7 +39,8 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
-         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8, orca_sees_plan=False):
+         predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8, orca_sees_plan=False,
+         goal_weight=0.0):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -47,6 +50,7 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
         robot.kinematics = 'holonomic'
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
+    eng.set_lookahead_goal_weight(goal_weight)
     bufs = eng.rollout_begin(seed_base=env.case_capacity['val'], seed_mod=env.case_size['test'], episode_limit=cases,
                              record_capacity=1)
     planner = eng.plan_reset(eng.plan_begin(candidates, horizon, elites, iterations, init_std * robot.v_pref, seed=seed))
@@ -118,6 +122,8 @@ def main():
     ap.add_argument('--chunk', type=int, default=8, help='--device-loop: real steps per call')
     ap.add_argument('--orca-sees-plan', action='store_true',
                     help="--futures ...,orca: that future's humans see the robot on the plan's nominal sequence")
+    ap.add_argument('--goal-weight', type=float, default=0.0,
+                    help="W: every candidate's return gains W per metre of progress towards the goal (0: the discounted return alone)")
     args = ap.parse_args()
     names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal', 'orca': 'orca'}
     futures = None
@@ -137,7 +143,8 @@ def main():
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
                       predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty,
-                      device_loop=args.device_loop, chunk=args.chunk, orca_sees_plan=args.orca_sees_plan))
+                      device_loop=args.device_loop, chunk=args.chunk, orca_sees_plan=args.orca_sees_plan,
+                      goal_weight=args.goal_weight))
     return 0
 
 

@@ -23,7 +23,11 @@ stays at --init-std.
 
 --human-model constant_velocity (every mode) scores the candidates with humans that keep their current
 velocity instead of reacting through ORCA (set_lookahead_human_model): what a planner outside the simulator can assume.  The
-real steps stay the simulator's."""
+real steps stay the simulator's.
+
+--goal-weight W (every mode) adds W * (metres of progress towards the goal over the sequence) to every
+candidate's score (set_lookahead_goal_weight): the terminal term without which collision-free candidates that do not arrive
+inside the horizon all tie at 0.0.  0 (the default) is the run without it."""
 import argparse
 import logging
 import os
@@ -64,7 +68,7 @@ def load_policy(model_dir, name):
 CEM_CHUNK = 16  # real steps per plan_rollout call: how often the host looks whether every case has ended
 
 
-def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, human_model='orca'):
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, human_model='orca', goal_weight=0.0):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -75,6 +79,7 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, h
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
     eng.set_lookahead_human_model(human_model)
+    eng.set_lookahead_goal_weight(goal_weight)
     space, _, _ = build_action_space(robot.v_pref)
     rank_by, extra = 'ret', {}
     if policy is not None:  # rank by the bootstrapped n-step return instead
@@ -139,13 +144,16 @@ def main():
     ap.add_argument('--init-std', type=float, default=0.5, help='--cem / --mppi: standard deviation a step starts from, in units of v_pref')
     ap.add_argument('--human-model', default='orca', choices=['orca', 'constant_velocity'],
                     help="how the humans move in the planner's lookahead (the real steps are always ORCA)")
+    ap.add_argument('--goal-weight', type=float, default=0.0,
+                    help="W: every candidate's score gains W per metre of progress towards the goal (0: the discounted return alone)")
     args = ap.parse_args()
     policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
     cem = None
     if args.cem or args.mppi:
         cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std,
                    temperature=args.temperature if args.mppi else None)
-    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem, human_model=args.human_model))
+    logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem, human_model=args.human_model,
+                      goal_weight=args.goal_weight))
     return 0
 
 

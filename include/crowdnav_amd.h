@@ -662,6 +662,37 @@ int cn_lookahead_get_human_model(const cn_engine* e, int* model_host);
  * One launch of a kernel of its own (lane = branch, the humans of an env shared by its K branches), not counted either. */
 
 /* ------------------------------------------------------------------------------------------------------
+ * Lookahead goal-progress term (no version bump: two new symbols; no struct, enum or counter touched).  A branch's return is
+ * the environment's: +success on arrival, the collision penalty, the discomfort penalty, nothing else — so over a horizon that
+ * does not reach the goal every collision-free candidate scores exactly 0.0 and a planner cannot tell which way the goal lies.
+ * This setting adds the terminal term every MPC-style planner has: a weight on the progress the branch made towards the goal.
+ * With w the engine's weight, (px0, py0) the robot's position as the engine state holds it when the launch runs, (gx, gy) its
+ * goal, (px, py) its position after the branch's last transition — the one final_state8 reports, whether the branch ended or
+ * ran the whole horizon — and norm2(x, y) = sqrt(fma(y, y, x * x)):
+ *     d0   = norm2(px0 - gx, py0 - gy)
+ *     d1   = norm2(px  - gx, py  - gy)
+ *     ret' = ret + w * (d0 - d1)          one subtraction, one multiply, one add, in that order, float64, no fused operation
+ * Added once, after the last reward of the branch, undiscounted, the same for every end code (a ReachGoal branch has
+ * d1 < radius: the term is continuous across arrival).  With w != 0, ret' takes the place of ret wherever a lookahead reports
+ * or uses it: out->ret of cn_lookahead_actions (both human models), cn_lookahead_paths, cn_lookahead_values and
+ * cn_lookahead_paths_values; score = ret' + table[steps] * V of the two *_values calls; every per-mode ret_m of
+ * cn_lookahead_modes, each at its own mode's last step with the robot's position after that step, before the reduction — hence
+ * score, worst_mode and the per_mode rows; and so whatever the cn_plan_* calls rank, best_score and the MPPI weights, in every
+ * planner form and every *_rollout closed loop.  Untouched: info, steps, time, final_state8, final_theta; the real steps inside
+ * the closed loops (cn_rollout_step's rewards, the episode records, ep_return); cn_step, every rollout, cn_sarl_select's
+ * one-step rewards.  Holonomic and CN_UNICYCLE engines and the `mixed` rule alike, wherever the call itself serves them.
+ * The term is added inside the lookahead kernels, by instantiations of their own (their goal forms), which alone read w: with
+ * w == 0.0 (what cn_create installs, or set back; -0.0 is 0.0) every call launches the kernels it launched before this setting
+ * existed, and every output is bit for bit what it was.
+ * A per-engine host-side setting: accepted on any engine, touches nothing on the device, survives cn_reset and the rollout
+ * calls, like the human model above.
+ * Refused before anything is touched, what depends on the argument alone first: a weight that is NaN, infinite or negative:
+ * CN_ERR_INVALID with the value in the message (-0.0 is not negative: accepted, and means 0.0); NULL e: CN_ERR_INVALID. */
+int cn_lookahead_set_goal_weight(cn_engine* e, double weight);        /* default 0.0 */
+/* NULL e, then NULL weight_host: CN_ERR_INVALID. */
+int cn_lookahead_get_goal_weight(const cn_engine* e, double* weight_host);
+
+/* ------------------------------------------------------------------------------------------------------
  * Lookahead under predicted human motion (no version bump: four new symbols; no struct, enum or counter touched).  The two
  * human models above are the ends of a range: ORCA reads every human's goal, constant velocity extrapolates forever.  A planner
  * outside the simulator has a predictor of its own — a learned trajectory model, a goal-directed extrapolation, a recorded
