@@ -11,11 +11,11 @@ neighbour parameters are literals in orca.py:60-66, the humans' safety space is 
 the entry's fixture tests/golden/settings_<name>.npz (oracle/gen_golden_settings.py) is made WITHOUT them, and the device is
 compared with the oracle alone where they are set."""
 import collections
-import contextlib
 import json
-import os
 
 import numpy as np
+
+from support import environ  # noqa: F401  (the suites take it from here)
 
 # what every key is when an entry does not change it (crowd_nav/configs/env.config + orca.py:60-66)
 SHIPPED = dict(
@@ -245,18 +245,3 @@ def accumulated(dt, k):
 def whole_config(config):
     """config over the shipped values: every key a host restatement reads."""
     return dict(SHIPPED, **config)
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """The engine's switches are read when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    os.environ.update({k: str(v) for k, v in values.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v

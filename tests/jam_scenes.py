@@ -14,6 +14,8 @@ Deterministic: numpy RandomState with fixed seeds.  test_jam_scenes_host.py prov
 every scene is what its name says; test_fused_jam_parity.py runs them through every rollout kernel."""
 import numpy as np
 
+from support import np_of
+
 T = 8  # steps per scene: by then every jam has dissolved to 0-1 infeasible agents, so quiet steps after a jam are included
 
 ROBOT_AT, ROBOT_GOAL = (-6.0, 0.0), (-6.0, 9.0)
@@ -139,14 +141,14 @@ OTHER_CASES = tuple(n for n, c in CASES.items() if c[0] is not HEADLINE)
 _scenes, _runs = {}, {}
 
 
-def scene(name):
+def scene(name, cases=CASES, made=_scenes):
     """(config, envs per workgroup, state [B, A, 8]) — built once; callers must not write into the state"""
-    if name not in _scenes:
-        cfg, epw, build = CASES[name]
+    if name not in made:
+        cfg, epw, build = cases[name]
         st = build()
         st.setflags(write=False)
-        _scenes[name] = (dict(cfg), epw, st)
-    return _scenes[name]
+        made[name] = (dict(cfg), epw, st)
+    return made[name]
 
 
 def workgroup_counts(fallback, epw):
@@ -200,3 +202,16 @@ def search_rising(oracle_mod, n_seeds=20000):
     for seed in np.flatnonzero(ok & (c[1] >= 3) & (c[1] >= c[0])):
         found.setdefault((int(c[0, seed]), int(c[1, seed])), []).append(int(seed))
     return found
+
+
+def same_state(eng, want, steps, where):
+    """the engine's state and global_time against the oracle's after `steps` steps: bit for bit"""
+    state, gtime = (np_of(x) for x in eng.get_state())
+    ws, wg = want['states'][steps], want['global_time'][steps]
+    assert state.dtype == ws.dtype == np.float64, (state.dtype, ws.dtype)
+    vel, wvel = state[:, :, 2:4].astype(np.float32), ws[:, :, 2:4].astype(np.float32)
+    assert np.array_equal(vel.view(np.uint32), wvel.view(np.uint32)), ('velocity bits', where, steps)
+    assert np.array_equal(state[:, :, 2:4], ws[:, :, 2:4]), ('velocity', where, steps)
+    assert np.array_equal(state[:, :, 0:2], ws[:, :, 0:2]), ('position', where, steps)
+    assert np.array_equal(state, ws), ('state', where, steps)
+    assert np.array_equal(gtime, wg), ('global_time', where, steps)

@@ -109,3 +109,16 @@ def lookahead(state8, gtime, table_actions, cfg=CFG, gamma=0.9):
             infos[b][k] = got['infos']
     out['infos'] = infos
     return out
+
+
+def robot_row(px=0.0, py=0.0, gx=0.0, gy=4.0):
+    return [px, py, 0.0, 0.0, gx, gy, 0.3, 1.0]
+
+
+def human_row(x, y, vx=0.0, vy=0.0):
+    return [x, y, vx, vy, -x, -y, 0.3, 1.0]
+
+
+def cfg_of(eng):
+    """An engine's values of the settings CFG names."""
+    return {k: float(eng.config[k]) for k in CFG}

@@ -2,13 +2,11 @@
 torch's SGD step on lstm_rl.ValueNetwork1 as the reference Trainer takes it, a numpy restatement of the formulas the device
 step is written from (torch's gate order i, f, g, o; back through time from dh_H = dJ[:, 6:]; 16-row partial sums for the weight
 gradients), and the project's rule for judging a float32 step against the float64 truth (tests/test_train_step.py)."""
-import os
-
 import numpy as np
 import torch
 
-from conftest import GOLDEN
-from sgd_step_reference import report  # noqa: F401  (the LSTM tables go to the same file, keys prefixed lstm/)
+import sgd_step_reference as sgd
+from sgd_step_reference import pool, report  # noqa: F401  (the LSTM tables go to the same file, keys prefixed lstm/)
 
 FIXTURES = ('rl_lstm_rl.npz', 'rl_lstm_rl_om.npz')
 NAMES = ['mlp.%d.%s' % (i, w) for i in (0, 2, 4, 6) for w in ('weight', 'bias')] + \
@@ -18,13 +16,7 @@ FACTOR, FLOOR = 8.0, 2.0 ** -20
 
 
 def load(fixture, H=5):
-    """(params {name: float32 array}, states [rows, H, D], values [rows]); H = 1, 3: the first humans; 8: rows 0-4 then 0-2."""
-    g = np.load(os.path.join(GOLDEN, fixture))
-    P = {k[6:]: g[k] for k in g.files if k.startswith('param_')}
-    assert list(P) == NAMES
-    S, V = g['memory_states'], g['memory_values']
-    S = np.concatenate([S, S[:, :H - 5]], 1) if H > 5 else S[:, :H]
-    return P, np.ascontiguousarray(S), np.ascontiguousarray(V)
+    return sgd.load(fixture, H, NAMES)
 
 
 def network(P, dtype, device='cpu'):
@@ -122,6 +114,7 @@ def manual_step(P, x, y, lr, mom, buf, dt):
 # ---- the rule (tests/test_train_step.py): per tensor the error of the momentum buffer after the step,
 # max|buf - buf64| / max(max|buf64|, 1e-6 G), pooled over the cases of one (fixture, H); E_new <= max(8 E_torch, 2^-20)
 
+
 def zero_gradient(name, H):
     """h_0 = 0, so at H = 1 nothing multiplies W_hh: its gradient is exactly zero and is judged absolutely."""
     return H == 1 and name == 'lstm.weight_hh_l0'
@@ -130,11 +123,6 @@ def zero_gradient(name, H):
 def errors(buf, buf64, grad64):
     G = max(np.abs(g).max() for g in grad64.values())
     return {k: np.abs(np.asarray(buf[k], np.float64) - buf64[k]).max() / max(np.abs(buf64[k]).max(), 1e-6 * G) for k in NAMES}, G
-
-
-def pool(into, new):
-    for k, v in new.items():
-        into[k] = max(into.get(k, 0.0), float(v))
 
 
 def check_pooled(E_torch, E_new, H, where):

@@ -9,6 +9,8 @@ import collections
 
 import numpy as np
 
+from env_setting_cases import setting_id  # noqa: F401  (a setting's name, for parametrize ids)
+
 GROUPS = 16        # kSarlGroups: (env, action) groups per tile = rows of a matrix-instruction tile
 K_CHUNK = 5        # kSarlKChunk: k-steps per trip of the k loop; a layer's kpad is a whole number of them
 NARROW_K = 40      # kNarrowK: k-steps of a column tile the narrow kernel holds in registers; longer layers take its tail loop
@@ -86,10 +88,6 @@ SETTINGS = (
 BY_NAME = {s.name: s for s in SETTINGS}
 assert len(BY_NAME) == len(SETTINGS)
 HUMANS = (1, 2, 5, 8, 9)  # 8: the largest crowd of a one-tile kernel; 9: streamed whatever the widths
-
-
-def setting_id(s):
-    return s.name
 
 
 def configure_kwargs(s):

@@ -1,4 +1,4 @@
-"""What test_predict_orca_host.py (no GPU) and test_predict_orca.py (GPU) share: the crowds, the oracle's statement of the ORCA
+"""What the predict_orca and predict_orca_robot suites, host (no GPU) and GPU, share: the crowds, the oracle's statement of the ORCA
 predictor's table — the environment itself, stepped with the robot unseen and fresh simulators — and the preconditions a scene
 must meet for the bit-for-bit comparison to mean something."""
 import numpy as np
@@ -48,3 +48,41 @@ def visible_first_step(oracle_mod, crowd, state, gtime):
 def differs_from(vel, other):
     """[B, H]: the furthest any row of human h's table lies from `other`'s (Euclidean, m/s)."""
     return np.sqrt(((vel - other) ** 2).sum(axis=-1)).max(axis=1)
+
+
+# ------------------------------------------------------------------------------------------------ the GPU suites' shared parts
+BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
+KEYS = ('ret', 'info', 'steps', 'time', 'final_state8', 'final_theta')
+# the closed loops' futures and plan updates
+FUTURES = {'one': dict(models='to_goal', orca_mode=0), 'two': dict(models=('to_goal', 'cv'), orca_mode=1, reduce='min')}
+UPDATES = {'cem': {}, 'mppi': dict(temperature=1.0, fit_std=False)}
+
+
+def engine(amd, crowd='h5', envs=B, steps=4, **cfg):
+    """A seeded reset and `steps` real steps with the action (0, 1): the humans are under way."""
+    cfg = dict(CROWDS[crowd], **cfg)
+    eng = amd.BatchedCrowdSim(num_envs=envs, robot_policy=cfg.pop('robot_policy', amd.ROBOT_EXTERNAL), **cfg)
+    eng.reset(1000 + np.arange(envs))
+    straight_on = [1.0, 0.0] if cfg.get('robot_kinematics') else [0.0, 1.0]
+    for _ in range(steps):
+        eng.step(np.tile(straight_on, (envs, 1)) if eng.config['robot_policy'] == amd.ROBOT_EXTERNAL else None, update=True,
+                 want_obs=False)
+    return eng
+
+
+def replay_scene(state, K=9, n=10):
+    """test_lookahead_paths.py (b)'s scene: the robot 1.0 ahead of human 1 on that human's way to its goal, its own goal 1.5 to
+    the side: straight to the goal is ReachGoal at the fifth step, standing still is run over (the humans do not see the
+    robot), walking ahead of human 1 — at its speed or a little slower — runs on."""
+    from crowdnav_amd.compat.sarl import build_action_space
+    acts = np.array([list(a) for a in build_action_space(1.0)[0]], dtype=np.float64)
+    placed = state.copy()
+    table = acts[np.random.RandomState(7).randint(len(acts), size=(len(state), K, n))]
+    for b in range(len(state)):
+        human = state[b, 1]
+        d = (human[4:6] - human[0:2]) / np.hypot(*(human[4:6] - human[0:2]))
+        side = np.array([-d[1], d[0]])
+        at = human[0:2] + d * 1.0
+        placed[b, 0, 0:2], placed[b, 0, 2:4], placed[b, 0, 4:6] = at, 0.0, at + side * 1.5
+        table[b, 0], table[b, 1], table[b, 2], table[b, 3] = side, 0.0, d, 0.9 * d
+    return placed, table

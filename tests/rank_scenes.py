@@ -19,6 +19,8 @@ agents), which is what the rank of the pair phase must reproduce; test_rank_scen
 it and ties the table to the oracle's velocities."""
 import numpy as np
 
+import jam_scenes
+
 T = 4  # steps per scene
 
 F = np.float32
@@ -97,13 +99,7 @@ _scenes, _runs = {}, {}
 
 
 def scene(name):
-    """(config, envs per workgroup, state [B, A, 8]) — built once; callers must not write into the state"""
-    if name not in _scenes:
-        cfg, epw, build = CASES[name]
-        st = build()
-        st.setflags(write=False)
-        _scenes[name] = (dict(cfg), epw, st)
-    return _scenes[name]
+    return jam_scenes.scene(name, CASES, _scenes)
 
 
 def neighbour_table(env, robot_visible, neighbor_dist=10.0, max_neighbors=10):

@@ -13,11 +13,11 @@ NAMES = ['%s.%d.%s' % (m, i, w) for m, idx in (('mlp1', (0, 2)), ('mlp2', (0, 2)
          for i in idx for w in ('weight', 'bias')]
 
 
-def load(fixture, H=5):
+def load(fixture, H=5, names=NAMES):
     """(params {name: float32 array}, states [rows, H, D], values [rows]); H = 1, 3: the first humans; 8: rows 0-4 then 0-2."""
     g = np.load(os.path.join(GOLDEN, fixture))
     P = {k[6:]: g[k] for k in g.files if k.startswith('param_')}
-    assert list(P) == NAMES
+    assert list(P) == names, list(P)
     S, V = g['memory_states'], g['memory_values']
     S = np.concatenate([S, S[:, :H - 5]], 1) if H > 5 else S[:, :H]
     return P, np.ascontiguousarray(S), np.ascontiguousarray(V)
@@ -135,3 +135,22 @@ def report(key, value):
     with open(path, 'w') as f:
         json.dump(data, f, indent=1, sort_keys=True)
         f.write('\n')
+
+
+def pool(into, new):
+    for k, v in new.items():
+        into[k] = max(into.get(k, 0.0), float(v))
+
+
+def cpu_trainer(ref, monkeypatch, switch, P, S, V):
+    """compat's Trainer on the CPU over `ref`'s network (this module or lstm_step_reference), and the losses of a batch and an
+    epoch under CROWDNAV_AMD_SGD_KERNEL = switch."""
+    from crowdnav_amd.compat.trainer import ReplayMemory, Trainer
+    monkeypatch.setenv('CROWDNAV_AMD_SGD_KERNEL', switch)
+    torch.manual_seed(11)
+    memory = ReplayMemory(1000)
+    for s, v in zip(S, V):
+        memory.push((torch.from_numpy(s), torch.from_numpy(v.reshape(1))))
+    trainer = Trainer(ref.network(P, torch.float32), memory, torch.device('cpu'), 100)
+    trainer.set_learning_rate(0.01)
+    return trainer, [trainer.optimize_batch(3), trainer.optimize_epoch(1)]

@@ -7,20 +7,13 @@ import re
 import pytest
 
 from conftest import ROOT
+from support import built  # noqa: F401  (built: module fixture)
 
 
 def _declared_symbols():
     text = open(os.path.join(ROOT, 'include', 'crowdnav_amd.h')).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(cn_[a-z0-9_]+)\s*\(', text)))
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_and_binding_agree(built):

@@ -17,21 +17,11 @@ Integer results bit-exact, float64 sums / states to 1e-9 (scenario generation: d
 import numpy as np
 import pytest
 
+from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
 
 REACH_GOAL, COLLISION, TIMEOUT = 2, 3, 4
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _ring_view(rec, K):

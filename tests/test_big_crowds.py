@@ -7,11 +7,7 @@ import pytest
 import torch
 
 from conftest import load_golden, report_argmax
-
-
-def _load(net, g):
-    net.load_state_dict({k[len('param_'):]: torch.from_numpy(v) for k, v in g.items() if k.startswith('param_')})
-    return net
+from support import load_params as _load
 
 
 def _select(g, **cfg):

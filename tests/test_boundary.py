@@ -3,24 +3,13 @@ through torch.distributed's 'nccl' backend AND through the C ABI's cn_gather_rec
 and the scenario ring's fill policy (launches inside the ring's budget skip the fill kernels; scenarios the register-only
 generator gives up on go through the redo pool)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 
+from support import amd, free_port as _free_port, np_of as _np  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _rollout(amd, B, launches, K=16, **cfg):
@@ -125,14 +114,6 @@ def test_summary_kernel_is_the_explorer_statistics_and_bitwise_reproducible(amd,
     assert 0.0 < success_rate <= 1.0 and 0.0 <= collision_rate < 1.0
     assert 8.0 < s[5] / s[2] < 25.0  # average nav time of the successful episodes
     assert torch.cuda.is_available()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def test_rccl_all_gather_runs_at_world_one(amd):

@@ -1,19 +1,12 @@
 """N>1 path on CPU: world_size-2 gloo processes exchange episode records exactly as ranks do over RCCL."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from support import free_port as _free_port
 
 
 def _fake_bufs(rank, B, K, world):

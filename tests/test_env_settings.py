@@ -13,22 +13,11 @@ import lookahead_cv_reference as cv
 import lookahead_paths_reference as paths
 import plan_reference as plan_ref
 from conftest import load_golden
+from support import amd, np_of as _np, same_bits as _same_bits  # noqa: F401  (amd: module fixture)
 
 FIXTURES, flat, environ = cases.fixture_settings(), cases.flat, cases.environ
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------ a. resets
@@ -237,11 +226,6 @@ def test_one_step_past_the_table_is_refused(amd):
 # ------------------------------------------------------------------------------------------------ d. traced rollouts, action tables
 ROBOT_ENTRIES = ['dt_inexact', 'speeds', 'radii_rewards']
 BEGIN = dict(seed_base=cases.SEED_BASE, seed_mod=cases.SEED_MOD, record_capacity=8)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize('external', [False, True], ids=['rollout_trace', 'rollout_actions'])

@@ -21,13 +21,12 @@ suite already pins to the oracle step by step.
 
 Both sides start from the same float64 state and the device's claim is bit identity with the float32 RVO2 restatement:
 nothing but equality is accepted (the running return is a float64 sum held to the suite's 1e-9)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import jam_scenes as js
+from jam_scenes import same_state as _same_state
+from support import amd, environ, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,54 +43,10 @@ RUNS = [(name, route, cut) for name in js.CASES for route in (ROUTES if name in 
         for cut in CUTS]
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
 def _engine(amd, name, switches):
     cfg, epw, st = js.scene(name)
     with environ(CROWDNAV_AMD_ENVS_PER_WAVE=epw, **switches):
         return amd.BatchedCrowdSim(num_envs=st.shape[0], robot_policy=amd.ROBOT_ORCA, **cfg)
-
-
-def _same_state(eng, want, steps, where):
-    """the engine's state and global_time against the oracle's after `steps` steps: bit for bit"""
-    state, gtime = (_np(x) for x in eng.get_state())
-    ws, wg = want['states'][steps], want['global_time'][steps]
-    assert state.dtype == ws.dtype == np.float64
-    vel, wvel = state[:, :, 2:4].astype(np.float32), ws[:, :, 2:4].astype(np.float32)
-    assert np.array_equal(vel.view(np.uint32), wvel.view(np.uint32)), ('velocity bits', where, steps)
-    assert np.array_equal(state[:, :, 2:4], ws[:, :, 2:4]), ('velocity', where, steps)
-    assert np.array_equal(state[:, :, 0:2], ws[:, :, 0:2]), ('position', where, steps)
-    assert np.array_equal(state, ws), ('state', where, steps)
-    assert np.array_equal(gtime, wg), ('global_time', where, steps)
 
 
 @pytest.mark.parametrize('name,route,cut', RUNS, ids=['%s-%s-%s' % r for r in RUNS])

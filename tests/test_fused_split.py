@@ -13,39 +13,11 @@ Multi-pass 3-D fallback (more than six infeasible agents of a workgroup in one s
 it (they produce 1, 2 or 3 infeasible agents per step).  test_fused_jam_parity.py does, from the huddles of jam_scenes.py — 7 to 10
 infeasible agents of a workgroup, on the one-wave and both two-wave kernels, step for step against the oracle — and
 test_jam_scenes_host.py proves on the oracle that those scenes reach it."""
-import contextlib
-import os
-
 import pytest
 
+from support import amd, environ, same_tensors as _same  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _run(amd, split, B, launches, ring_depth=None, radius=4.0, **begin):
@@ -61,13 +33,6 @@ def _run(amd, split, B, launches, ring_depth=None, radius=4.0, **begin):
     out = dict(bufs)
     out['state'], out['global_time'], out['rollout_summary'] = state, gtime, eng.rollout_summary()
     return out
-
-
-def _same(a, b):
-    import torch
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
 
 
 @pytest.fixture(scope='module')

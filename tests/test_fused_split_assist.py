@@ -10,41 +10,13 @@ that decides which iterations have the third barrier hangs the workgroup, so the
 it everything after.
 
 The geometry is the headline one: 5 humans, a visible ORCA robot, 2 envs per workgroup (CROWDNAV_AMD_ENVS_PER_WAVE=2)."""
-import contextlib
-import os
-
 import pytest
+
+from support import amd, environ, same_tensors as _same  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
 ASSIST = (0, 1)
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _run(amd, assist, B, launches, ring_depth=None, **begin):
@@ -63,13 +35,6 @@ def _run(amd, assist, B, launches, ring_depth=None, **begin):
     out = dict(bufs)
     out['state'], out['global_time'], out['rollout_summary'] = state, gtime, eng.rollout_summary()
     return out
-
-
-def _same(a, b):
-    import torch
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
 
 
 CASES = {

@@ -6,20 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import TRAJ_FIXTURES, episodes_of, flat_steps, load_golden
+from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def test_mt19937_matches_numpy_stream(amd):
@@ -393,7 +382,7 @@ def test_window_generator_give_up_keeps_the_sequential_stream(amd, monkeypatch, 
     (what cn_sarl_explore draws from: mt_key / mt_pos) must be those of the plain sequential loop."""
     import ctypes as C
     import torch
-    from test_generator_window_emulation import attempts_of, sequential
+    from generator_window_emulation import attempts_of, sequential
     monkeypatch.setenv('CROWDNAV_AMD_MAX_ATTEMPTS_LOG2', str(cap_log2))
     B, H, R, K = 64, 20, 4.0, 81
     eng = amd.BatchedCrowdSim(num_envs=B, num_humans=H, circle_radius=R, robot_policy=amd.ROBOT_EXTERNAL, robot_visible=1)
@@ -613,7 +602,7 @@ def test_free_running_soak_vs_oracle(amd, oracle_mod, humans, envs, rounds, radi
 @pytest.mark.gpu
 def test_survey_known_answer_velocities_on_device(amd):
     """The same known-answer vectors (an independent float32 restatement of RVO2) through cn_step."""
-    from test_oracle_golden import SURVEY_KAT_CASE0
+    from oracle_golden_cases import SURVEY_KAT_CASE0
     g = load_golden('resets.npz')
     eng = amd.BatchedCrowdSim(num_envs=1, num_humans=5, robot_policy=amd.ROBOT_ORCA, robot_visible=0)
     eng.set_state(g['test_h5_states'][:1], np.zeros(1))

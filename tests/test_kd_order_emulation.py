@@ -1,196 +1,8 @@
-"""CPU emulation of the device's kd-tree bookkeeping (crowdnav_amd/csrc/kd_order.h) against a direct transcription of
-RVO2's KdTree (buildAgentTreeRecursive / queryAgentTreeRecursive, restated in oracle/rvo2_oracle.cpp:162-256).
-
-RVO2 visits an agent's candidate neighbours in kd-tree order once its simulator holds more than 10 agents, and keeps the
-permutation the tree partitions IN PLACE from step to step; the order only shows when two candidates are at EXACTLY the same
-float32 squared distance.  The device does not run RVO2's recursion per simulator.  It uses three facts, checked here on
-random and on lattice (tie-heavy) point sets over many steps:
-  1. the tree STRUCTURE (which position ranges split, at which count, with which agents on the lower side) depends on the
-     point SET only, so it is built once per env (breadth first, on sets) and shared by the env's 21 simulators, whose
-     permutations differ;
-  2. RVO2's two-pointer partition equals: the i-th misplaced element of the lower zone (from the left) swaps with the i-th
-     misplaced element of the upper zone (from the right) — a few bit operations on position masks;
-  3. the neighbour list RVO2 ends up with is the first maxNeighbors candidates of the stable order by (distSq, position in
-     the nearer-child-first traversal of the WHOLE tree): pruned subtrees only hold candidates that would be rejected."""
+"""The emulation of the device's kd-tree bookkeeping (kd_order_emulation.py) against its transcription of RVO2's KdTree, on random
+and on lattice (tie-heavy) point sets over many steps."""
 import numpy as np
 
-LEAF = 10
-f32 = np.float32
-
-
-# ------------------------------------------------------------------ RVO2, transcribed
-class RvoTree(object):
-    def __init__(self, n):
-        self.order = list(range(n))  # persistent permutation (KdTree::agents_)
-        self.nodes = {}
-
-    def build(self, pos):
-        self.nodes = {}
-        self._build(pos, 0, len(self.order), 0)
-
-    def _build(self, pos, begin, end, node):
-        xs = [pos[self.order[i]] for i in range(begin, end)]
-        minx = maxx = xs[0][0]
-        miny = maxy = xs[0][1]
-        for p in xs[1:]:
-            maxx, minx = max(maxx, p[0]), min(minx, p[0])
-            maxy, miny = max(maxy, p[1]), min(miny, p[1])
-        rec = dict(begin=begin, end=end, box=(minx, maxx, miny, maxy), left=None, right=None)
-        self.nodes[node] = rec
-        if end - begin > LEAF:
-            vertical = f32(maxx - minx) > f32(maxy - miny)
-            split = f32(f32(0.5) * f32(maxx + minx)) if vertical else f32(f32(0.5) * f32(maxy + miny))
-            coord = lambda k: pos[self.order[k]][0 if vertical else 1]  # noqa: E731
-            left, right = begin, end
-            while left < right:
-                while left < right and coord(left) < split:
-                    left += 1
-                while right > left and coord(right - 1) >= split:
-                    right -= 1
-                if left < right:
-                    self.order[left], self.order[right - 1] = self.order[right - 1], self.order[left]
-                    left += 1
-                    right -= 1
-            if left == begin:
-                left += 1
-                right += 1
-            rec['left'], rec['right'] = node + 1, node + 2 * (left - begin)
-            self._build(pos, begin, left, rec['left'])
-            self._build(pos, left, end, rec['right'])
-
-    def neighbours(self, pos, me, max_nb, range_sq):
-        """KdTree::queryAgentTreeRecursive + Agent::insertAgentNeighbor: [(distSq, id)], ascending"""
-        out = []
-        rs = [f32(range_sq)]
-
-        def offer(other):
-            if other == me:
-                return
-            dx, dy = f32(pos[me][0] - pos[other][0]), f32(pos[me][1] - pos[other][1])
-            d = f32(f32(dx * dx) + f32(dy * dy))
-            if d < rs[0]:
-                if len(out) < max_nb:
-                    out.append((d, other))
-                i = len(out) - 1
-                while i != 0 and d < out[i - 1][0]:
-                    out[i] = out[i - 1]
-                    i -= 1
-                out[i] = (d, other)
-                if len(out) == max_nb:
-                    rs[0] = out[-1][0]
-
-        def box_dist(rec):
-            minx, maxx, miny, maxy = rec['box']
-            px, py = pos[me]
-            z = f32(0)
-            t = [max(z, f32(minx - px)), max(z, f32(px - maxx)), max(z, f32(miny - py)), max(z, f32(py - maxy))]
-            acc = f32(t[0] * t[0])
-            for v in t[1:]:
-                acc = f32(acc + f32(v * v))
-            return acc
-
-        def query(node):
-            rec = self.nodes[node]
-            if rec['end'] - rec['begin'] <= LEAF:
-                for i in range(rec['begin'], rec['end']):
-                    offer(self.order[i])
-                return
-            dl, dr = box_dist(self.nodes[rec['left']]), box_dist(self.nodes[rec['right']])
-            if dl < dr:
-                if dl < rs[0]:
-                    query(rec['left'])
-                    if dr < rs[0]:
-                        query(rec['right'])
-            elif dr < rs[0]:
-                query(rec['right'])
-                if dl < rs[0]:
-                    query(rec['left'])
-
-        query(0)
-        return out
-
-
-# ------------------------------------------------------------------ the device's formulation
-def shared_tree(pos, members):
-    """Breadth-first over SETS: [(begin, end, n_left, left_mask)] of the nodes that split; no permutation involved."""
-    nodes, queue = [], [(0, len(members), sum(1 << a for a in members))]
-    while queue:
-        begin, end, mask = queue.pop(0)
-        pts = [pos[a] for a in range(64) if mask >> a & 1]
-        minx, maxx = min(p[0] for p in pts), max(p[0] for p in pts)
-        miny, maxy = min(p[1] for p in pts), max(p[1] for p in pts)
-        vertical = f32(maxx - minx) > f32(maxy - miny)
-        split = f32(f32(0.5) * f32(maxx + minx)) if vertical else f32(f32(0.5) * f32(maxy + miny))
-        left = sum(1 << a for a in range(64) if mask >> a & 1 and pos[a][0 if vertical else 1] < split)
-        nl = bin(left).count('1')
-        assert nl > 0, 'degenerate split (all points within an ulp): not generated by these tests'
-        nodes.append((begin, end, nl, left))
-        if nl > LEAF:
-            queue.append((begin, begin + nl, left))
-        if end - begin - nl > LEAF:
-            queue.append((begin + nl, end, mask & ~left))
-    return nodes
-
-
-def partition_bits(row, begin, end, nl, left):
-    """RVO2's two-pointer partition as mask arithmetic on positions (kd_partition)."""
-    is_l = sum(1 << p for p in range(begin, end) if left >> row[p] & 1)
-    zone = ((1 << (begin + nl)) - 1) & ~((1 << begin) - 1)
-    rng = ((1 << end) - 1) & ~((1 << begin) - 1)
-    bad_l, bad_r = ~is_l & zone, is_l & rng & ~zone
-    while bad_l:
-        p = (bad_l & -bad_l).bit_length() - 1
-        q = bad_r.bit_length() - 1
-        row[p], row[q] = row[q], row[p]
-        bad_l &= bad_l - 1
-        bad_r &= ~(1 << q)
-    assert bad_r == 0
-
-
-def visit_order(pos, row, nodes, me):
-    """position of every agent in the nearer-child-first traversal of the whole tree (kd_visit_order)"""
-    split = {(b, e): nl for b, e, nl, _ in nodes}
-
-    def box_dist(b, e):
-        pts = [pos[row[p]] for p in range(b, e)]
-        minx, maxx = min(p[0] for p in pts), max(p[0] for p in pts)
-        miny, maxy = min(p[1] for p in pts), max(p[1] for p in pts)
-        px, py = pos[me]
-        z = f32(0)
-        t = [max(z, f32(minx - px)), max(z, f32(px - maxx)), max(z, f32(miny - py)), max(z, f32(py - maxy))]
-        acc = f32(t[0] * t[0])
-        for v in t[1:]:
-            acc = f32(acc + f32(v * v))
-        return acc
-
-    visit, stack, k = {}, [(0, len(row))], 0
-    while stack:
-        b, e = stack.pop()
-        if (b, e) in split:
-            nl = split[(b, e)]
-            dl, dr = box_dist(b, b + nl), box_dist(b + nl, e)
-            near, far = ((b, b + nl), (b + nl, e)) if dl < dr else ((b + nl, e), (b, b + nl))
-            stack.append(far)
-            stack.append(near)
-        else:
-            for p in range(b, e):
-                visit[row[p]] = k
-                k += 1
-    return visit
-
-
-def device_neighbours(pos, row, nodes, me, max_nb, range_sq):
-    visit = visit_order(pos, row, nodes, me)
-    cands = []
-    for other in row:
-        if other == me:
-            continue
-        dx, dy = f32(pos[me][0] - pos[other][0]), f32(pos[me][1] - pos[other][1])
-        d = f32(f32(dx * dx) + f32(dy * dy))
-        if d < f32(range_sq):
-            cands.append((d, visit[other], other))
-    cands.sort()
-    return [(d, o) for d, _, o in cands[:max_nb]]
+from kd_order_emulation import RvoTree, device_neighbours, f32, partition_bits, shared_tree
 
 
 def _scenes(rng, n, steps, lattice):

@@ -8,22 +8,11 @@ simulators whose permutations carry the history of earlier steps."""
 import numpy as np
 import pytest
 
-from test_kd_order_emulation import LEAF, device_neighbours, partition_bits, shared_tree
+from kd_order_emulation import LEAF, device_neighbours, partition_bits, shared_tree
+from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def lattice_state(rng, B, A, step=0.5, span=3.0, speed=True):

@@ -4,45 +4,13 @@ still looks at most D scenarios ahead.  Every case runs the same calls on two fr
 every fill in front of its launch), and compares EVERY output bit for bit — each buffer of rollout_begin, get_state,
 rollout_summary — and, where test_ring_wrap.py does, the oracle's rollout.  The rule's own arithmetic is checked without a
 GPU by test_fill_plan_host.py."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from ring_cases import oracle_rollout, records_in_order
+from support import amd, environ, np_of as _np, same_tensors as _same  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
 
 K = 64
 BEGIN = dict(seed_base=1000, seed_mod=500, episode_limit=-1, record_capacity=K, per_env_transitions=True)
@@ -75,32 +43,12 @@ def _run(amd, lagged, B, depth, launches, route='fused_split', **engine):
     return _outputs(eng, bufs), deltas
 
 
-def _same(a, b):
-    import torch
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
-
-
 def _oracle(oracle_mod, B, steps, humans=5):
-    o = oracle_mod.CrowdOracle(num_envs=B, robot_policy=1, num_humans=humans, robot_visible=1)
-    o.reset(1000 + np.arange(B))
-    ep_index, cur_steps, cur_ret = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float64)
-    total, rec = o.rollout(steps, 1000, 500, K, ep_index, cur_steps, cur_ret)
-    return o, total, rec, cur_steps, cur_ret
+    return oracle_rollout(oracle_mod, B, steps, K, num_humans=humans, robot_visible=1)
 
 
 def _records_in_order(out, rec):
-    """every episode the engine finished is the oracle's episode of the same ordinal (test_ring_wrap.py)"""
-    cnt = _np(out['ep_count'])
-    assert (cnt <= rec['count']).all() and cnt.max() <= K
-    got_out, steps, ret = _np(out['ep_outcome']), _np(out['ep_steps']), _np(out['ep_return'])
-    for b in range(len(cnt)):
-        k = cnt[b]
-        assert np.array_equal(got_out[b, :k], rec['outcome'][b, :k]), b
-        assert np.array_equal(steps[b, :k], rec['steps'][b, :k]), b
-        assert np.allclose(ret[b, :k], rec['ret'][b, :k], rtol=0, atol=1e-12), b
-    return cnt
+    return records_in_order(out, rec, K)
 
 
 @pytest.mark.parametrize('depth', [2, 3])

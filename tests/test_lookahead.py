@@ -14,6 +14,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import (  # noqa: F401  (amd: module fixture)
+    action_space as _space, action_table, amd, external_engine as _engine, np_of as _np, restore as _restore,
+    snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,34 +24,8 @@ BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
 DT, V_PREF = 0.25, 1.0  # the engines' defaults (time_step, robot_v_pref)
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _engine(amd, B, H, **cfg):
-    return amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=amd.ROBOT_EXTERNAL, **cfg)
-
-
-def _space(unicycle=False):
-    from crowdnav_amd.compat.sarl import build_action_space
-    space, _, _ = (build_action_space(1.0, 5, 5, 'unicycle') if unicycle else build_action_space(1.0))
-    acts = np.array([list(a) for a in space], dtype=np.float64)
-    assert len(acts) == (26 if unicycle else 81)
-    return acts
-
-
 def _table(B, K, n, unicycle=False, seed=11):
-    """[B, K, n, 2] float64: seeded random rows of the 81-action table (26 (v, r) actions for a unicycle)."""
-    acts = _space(unicycle)
-    return acts[np.random.RandomState(seed).randint(len(acts), size=(B, K, n))]
+    return action_table(B, K, n, unicycle=unicycle, seed=seed)
 
 
 def _step_loop(eng, seq, gamma=0.9):
@@ -82,17 +59,6 @@ def _assert_branch(look, k, want, what=''):
         if key in look:
             got = np.ascontiguousarray(look[key][:, k])
             assert got.dtype == ref.dtype and got.shape == ref.shape and got.tobytes() == ref.tobytes(), (what, key, k, got, ref)
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
-
-
-def _restore(eng, snap):
-    eng.set_state(snap[0], snap[1])
-    eng.set_theta(snap[2])
 
 
 def test_the_predicted_future_is_the_one_that_happens(amd):

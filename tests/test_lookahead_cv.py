@@ -16,9 +16,13 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT
 
 import lookahead_cv_reference as ref
+from lookahead_cv_reference import cfg_of as _cfg_of
+from support import (  # noqa: F401  (amd: module fixture)
+    action_table as _table, amd, configure_sarl, external_engine, np_of as _np, prior_plan as _plan, same_bits as _same_bits,
+    snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,45 +31,10 @@ DT, V_PREF, GAMMA = 0.25, 1.0, 0.9
 CV, ORCA = 'constant_velocity', 'orca'
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-
-
 def _engine(amd, B, H, model=CV, **cfg):
-    eng = amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=amd.ROBOT_EXTERNAL, **cfg)
+    eng = external_engine(amd, B, H, **cfg)
     eng.set_lookahead_human_model(model)
     return eng
-
-
-def _space(unicycle=False):
-    from crowdnav_amd.compat.sarl import build_action_space
-    space, _, _ = (build_action_space(1.0, 5, 5, 'unicycle') if unicycle else build_action_space(1.0))
-    return np.array([list(a) for a in space], dtype=np.float64)
-
-
-def _table(B, K, n, seed=11):
-    acts = _space()
-    assert len(acts) == 81
-    return acts[np.random.RandomState(seed).randint(len(acts), size=(B, K, n))]
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
 
 
 def _look(eng, table, **kw):
@@ -158,10 +127,6 @@ def _moving_engine(amd, case, B=3, model=CV, **more):
     gtime[B - 1] = eng.config['time_limit'] - 1.0 - 2.0
     eng.set_state(state, gtime)
     return eng, state, gtime
-
-
-def _cfg_of(eng):
-    return {k: float(eng.config[k]) for k in ref.CFG}
 
 
 _REFERENCE = {}
@@ -314,14 +279,9 @@ def test_n_zero_is_a_no_op_under_either_model(amd):
 
 # ------------------------------------------------------------------------------------------------ 4. what inherits
 def _sarl_engine(amd, B, H=5, **cfg):
-    import torch
-    from crowdnav_amd.compat.sarl import build_action_space
     eng = _engine(amd, B, H, robot_visible=1, **cfg)
     eng.reset(1000 + np.arange(B))
-    eng.sarl_configure(actions=np.array([list(a) for a in build_action_space(1.0)[0]], dtype=np.float64), with_om=False)
-    g = load_golden('sarl_plain.npz')
-    eng.sarl_set_weights({k[len('param_'):]: torch.from_numpy(v) for k, v in g.items() if k.startswith('param_')})
-    return eng
+    return configure_sarl(eng)
 
 
 def test_bootstrap_under_the_model(amd):
@@ -350,10 +310,6 @@ def test_bootstrap_under_the_model(amd):
             boot = math.pow(GAMMA, int(look['steps'][b, k]) * DT * V_PREF) * float(np.float64(look['value'][b, k]))
             score = look['ret'][b, k] if ended[b, k] else look['ret'][b, k] + boot
             assert _same_bits(look['score'][b, k], np.float64(score)), (b, k)
-
-
-def _plan(eng, K=5, n=4, E=2, I=1, **kw):
-    return eng.plan_reset(eng.plan_begin(K, n, E, I, 0.3, seed=(0x1234 << 32) | 0x9abcdef1, **kw))
 
 
 @pytest.mark.parametrize('update', ['cem', 'mppi'])

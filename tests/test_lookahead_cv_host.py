@@ -10,18 +10,12 @@ import pytest
 from conftest import ROOT
 
 import lookahead_cv_reference as ref
+from lookahead_cv_reference import human_row as _human, robot_row as _robot
+from support import built  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('enum { CN_HUMANS_ORCA = 0, CN_HUMANS_CONSTANT_VELOCITY = 1 };',
                 'int cn_lookahead_set_human_model(cn_engine* e, int model);',
                 'int cn_lookahead_get_human_model(const cn_engine* e, int* model_host);')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -67,14 +61,6 @@ def test_the_python_surface_exists(built):
 
 
 # ---------------------------------------------------------------------------------------- the restatement, single steps
-def _robot(px=0.0, py=0.0, gx=0.0, gy=4.0):
-    return [px, py, 0.0, 0.0, gx, gy, 0.3, 1.0]
-
-
-def _human(x, y, vx=0.0, vy=0.0):
-    return [x, y, vx, vy, -x, -y, 0.3, 1.0]
-
-
 def test_norm2_is_the_fused_form():
     assert ref.norm2(3.0, 4.0) == 5.0 and ref.norm2(0.0, 0.0) == 0.0
     # x * x is rounded, y * y is not: y * y = 1 + 2^-26 + 2^-54 exactly, x * x = 1.5625 * 2^-54; unfused, y * y loses its

@@ -20,6 +20,8 @@ from conftest import load_golden
 import lookahead_cv_reference as cv_ref
 import lookahead_modes_reference as modes_ref
 from lookahead_goal_reference import goal_term
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, assert_twins_equal as _assert_loops_equal, np_of as _np, same_bits as _same_bits, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,23 +32,6 @@ CV, ORCA = 'constant_velocity', 'orca'
 ROWS = ('info', 'steps', 'time', 'final_state8', 'final_theta')  # what the term leaves alone
 WEIGHTS = (0.1, 0.25)
 KINDS = {'holonomic': dict(), 'unicycle': dict(robot_kinematics=1), 'mixed': dict(scenario_rule=2)}
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
 
 
 # ------------------------------------------------------------------------------------------------ the scene
@@ -362,25 +347,6 @@ def _closed_loop_twins(amd, count):
         bufs = eng.rollout_begin(**BEGIN)
         made.append((eng, bufs, eng.plan_reset(eng.plan_begin(16, N, 4, 2, 0.3, seed=5, smoothing=0.25, min_std=0.01))))
     return made
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
-
-
-def _assert_loops_equal(x, xbufs, xplan, y, ybufs, yplan):
-    import torch
-    for a, b in zip(_snapshot(x), _snapshot(y)):
-        assert torch.equal(a, b)
-    for k, v in ybufs.items():
-        assert torch.equal(v, xbufs[k]), k
-    assert sorted(xplan.tensors()) == sorted(yplan.tensors())
-    for k, v in yplan.tensors().items():
-        assert torch.equal(v, xplan.tensors()[k]), k
-    assert torch.equal(x.rollout_records(), y.rollout_records())
-    assert x.launch_counts() == y.launch_counts()
 
 
 def _assert_real_steps_know_nothing_of_the_term(x, xbufs, z, zbufs, actions):

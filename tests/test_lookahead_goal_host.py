@@ -11,17 +11,10 @@ import pytest
 from conftest import ROOT
 
 import lookahead_goal_reference as goal
+from support import built  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('int cn_lookahead_set_goal_weight(cn_engine* e, double weight);',
                 'int cn_lookahead_get_goal_weight(const cn_engine* e, double* weight_host);')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):

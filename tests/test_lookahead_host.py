@@ -7,25 +7,11 @@ import os
 import pytest
 
 from conftest import ROOT
+from support import built, lookahead_out as _out, NOWHERE  # noqa: F401  (built: module fixture)
 
 DECLARATION = ('int cn_lookahead_actions(cn_engine* e, int n_steps, int n_candidates, const double* actions /* [B][K][n][2] */,\n'
                '                         const cn_lookahead_out* out);')
-NOWHERE = C.c_void_p(0x10)  # not NULL, not an address of anything
 REQUIRED = ('ret', 'info', 'steps', 'time')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
-
-
-def _out(lib, **missing):
-    rows = {k: 0x10 for k in REQUIRED + ('final_state8', 'final_theta')}
-    rows.update(missing)
-    return lib.CnLookaheadOut(**rows)
 
 
 def test_header_binding_and_library_agree_on_the_entry_point(built):

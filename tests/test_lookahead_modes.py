@@ -18,29 +18,14 @@ import pytest
 from conftest import ROOT
 
 import lookahead_modes_reference as ref
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, np_of as _np, same_bits as _same_bits, smoothed_plan as _plan, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
 ROWS = ('ret', 'info', 'steps', 'time')
 REDUCED = ('score', 'risk', 'worst_mode', 'worst_info', 'worst_steps', 'worst_time')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
 
 
 def _engine(amd, B, H, **cfg):
@@ -196,12 +181,6 @@ def test_prefixes_and_rows_behind_the_ends(amd):
 
 
 # ------------------------------------------------------------------------------------------------ (e) nothing moved
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
-
-
 def test_the_engine_is_untouched(amd):
     import torch
     B, K, n, M = 3, 5, 12, 3
@@ -277,10 +256,6 @@ def test_n_zero_is_a_no_op_and_live_refusals(amd):
 
 
 # ------------------------------------------------------------------------------------------------ (f) planners
-def _plan(eng, K=5, n=4, E=2, I=3, **kw):
-    return eng.plan_reset(eng.plan_begin(K, n, E, I, 0.3, seed=(0x1234 << 32) | 0x9abcdef1, smoothing=0.25, min_std=0.01, **kw))
-
-
 @pytest.mark.parametrize('reduce', ['mean', 'min'])
 @pytest.mark.parametrize('update', ['cem', 'mppi'])
 def test_a_planning_step_is_draw_lookahead_modes_update(amd, update, reduce):

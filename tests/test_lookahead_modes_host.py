@@ -13,6 +13,7 @@ import pytest
 from conftest import ROOT
 
 import lookahead_modes_reference as ref
+from support import built, DANGLING, filled  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('enum { CN_MODES_MEAN = 0, CN_MODES_MIN = 1 };',
                 '''int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double* actions /* [B][K][n][2] */,
@@ -21,15 +22,6 @@ DECLARATIONS = ('enum { CN_MODES_MEAN = 0, CN_MODES_MIN = 1 };',
                 '''int cn_plan_mppi_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes,
                        double temperature, int fit_std, uint32_t counter);''')
 NAMES = ('cn_lookahead_modes', 'cn_plan_cem_modes', 'cn_plan_mppi_modes')
-DANGLING = 0x1000  # an address nothing lives at: the refusals below must not read through it
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -68,9 +60,7 @@ def _modes(built, **fields):
 
 
 def _out(built, **fields):
-    base = {name: DANGLING for name, _ in built.CnModesOut._fields_}
-    base.update(fields)
-    return built.CnModesOut(**base)
+    return filled(built.CnModesOut, DANGLING, **fields)
 
 
 def test_lookahead_refusals_that_need_no_engine(built):

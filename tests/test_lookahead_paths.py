@@ -17,9 +17,13 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT
 
+from lookahead_cv_reference import cfg_of as _cfg_of
 import lookahead_paths_reference as ref
+from support import (  # noqa: F401  (amd: module fixture)
+    action_table as _table, amd, external_engine as _engine, np_of as _np, same_bits as _same_bits, sarl_engine as _sarl_engine,
+    smoothed_plan as _plan, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,44 +33,6 @@ CV, ORCA = 'constant_velocity', 'orca'
 KEYS = ('ret', 'info', 'steps', 'time', 'final_state8', 'final_theta')
 SHAPES = [(5, 1), (5, 4), (5, 33), (70, 1), (70, 4), (70, 33)]
 UNROUNDABLE = 0.3 + 2.0 ** -40  # a velocity float32 cannot hold
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-
-
-def _engine(amd, B, H, **cfg):
-    return amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=amd.ROBOT_EXTERNAL, **cfg)
-
-
-def _space(unicycle=False):
-    from crowdnav_amd.compat.sarl import build_action_space
-    space, _, _ = (build_action_space(1.0, 5, 5, 'unicycle') if unicycle else build_action_space(1.0))
-    return np.array([list(a) for a in space], dtype=np.float64)
-
-
-def _table(B, K, n, seed=11, unicycle=False):
-    acts = _space(unicycle)
-    return acts[np.random.RandomState(seed).randint(len(acts), size=(B, K, n))]
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
 
 
 def _paths(eng, table, vel, **kw):
@@ -80,10 +46,6 @@ def _look(eng, table, model, **kw):
     out = {k: _np(v) for k, v in eng.lookahead(table, **kw).items()}
     eng.set_lookahead_human_model(was)
     return out
-
-
-def _cfg_of(eng):
-    return {k: float(eng.config[k]) for k in ref.CFG}
 
 
 CASES = {'h1': dict(H=1, cfg=dict(discomfort_dist=0.5)), 'h5': dict(H=5, cfg=dict(discomfort_dist=0.5)), 'h12': dict(H=12, cfg=dict()),
@@ -432,21 +394,6 @@ def test_n_zero_is_a_no_op(amd):
 
 
 # ------------------------------------------------------------------------------------------------ (f) bootstrap
-def _sarl_engine(amd, B, H=5, with_om=False, **cfg):
-    import torch
-    from crowdnav_amd.compat.sarl import ValueNetwork
-    eng = _engine(amd, B, H, robot_visible=1, **cfg)
-    eng.reset(1000 + np.arange(B))
-    eng.sarl_configure(actions=_space(), with_om=with_om)
-    if with_om:
-        torch.manual_seed(7)
-        eng.sarl_set_weights(ValueNetwork(61, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4).state_dict())
-    else:
-        g = load_golden('sarl_plain.npz')
-        eng.sarl_set_weights({k[len('param_'):]: torch.from_numpy(v) for k, v in g.items() if k.startswith('param_')})
-    return eng
-
-
 def test_bootstrap(amd):
     from crowdnav_amd import predict
     B, K, n = 3, 70, 6
@@ -500,10 +447,6 @@ def test_bootstrap_refusals_are_those_of_lookahead_values(amd):
 
 
 # ------------------------------------------------------------------------------------------------ (g) planners
-def _plan(eng, K=5, n=4, E=2, I=3, **kw):
-    return eng.plan_reset(eng.plan_begin(K, n, E, I, 0.3, seed=(0x1234 << 32) | 0x9abcdef1, smoothing=0.25, min_std=0.01, **kw))
-
-
 @pytest.mark.parametrize('bootstrap', [False, True])
 @pytest.mark.parametrize('update', ['cem', 'mppi'])
 def test_a_planning_step_is_draw_lookahead_paths_update(amd, update, bootstrap):

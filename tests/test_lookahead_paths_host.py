@@ -14,6 +14,7 @@ from conftest import ROOT
 
 import lookahead_cv_reference as cv
 import lookahead_paths_reference as ref
+from support import built, DANGLING, filled  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('''int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candidates,
                        const double* actions   /* [B][K][n][2] */,
@@ -27,15 +28,6 @@ DECLARATIONS = ('''int cn_lookahead_paths(cn_engine* e, int n_steps, int n_candi
                 '''int cn_plan_mppi_paths(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan,
                        const double* human_vel, double temperature, int fit_std, uint32_t counter);''')
 NAMES = ('cn_lookahead_paths', 'cn_lookahead_paths_values', 'cn_plan_cem_paths', 'cn_plan_mppi_paths')
-DANGLING = 0x1000  # an address nothing lives at: the refusals below must not read through it
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -59,9 +51,7 @@ def test_header_binding_and_library_agree(built):
 
 
 def _out(built, **null):
-    fields = dict(ret=DANGLING, info=DANGLING, steps=DANGLING, time=DANGLING, final_state8=DANGLING, final_theta=DANGLING)
-    fields.update({k: None for k in null})
-    return built.CnLookaheadOut(**fields)
+    return filled(built.CnLookaheadOut, DANGLING, **dict.fromkeys(null))
 
 
 def test_lookahead_refusals_that_need_no_engine(built):

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import net_width_cases as cases
-from test_om_grid import _env
+from support import environ as _env
 
 pytestmark = pytest.mark.gpu
 FACTOR, FLOOR = 8.0, 2.0 ** -20

@@ -12,7 +12,6 @@ reports: sarl_export('next_obs') for decisions, get_state() for transforms.  A m
 Values: V against torch float64 on an input built on the HOST (X[..., :13] + the mirror's maps, not the exported map
 columns), E = max|V - V64| / max|V64| per case, E_kernel <= max(8 E_torch32, 2^-20) — test_train_step.py's FACTOR and FLOOR,
 for the reasons given there.  CROWDNAV_AMD_OM_GRID_REPORT=<file> appends the measured pairs and routes."""
-import contextlib
 import functools
 import os
 
@@ -21,22 +20,12 @@ import pytest
 import torch
 
 import om_grid_cases as cases
+from support import environ as _env
 
 pytestmark = pytest.mark.gpu
 FACTOR, FLOOR = 8.0, 2.0 ** -20
 IDS = [cases.setting_id(s) for s in cases.GRID]
 LSTM = dict(model='lstm_rl', mlp1_dims=(50, 1), mlp3_dims=(150, 100, 100, 1))
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
 
 
 def _report(line):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import TRAJ_FIXTURES, episodes_of, flat_steps, load_golden
+from oracle_golden_cases import SURVEY_KAT_CASE0
 
 
 @pytest.mark.parametrize('name', sorted(TRAJ_FIXTURES))
@@ -118,16 +119,6 @@ def test_unicycle_robot_steps_vs_reference(oracle_mod):
     assert np.abs(state - g['next_states']).max() <= 1e-12
     assert np.abs(o.get_theta() - g['next_theta']).max() <= 1e-12
     assert np.array_equal(state[:, 1:], g['next_states'][:, 1:])  # humans do not depend on the robot's kinematics
-
-
-SURVEY_KAT_CASE0 = [  # test case 0, ORCA robot, robot invisible — an INDEPENDENT float32 restatement
-    ((-0.051465511322021484, 0.45335352420806885),
-     '7424d63eb76eca3e 54b22d3f3cac3d3c 8e4c2cbf7e45a4bd cef9a9be10f4113f 100e253ff8dc75be'),
-    ((0.08838461339473724, 0.512067437171936),
-     '937cd13e6ac1e13e d51f243f9bd3923c ea9c24bf57a289bd b972adbe7e250a3f e88f313f5b7393be'),
-    ((0.07480747997760773, 0.5604285597801208),
-     'ff69c03e5c7df23e c2471a3fb26bff3c efb71dbfd3e653bd f3b4a1be45cd053f 8fbd533fe931aabe'),
-]
 
 
 def test_survey_known_answer_velocities(oracle_mod):

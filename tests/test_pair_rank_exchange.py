@@ -10,13 +10,12 @@ headline geometry runs generic / fused (one wave) / split / split_assist, the ot
 T = 4 steps: one step per call — after EVERY step the state, global_time and the running episode's accumulators (steps,
 return: the rewards so far; Danger steps and their dmin sum: the infos so far; no episode finished: the dones so far) are the
 oracle's — and one call.  Nothing but equality is accepted (the running return is a float64 sum held to the suite's 1e-9)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from jam_scenes import same_state as _same_state
 import rank_scenes as rs
+from support import amd, environ, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,48 +29,6 @@ ROUTES = {
 CUTS = {'per_step': [1] * T, 'one_call': [T]}
 RUNS = [(name, route, cut) for name in rs.CASES for route in (ROUTES if name in rs.HEADLINE_CASES else ('generic', 'fused'))
         for cut in CUTS]
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_state(eng, want, steps, where):
-    state, gtime = (_np(x) for x in eng.get_state())
-    ws, wg = want['states'][steps], want['global_time'][steps]
-    assert state.dtype == ws.dtype == np.float64
-    vel, wvel = state[:, :, 2:4].astype(np.float32), ws[:, :, 2:4].astype(np.float32)
-    assert np.array_equal(vel.view(np.uint32), wvel.view(np.uint32)), ('velocity bits', where, steps)
-    assert np.array_equal(state[:, :, 0:2], ws[:, :, 0:2]), ('position', where, steps)
-    assert np.array_equal(state, ws), ('state', where, steps)
-    assert np.array_equal(gtime, wg), ('global_time', where, steps)
 
 
 def _same_book(amd, eng, bufs, want, steps, where):

@@ -18,56 +18,20 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT
 
 import plan_mppi_reference as mref
 import plan_reference as ref
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, begin_plan as _plan, np_of as _np, put as _put, same_bits as _same_bits, sarl_engine as _sarl_engine,
+    seeded_engine as _engine, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
 V_PREF = 1.0  # the engines' default robot_v_pref
-SEED = (0x1234 << 32) | 0x9abcdef1
 SHAPES = [(5, 4), (70, 4), (5, 33), (70, 33)]
 OUTPUTS = ('order', 'best_actions', 'best_score', 'action', 'mean', 'std')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-
-
-def _engine(amd, B=3, H=5, **cfg):
-    eng = amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=amd.ROBOT_EXTERNAL, **cfg)
-    eng.reset(1000 + np.arange(B))
-    return eng
-
-
-def _put(t, a):
-    import torch
-    t.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(t.device))
-
-
-def _plan(eng, K=5, n=4, E=2, I=1, init_std=0.3, **kw):
-    return eng.plan_begin(K, n, E, I, init_std, seed=kw.pop('seed', SEED), **kw)
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
 
 
 def _inputs(B, K, n, seed):
@@ -242,20 +206,6 @@ def test_three_iterations_are_three_calls(amd):
 
 
 # ------------------------------------------------------------------------------------------------ 4. bootstrap
-def _sarl_engine(amd, B, H=5, weights=True, with_om=False, **cfg):
-    import torch
-    from crowdnav_amd.compat.sarl import ValueNetwork, build_action_space
-    eng = _engine(amd, B, H, robot_visible=1, **cfg)
-    eng.sarl_configure(actions=np.array([list(a) for a in build_action_space(1.0)[0]], dtype=np.float64), with_om=with_om)
-    if with_om:
-        torch.manual_seed(7)
-        eng.sarl_set_weights(ValueNetwork(61, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4).state_dict())
-    elif weights:
-        g = load_golden('sarl_plain.npz')
-        eng.sarl_set_weights({k[len('param_'):]: torch.from_numpy(v) for k, v in g.items() if k.startswith('param_')})
-    return eng
-
-
 def test_bootstrap_weighs_by_the_score_of_lookahead_values(amd):
     import torch
     B, K, n, T = 3, 70, 4, 0.05

@@ -12,8 +12,8 @@ from conftest import ROOT
 
 import plan_mppi_reference as mref
 import plan_reference as ref
+from support import built, host_cfg as _cfg, host_plan as _plan, NOWHERE  # noqa: F401  (built: module fixture)
 
-NOWHERE = C.c_void_p(0x10)  # not NULL, not an address of anything
 SYMBOLS = ('cn_plan_mppi_update', 'cn_plan_mppi', 'cn_plan_mppi_rollout')
 DECLARATIONS = (
     'int cn_plan_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, double temperature, int fit_std, '
@@ -24,14 +24,6 @@ DECLARATIONS = (
     'const cn_plan* plan,\n                         double temperature, int fit_std, uint32_t counter);')
 REQUIRED = ('mean', 'std', 'best_actions', 'best_score', 'action', 'candidates')
 LOOK_REQUIRED = ('ret', 'info', 'steps', 'time')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -68,21 +60,6 @@ def test_the_python_entry_points_exist(built):
     eng._rollout = (None, None)
     with pytest.raises(ValueError, match='plan_begin'):
         eng.plan_mppi_rollout(object(), 1, 1.0, 0, fit_std=True)
-
-
-def _cfg(lib, **over):
-    d = dict(n_steps=4, n_candidates=5, n_elites=2, iterations=1, bootstrap=0, sort_humans=0, init_std=0.5, min_std=0.0,
-             smoothing=0.0, seed=1)
-    d.update(over)
-    return lib.CnPlanCfg(**d)
-
-
-def _plan(lib, look_missing=(), **missing):
-    look = {k: 0x10 for k in LOOK_REQUIRED + ('final_state8', 'final_theta')}
-    look.update({k: None for k in look_missing})
-    rows = {k: 0x10 for k in REQUIRED + ('value', 'score', 'order')}
-    rows.update(missing)
-    return lib.CnPlan(look=lib.CnLookaheadOut(**look), **rows)
 
 
 def _calls(lib):

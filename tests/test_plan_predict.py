@@ -4,46 +4,20 @@ table feeds lookahead_paths to the bits of the constant-velocity lookahead; 4. t
 engine (host prediction, plan_*_paths / plan_*_modes, rollout_step, plan_shift), bit for bit on everything either leaves behind;
 5. n_real = 0 and chunked calls; 6. the refusals that need an engine; 7. the example prints the same line either way."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
 import plan_predict_cases as cases
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, assert_twins_equal as _assert_twins_equal, example_line as _example_line, np_of as _np, roll_on as _roll_on,
+    same_bits as _same_bits, sarl_engine, seeded_engine as _engine, smoothed_plan as _plan, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
 DT = cases.DT
-SEED = (0x1234 << 32) | 0x9abcdef1
 MODELS = {'cv': 'cv', 'to_goal': 'to_goal', 'two': ('cv', 'to_goal'), 'eight': ('cv', 'to_goal') * 4}
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-
-
-def _engine(amd, B=3, H=5, **cfg):
-    eng = amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=cfg.pop('robot_policy', amd.ROBOT_EXTERNAL), **cfg)
-    eng.reset(1000 + np.arange(B))
-    return eng
 
 
 def _advance(eng, steps=3):
@@ -57,12 +31,6 @@ def _host_table(state8, n, models):
     from crowdnav_amd import predict
     one = lambda name: predict.constant_velocity(state8, n) if name == 'cv' else predict.to_goal(state8, n, DT)  # noqa: E731
     return one(models) if isinstance(models, str) else predict.stack_modes(*(one(name) for name in models))
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel
@@ -112,15 +80,6 @@ def test_predict_gives_the_parked_placeholders_zeros(amd):
 
 
 # ------------------------------------------------------------------------------------------------ 2. a reader
-def _roll_on(eng, kind, steps):
-    import torch
-    for _ in range(steps):
-        if kind == 'orca_robot':
-            eng.rollout(1)
-        else:
-            eng.rollout_step(torch.tensor([[0.3, 0.2]] * eng.B, dtype=torch.float64, device=eng.device))
-
-
 @pytest.mark.parametrize('kind', ['external', 'orca_robot', 'unicycle'])
 def test_predict_moves_nothing_of_the_engine(amd, kind):
     import torch
@@ -172,18 +131,8 @@ def test_the_cv_table_feeds_lookahead_paths_to_the_bits_of_the_cv_lookahead(amd)
 
 
 # ------------------------------------------------------------------------------------------------ 4. the closed loop
-def _plan(eng, K=5, n=4, E=2, I=2, **kw):
-    return eng.plan_reset(eng.plan_begin(K, n, E, I, 0.3, seed=SEED, smoothing=0.25, min_std=0.01, **kw))
-
-
 def _sarl_engine(amd, B, H=5, **cfg):
-    import torch
-    from crowdnav_amd.compat.sarl import ValueNetwork, build_action_space
-    eng = _engine(amd, B, H, robot_visible=1, **cfg)
-    eng.sarl_configure(actions=np.array([list(a) for a in build_action_space(1.0)[0]], dtype=np.float64))
-    torch.manual_seed(7)
-    eng.sarl_set_weights(ValueNetwork(13, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4).state_dict())
-    return eng
+    return sarl_engine(amd, B, H, weights='seeded', **cfg)
 
 
 WEIGHTS = np.array([[0.75, 0.25], [0.5, 0.5], [0.125, 0.875]])
@@ -217,19 +166,6 @@ def _twins(amd, futures, time_limit, episode_limit, B=3):
         bufs = eng.rollout_begin(episode_limit=episode_limit, **BEGIN)
         made.append((eng, bufs, _plan(eng, bootstrap=boot)))
     return made
-
-
-def _assert_twins_equal(x, xbufs, xplan, y, ybufs, yplan):
-    import torch
-    for a, b in zip(_snapshot(x), _snapshot(y)):
-        assert torch.equal(a, b)
-    for k, v in ybufs.items():
-        assert torch.equal(v, xbufs[k]), k
-    assert sorted(xplan.tensors()) == sorted(yplan.tensors())
-    for k, v in yplan.tensors().items():
-        assert torch.equal(v, xplan.tensors()[k]), k
-    assert torch.equal(x.rollout_records(), y.rollout_records())
-    assert x.launch_counts() == y.launch_counts()
 
 
 @pytest.mark.parametrize('time_limit,episode_limit', [(1.0, 17), (2.0, 5)])
@@ -369,16 +305,6 @@ def test_refusals_on_an_engine(amd):
 EXAMPLE = {'to_goal': ['--predictor', 'to_goal'],
            'futures_min_mppi': ['--futures', 'cv,to_goal', '--reduce', 'min', '--risk-penalty', '0.5', '--mppi']}
 _host_lines = {}
-
-
-def _example_line(args):
-    cmd = [sys.executable, os.path.join(ROOT, 'examples', 'predicted_paths_planner.py'), '--cases', '4', '--candidates', '8', '--horizon', '4'] + args
-    done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    text = done.stdout.decode()
-    assert done.returncode == 0, text
-    lines = [line.split('INFO: ', 1)[1] for line in text.splitlines() if 'TEST  has success rate:' in line]
-    assert len(lines) == 1 and 'collision rate:' in lines[0] and 'total reward:' in lines[0], text
-    return lines[0]
 
 
 @pytest.mark.parametrize('chunk', [[], ['--chunk', '3']], ids=['chunk8', 'chunk3'])

@@ -12,6 +12,7 @@ import pytest
 from conftest import ROOT
 
 import plan_predict_cases as cases
+from support import built, DANGLING, models as _models, predictors as _predictors  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('enum { CN_PREDICT_CONSTANT_VELOCITY = 0, CN_PREDICT_TO_GOAL = 1 };',
                 '''int cn_predict(cn_engine* e, int n_steps, int n_modes,
@@ -23,15 +24,6 @@ DECLARATIONS = ('enum { CN_PREDICT_CONSTANT_VELOCITY = 0, CN_PREDICT_TO_GOAL = 1
                                  const cn_plan* plan, const cn_predictors* pred, double temperature, int fit_std,
                                  uint32_t counter);''')
 NAMES = ('cn_predict', 'cn_plan_cem_predict_rollout', 'cn_plan_mppi_predict_rollout')  # + struct cn_predictors, enum CN_PREDICT_*
-DANGLING = 0x1000  # an address nothing lives at: the refusals below must not read through it
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -64,10 +56,6 @@ def test_header_binding_and_library_agree(built):
     assert C.sizeof(built.CnLookaheadOut) == 48 and C.sizeof(built.CnModesOut) == 80
 
 
-def _models(*values):
-    return (C.c_int32 * len(values))(*values)
-
-
 def test_predict_refusals_that_need_no_engine(built):
     lib = built.load()
     INV, UNS = built.CN_ERR_INVALID, built.CN_ERR_UNSUPPORTED
@@ -94,15 +82,6 @@ def test_predict_refusals_that_need_no_engine(built):
     refused((None, 4, 2, good, DANGLING), 'cn_predict: engine is NULL')
     refused((None, 0, 2, good, DANGLING), 'cn_predict: engine is NULL')
     refused((None, 0, 8, _models(0, 1, 0, 1, 0, 1, 0, 1), DANGLING), 'cn_predict: engine is NULL')
-
-
-def _predictors(built, **fields):
-    base = dict(n_modes=2, model=_models(0, 1, 0, 0, 0, 0, 0, 0), reduce=built.MODES_MEAN, risk_penalty=0.5, human_vel=DANGLING,
-                weight=DANGLING)
-    base.update(fields)
-    if not isinstance(base['model'], C.c_int32 * 8):
-        base['model'] = (C.c_int32 * 8)(*(list(base['model']) + [0] * (8 - len(base['model']))))
-    return built.CnPredictors(**base)
 
 
 def test_rollout_refusals_that_need_no_engine(built):

@@ -10,48 +10,14 @@ import numpy as np
 import pytest
 
 import predict_orca_cases as cases
+from predict_orca_cases import BEGIN, FUTURES, KEYS, UPDATES, engine as _engine, replay_scene as _replay_scene
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, example_line as _example_line, np_of as _np, roll_on as _roll_on, same_bits as _same_bits, smoothed_plan as _plan,
+    snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 B, N = cases.B, cases.N
-BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
-SEED = (0x1234 << 32) | 0x9abcdef1
-KEYS = ('ret', 'info', 'steps', 'time', 'final_state8', 'final_theta')
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(_np(got) if hasattr(got, 'detach') else got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-
-
-def _engine(amd, crowd='h5', envs=B, steps=4, **cfg):
-    """A seeded reset and `steps` real steps with the action (0, 1): the humans are under way."""
-    cfg = dict(cases.CROWDS[crowd], **cfg)
-    eng = amd.BatchedCrowdSim(num_envs=envs, robot_policy=cfg.pop('robot_policy', amd.ROBOT_EXTERNAL), **cfg)
-    eng.reset(1000 + np.arange(envs))
-    straight_on = [1.0, 0.0] if cfg.get('robot_kinematics') else [0.0, 1.0]
-    for _ in range(steps):
-        eng.step(np.tile(straight_on, (envs, 1)) if eng.config['robot_policy'] == amd.ROBOT_EXTERNAL else None, update=True,
-                 want_obs=False)
-    return eng
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
 
 
 # ------------------------------------------------------------------------------------------------ 1. the environment is the oracle
@@ -89,24 +55,6 @@ def test_the_environment_is_the_oracle(amd, oracle_mod, crowd, seen_before):
 
 
 # ------------------------------------------------------------------------------------------------ 2. replay
-def _replay_scene(state, K=9, n=10):
-    """test_lookahead_paths.py (b)'s scene: the robot 1.0 ahead of human 1 on that human's way to its goal, its own goal 1.5 to
-    the side: straight to the goal is ReachGoal at the fifth step, standing still is run over (the humans do not see the
-    robot), walking ahead of human 1 — at its speed or a little slower — runs on."""
-    from crowdnav_amd.compat.sarl import build_action_space
-    acts = np.array([list(a) for a in build_action_space(1.0)[0]], dtype=np.float64)
-    placed = state.copy()
-    table = acts[np.random.RandomState(7).randint(len(acts), size=(len(state), K, n))]
-    for b in range(len(state)):
-        human = state[b, 1]
-        d = (human[4:6] - human[0:2]) / np.hypot(*(human[4:6] - human[0:2]))
-        side = np.array([-d[1], d[0]])
-        at = human[0:2] + d * 1.0
-        placed[b, 0, 0:2], placed[b, 0, 2:4], placed[b, 0, 4:6] = at, 0.0, at + side * 1.5
-        table[b, 0], table[b, 1], table[b, 2], table[b, 3] = side, 0.0, d, 0.9 * d
-    return placed, table
-
-
 @pytest.mark.parametrize('crowd', ['h1', 'h5', 'h12'])
 def test_replay_of_orca(amd, crowd):
     """lookahead_paths(actions, predict_orca(n)) equals lookahead(actions) under 'orca' on every output of all K = 9 branches:
@@ -161,15 +109,6 @@ def test_slots_prefixes_and_other_envs(amd, crowd):
 
 
 # ------------------------------------------------------------------------------------------------ 4. nothing moves
-def _roll_on(eng, kind, steps):
-    import torch
-    for _ in range(steps):
-        if kind == 'orca_robot':
-            eng.rollout(1)
-        else:
-            eng.rollout_step(torch.tensor([[0.3, 0.2]] * eng.B, dtype=torch.float64, device=eng.device))
-
-
 KINDS = {'external': ('h12', {}), 'orca_robot': ('h12', dict(robot_policy=1)), 'unicycle': ('h5', dict(robot_kinematics=1))}
 
 
@@ -219,14 +158,6 @@ def test_predict_orca_moves_nothing_of_the_engine(amd, kind):
 
 
 # ------------------------------------------------------------------------------------------------ 5. the closed loop
-FUTURES = {'one': dict(models='to_goal', orca_mode=0), 'two': dict(models=('to_goal', 'cv'), orca_mode=1, reduce='min')}
-UPDATES = {'cem': {}, 'mppi': dict(temperature=1.0, fit_std=False)}
-
-
-def _plan(eng, K=5, n=4, E=2, I=2, **kw):
-    return eng.plan_reset(eng.plan_begin(K, n, E, I, 0.3, seed=SEED, smoothing=0.25, min_std=0.01, **kw))
-
-
 def _loop_step(eng, plan, futures, update, counter, n):
     """One step of the loop the rollout replaces, every part by its own call."""
     many = not isinstance(futures['models'], str)
@@ -364,20 +295,6 @@ def test_refusals_on_an_engine(amd):
 
 
 # ------------------------------------------------------------------------------------------------ 6. the example
-def _example_line(args):
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    cmd = [sys.executable, os.path.join(ROOT, 'examples', 'predicted_paths_planner.py'), '--cases', '4', '--candidates', '8', '--horizon', '4'] + args
-    done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    text = done.stdout.decode()
-    assert done.returncode == 0, text
-    lines = [line.split('INFO: ', 1)[1] for line in text.splitlines() if 'TEST  has success rate:' in line]
-    assert len(lines) == 1 and 'collision rate:' in lines[0] and 'total reward:' in lines[0], text
-    return lines[0]
-
-
 def test_the_example_takes_the_orca_future_with_and_without_the_device_loop(amd):
     """--futures to_goal,orca: the per-step loop (predict_orca per real step) and the one-call loop (plan_predict_orca_rollout, in
     chunks of 3) print the same line."""

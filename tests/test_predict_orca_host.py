@@ -13,6 +13,7 @@ import pytest
 from conftest import ROOT
 
 import predict_orca_cases as cases
+from support import built, DANGLING, predictors as _predictors, Recorder as _Recorder  # noqa: F401  (built: module fixture)
 
 DECLARATIONS = ('''int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode,
                     double* human_vel /* DEVICE [B][n_modes][n_steps][A-1][2], 16-byte aligned */);''',
@@ -22,15 +23,6 @@ DECLARATIONS = ('''int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, i
                                       const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
                                       int fit_std, uint32_t counter);''')
 NAMES = ('cn_predict_orca', 'cn_plan_cem_predict_orca_rollout', 'cn_plan_mppi_predict_orca_rollout')
-DANGLING = 0x1000  # an address nothing lives at: the refusals below must not read through it
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree(built):
@@ -89,18 +81,6 @@ def test_predict_orca_refusals_in_order(built):
     refused((None, 0, 8, 7, DANGLING), 'cn_predict_orca: engine is NULL')
 
 
-def _models(*values):
-    return (C.c_int32 * 8)(*(list(values) + [0] * (8 - len(values))))
-
-
-def _predictors(built, **fields):
-    base = dict(n_modes=2, model=_models(0, 1), reduce=built.MODES_MEAN, risk_penalty=0.5, human_vel=DANGLING, weight=DANGLING)
-    base.update(fields)
-    if not isinstance(base['model'], C.c_int32 * 8):
-        base['model'] = _models(*base['model'])
-    return built.CnPredictors(**base)
-
-
 def test_rollout_refusals_in_order(built):
     """cn_plan_*_predict_rollout's refusals, in their order and with this call's name; orca_mode directly behind the models."""
     lib = built.load()
@@ -156,22 +136,6 @@ def test_rollout_refusals_in_order(built):
     assert mppi(C.byref(cfg), C.byref(plan), C.byref(_predictors(built, model=[0, 3])), T=0.0) == INV
     assert 'model[1] = 3 unknown' in lib.cn_last_error().decode()
     assert mppi(C.byref(cfg), C.byref(plan), C.byref(ok), mode=2, T=0.0) == INV and 'orca_mode = 2' in lib.cn_last_error().decode()
-
-
-class _Recorder(object):
-    """The library stubbed: every cn_* symbol records its call and returns CN_OK."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith('cn_'):
-            raise AttributeError(name)
-
-        def symbol(*args):
-            self.calls.append((name, args))
-            return 0
-        return symbol
 
 
 def test_the_python_surface_and_its_own_checks(built):

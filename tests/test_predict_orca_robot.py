@@ -13,19 +13,14 @@ import pytest
 
 import predict_orca_cases as base
 import predict_orca_robot_cases as cases
-from test_predict_orca import BEGIN, FUTURES, KEYS, UPDATES, _engine, _example_line, _np, _plan, _replay_scene, _same_bits, _snapshot
+from predict_orca_cases import BEGIN, FUTURES, KEYS, UPDATES, engine as _engine, replay_scene as _replay_scene
+from support import (  # noqa: F401  (amd: module fixture)
+    amd, example_line as _example_line, np_of as _np, roll_on as _roll_on, same_bits as _same_bits, smoothed_plan as _plan,
+    snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 B, N = cases.B, cases.N
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
 
 
 def _placed(eng):
@@ -156,15 +151,6 @@ def test_strides_slots_prefixes_and_other_envs(amd, crowd):
 # ------------------------------------------------------------------------------------------------ 4. any engine, and nothing moves
 KINDS = {'robot_unseen': ('h12', dict(robot_visible=0)), 'orca_robot': ('h12', dict(robot_policy=1, robot_visible=1)),
          'unicycle': ('h5', dict(robot_kinematics=1, robot_visible=0))}
-
-
-def _roll_on(eng, kind, steps):
-    import torch
-    for _ in range(steps):
-        if kind == 'orca_robot':
-            eng.rollout(1)
-        else:
-            eng.rollout_step(torch.tensor([[0.3, 0.2]] * eng.B, dtype=torch.float64, device=eng.device))
 
 
 @pytest.mark.parametrize('kind', sorted(KINDS))

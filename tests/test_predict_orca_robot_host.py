@@ -13,18 +13,9 @@ from conftest import ROOT
 
 import predict_orca_cases as base
 import predict_orca_robot_cases as cases
-from test_predict_orca_host import _Recorder, _predictors
+from support import built, DANGLING, predictors as _predictors, Recorder as _Recorder  # noqa: F401  (built: module fixture)
 
 NAMES = ('cn_predict_orca_robot', 'cn_plan_cem_predict_orca_nominal_rollout', 'cn_plan_mppi_predict_orca_nominal_rollout')
-DANGLING = 0x1000  # an address nothing lives at: the refusals below must not read through it
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def _flat(text):
@@ -264,7 +255,7 @@ def test_the_unicycle_scene_bites(oracle_mod):
 @pytest.mark.parametrize('crowd', ['h1', 'h5', 'h12'])
 def test_the_replay_scene_bites(oracle_mod, crowd):
     """_replay_scene's K = 9 branches on an oracle whose humans see the robot: a Collision, a ReachGoal and one that runs all n."""
-    from test_predict_orca import _replay_scene
+    from predict_orca_cases import replay_scene as _replay_scene
     state, gtime = cases.start(oracle_mod, crowd)
     placed, table = _replay_scene(state, 9, 10)
     info, steps = cases.oracle_branches(oracle_mod, crowd, placed, gtime, table)

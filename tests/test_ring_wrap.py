@@ -6,73 +6,17 @@ by one (`ring_claim` / `ring_ready` carry the episode ordinal).  With the defaul
 ~1 900 steps; CROWDNAV_AMD_RING_DEPTH = 3 (5 for the wave generators) makes it wrap every few dozen steps, and one run
 goes through the default ring at full depth.  Everything is compared with the oracle's rollout
 (oracle/crowd_oracle.cpp: co_rollout; episode c of env b seeded seed_base + (b + j B) % seed_mod, crowd_sim.py:272-283)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
+
+from ring_cases import oracle_rollout as _oracle, records_in_order as _records_in_order, ring_engine as _engine
+from support import amd, environ, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-@contextlib.contextmanager
 def ring_depth(depth):
-    """cn_create reads CROWDNAV_AMD_RING_DEPTH when the engine is built."""
-    old = os.environ.get('CROWDNAV_AMD_RING_DEPTH')
-    if depth is None:
-        os.environ.pop('CROWDNAV_AMD_RING_DEPTH', None)
-    else:
-        os.environ['CROWDNAV_AMD_RING_DEPTH'] = str(depth)
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop('CROWDNAV_AMD_RING_DEPTH', None)
-        else:
-            os.environ['CROWDNAV_AMD_RING_DEPTH'] = old
-
-
-def _oracle(oracle_mod, B, steps, K, **cfg):
-    o = oracle_mod.CrowdOracle(num_envs=B, robot_policy=1, **cfg)
-    o.reset(1000 + np.arange(B))
-    ep_index, cur_steps, cur_ret = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float64)
-    total, rec = o.rollout(steps, 1000, 500, K, ep_index, cur_steps, cur_ret)
-    return o, total, rec, cur_steps, cur_ret
-
-
-def _engine(amd, B, launches, K, depth, flags=0, **cfg):
-    with ring_depth(depth):
-        eng = amd.BatchedCrowdSim(num_envs=B, robot_policy=amd.ROBOT_ORCA, flags=flags, **cfg)
-    bufs = eng.rollout_begin(seed_base=1000, seed_mod=500, episode_limit=-1, record_capacity=K)
-    for n in launches:
-        eng.rollout(n)
-    eng.sync()
-    return eng, bufs
-
-
-def _records_in_order(bufs, rec, K):
-    """every episode the engine finished is the oracle's episode of the same ordinal: outcome, length, return"""
-    cnt = _np(bufs['ep_count'])
-    assert (cnt <= rec['count']).all() and cnt.max() <= K
-    out, steps, ret = _np(bufs['ep_outcome']), _np(bufs['ep_steps']), _np(bufs['ep_return'])
-    for b in range(len(cnt)):
-        k = cnt[b]
-        assert np.array_equal(out[b, :k], rec['outcome'][b, :k]), b
-        assert np.array_equal(steps[b, :k], rec['steps'][b, :k]), b
-        assert np.allclose(ret[b, :k], rec['ret'][b, :k], rtol=0, atol=1e-12), b
-    return cnt
+    return environ(CROWDNAV_AMD_RING_DEPTH=depth)
 
 
 def _mixed(total, lengths):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from rl_pipeline_cases import setup as _setup
 
 RL_FIXTURES = ['rl_sarl_plain.npz', 'rl_sarl_om.npz', 'rl_cadrl.npz', 'rl_lstm_rl.npz', 'rl_lstm_rl_om.npz',
                'rl_lstm_rl2.npz']
@@ -125,30 +126,6 @@ def test_rl_fixture_is_self_consistent_cpu():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _setup(g):
-    import crowdnav_amd.compat as c
-    from crowdnav_amd.compat.sarl import default_policy_config
-    with_om, visible = bool(int(g['with_om'])), bool(int(g['robot_visible']))
-    name = str(g['policy']) if 'policy' in g else 'sarl'
-    cfg = c.default_env_config({('robot', 'visible'): 'true' if visible else 'false'})
-    env = c.CrowdSim()
-    env.configure(cfg)
-    robot = c.Robot(cfg, 'robot')
-    policy = c.policy_factory[name]()
-    overrides = {(name, 'with_om'): 'true' if with_om else 'false'} if name != 'cadrl' else {}
-    if 'pairwise' in g and int(g['pairwise']):
-        overrides[('lstm_rl', 'with_interaction_module')] = 'true'
-    policy.configure(default_policy_config(overrides))
-    policy.get_model().load_state_dict({k[len('param_'):]: torch.from_numpy(v) for k, v in g.items()
-                                        if k.startswith('param_')})
-    robot.set_policy(policy)
-    env.set_robot(robot)
-    policy.set_device(torch.device('cpu'))
-    policy.set_env(env)
-    policy.set_epsilon(float(g['epsilon']))
-    return c, env, robot, policy
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('route', ['CROWDNAV_AMD_SARL_NARROW', 'CROWDNAV_AMD_SARL_FUSED_STEP', 'CROWDNAV_AMD_RL_PINNED'])
 def test_single_episode_sampling_with_pinned_histories_off_the_two_launch_route(route, monkeypatch):

@@ -8,35 +8,16 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from support import (  # noqa: F401  (amd: module fixture)
+    action_table, amd, external_engine as _engine, np_of as _np, same_tensors as _same)
 
 pytestmark = pytest.mark.gpu
 
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
 
 
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _engine(amd, B, H, **cfg):
-    return amd.BatchedCrowdSim(num_envs=B, num_humans=H, robot_policy=amd.ROBOT_EXTERNAL, **cfg)
-
-
 def _table(B, T, unicycle=False, seed=7):
-    """[B, T, 2] float64 drawn from the 81-action space of the value-network policies (26 (v, r) actions for a unicycle)."""
-    from crowdnav_amd.compat.sarl import build_action_space
-    space, _, _ = (build_action_space(1.0, 5, 5, 'unicycle') if unicycle else build_action_space(1.0))
-    acts = np.array([list(a) for a in space], dtype=np.float64)
-    assert len(acts) == (26 if unicycle else 81)
-    return acts[np.random.RandomState(seed).randint(len(acts), size=(B, T))]
+    return action_table(B, T, unicycle=unicycle, seed=seed)
 
 
 def _after(eng, bufs):
@@ -45,13 +26,6 @@ def _after(eng, bufs):
     out['state'], out['global_time'] = eng.get_state()
     out['theta'] = eng.get_theta()
     return out
-
-
-def _same(a, b):
-    import torch
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
 
 
 def _step_loop(eng, bufs, table, snapshots=None):
@@ -271,7 +245,7 @@ def test_reference_episodes_replayed(amd, name):
     Reward tolerance: 1e-6, what tests/test_rl_pipeline.py allows between these fixtures' memory_values — float32 TD targets
     whose terminal rows ARE these rewards — and the device's."""
     import torch
-    from test_rl_pipeline import _setup
+    from rl_pipeline_cases import setup as _setup
     g = load_golden(name)
     c, env, robot, policy = _setup(g)
     k, steps = int(g['k']), g['ep_steps'].astype(np.int64)

@@ -6,18 +6,10 @@ import os
 import pytest
 
 from conftest import ROOT
+from support import built, NOWHERE  # noqa: F401  (built: module fixture)
 
 DECLARATION = ('int cn_rollout_actions(cn_engine* e, const cn_rollout_io* io, int n_steps, const double* actions, '
                'const cn_trace_out* out);')
-NOWHERE = C.c_void_p(0x10)  # not NULL, not an address of anything
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
 
 
 def test_header_binding_and_library_agree_on_the_entry_point(built):

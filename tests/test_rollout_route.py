@@ -1,34 +1,10 @@
 """cn_rollout_route / BatchedCrowdSim.rollout_route: which transition kernel a cn_rollout call would launch, asked of the
 host without launching anything (`crowdnav_amd.hip`: rollout_route — the one place the route is chosen)."""
-import contextlib
-import os
-
 import pytest
 
+from support import amd, environ  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    os.environ.update({k: str(v) for k, v in values.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _engine(amd, B, H=5, **env):

@@ -6,22 +6,11 @@ import numpy as np
 import pytest
 
 from conftest import TRAJ_FIXTURES, episodes_of, load_golden
+from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
 FILL = dict(state8=-123.0, step=-5, reward=-123.0, info=77, dmin=-123.0)  # what rows the kernel must not write keep
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _engine(amd, B, H, **cfg):

@@ -7,14 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
+from support import built  # noqa: F401  (built: module fixture)
 
 
 def test_header_declares_and_library_exports_the_entry_point(built):

@@ -8,13 +8,10 @@ import pytest
 import torch
 
 from conftest import load_golden
+from sarl_attention_cases import check as _check
+from support import value_network as _net
 
 FIXTURES = ('plain', 'om', 'h12', 'mixed')
-
-
-def _net(d):
-    from crowdnav_amd.compat.sarl import ValueNetwork
-    return ValueNetwork(d, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
 
 
 def _fixture_net(g, name):
@@ -34,17 +31,6 @@ def _parked_states(states):
                 x = 1.0e6 + 100.0 * i
                 s[b, i] = [x, 1.0e6, 0.0, 0.0, x, 1.0e6, 0.3, 1.0]
     return s
-
-
-def _weights(net, x):
-    """every row's softmax weights exactly as ValueNetwork.forward computes them (it keeps only row 0's): x [n, h, d]"""
-    n, h, d = x.shape
-    with torch.no_grad():
-        hidden = net.mlp1(x.reshape(-1, d))
-        glob = hidden.view(n, h, -1).mean(1, keepdim=True).expand(n, h, net.global_state_dim)
-        scores = net.attention(torch.cat([hidden, glob.reshape(-1, net.global_state_dim)], dim=1)).view(n, h)
-        e = torch.exp(scores) * (scores != 0).float()
-        return (e / e.sum(dim=1, keepdim=True)).numpy()
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------
@@ -82,29 +68,6 @@ def _engine(humans, B, with_om, seed=3000, radius=None):
     eng.reset(seed + np.arange(B))
     eng.step(np.zeros((B, 2)), update=True)
     return eng
-
-
-def _check(eng, net, counts=None):
-    """attention vs the torch mirror on the exported X (1e-6), sums to 1 over the humans present, 0 for absent ones; values /
-    best / action bit-identical to cn_sarl_select on the same state"""
-    plain = eng.sarl_select()
-    plain = {k: plain[k].cpu().numpy() for k in ('values', 'best', 'action')}
-    out = eng.sarl_select(want_attention=True)
-    att = out['attention'].cpu().numpy()
-    X = eng.sarl_export('X').cpu()
-    for k in ('values', 'best', 'action'):
-        assert np.array_equal(out[k].cpu().numpy(), plain[k]), k
-    B, K, H, d = X.shape
-    assert att.shape == (B, K, H) and att.dtype == np.float32
-    if counts is None:
-        counts = np.full(B, H)
-    for b in range(B):
-        n = int(counts[b])
-        want = _weights(net, X[b, :, :n])
-        assert np.abs(att[b, :, :n] - want).max() <= 1e-6
-        assert np.abs(att[b, :, :n].astype(np.float64).sum(1) - 1.0).max() <= 1e-6
-        assert (att[b, :, n:] == 0).all()
-    return att
 
 
 ROUTES = {  # (CROWDNAV_AMD_SARL_REG, CROWDNAV_AMD_SARL_NARROW), the launch counter of the narrow route

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import load_golden, report_argmax
+from support import value_network as _net
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +32,6 @@ FIVE_HUMAN_FIXTURES = {
 @pytest.fixture(autouse=True)
 def _leave_the_narrow_tiles(monkeypatch):
     monkeypatch.setenv('CROWDNAV_AMD_SARL_NARROW', '0')
-
-
-def _net(d):
-    from crowdnav_amd.compat.sarl import ValueNetwork
-    return ValueNetwork(d, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
 
 
 def _actions():
@@ -160,7 +156,7 @@ def test_split_f16_vs_float64_with_larger_activations(humans, B, with_om):
 def test_split_f16_select_attention(humans, B, with_om):
     """values / best / action bit-identical to the plain split select; the weights within tests/test_sarl_attention.py's
     tolerance (1e-6) of the torch mirror on the exported X, summing to 1"""
-    from test_sarl_attention import _check
+    from sarl_attention_cases import check as _check
     torch.manual_seed(100 + humans)
     net = _net(61 if with_om else 13)
     eng = _engine(humans, B, seed=3000)

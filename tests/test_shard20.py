@@ -8,7 +8,8 @@ and the statistics a call leaves behind (cn_rollout_io.summary / .blocks) with t
 import numpy as np
 import pytest
 
-from test_ring_wrap import _engine, _np, _oracle, _records_in_order, amd  # noqa: F401  (amd: module fixture)
+from ring_cases import oracle_rollout as _oracle, records_in_order as _records_in_order, ring_engine as _engine
+from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -9,40 +9,12 @@ functions produce the numbers on both paths, so nothing but exact equality is ac
 under test ran at all: episode starts adopted, iterations redone.
 
 Solved velocities: `ring_vel0` of a slot against `cn_orca` of an engine set to the slot's scenario, bit for bit."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from support import amd, environ, same_tensors as _same  # noqa: F401  (amd: module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _engine(amd, split, B, ring_depth=None, lagged=None, assist=None):
@@ -72,13 +44,6 @@ def _run(amd, split, B, calls, ring_depth=None, lagged=None, assist=None, **begi
     out = dict(bufs)
     out['state'], out['global_time'], out['rollout_summary'] = state, gtime, eng.rollout_summary()
     return out, counts, eng.launch_counts()
-
-
-def _same(a, b):
-    import torch
-    assert a.keys() == b.keys()
-    for k in a:
-        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
 
 
 def _both(amd, B, calls, **kw):

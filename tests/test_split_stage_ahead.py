@@ -14,47 +14,15 @@ Every case runs the two-wave kernel against the one-wave kernel (CROWDNAV_AMD_FU
 cases without a pause or a retirement — the oracle models neither — also run against the oracle: global_time, episode counts,
 record rings (outcome, steps, time, Danger steps) and the running episode's counters exactly; returns (float64 sums) and the
 state — which after an auto-reset holds device-generated scenarios — to the suite's 1e-9."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
+
+from support import amd, environ, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
 DT = 0.25
 K = 16  # record ring slots
-
-
-@pytest.fixture(scope='module')
-def amd():
-    import torch
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    for k, v in values.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _cfg(time_limit):

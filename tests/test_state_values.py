@@ -10,28 +10,13 @@ import numpy as np
 import pytest
 import torch
 
+from support import (  # noqa: F401  (amd: module fixture)
+    action_space as _space, amd, np_of as _np, restore as _restore, same_bits as _same_bits, snapshot as _snapshot)
+
 pytestmark = pytest.mark.gpu
 
 DT, V_PREF, GAMMA = 0.25, 1.0, 0.9  # the engines' defaults (time_step, robot_v_pref) and sarl_configure's / cn_create's gamma
 ROUTE_ENV = {'default': {}, 'lds': {'CROWDNAV_AMD_SARL_NARROW': '0'}, 'reg': {'CROWDNAV_AMD_SARL_REG': '2'}}
-
-
-@pytest.fixture(scope='module')
-def amd():
-    assert torch.cuda.is_available(), 'gpu tests need a MI355X'
-    import crowdnav_amd
-    return crowdnav_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _space(unicycle=False):
-    from crowdnav_amd.compat.sarl import build_action_space
-    space, _, _ = (build_action_space(1.0, 5, 5, 'unicycle') if unicycle else build_action_space(1.0))
-    return np.array([list(a) for a in space], dtype=np.float64)
-
 
 _NETS = {}
 
@@ -86,11 +71,6 @@ def _bound_and_oracle(eng, model):
     for every model but CADRL, which runs the one-tile LDS kernel there."""
     narrow_rows = eng.sarl_network_route() == 'narrow' and model != 'cadrl'
     return (2e-6, True) if narrow_rows else (2e-5, False)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 CASES = ([('sarl', h, 0) for h in (1, 3, 5, 8)] + [('cadrl', h, 0) for h in (1, 5)] +
@@ -202,17 +182,6 @@ def test_one_step_is_the_decision(amd, H):
     assert _same_bits(look['score'][~ended], values[~ended])
     assert _same_bits(look['score'][ended], look['ret'][ended])
     eng.close()
-
-
-def _snapshot(eng):
-    eng.sync()
-    state, gtime = eng.get_state()
-    return state.clone(), gtime.clone(), eng.get_theta().clone()
-
-
-def _restore(eng, snap):
-    eng.set_state(snap[0], snap[1])
-    eng.set_theta(snap[2])
 
 
 def _step_loop(eng, seq):

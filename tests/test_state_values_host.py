@@ -8,28 +8,14 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import built, lookahead_out as _out, NOWHERE  # noqa: F401  (built: module fixture)
 
 STATE_VALUES = ('int cn_sarl_state_values(cn_engine* e, const double* state8, const double* theta, int64_t n, int sort_humans, '
                 'float* value);')
 LOOKAHEAD_VALUES = ('int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const double* actions, '
                     'const cn_lookahead_out* out,\n'
                     '                        int sort_humans, float* value, double* score);')
-NOWHERE = C.c_void_p(0x10)  # not NULL, not an address of anything
 REQUIRED = ('ret', 'info', 'steps', 'time')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
-
-
-def _out(lib, **missing):
-    rows = {k: 0x10 for k in REQUIRED + ('final_state8', 'final_theta')}
-    rows.update(missing)
-    return lib.CnLookaheadOut(**rows)
 
 
 def test_header_bindings_and_library_agree_on_the_entry_points(built):

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import sgd_step_reference as ref
+from sgd_step_reference import pool
 
 pytestmark = pytest.mark.gpu
 FACTOR, FLOOR = 8.0, 2.0 ** -20
@@ -61,11 +62,6 @@ class Kernel(object):
 def errors(buf, buf64, grad64):
     G = max(np.abs(g).max() for g in grad64.values())
     return {k: np.abs(buf[k].astype(np.float64) - buf64[k]).max() / max(np.abs(buf64[k]).max(), 1e-6 * G) for k in ref.NAMES}, G
-
-
-def pool(into, new):
-    for k, v in new.items():
-        into[k] = max(into.get(k, 0.0), float(v))
 
 
 def check_pooled(E_torch, E_kernel, H, where):

@@ -2,6 +2,7 @@
 the ABI surface, argument validation before the device is touched, the arithmetic the kernels are written from against
 torch autograd in float64, and that the switch changes nothing where the kernel path does not apply."""
 import ctypes as C
+import functools
 import os
 import re
 
@@ -11,16 +12,10 @@ import torch
 
 import sgd_step_reference as ref
 from conftest import ROOT
+from support import built  # noqa: F401  (built: module fixture)
 
 NEW_CALLS = ('cn_trainer_create', 'cn_trainer_destroy', 'cn_trainer_set_stream', 'cn_train_step', 'cn_trainer_steps')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
+_cpu_trainer = functools.partial(ref.cpu_trainer, ref)
 
 
 def test_header_binding_and_library_agree_on_the_trainer_calls(built):
@@ -128,18 +123,6 @@ def test_float64_emulation_equals_autograd_at_other_input_widths(D, built):
     rc, msg, h = _create(built, input_dim=D)
     assert rc == built.CN_OK, msg
     assert built.load().cn_trainer_destroy(h) == built.CN_OK
-
-
-def _cpu_trainer(monkeypatch, switch, P, S, V):
-    from crowdnav_amd.compat.trainer import ReplayMemory, Trainer
-    monkeypatch.setenv('CROWDNAV_AMD_SGD_KERNEL', switch)
-    torch.manual_seed(11)
-    memory = ReplayMemory(1000)
-    for s, v in zip(S, V):
-        memory.push((torch.from_numpy(s), torch.from_numpy(v.reshape(1))))
-    trainer = Trainer(ref.network(P, torch.float32), memory, torch.device('cpu'), 100)
-    trainer.set_learning_rate(0.01)
-    return trainer, [trainer.optimize_batch(3), trainer.optimize_epoch(1)]
 
 
 def test_switch_on_without_a_gpu_model_is_todays_path_bit_for_bit(monkeypatch):

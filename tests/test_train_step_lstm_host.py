@@ -3,6 +3,7 @@ can see it: what the library accepts and refuses before a device is touched, the
 torch autograd (float64: equal; float32 in the kernel's summation order: within the rule the GPU test applies), and that the
 switch changes nothing where the kernel path does not apply."""
 import ctypes as C
+import functools
 import re
 
 import numpy as np
@@ -10,14 +11,10 @@ import pytest
 import torch
 
 import lstm_step_reference as ref
+import sgd_step_reference
+from support import built  # noqa: F401  (built: module fixture)
 
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as ge
-    ge.build()
-    from crowdnav_amd import _lib
-    return _lib
+_cpu_trainer = functools.partial(sgd_step_reference.cpu_trainer, ref)
 
 
 def _create(built, num_humans=5, max_batch=100, input_dim=13, **kw):
@@ -124,18 +121,6 @@ def test_float32_emulation_in_the_kernels_order_meets_the_gpu_rule(fixture, H):
     assert not bad, bad
     assert absolute < ref.FLOOR
     assert L_m <= max(ref.FACTOR * L_t, ref.FLOOR), (L_t, L_m)
-
-
-def _cpu_trainer(monkeypatch, switch, P, S, V):
-    from crowdnav_amd.compat.trainer import ReplayMemory, Trainer
-    monkeypatch.setenv('CROWDNAV_AMD_SGD_KERNEL', switch)
-    torch.manual_seed(11)
-    memory = ReplayMemory(1000)
-    for s, v in zip(S, V):
-        memory.push((torch.from_numpy(s), torch.from_numpy(v.reshape(1))))
-    trainer = Trainer(ref.network(P, torch.float32), memory, torch.device('cpu'), 100)
-    trainer.set_learning_rate(0.01)
-    return trainer, [trainer.optimize_batch(3), trainer.optimize_epoch(1)]
 
 
 def test_switch_on_without_a_gpu_model_is_todays_path_bit_for_bit(monkeypatch):

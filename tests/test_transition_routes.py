@@ -7,14 +7,12 @@ lookahead_paths and lookahead_modes (2 equal tables), all with n = 1, must give 
 lookahead_cv_reference.transition bit for bit, and step and rollout_actions its dmin.  Scenes: the corners of
 test_lookahead_cv_host.py — head-on collision, graze inside discomfort_dist, zero relative motion, timeout ahead of a
 collision, the three orderings of near / hit / nearer — one env per scene, engines of 1 to 3 humans, holonomic external robot."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import lookahead_cv_reference as ref
-from test_lookahead_cv_host import _human, _robot
+from lookahead_cv_reference import human_row as _human, robot_row as _robot
+from support import environ, np_of as _np, same_bits as _same_bits
 
 NEAR, HIT, NEARER = (0.0, -0.65), (0.5, 0.0), (0.0, -0.61)
 # name: (human rows, global_time, action, the info worked out by hand)
@@ -52,31 +50,7 @@ def test_the_reference_gives_the_infos_worked_out_by_hand():
     assert b[1][4]['reward'][0] == -0.25 and b[1][4]['reward'][3] == 0.0
 
 
-@contextlib.contextmanager
-def environ(**values):
-    """cn_create reads the engine's switches when the engine is built."""
-    old = {k: os.environ.get(k) for k in values}
-    os.environ.update({k: str(v) for k, v in values.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
 
 
 @pytest.mark.gpu
