@@ -256,6 +256,9 @@ SYMBOLS = {
     'cn_plan_mppi_predict_orca_nominal_rollout': (C.c_int, [_P, C.POINTER(CnRolloutIo), C.c_int, C.POINTER(CnPlanCfg),
                                                             C.POINTER(CnPlan), C.POINTER(CnPredictors), C.c_int, C.c_double, C.c_int,
                                                             C.c_uint32]),
+    # the planners on a unicycle engine: the rotation bound and the rotation deviation, which opt the engine in (no version bump)
+    'cn_plan_set_unicycle': (C.c_int, [_P, C.c_double, C.c_double]),
+    'cn_plan_get_unicycle': (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

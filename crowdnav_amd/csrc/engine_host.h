@@ -104,6 +104,8 @@ struct cn_engine {
     int look_human_model = CN_HUMANS_ORCA;  // cn_lookahead_set_human_model: read by cn_lookahead_actions and by nothing else
     double look_goal_weight = 0.0;  // cn_lookahead_set_goal_weight: != 0 launches the goal forms of the four lookahead kernels
     double look_goal_dev = 0.0;     // the weight last uploaded behind look_dev (the slab is zeroed: 0.0 until one is)
+    double plan_max_rotation = 0.0;  // cn_plan_set_unicycle: R > 0 opts a CN_UNICYCLE engine into the cn_plan_* calls, rows (v, r)
+    double plan_std_rotation = 0.0;  // ... and the initial deviation of r (cfg->init_std stays v's)
     ScenarioRing ring;
     bool io_valid = false;
     bool rollout_begun = false;          // cn_rollout_begin has run: the seed numbering below is fixed until the next one

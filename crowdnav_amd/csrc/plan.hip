@@ -10,6 +10,8 @@
 // third predictor beside cn_predict's two, and the *_predict_orca_rollout calls that write it over one slot of cn_predict's table.
 // cn_predict_orca_robot is the same launch with the robot in the humans' sight on a table of actions; the *_nominal_rollout calls
 // give it the plan's clipped mean, candidate 0 of the planning step's first draw.
+// A CN_UNICYCLE engine is served once cn_plan_set_unicycle has named its rotation bound: rows (v, r), the *_uni_kernel forms of
+// the reset, draw, MPPI update and shift; the refit is component-wise and the same kernel.
 #include "engine_host.h"
 #include "plan_kernels.h"
 #include "predict_orca_kernel.h"
@@ -21,6 +23,10 @@ struct Mppi {
     double temperature;
     int fit_std;
 };
+
+// The engine plans over (v, r): a CN_UNICYCLE engine whose caller has made cn_plan_set_unicycle (which refuses every other engine).
+// The one place that decides between the holonomic kernels and the *_uni_kernel forms.
+inline bool plan_unicycle(const cn_engine* e) { return e->plan_max_rotation > 0.0; }
 
 // Refusals 1-5 of the header, in its order; nothing is enqueued (cn_lookahead_values with n_steps == 0 checks and returns).
 // The cn_plan_mppi_* calls add theirs between the cfg ranges and the engine.
@@ -72,9 +78,11 @@ int plan_check(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const 
         return fail(CN_ERR_INVALID, "%s: temperature must be > 0 and finite (got %g)", who, mppi->temperature);
     if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
     if (e->P.robot_orca) return fail(CN_ERR_INVALID, "%s is for CN_ROBOT_EXTERNAL engines (an ORCA robot takes no actions)", who);
-    if (e->P.robot_unicycle)
+    // (the gate: pinned behaviour until the caller names the rotation bound — a choice of theirs, not a fact of the environment)
+    if (e->P.robot_unicycle && !plan_unicycle(e))
         return fail(CN_ERR_UNSUPPORTED, "%s: CN_UNICYCLE engines are not served: the plan is a Gaussian over (vx, vy) clipped to "
-                    "the speed disc; one over (v, r) needs its own clip rule", who);
+                    "the speed disc; one over (v, r) needs its own clip rule.  cn_plan_set_unicycle names it (the rotation bound and "
+                    "the rotation deviation) and opts this engine in", who);
     if (cfg->bootstrap)
         return cn_lookahead_values(e, 0, cfg->n_candidates, plan->candidates, &plan->look, cfg->sort_humans, plan->value, plan->score);
     return cn_lookahead_check(e, cfg->n_steps, cfg->n_candidates, plan->candidates, &plan->look);
@@ -104,9 +112,15 @@ inline unsigned plan_grid(size_t lanes) { return (unsigned)((lanes + cn::kPlanBl
 
 int run_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const uint8_t* mask) {
     const cn::Params& P = e->P;
-    hipLaunchKernelGGL(cn::plan_reset_kernel, dim3(plan_grid((size_t)P.B * cfg->n_steps)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
-                       cfg->n_steps, P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal, (const double2*)e->S.rv,
-                       mask, (double2*)plan->mean, (double2*)plan->std);
+    if (plan_unicycle(e))  // lane = env: the prior is a recurrence in t
+        hipLaunchKernelGGL(cn::plan_reset_uni_kernel, dim3(plan_grid((size_t)P.B)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
+                           cfg->n_steps, P.dt, cfg->init_std, e->plan_std_rotation, e->plan_max_rotation, (const double2*)e->S.pos,
+                           (const double2*)e->S.goal, (const double2*)e->S.rv, (const double*)e->S.theta, mask, (double2*)plan->mean,
+                           (double2*)plan->std);
+    else
+        hipLaunchKernelGGL(cn::plan_reset_kernel, dim3(plan_grid((size_t)P.B * cfg->n_steps)), dim3(cn::kPlanBlock), 0, e->stream, P.B,
+                           P.A, cfg->n_steps, P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal,
+                           (const double2*)e->S.rv, mask, (double2*)plan->mean, (double2*)plan->std);
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -114,9 +128,15 @@ int run_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const u
 int run_draw(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t counter) {
     const cn::Params& P = e->P;
     const size_t rows = (size_t)P.B * cfg->n_candidates * cfg->n_steps;  // (below 2^59 and B K within an int: cn_lookahead_check)
-    hipLaunchKernelGGL(cn::plan_draw_kernel, dim3(plan_grid(rows)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A, cfg->n_candidates,
-                       cfg->n_steps, (uint32_t)(cfg->seed & 0xffffffffu), (uint32_t)(cfg->seed >> 32), counter, (const double2*)e->S.rv,
-                       (const double2*)plan->mean, (const double2*)plan->std, (double2*)plan->candidates);
+    const uint32_t seed_lo = (uint32_t)(cfg->seed & 0xffffffffu), seed_hi = (uint32_t)(cfg->seed >> 32);
+    if (plan_unicycle(e))
+        hipLaunchKernelGGL(cn::plan_draw_uni_kernel, dim3(plan_grid(rows)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
+                           cfg->n_candidates, cfg->n_steps, seed_lo, seed_hi, counter, e->plan_max_rotation, (const double2*)e->S.rv,
+                           (const double2*)plan->mean, (const double2*)plan->std, (double2*)plan->candidates);
+    else
+        hipLaunchKernelGGL(cn::plan_draw_kernel, dim3(plan_grid(rows)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A, cfg->n_candidates,
+                           cfg->n_steps, seed_lo, seed_hi, counter, (const double2*)e->S.rv, (const double2*)plan->mean,
+                           (const double2*)plan->std, (double2*)plan->candidates);
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -131,11 +151,17 @@ int run_refit(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, int kee
 }
 
 int run_mppi_update(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const Mppi& mppi, int keep_best) {
-    hipLaunchKernelGGL(cn::plan_mppi_kernel, dim3(e->P.B), dim3(64), 0, e->stream, e->P.A, cfg->n_candidates, cfg->n_steps,
-                       mppi.fit_std ? 1 : 0, keep_best ? 1 : 0, mppi.temperature, cfg->smoothing, cfg->min_std,
-                       (const double*)(cfg->bootstrap ? plan->score : plan->look.ret), (const double2*)plan->candidates,
-                       (const double2*)e->S.rv, plan->mean, plan->std, (double2*)plan->best_actions, plan->best_score,
-                       (double2*)plan->action, plan->order);
+    const double* score = cfg->bootstrap ? plan->score : plan->look.ret;
+    if (plan_unicycle(e))
+        hipLaunchKernelGGL(cn::plan_mppi_uni_kernel, dim3(e->P.B), dim3(64), 0, e->stream, e->P.A, cfg->n_candidates, cfg->n_steps,
+                           mppi.fit_std ? 1 : 0, keep_best ? 1 : 0, mppi.temperature, cfg->smoothing, cfg->min_std,
+                           e->plan_max_rotation, score, (const double2*)plan->candidates, (const double2*)e->S.rv, plan->mean,
+                           plan->std, (double2*)plan->best_actions, plan->best_score, (double2*)plan->action, plan->order);
+    else
+        hipLaunchKernelGGL(cn::plan_mppi_kernel, dim3(e->P.B), dim3(64), 0, e->stream, e->P.A, cfg->n_candidates, cfg->n_steps,
+                           mppi.fit_std ? 1 : 0, keep_best ? 1 : 0, mppi.temperature, cfg->smoothing, cfg->min_std, score,
+                           (const double2*)plan->candidates, (const double2*)e->S.rv, plan->mean, plan->std,
+                           (double2*)plan->best_actions, plan->best_score, (double2*)plan->action, plan->order);
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -169,9 +195,15 @@ int run_plan(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, uint32_t
 
 int run_shift(cn_engine* e, const cn_rollout_io* io, const cn_plan_cfg* cfg, const cn_plan* plan) {
     const cn::Params& P = e->P;
-    hipLaunchKernelGGL(cn::plan_shift_kernel, dim3(plan_grid((size_t)2 * P.B)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A, cfg->n_steps,
-                       P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal, (const double2*)e->S.rv,
-                       (const uint8_t*)io->active, (const int32_t*)io->cur_steps, plan->mean, plan->std);
+    if (plan_unicycle(e))
+        hipLaunchKernelGGL(cn::plan_shift_uni_kernel, dim3(plan_grid((size_t)2 * P.B)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
+                           cfg->n_steps, P.dt, cfg->init_std, e->plan_std_rotation, e->plan_max_rotation, (const double2*)e->S.pos,
+                           (const double2*)e->S.goal, (const double2*)e->S.rv, (const double*)e->S.theta, (const uint8_t*)io->active,
+                           (const int32_t*)io->cur_steps, plan->mean, plan->std);
+    else
+        hipLaunchKernelGGL(cn::plan_shift_kernel, dim3(plan_grid((size_t)2 * P.B)), dim3(cn::kPlanBlock), 0, e->stream, P.B, P.A,
+                           cfg->n_steps, P.dt, cfg->init_std, (const double2*)e->S.pos, (const double2*)e->S.goal,
+                           (const double2*)e->S.rv, (const uint8_t*)io->active, (const int32_t*)io->cur_steps, plan->mean, plan->std);
     CN_HIP(hipGetLastError());
     return CN_OK;
 }
@@ -311,6 +343,26 @@ int predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* human
 }  // namespace
 
 extern "C" {
+
+int cn_plan_set_unicycle(cn_engine* e, double max_rotation, double init_std_rotation) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_plan_set_unicycle: engine is NULL");
+    if (!std::isfinite(max_rotation) || !(max_rotation > 0.0) || max_rotation > 3.141592653589793)
+        return fail(CN_ERR_INVALID, "cn_plan_set_unicycle: max_rotation must be in (0, pi] (got %g)", max_rotation);
+    if (!std::isfinite(init_std_rotation) || !(init_std_rotation > 0.0))
+        return fail(CN_ERR_INVALID, "cn_plan_set_unicycle: init_std_rotation must be > 0 and finite (got %g)", init_std_rotation);
+    if (!e->P.robot_unicycle || e->P.robot_orca)
+        return fail(CN_ERR_INVALID, "cn_plan_set_unicycle is for CN_UNICYCLE engines with a CN_ROBOT_EXTERNAL robot: no other engine's "
+                    "planner would read the setting");
+    e->plan_max_rotation = max_rotation, e->plan_std_rotation = init_std_rotation;
+    return CN_OK;
+}
+
+int cn_plan_get_unicycle(cn_engine* e, double* max_rotation, double* init_std_rotation) {
+    if (!e) return fail(CN_ERR_INVALID, "cn_plan_get_unicycle: engine is NULL");
+    if (!max_rotation || !init_std_rotation) return fail(CN_ERR_INVALID, "cn_plan_get_unicycle: an output is NULL");
+    *max_rotation = e->plan_max_rotation, *init_std_rotation = e->plan_std_rotation;
+    return CN_OK;
+}
 
 int cn_plan_reset(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const uint8_t* mask) {
     int rc = plan_check(e, cfg, plan, "cn_plan_reset");

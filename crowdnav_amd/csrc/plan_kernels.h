@@ -1,7 +1,9 @@
 // Device side of the shooting planners (cn_plan_*, plan.hip): the kernels between "score K action sequences per env"
 // (cn_lookahead_actions / cn_lookahead_values) and "a robot that plans" — draw the candidates, rank them and update the sampling
 // distribution (CEM: refit to the elites; MPPI: softmax-weighted mean), shift the plan behind a real step, seed it with the
-// goal-directed prior.  Holonomic external robots only.
+// goal-directed prior.  External robots: holonomic ones, rows (vx, vy) clipped to the speed disc; and, once cn_plan_set_unicycle
+// has named the rotation bound, unicycle ones, rows (v, r) clipped to the box [0, v_pref] x [-R, R] — kernels of their own
+// (the *_uni_kernel forms below), so that no float64 atan2 / cos / sin of the unicycle prior enters a holonomic kernel.
 //
 // The arithmetic is the header's (include/crowdnav_amd.h, "Device CEM planner" and "Device MPPI update"), one IEEE operation per
 // product and sum in the order written there (the library is built with -ffp-contract=off), so that tests/plan_reference.py and
@@ -13,6 +15,10 @@
 //   plan_mppi_kernel   workgroup = env, one wave  the same ranks and best row; weights exp((s - s_max) / T) in LDS; weighted mean / std
 //   plan_shift_kernel  lane = (env, component)    walks t upwards in place: row t <- row t + 1, or the prior at an episode start
 //   predict_kernel     lane = (env, mode, human)  the table of predicted human velocities the *_paths / *_modes planners score against
+// Unicycle forms: plan_draw_uni_kernel and plan_mppi_uni_kernel are the lane bodies above under UNI = true (the clip alone
+// differs); plan_reset_uni_kernel is lane = env, because the (v, r) prior is a recurrence in t (position and heading), walked as
+// predict_kernel walks to_goal; plan_shift_uni_kernel keeps lane = (env, component) for the shifted envs and hands a re-seeded
+// env's recurrence to its component-0 lane.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -49,6 +55,56 @@ __device__ inline double2 plan_prior(const double2* pos, const double2* goal, co
     return make_double2((dx / dist) * speed, (dy / dist) * speed);
 }
 
+// The (v, r) clip of a unicycle row: the box [0, v_pref] x [-R, R] (no reverse gear)
+__device__ inline double2 plan_clip_uni(double2 a, double v_pref, double R) {
+    a.x = a.x < 0.0 ? 0.0 : (a.x > v_pref ? v_pref : a.x);
+    a.y = a.y < -R ? -R : (a.y > R ? R : a.y);
+    return a;
+}
+
+// The clip of either robot.  Holonomic: onto the speed disc.
+template <bool UNI>
+__device__ __forceinline__ double2 plan_clip(double2 a, double v_pref, double R) {
+    if (UNI) return plan_clip_uni(a, v_pref, R);
+    const double nrm = sqrt(a.x * a.x + a.y * a.y);
+    if (nrm > v_pref) {
+        const double s = v_pref / nrm;
+        a.x *= s, a.y *= s;
+    }
+    return a;
+}
+
+// The goal-directed prior of a unicycle, a recurrence in t: turn towards the goal by at most R, then drive at full speed (or
+// what reaches the goal in one step) along the new heading — robot_step's end point, in its operation order.  The turn is
+// the bearing's difference to the heading wrapped into [-pi, pi) by explicit operations.
+struct PlanUniState {
+    double px, py, th;
+};
+__device__ inline double2 plan_prior_uni_step(PlanUniState& s, double gx, double gy, double v_pref, double dt, double R) {
+    const double dx = gx - s.px, dy = gy - s.py;
+    const double dist = sqrt(dx * dx + dy * dy);
+    const double reach = dist / dt;
+    const double speed = v_pref < reach ? v_pref : reach;
+    if (!(dist > 0.0)) return make_double2(0.0, 0.0);
+    const double bearing = atan2(dy, dx);
+    const double d = bearing - s.th;
+    const double turn = d - 6.283185307179586 * floor((d + 3.141592653589793) / 6.283185307179586);
+    const double r = turn < -R ? -R : (turn > R ? R : turn);
+    s.th = s.th + r;
+    s.px = s.px + cos(s.th) * speed * dt;
+    s.py = s.py + sin(s.th) * speed * dt;
+    return make_double2(speed, r);
+}
+// ... all n rows of env b into mean[b]
+__device__ inline void plan_prior_uni(const double2* pos, const double2* goal, const double2* rv, const double* theta, size_t b, int A,
+                                      int n, double dt, double R, double2* mean) {
+    const size_t r = b * A;
+    const double2 p = pos[r], g = goal[r];
+    const double v_pref = rv[r].y;
+    PlanUniState s{p.x, p.y, theta[b]};
+    for (int t = 0; t < n; ++t) mean[b * n + t] = plan_prior_uni_step(s, g.x, g.y, v_pref, dt, R);
+}
+
 __global__ __launch_bounds__(kPlanBlock) void plan_reset_kernel(int B, int A, int n, double dt, double init_std, const double2* pos,
                                                                 const double2* goal, const double2* rv, const uint8_t* mask,
                                                                 double2* mean, double2* std) {
@@ -60,11 +116,24 @@ __global__ __launch_bounds__(kPlanBlock) void plan_reset_kernel(int B, int A, in
     std[i] = make_double2(init_std, init_std);
 }
 
+// The unicycle prior: lane = env, t sequential.  A lane stores n consecutive 16-byte rows of mean and of std.
+__global__ __launch_bounds__(kPlanBlock) void plan_reset_uni_kernel(int B, int A, int n, double dt, double init_std, double std_rotation,
+                                                                    double max_rotation, const double2* pos, const double2* goal,
+                                                                    const double2* rv, const double* theta, const uint8_t* mask,
+                                                                    double2* mean, double2* std) {
+    const size_t b = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
+    if (b >= (size_t)B) return;
+    if (mask && !mask[b]) return;
+    plan_prior_uni(pos, goal, rv, theta, b, A, n, dt, max_rotation, mean);
+    for (int t = 0; t < n; ++t) std[b * n + t] = make_double2(init_std, std_rotation);
+}
+
 // Streaming: consecutive lanes write consecutive 16-byte rows (t fastest).  The counter words are (t, k, b, counter), so a row
 // does not depend on B, K or n.
-__global__ __launch_bounds__(kPlanBlock) void plan_draw_kernel(int B, int A, int K, int n, uint32_t seed_lo, uint32_t seed_hi,
-                                                               uint32_t counter, const double2* rv, const double2* mean,
-                                                               const double2* std, double2* candidates) {
+template <bool UNI>
+__device__ __forceinline__ void plan_draw_lane(int B, int A, int K, int n, uint32_t seed_lo, uint32_t seed_hi, uint32_t counter,
+                                               double max_rotation, const double2* rv, const double2* mean, const double2* std,
+                                               double2* candidates) {
     const size_t i = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
     if (i >= (size_t)B * K * n) return;
     const uint32_t t = (uint32_t)(i % n), k = (uint32_t)((i / n) % K), b = (uint32_t)(i / ((size_t)n * K));
@@ -79,12 +148,18 @@ __global__ __launch_bounds__(kPlanBlock) void plan_draw_kernel(int B, int A, int
         a.x = a.x + sd.x * (r * cos(ang));
         a.y = a.y + sd.y * (r * sin(ang));
     }
-    const double nrm = sqrt(a.x * a.x + a.y * a.y), v_pref = rv[(size_t)b * A].y;
-    if (nrm > v_pref) {
-        const double s = v_pref / nrm;
-        a.x *= s, a.y *= s;
-    }
-    candidates[i] = a;
+    candidates[i] = plan_clip<UNI>(a, rv[(size_t)b * A].y, max_rotation);
+}
+__global__ __launch_bounds__(kPlanBlock) void plan_draw_kernel(int B, int A, int K, int n, uint32_t seed_lo, uint32_t seed_hi,
+                                                               uint32_t counter, const double2* rv, const double2* mean,
+                                                               const double2* std, double2* candidates) {
+    plan_draw_lane<false>(B, A, K, n, seed_lo, seed_hi, counter, 0.0, rv, mean, std, candidates);
+}
+// ... rows (v, r), clipped to the box
+__global__ __launch_bounds__(kPlanBlock) void plan_draw_uni_kernel(int B, int A, int K, int n, uint32_t seed_lo, uint32_t seed_hi,
+                                                                   uint32_t counter, double max_rotation, const double2* rv,
+                                                                   const double2* mean, const double2* std, double2* candidates) {
+    plan_draw_lane<true>(B, A, K, n, seed_lo, seed_hi, counter, max_rotation, rv, mean, std, candidates);
 }
 
 // rank(k) = #{j : s_j > s_k, or s_j == s_k and j < k} over the env's scores in LDS: a permutation of 0..K-1 for finite scores
@@ -155,64 +230,18 @@ __global__ __launch_bounds__(64) void plan_mppi_kernel(int A, int K, int n, int 
                                                        double smoothing, double min_std, const double* score,
                                                        const double2* candidates, const double2* rv, double* mean, double* std,
                                                        double2* best_actions, double* best_score, double2* action, int32_t* order) {
-    __shared__ double sc[kPlanMaxCandidates];
-    __shared__ double wt[kPlanMaxCandidates];
-    __shared__ double first[2];
-    __shared__ int top_k;
-    const int lane = threadIdx.x;
-    const size_t b = blockIdx.x;
-    const double held = best_score[b];  // (read by every lane before lane 0 may replace it below)
-    for (int k = lane; k < K; k += 64) sc[k] = score[b * K + k];
-    if (lane == 0) top_k = 0;  // (NaN scores rank nothing sensibly; the index read below still addresses the env's own candidates)
-    __syncthreads();
-    for (int k = lane; k < K; k += 64) {
-        const int rank = plan_rank(sc, K, k);
-        if (order) order[b * K + rank] = k;
-        if (rank == 0) top_k = k;
-    }
-    __syncthreads();
-    const int top = top_k;
-    const double s_top = sc[top];
-    if (!keep_best || s_top > held) {  // strict: the earliest holder of a score keeps it
-        const double2* src = candidates + (b * K + top) * n;
-        for (int t = lane; t < n; t += 64) best_actions[b * n + t] = src[t];
-        if (lane == 0) best_score[b] = s_top;
-    }
-    for (int k = lane; k < K; k += 64) wt[k] = exp((sc[k] - s_top) / temperature);
-    __syncthreads();
-    double Z = 0.0;
-    for (int k = 0; k < K; ++k) Z = Z + wt[k];
-    const double* cand = reinterpret_cast<const double*>(candidates) + b * K * n * 2;
-    const double keep = 1.0 - smoothing;
-    for (int c = lane; c < 2 * n; c += 64) {  // component (t, xy) of the plan: sums over all candidates in index order
-        double num = 0.0;
-        for (int k = 0; k < K; ++k) num = num + wt[k] * cand[(size_t)k * n * 2 + c];
-        const double m = num / Z;
-        const size_t at = b * n * 2 + c;
-        const double updated = smoothing * mean[at] + keep * m;
-        mean[at] = updated;
-        if (c < 2) first[c] = updated;
-        if (fit_std) {
-            double dev2 = 0.0;
-            for (int k = 0; k < K; ++k) {
-                const double d = cand[(size_t)k * n * 2 + c] - m;
-                dev2 = dev2 + wt[k] * (d * d);
-            }
-            const double sd = sqrt(dev2 / Z);
-            const double blended = smoothing * std[at] + keep * sd;
-            std[at] = blended < min_std ? min_std : blended;
-        }
-    }
-    __syncthreads();
-    if (lane == 0) {
-        double2 a = make_double2(first[0], first[1]);
-        const double nrm = sqrt(a.x * a.x + a.y * a.y), v_pref = rv[b * A].y;
-        if (nrm > v_pref) {
-            const double s = v_pref / nrm;
-            a.x *= s, a.y *= s;
-        }
-        action[b] = a;
-    }
+    constexpr bool UNI = false;
+    const double max_rotation = 0.0;
+#include "plan_mppi_body.inc"
+}
+// ... the first row (v, r), clipped to the box
+__global__ __launch_bounds__(64) void plan_mppi_uni_kernel(int A, int K, int n, int fit_std, int keep_best, double temperature,
+                                                           double smoothing, double min_std, double max_rotation, const double* score,
+                                                           const double2* candidates, const double2* rv, double* mean, double* std,
+                                                           double2* best_actions, double* best_score, double2* action,
+                                                           int32_t* order) {
+    constexpr bool UNI = true;
+#include "plan_mppi_body.inc"
 }
 
 // After a real step.  In place, so one lane owns component c of env b and walks t upwards (row t + 1 is read before it is
@@ -236,6 +265,29 @@ __global__ __launch_bounds__(kPlanBlock) void plan_shift_kernel(int B, int A, in
         for (int t = 0; t + 1 < n; ++t) m[2 * t] = m[2 * (t + 1)];
     }
     for (int t = 0; t < n; ++t) s[2 * t] = init_std;
+}
+
+// The unicycle form: the same lanes; the shifted envs walk t per component as above.  A re-seeded env's prior is a recurrence
+// over both components, so its component-0 lane writes the whole 16-byte rows of the mean and its component-1 lane only its
+// deviations (init_std for v, std_rotation for r).
+__global__ __launch_bounds__(kPlanBlock) void plan_shift_uni_kernel(int B, int A, int n, double dt, double init_std, double std_rotation,
+                                                                    double max_rotation, const double2* pos, const double2* goal,
+                                                                    const double2* rv, const double* theta, const uint8_t* active,
+                                                                    const int32_t* cur_steps, double* mean, double* std) {
+    const int i = blockIdx.x * kPlanBlock + threadIdx.x;
+    if (i >= 2 * B) return;
+    const size_t b = (size_t)(i >> 1);
+    const int c = i & 1;
+    if (!active[b]) return;
+    double* m = mean + b * n * 2 + c;
+    double* s = std + b * n * 2 + c;
+    if (cur_steps[b] == 0) {
+        if (c == 0) plan_prior_uni(pos, goal, rv, theta, b, A, n, dt, max_rotation, reinterpret_cast<double2*>(mean));
+    } else {
+        for (int t = 0; t + 1 < n; ++t) m[2 * t] = m[2 * (t + 1)];
+    }
+    const double sd = c ? std_rotation : init_std;
+    for (int t = 0; t < n; ++t) s[2 * t] = sd;
 }
 
 // The shipped predictors (cn_predict; crowdnav_amd/predict.py restates them on a host copy of the state bit for bit):

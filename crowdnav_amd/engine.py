@@ -516,15 +516,37 @@ class BatchedCrowdSim(object):
             mean, std, best_actions float64 [B, n, 2]; best_score float64 [B]; action float64 [B, 2]
             candidates float64 [B, K, n, 2]; order int32 [B, K] (candidate index at rank r)
             look: the dict lookahead() returns, rows of the last iteration (with bootstrap: final state, value, score too)
-        mean starts at zero and std at init_std: call plan_reset() for the goal-directed prior.  Holonomic ROBOT_EXTERNAL
-        engines; the settings are checked by the first call that uses the plan.  The planner's candidates are scored under the
+        mean starts at zero and std at init_std: call plan_reset() for the goal-directed prior.  ROBOT_EXTERNAL engines: a
+        holonomic robot, action rows (vx, vy); a unicycle robot once set_plan_unicycle() has been called, and then every row —
+        mean, std, candidates, best_actions, action — is (v, r).  The settings are checked by the first call that uses the plan.  The planner's candidates are scored under the
         engine's lookahead_human_model (set_lookahead_human_model), as it stands when each plan_* call is made.  With
         set_lookahead_goal_weight(w != 0), the ret and score the planner ranks include w * (progress towards the goal)."""
         K, n = int(K), int(n)
         if K < 1 or n < 1:
             raise ValueError('plan_begin: K and n must be >= 1')
-        return Plan(self, K, n, int(elites), int(iterations), float(init_std), float(min_std), float(smoothing), int(seed),
+        plan = Plan(self, K, n, int(elites), int(iterations), float(init_std), float(min_std), float(smoothing), int(seed),
                     bool(bootstrap), bool(sort_humans))
+        std_rotation = getattr(self, '_plan_std_rotation', 0.0)  # (kept by set_plan_unicycle: no library call here)
+        if std_rotation > 0.0:  # the engine plans over (v, r): std starts at (init_std, init_std_rotation), as plan_reset leaves it
+            plan.std[..., 1] = std_rotation
+        return plan
+
+    def set_plan_unicycle(self, max_rotation, init_std_rotation):
+        """Opt a unicycle ROBOT_EXTERNAL engine into the plan_* calls (cn_plan_set_unicycle): action rows are then (v, r),
+        clipped to v in [0, v_pref] and r in [-max_rotation, max_rotation] in place of the speed disc; plan_reset's prior turns
+        towards the goal by at most max_rotation per step from get_theta()'s heading and drives at full speed; std starts at
+        (the plan's init_std, init_std_rotation).  max_rotation in (0, pi] (the reference's action space: pi / 4),
+        init_std_rotation > 0, radians.  Until it is called every plan_* call refuses a unicycle engine; it cannot be unset, and
+        stays set across reset().  Any other engine: CN_ERR_INVALID."""
+        check(self._lib.cn_plan_set_unicycle(self._h, float(max_rotation), float(init_std_rotation)))
+        self._plan_std_rotation = float(init_std_rotation)
+
+    @property
+    def plan_unicycle(self):
+        """(max_rotation, init_std_rotation) as set_plan_unicycle set them; (0.0, 0.0) until it has (cn_plan_get_unicycle)."""
+        r, s = C.c_double(), C.c_double()
+        check(self._lib.cn_plan_get_unicycle(self._h, C.byref(r), C.byref(s)))
+        return r.value, s.value
 
     def _plan_call(self, name, plan, *args, rollout=False, n_real=None, counter=None):
         """check(cn_plan_<name>(engine, [io, [n_real,]] cfg, plan, *args[, counter])), the one way to the planner's entry points.
@@ -540,7 +562,9 @@ class BatchedCrowdSim(object):
 
     def plan_reset(self, plan, mask=None):
         """The goal-directed prior (cn_plan_reset): mean = full speed — or what reaches the goal in one step — from the robot
-        towards its goal at every t, std = init_std; for the envs of `mask` ([B] bool / uint8, None = all)."""
+        towards its goal at every t, std = init_std; for the envs of `mask` ([B] bool / uint8, None = all).  With
+        set_plan_unicycle: rows (v, r) that turn towards the goal by at most max_rotation a step, then drive straight; std =
+        (init_std, init_std_rotation)."""
         m, temporary = self._borrow(mask, torch.uint8, (self.B,))
         self._plan_call('reset', plan, _ptr(m))
         self._release(temporary)
@@ -548,7 +572,8 @@ class BatchedCrowdSim(object):
 
     def plan_draw(self, plan, counter):
         """plan.candidates <- K sequences per env from N(mean, std), clipped to the robot's speed; candidate 0 is the mean
-        (cn_plan_draw).  Philox4x32-10 keyed by the plan's seed, counter words (t, k, b, counter)."""
+        (cn_plan_draw).  Philox4x32-10 keyed by the plan's seed, counter words (t, k, b, counter).  With set_plan_unicycle: rows
+        (v, r), clipped to [0, v_pref] x [-max_rotation, max_rotation]."""
         self._plan_call('draw', plan, counter=counter)
         return plan.candidates
 
@@ -566,7 +591,8 @@ class BatchedCrowdSim(object):
 
     def plan_shift(self, plan):
         """After rollout_step(plan.action) (cn_plan_shift): the plan of a running env moves up by one step (std back to
-        init_std), an env whose episode has just ended gets the prior of its new scenario, a retired env is left alone."""
+        init_std), an env whose episode has just ended gets the prior of its new scenario, a retired env is left alone.  With
+        set_plan_unicycle: rows (v, r), std back to (init_std, init_std_rotation)."""
         self._plan_call('shift', plan, rollout=True)
         return plan
 
@@ -579,8 +605,8 @@ class BatchedCrowdSim(object):
     def plan_mppi_update(self, plan, temperature, fit_std=False, keep_best=False):
         """The MPPI update in place of plan_refit (cn_plan_mppi_update): the same ranks, order and best_*; every candidate
         weighted by exp((score - best score) / temperature); mean <- the weighted mean (through smoothing), std <- the weighted
-        deviation only with fit_std; plan.action <- the updated mean's first row, clipped to the robot's speed.  The plan's
-        `elites` is not read."""
+        deviation only with fit_std; plan.action <- the updated mean's first row, clipped to the robot's speed (with
+        set_plan_unicycle: a (v, r) row clipped to its box).  The plan's `elites` is not read."""
         self._plan_call('mppi_update', plan, float(temperature), int(bool(fit_std)), int(bool(keep_best)))
         return plan
 

@@ -25,9 +25,13 @@ with --device-loop the one call is plan_predict_orca_rollout, which writes that 
 real step plan_draw, then BatchedCrowdSim.predict_orca_robot on candidate 0, the clipped mean; with
 --device-loop the one call is plan_predict_orca_nominal_rollout.
 --goal-weight W (every mode above, --device-loop included) adds W * (metres of progress towards the goal over
-the sequence) to every candidate's return under every future (set_lookahead_goal_weight); 0 (the default) is the run without it."""
+the sequence) to every candidate's return under every future (set_lookahead_goal_weight); 0 (the default) is the run without it.
+--kinematics unicycle [--max-rotation R] [--rotation-std S] (every mode above): a unicycle robot, the plan a
+Gaussian over (v, r) with r clipped to [-R, R] (set_plan_unicycle; R defaults to pi / 4, the reference's action-space bound)
+and r's deviation starting at S radians."""
 import argparse
 import logging
+import math
 import os
 import sys
 
@@ -40,17 +44,18 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
          predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8, orca_sees_plan=False,
-         goal_weight=0.0):
+         goal_weight=0.0, kinematics='holonomic', max_rotation=math.pi / 4, rotation_std=0.5):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
     robot = cn.Robot(env_cfg, 'robot')
     env.set_robot(robot)
-    if robot.kinematics is None:  # ([robot] policy = none: the planner's actions are (vx, vy))
-        robot.kinematics = 'holonomic'
+    robot.kinematics = kinematics  # ([robot] policy = none: the planner says what its action rows are, (vx, vy) or (v, r))
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
     eng.set_lookahead_goal_weight(goal_weight)
+    if kinematics == 'unicycle':  # rows (v, r): the rotation bound and r's deviation opt the engine in
+        eng.set_plan_unicycle(max_rotation, rotation_std)
     bufs = eng.rollout_begin(seed_base=env.case_capacity['val'], seed_mod=env.case_size['test'], episode_limit=cases,
                              record_capacity=1)
     planner = eng.plan_reset(eng.plan_begin(candidates, horizon, elites, iterations, init_std * robot.v_pref, seed=seed))
@@ -102,7 +107,7 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
         'TEST', len(success) / cases, len(collision) / cases, average(success) if success else env.time_limit, average(returns)))
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cases', type=int, default=8, help='test cases 0 .. cases - 1, one env each')
     ap.add_argument('--candidates', type=int, default=16, help='K: sequences scored per env and iteration')
@@ -124,6 +129,16 @@ def main():
                     help="--futures ...,orca: that future's humans see the robot on the plan's nominal sequence")
     ap.add_argument('--goal-weight', type=float, default=0.0,
                     help="W: every candidate's return gains W per metre of progress towards the goal (0: the discounted return alone)")
+    ap.add_argument('--kinematics', default='holonomic', choices=['holonomic', 'unicycle'],
+                    help='the robot: action rows (vx, vy), or (v, r) for a unicycle')
+    ap.add_argument('--max-rotation', type=float, default=math.pi / 4, help='--kinematics unicycle: R, r is clipped to [-R, R] radians per step')
+    ap.add_argument('--rotation-std', type=float, default=0.5,
+                    help="--kinematics unicycle: standard deviation r's steps start from, in radians")
+    return ap
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     names = {'cv': 'constant_velocity', 'constant_velocity': 'constant_velocity', 'to_goal': 'to_goal', 'orca': 'orca'}
     futures = None
@@ -144,7 +159,8 @@ def main():
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
                       predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty,
                       device_loop=args.device_loop, chunk=args.chunk, orca_sees_plan=args.orca_sees_plan,
-                      goal_weight=args.goal_weight))
+                      goal_weight=args.goal_weight, kinematics=args.kinematics, max_rotation=args.max_rotation,
+                      rotation_std=args.rotation_std))
     return 0
 
 

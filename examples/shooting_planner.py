@@ -27,9 +27,14 @@ real steps stay the simulator's.
 
 --goal-weight W (every mode) adds W * (metres of progress towards the goal over the sequence) to every
 candidate's score (set_lookahead_goal_weight): the terminal term without which collision-free candidates that do not arrive
-inside the horizon all tie at 0.0.  0 (the default) is the run without it."""
+inside the horizon all tie at 0.0.  0 (the default) is the run without it.
+
+--kinematics unicycle [--max-rotation R] [--rotation-std S] (every mode) drives a unicycle robot: action rows
+are (v, r).  The random-shooting mode draws from the unicycle action table; --cem / --mppi plan over (v, r) with r clipped to
+[-R, R] (set_plan_unicycle; R defaults to pi / 4, the reference's action-space bound) and r's deviation starting at S radians."""
 import argparse
 import logging
+import math
 import os
 import sys
 
@@ -68,19 +73,22 @@ def load_policy(model_dir, name):
 CEM_CHUNK = 16  # real steps per plan_rollout call: how often the host looks whether every case has ended
 
 
-def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, human_model='orca', goal_weight=0.0):
+def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, human_model='orca', goal_weight=0.0,
+         kinematics='holonomic', max_rotation=math.pi / 4, rotation_std=0.5):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
     robot = cn.Robot(env_cfg, 'robot')
     env.set_robot(robot)
-    if robot.kinematics is None:  # ([robot] policy = none: the planner's actions are (vx, vy))
-        robot.kinematics = 'holonomic'
+    robot.kinematics = kinematics  # ([robot] policy = none: the planner says what its action rows are, (vx, vy) or (v, r))
     eng = crowdnav_amd.BatchedCrowdSim(**env.engine_config(cases, env.human_num, env.test_sim, crowdnav_amd.ROBOT_EXTERNAL))
     eng.set_gamma(gamma)
     eng.set_lookahead_human_model(human_model)
     eng.set_lookahead_goal_weight(goal_weight)
-    space, _, _ = build_action_space(robot.v_pref)
+    unicycle = kinematics == 'unicycle'
+    if unicycle:  # the planners' rows are (v, r): the rotation bound and r's deviation opt the engine in
+        eng.set_plan_unicycle(max_rotation, rotation_std)
+    space, _, _ = build_action_space(robot.v_pref, 5, 5, 'unicycle') if unicycle else build_action_space(robot.v_pref)
     rank_by, extra = 'ret', {}
     if policy is not None:  # rank by the bootstrapped n-step return instead
         if policy.kinematics != robot.kinematics:
@@ -127,7 +135,7 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, policy=None, cem=None, h
         'TEST', len(success) / cases, len(collision) / cases, average(success) if success else env.time_limit, average(returns)))
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cases', type=int, default=8, help='test cases 0 .. cases - 1, one env each')
     ap.add_argument('--candidates', type=int, default=16, help='K: sequences scored per env and step')
@@ -146,14 +154,25 @@ def main():
                     help="how the humans move in the planner's lookahead (the real steps are always ORCA)")
     ap.add_argument('--goal-weight', type=float, default=0.0,
                     help="W: every candidate's score gains W per metre of progress towards the goal (0: the discounted return alone)")
-    args = ap.parse_args()
+    ap.add_argument('--kinematics', default='holonomic', choices=['holonomic', 'unicycle'],
+                    help='the robot: action rows (vx, vy), or (v, r) for a unicycle')
+    ap.add_argument('--max-rotation', type=float, default=math.pi / 4,
+                    help='--kinematics unicycle with --cem / --mppi: R, r is clipped to [-R, R] radians per step')
+    ap.add_argument('--rotation-std', type=float, default=0.5,
+                    help="--kinematics unicycle with --cem / --mppi: standard deviation r's steps start from, in radians")
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     policy = load_policy(args.model_dir, args.policy) if args.model_dir else None
     cem = None
     if args.cem or args.mppi:
         cem = dict(elites=min(args.elites, args.candidates), iterations=args.iterations, init_std=args.init_std,
                    temperature=args.temperature if args.mppi else None)
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, policy=policy, cem=cem, human_model=args.human_model,
-                      goal_weight=args.goal_weight))
+                      goal_weight=args.goal_weight, kinematics=args.kinematics, max_rotation=args.max_rotation,
+                      rotation_std=args.rotation_std))
     return 0
 
 

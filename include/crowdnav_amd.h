@@ -807,7 +807,7 @@ int cn_lookahead_modes(cn_engine* e, int n_steps, int n_candidates, const double
  * look.steps and look.time the worst mode's rows; the draw, refit, MPPI update and cn_plan_shift are untouched and rank
  * look.ret.  human_vel is [B][M][cfg->n_steps][A - 1][2].  Refused: NULL modes first; then every refusal of the cn_plan_* calls;
  * then cfg->bootstrap != 0: CN_ERR_UNSUPPORTED naming bootstrap; then cn_lookahead_modes' refusals.  No *_rollout form, for the
- * reason given above; a CN_UNICYCLE engine stays refused as by every cn_plan_* call (cn_lookahead_modes itself serves it). */
+ * reason given above; a CN_UNICYCLE engine without cn_plan_set_unicycle stays refused as by every cn_plan_* call. */
 int cn_plan_cem_modes (cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes, uint32_t counter);
 int cn_plan_mppi_modes(cn_engine* e, const cn_plan_cfg* cfg, const cn_plan* plan, const cn_path_modes* modes,
                        double temperature, int fit_std, uint32_t counter);
@@ -855,8 +855,9 @@ int cn_lookahead_values(cn_engine* e, int n_steps, int n_candidates, const doubl
  * scored by the lookahead, ranked, and the distribution refitted to the E best (cross-entropy method), I times per real step;
  * the best sequence's first action is taken, and the plan shifted by one step — or re-seeded where an episode ended.  Drawing,
  * ranking, refitting, shifting and the closed loop run on the device, enqueued on the engine's stream; no call synchronises.
- * CN_ROBOT_EXTERNAL engines with a holonomic robot only; a CN_UNICYCLE engine is CN_ERR_UNSUPPORTED.  All arrays are DEVICE
- * memory, caller-owned, and must stay valid until the work has run; cfg and plan themselves are copied by the call.  Action
+ * CN_ROBOT_EXTERNAL engines: a holonomic robot, action rows (vx, vy); a CN_UNICYCLE engine is CN_ERR_UNSUPPORTED until
+ * cn_plan_set_unicycle (below, "Unicycle planners") has named its rotation bound, and then planned with rows (v, r).  All arrays
+ * are DEVICE memory, caller-owned, and must stay valid until the work has run; cfg and plan themselves are copied by the call.  Action
  * rows (mean, std, best_actions, action, candidates) are read and written as 16-byte words: align them to 16 bytes.
  *
  * The arithmetic below is float64, every product and sum a separate IEEE operation in the order written, so that a host
@@ -891,7 +892,8 @@ typedef struct cn_plan {
 /* Every cn_plan_* call refuses, in this order and before anything is enqueued: NULL cfg, plan or a required array (everything
  * of cn_plan but `order`; look.final_state8, value and score iff cfg->bootstrap): CN_ERR_INVALID with the name; cfg out of the
  * ranges above: CN_ERR_INVALID — n_candidates > 1024, n_elites > 64 and n_steps > 256: CN_ERR_UNSUPPORTED with the number;
- * NULL engine or a CN_ROBOT_ORCA engine: CN_ERR_INVALID; a CN_UNICYCLE engine: CN_ERR_UNSUPPORTED; then whatever
+ * NULL engine or a CN_ROBOT_ORCA engine: CN_ERR_INVALID; a CN_UNICYCLE engine without cn_plan_set_unicycle: CN_ERR_UNSUPPORTED;
+ * then whatever
  * cn_lookahead_actions refuses for (n_steps, n_candidates, candidates, look) and, with bootstrap, cn_lookahead_values, with
  * their messages; cn_plan_shift and cn_plan_rollout then what cn_rollout_step refuses for the io block. */
 
@@ -962,6 +964,39 @@ int cn_plan_mppi_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps
                          double temperature, int fit_std, uint32_t counter);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Unicycle planners (no version bump: two new symbols; cn_plan_cfg, cn_plan and CN_LAUNCH_COUNTERS unchanged).  A unicycle
+ * robot's action is ActionRot (v, r): a speed and a rotation.  How far it may turn per step is the caller's choice, not a fact
+ * of the environment (the reference puts it in the policy's action space: +-pi/4), and v and r have different units, so the
+ * plan needs a rotation bound R and a second initial deviation.  cn_plan_set_unicycle names both and OPTS THE ENGINE IN: until
+ * it has been called, every cn_plan_* call refuses a CN_UNICYCLE engine as before (CN_ERR_UNSUPPORTED, at the same place of the
+ * refusal order, nothing enqueued); afterwards every cn_plan_* call serves it — reset, draw, refit, cem, shift, rollout, the
+ * MPPI calls, the *_paths and *_modes planners and every *_predict_*rollout — with action rows (v, r) in mean, std, candidates,
+ * best_actions and action.  A host-side setting like cn_lookahead_set_goal_weight: it survives cn_reset, cannot be unset (the
+ * engine's lifetime is its scope), and the getter gives (0, 0) until it is made.  The setter refuses, in this order: NULL
+ * engine; max_rotation not finite, <= 0 or > pi; init_std_rotation not finite or <= 0; an engine that is not CN_UNICYCLE, or is
+ * CN_ROBOT_ORCA (the setting would never be read): all CN_ERR_INVALID, the middle two naming the argument.
+ *
+ * The arithmetic on such an engine, float64, one IEEE operation per product and sum in the order written, with R = max_rotation:
+ *   clip   (in place of the speed-disc rule, in cn_plan_draw and for cn_plan_mppi_update's action; every row, k = 0 included)
+ *            v <- v < 0 ? 0 : (v > v_pref ? v_pref : v)         (no reverse gear)
+ *            r <- r < -R ? -R : (r > R ? R : r)
+ *   draw   the same Philox block and Box-Muller pair: v = mean.v + std.v z0, r = mean.r + std.r z1, then the clip
+ *   prior  (cn_plan_reset; cn_plan_shift where cur_steps == 0) a recurrence in t from the robot's (px, py), its goal and its
+ *          heading th = theta[b] as the engine holds them; per t:
+ *            dx = gx - px, dy = gy - py, dist = sqrt(dx dx + dy dy), speed = min(v_pref, dist / time_step)
+ *            if !(dist > 0): mean[b][t] = (0, 0), nothing moves
+ *            else: bearing = atan2(dy, dx), d = bearing - th, turn = d - 2 pi floor((d + pi) / (2 pi))   (in [-pi, pi))
+ *                  r = turn < -R ? -R : (turn > R ? R : turn),  mean[b][t] = (speed, r),  th <- th + r
+ *                  px <- px + cos(th) speed time_step,  py <- py + sin(th) speed time_step   (the step's own end point)
+ *          std[b][t] = (cfg->init_std, init_std_rotation); cn_plan_shift writes that pair on every env it shifts, too
+ *          (atan2 / cos / sin are the device libm's: a host restatement agrees to the last bits, not bit for bit)
+ *   refit, MPPI sums   component-wise, unchanged: r stays within [-R, R], so no angle wraps; min_std floors both components
+ *   nominal rollouts   candidate 0 of the first draw is the clipped mean in (v, r), which cn_predict_orca_robot follows from the
+ *                      engine's heading */
+int cn_plan_set_unicycle(cn_engine* e, double max_rotation, double init_std_rotation);
+int cn_plan_get_unicycle(cn_engine* e, double* max_rotation, double* init_std_rotation);   /* (0, 0) until set */
+
+/* ------------------------------------------------------------------------------------------------------
  * Device predictors and the closed loop on predicted futures (no version bump: three new symbols, one new struct, one new enum;
  * no existing struct, enum or counter touched).  cn_lookahead_paths / cn_lookahead_modes take the humans' predicted velocities
  * from the caller, and a caller with a predictor of their own keeps the per-step calls above.  The two predictors the project
@@ -1011,8 +1046,8 @@ typedef struct cn_predictors {      /* 64 bytes */
  * has just ended is predicted from its new scenario; one still waiting for a scenario from its stale state, as cn_plan_shift
  * seeds its prior from it.  After the call pred->human_vel holds the table the LAST planning step scored against.  Refused, in
  * this order, before anything is enqueued: NULL pred, NULL pred->human_vel: CN_ERR_INVALID naming it; n_modes and the models as
- * by cn_predict; everything cn_plan_rollout / cn_plan_mppi_rollout refuses, in their order (CN_ROBOT_ORCA and CN_UNICYCLE
- * engines stay refused, as by every cn_plan_* call); for M > 1 cfg->bootstrap != 0: CN_ERR_UNSUPPORTED naming bootstrap, then
+ * by cn_predict; everything cn_plan_rollout / cn_plan_mppi_rollout refuses, in their order (CN_ROBOT_ORCA engines,
+ * and CN_UNICYCLE ones without cn_plan_set_unicycle, stay refused, as by every cn_plan_* call); for M > 1 cfg->bootstrap != 0: CN_ERR_UNSUPPORTED naming bootstrap, then
  * cn_lookahead_modes' refusals; the table's rows beyond an int: CN_ERR_UNSUPPORTED.  n_real_steps == 0: CN_OK, nothing enqueued. */
 int cn_plan_cem_predict_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
                                  const cn_plan* plan, const cn_predictors* pred, uint32_t counter);
@@ -1057,8 +1092,8 @@ int cn_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode,
  * must still be a valid CN_PREDICT_* value: it is computed and overwritten (a launch of a few microseconds); struct
  * cn_predictors and its checks are as above.  Refused, before anything is enqueued: everything cn_plan_*_predict_rollout
  * refuses, in their order and with this call's name, and — after the models, before the engine is looked at — orca_mode
- * outside 0 .. M - 1: CN_ERR_INVALID with both numbers.  CN_ROBOT_ORCA and CN_UNICYCLE engines stay refused, as by every
- * cn_plan_* call, and so does M > 1 with cfg->bootstrap. */
+ * outside 0 .. M - 1: CN_ERR_INVALID with both numbers.  CN_ROBOT_ORCA engines, and CN_UNICYCLE ones without
+ * cn_plan_set_unicycle, stay refused, as by every cn_plan_* call, and so does M > 1 with cfg->bootstrap. */
 int cn_plan_cem_predict_orca_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
                                       const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter);
 int cn_plan_mppi_predict_orca_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
@@ -1104,7 +1139,8 @@ int cn_predict_orca_robot(cn_engine* e, int n_steps, int n_modes, int mode,
  *   the paths (M == 1) or modes planner with counter c — its iteration 0 draws with c again, the same bits, so the call does
  *   not launch that draw a second time; cn_rollout_step; cn_plan_shift.
  * ONE prediction per planning step, not one per CEM / MPPI iteration.  Arguments, checks and their order: those of the
- * cn_plan_*_predict_orca_rollout calls, under these names; CN_ROBOT_ORCA and CN_UNICYCLE engines stay refused. */
+ * cn_plan_*_predict_orca_rollout calls, under these names; CN_ROBOT_ORCA engines, and CN_UNICYCLE ones without
+ * cn_plan_set_unicycle, stay refused. */
 int cn_plan_cem_predict_orca_nominal_rollout (cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
                                               const cn_plan* plan, const cn_predictors* pred, int orca_mode, uint32_t counter);
 int cn_plan_mppi_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io* io, int n_real_steps, const cn_plan_cfg* cfg,
