@@ -13,11 +13,16 @@ CRAFTED = ((1.0, 0.0, 0.3, 0.1, 1.0, 0.0, 0.3, 1.0),      # stands on its goal, 
 CASES = ('zero', 'exact', 'short', 'cruise')
 
 
-def crafted_state(H):
-    """[1 + H, 8]: the robot and the crafted humans cut to H, or padded by going round them again, each round 8 m further out."""
+def crafted_state(H, dt=DT, v_pref=None):
+    """[1 + H, 8]: the robot and the crafted humans cut to H, or padded by going round them again, each round 8 m further out.
+    dt, v_pref: the human of the `exact` case gets that v_pref (None: the 1.0 it has) and its goal at gx = v_pref * dt, the
+    float64 product, so that its distance is the reach of one step at any time step — at the defaults the row keeps its bits."""
     rows = [ROBOT]
     for h in range(H):
         row, shift = list(CRAFTED[h % len(CRAFTED)]), 8.0 * (h // len(CRAFTED))
+        if h % len(CRAFTED) == 1:
+            row[7] = row[7] if v_pref is None else float(v_pref)
+            row[4] = row[7] * float(dt)
         row[0], row[4] = row[0] + shift, row[4] + shift
         rows.append(tuple(row))
     return np.array(rows, dtype=np.float64)

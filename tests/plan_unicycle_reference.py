@@ -32,17 +32,19 @@ def draw(mean, std, K, seed, counter, v_pref, R):
     return clip(a, np.broadcast_to(np.asarray(v_pref, np.float64), (B,))[:, None, None], R)
 
 
-def wrap(d):
+def wrap(d, real=np.float64):
     """d -> the same angle in [-pi, pi), by the header's explicit operations."""
-    d = np.float64(d)
-    return d - TWO_PI * np.floor((d + PI) / TWO_PI)
+    d = real(d)
+    return d - real(TWO_PI) * np.floor((d + real(PI)) / real(TWO_PI))
 
 
-def prior_rows(px, py, gx, gy, v_pref, theta, dt, R, n, turns=None):
-    """The prior of ONE env: rows [n, 2] of (v, r).  turns (a list): receives the unclipped turn of every step that has one."""
-    px, py, th = np.float64(px), np.float64(py), np.float64(theta)
-    gx, gy, v_pref, dt, R = np.float64(gx), np.float64(gy), np.float64(v_pref), np.float64(dt), np.float64(R)
-    rows = np.zeros((n, 2))
+def prior_rows(px, py, gx, gy, v_pref, theta, dt, R, n, turns=None, real=np.float64):
+    """The prior of ONE env: rows [n, 2] of (v, r).  turns (a list): receives the unclipped turn of every step that has one.
+    real: the type every operation is made in — np.float64, the device's; np.longdouble states the same recurrence on the same
+    float64 inputs (pi and 2 pi too) at a higher precision, the truth two float64 evaluations are measured against."""
+    px, py, th = real(px), real(py), real(theta)
+    gx, gy, v_pref, dt, R = real(gx), real(gy), real(v_pref), real(dt), real(R)
+    rows = np.zeros((n, 2), dtype=real)
     for t in range(n):
         dx, dy = gx - px, gy - py
         dist = np.sqrt(dx * dx + dy * dy)
@@ -50,7 +52,7 @@ def prior_rows(px, py, gx, gy, v_pref, theta, dt, R, n, turns=None):
             continue
         reach = dist / dt
         speed = v_pref if v_pref < reach else reach
-        turn = wrap(np.arctan2(dy, dx) - th)
+        turn = wrap(np.arctan2(dy, dx) - th, real)
         if turns is not None:
             turns.append(float(turn))
         r = -R if turn < -R else (R if turn > R else turn)
@@ -61,9 +63,9 @@ def prior_rows(px, py, gx, gy, v_pref, theta, dt, R, n, turns=None):
     return rows
 
 
-def prior(state8, theta, dt, R, n, turns=None):
+def prior(state8, theta, dt, R, n, turns=None, real=np.float64):
     """state8 [B, A, 8] (px, py, vx, vy, gx, gy, radius, v_pref), agent 0 the robot; theta [B] -> the prior [B, n, 2]."""
-    return np.stack([prior_rows(r[0], r[1], r[4], r[5], r[7], th, dt, R, n, turns) for r, th in zip(state8[:, 0], theta)])
+    return np.stack([prior_rows(r[0], r[1], r[4], r[5], r[7], th, dt, R, n, turns, real) for r, th in zip(state8[:, 0], theta)])
 
 
 def reset(state8, theta, dt, R, mean, std, init_std, std_rotation, mask=None):

@@ -13,6 +13,7 @@ import lookahead_cv_reference as cv
 import lookahead_paths_reference as paths
 import plan_reference as plan_ref
 from conftest import load_golden
+from env_settings_planning_cases import action_table as _table, lookahead_scene as _lookahead_scene
 from support import amd, np_of as _np, same_bits as _same_bits  # noqa: F401  (amd: module fixture)
 
 FIXTURES, flat, environ = cases.fixture_settings(), cases.flat, cases.environ
@@ -273,31 +274,6 @@ def test_traced_rollouts_are_the_step_loops(amd, name, external):
 
 # ------------------------------------------------------------------------------------------------ e. the three lookaheads
 SHAPES = [(5, 33), (70, 4)]
-
-
-def _lookahead_scene(amd, oracle_mod, s, B=3, **extra):
-    """An external-robot engine of the entry, its start states moved on by 3 s of the oracle's ORCA robot (the crowd is about to
-    meet), env 0's clock two and a half steps short of the Timeout rule."""
-    config = cases.engine_config(s, robot_visible=1, **extra)
-    o = oracle_mod.CrowdOracle(num_envs=B, robot_policy=1, **config)
-    o.reset(cases.seeds(s, B))
-    for _ in range(int(round(3.0 / cases.whole_config(s.config)['time_step']))):
-        o.step(None, update=True)
-    state, gtime = o.get_state()
-    c = cases.whole_config(s.config)
-    gtime = gtime.copy()
-    gtime[0] = c['time_limit'] - 1.0 - 2.5 * c['time_step']
-    eng = amd.BatchedCrowdSim(num_envs=B, robot_policy=amd.ROBOT_EXTERNAL, **config)
-    eng.set_gamma(cases.GAMMA)
-    eng.set_state(state, gtime)
-    return eng, state, gtime, c
-
-
-def _table(B, K, n, v_pref, seed=3):
-    rng = np.random.RandomState(seed)
-    t = rng.uniform(-1.0, 1.0, (B, K, n, 2)) * v_pref
-    t[:, 0] = [0.0, v_pref]  # candidate 0: straight on
-    return t
 
 
 def _step_loops(amd, config, state, gtime, table, gamma_table):
