@@ -1,7 +1,9 @@
 // Host side shared by the translation units of libcrowdnav_amd.so: the engine object behind the opaque cn_engine handle, error
-// text, the slab allocator and the launch helpers.  crowdnav_amd.hip holds the env / rollout entry points and their kernels,
-// sarl_abi.hip the value-network decision (cn_sarl_*) and its kernels: two code objects, compiled in parallel, no device
-// symbol shared between them.
+// text, the slab allocator and the launch helpers.  Every *.hip of this directory is one unit and one code object, compiled side
+// by side, no device symbol shared between them: crowdnav_amd.hip holds the env / rollout entry points and their kernels,
+// sarl_abi.hip the value-network decision (cn_sarl_*) and the kernels around the network, sarl_lds.hip / sarl_reg.hip /
+// sarl_reg_chunk.hip / sarl_reg_seq.hip / sarl_f16.hip the network's kernel families behind sarl_host.h, sarl_train.hip the SGD step, plan.hip the
+// planners and predictors.
 #pragma once
 #include <hip/hip_runtime.h>
 

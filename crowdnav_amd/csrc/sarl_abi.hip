@@ -1,70 +1,11 @@
-// C ABI of the SARL robot decision (declared in include/crowdnav_amd.h): cn_sarl_* and the value-network kernels, a
-// translation unit of its own (engine_host.h has what it shares with crowdnav_amd.hip).
-#include "engine_host.h"
+// C ABI of the SARL robot decision (declared in include/crowdnav_amd.h): the cn_sarl_* entry points, validation, the route
+// choice, the packed layers every route uploads, and the decision-side kernels — features, select, explore, transform, the
+// narrow value-network kernel and the fused sampling step.  The other value-network kernels are instantiated, packed for and
+// launched by units of their own (sarl_lds.hip, sarl_reg.hip, sarl_reg_chunk.hip, sarl_reg_seq.hip, sarl_f16.hip) behind sarl_host.h.
+#include "sarl_host.h"
 #include "sarl_kernels.h"
-#include "sarl_lds_kernels.h"
 #include "sarl_narrow_kernel.h"
-#include "sarl_reg_kernel.h"
-#include "sarl_f16_kernel.h"
 #include "sarl_step_fused.h"
-
-// The kernel family that runs the value network: chosen once per configuration (sarl_choose_route), then read by
-// cn_sarl_set_weights (which weight streams to pack) and sarl_select (which launcher).  DESIGN.md §3.5 has the conditions.
-enum class SarlRoute {
-    LdsTile,       // sarl_mlp_pipe_kernel<H, ATT> / cadrl_mlp_kernel<H> / lstm_mlp_kernel<H>: a tile's activations in LDS
-    LdsChunked,    // sarl_mlp_chunked_kernel<.., ATT> / cadrl_mlp_chunked_kernel / lstm_mlp_anyh_kernel: the humans do not fit one tile's LDS
-    Narrow,        // sarl_narrow_kernel<LSTM, ATT>: a few decisions (train.py's single-episode sampling) on tiles of 16 / H groups, one per workgroup
-    RegSarl, RegSarlChunk,        // activations in registers: sarl_reg_kernel<4, NT, PRE, ATT> (1..5 humans), sarl_reg_chunk_kernel<NT, PRE, ATT> (6+)
-    RegCadrl, RegLstm, RegLstm2,  // cadrl_reg_kernel<NT>, lstm_reg_kernel<4 / 16>, lstm2_reg_kernel<4 / 16> (lstm_rl.ValueNetwork2)
-    SplitF16,      // sarl_f16_kernel<XKB, NT, ATT>: CN_PRECISION_F16X2, activations in registers, split-f16 matrix instructions
-};
-// cn_sarl_network_route reports the route as CN_SARL_ROUTE_*: the same order
-static_assert((int)SarlRoute::LdsTile == CN_SARL_ROUTE_LDS_TILE && (int)SarlRoute::LdsChunked == CN_SARL_ROUTE_LDS_CHUNKED &&
-              (int)SarlRoute::Narrow == CN_SARL_ROUTE_NARROW && (int)SarlRoute::RegSarl == CN_SARL_ROUTE_REG_SARL &&
-              (int)SarlRoute::RegSarlChunk == CN_SARL_ROUTE_REG_SARL_CHUNK && (int)SarlRoute::RegCadrl == CN_SARL_ROUTE_REG_CADRL &&
-              (int)SarlRoute::RegLstm == CN_SARL_ROUTE_REG_LSTM && (int)SarlRoute::RegLstm2 == CN_SARL_ROUTE_REG_LSTM2 &&
-              (int)SarlRoute::SplitF16 == CN_SARL_ROUTE_SPLIT_F16);
-
-struct cn_sarl {
-    cn_sarl_config cfg = {};
-    cn::SarlCfg C = {};
-    cn::SarlNet net = {};
-    cn::SarlNetRef ref = {};        // the same layers as offsets into `arena` (persistent value-network kernel)
-    float* arena = nullptr;         // one allocation for every layer's packed weights and biases
-    size_t arena_used = 0;
-    double* actions = nullptr;      // [K][2] device copy of the action table
-    float* orca_vel = nullptr;      // [B][A][2]
-    double* next_obs = nullptr;     // [B][H][5]
-    float* om = nullptr;            // [B][H][cells*channels]
-    double* reward = nullptr;       // [B][K]
-    float* X = nullptr;             // [tiles][H][ks_x][64] (MFMA A-fragment order)
-    float* V = nullptr;             // [B*K]
-    int* hcount = nullptr;          // [tiles * 16] humans present per (env, action) group (num_humans unless the `mixed` rule parks some)
-    size_t n_groups = 0, n_tiles = 0, lds_bytes = 0;  // lds_bytes: of the LDS kernel the configuration would run (LdsTile / LdsChunked)
-    bool weights_set = false;
-    SarlRoute route = SarlRoute::LdsTile;
-    bool narrow() const { return route == SarlRoute::Narrow; }
-    int stream_key = 0;             // key of reg_stream: 4 (13 features), kRegSarlPre, kRegChunkA / APre, kRegCadrl, kRegLstmGates / kRegLstmMlp1 + 4 / 16
-    float* reg_stream = nullptr;    // register-resident routes: weight streams of reg_total_quads(key) quads of 256 floats
-    float* reg_stream2 = nullptr;   // RegLstm / RegLstm2: the value head's stream, kRegLstmHead (reg_stream is the gate layer's / mlp1's)
-    float* reg_stream3 = nullptr;   // RegLstm2: the gate layer's; RegSarlChunk: streams A, G, B = reg_stream, reg_stream2, reg_stream3
-    float* reg_scratch = nullptr;   // RegSarlChunk: per-wave parking space for mlp1's output
-    int chunk_nt = 0, n_chunks = 0;
-    int cadrl_nt = 0, cadrl_chunks = 0;  // RegCadrl: humans per chunk (1..5), chunks per tile (1 up to 5 humans)
-    bool pre = false;  // RegSarl / RegSarlChunk on 61 inputs: the 48 map cells' half of mlp1.0 is hoisted out of the action loop (sarl_om_term_kernel), X holds k-steps 0..3 only
-    float* om_w = nullptr;          // mlp1.0's occupancy-map columns [48][160 slots] and its bias [160] (sarl_om_weights_kernel)
-    float* om_term = nullptr;       // b + W[:, 13:61] om per (env, human), [B * H][160] in accumulator order
-    int n_cus = 0;
-    size_t narrow_tiles = 0, narrow_lds = 0;
-    bool fused_step = false;        // cn_sarl_sample_step on the narrow route: decision + transition + next ORCA as one kernel (CROWDNAV_AMD_SARL_FUSED_STEP)
-    _Float16* f16_stream = nullptr; // SplitF16: Wh / Wl of every (output tile, input block) in the order of use (sarl_f16_pack_kernel)
-    float* f16_bias = nullptr;      // ... and the biases in accumulator order
-    int* narrow_counter = nullptr;  // cn_sarl_sample_step: workgroups of sarl_narrow_kernel that have written their V
-    double* narrow_value = nullptr; // ... and reward + gamma V per (env, action), each written by the tile that computed V
-    float* state_rows = nullptr;    // cn_sarl_state_values on the narrow tiles: a pass's rows [n_groups][H][13] (allocated by the first call)
-    cn::PackJobs pack_jobs = {};    // cn_sarl_set_weights: the layers to repack, run as one launch (sarl_pack_flush)
-    int pack_blocks = 0;
-};
 
 void cn_sarl_release(cn_engine* e) {
     delete e->sarl;  // device buffers are owned by the engine's slabs
@@ -73,9 +14,6 @@ void cn_sarl_release(cn_engine* e) {
 
 namespace {
 
-bool is_cadrl(const cn_sarl_config& c) { return c.model == CN_MODEL_CADRL; }
-bool is_lstm(const cn_sarl_config& c) { return c.model == CN_MODEL_LSTM_RL; }
-bool is_pairwise(const cn_sarl_config& c) { return is_lstm(c) && c.interaction_dims[0] > 0; }  // lstm_rl.ValueNetwork2
 int om_width(const cn_sarl_config& c) { return c.with_om ? c.cell_num * c.cell_num * c.om_channel_size : 0; }
 
 int sarl_validate(const cn_sarl_config* c, int H) {
@@ -122,8 +60,8 @@ int sarl_alloc_layer(cn_sarl* s, cn::PackedLinear& L, int N, int K) {
     return CN_OK;
 }
 
-// The packed layers of the model, each with its place in the arena; the LDS buffers (k-steps per row tile), the bytes of the LDS
-// kernel and the tile counts.  *lds_chunked: that kernel is the chunked one, the humans do not fit one tile's LDS.
+// The packed layers of the model, each with its place in the arena; the LDS buffers (k-steps per row tile) and the bytes of the LDS
+// kernel (sarl_lds_size), the tile counts.  *lds_chunked: that kernel is the chunked one, the humans do not fit one tile's LDS.
 int sarl_size_network(cn_sarl* s, bool* lds_chunked) {
     const cn_sarl_config* c = &s->cfg;
     cn::SarlNet& net = s->net;
@@ -155,39 +93,7 @@ int sarl_size_network(cn_sarl* s, bool* lds_chunked) {
         const int rc = sarl_alloc_layer(s, net.L[l], N, K);
         if (rc) return rc;
     }
-    auto max2 = [](int a, int b) { return a > b ? a : b; };
-    // k-steps per row tile of each LDS buffer = whole column tiles of the widest layer written into it
-    auto ks_of = [](int n) { return cn::sarl_ks(n); };
-    bool& chunked = *lds_chunked;
-    net.ks_x = ks_of(in_dim);
-    net.ks_a = ks_of(max2(max2(max2(m1a, m2a), max2(a0, 6 + m2b)), max2(max2(j0, j1), j2)));
-    net.ks_b = max2(ks_of(max2(m1b, a1)), net.ks_x);
-    net.ks_c = ks_of(m2b);
-    net.ks_s = 4;
-    if (lstm) {
-        net.ks_a = ks_of(max2(max2(j0, j1), max2(j2, 6 + hid)));
-        net.ks_b = net.ks_c = 0;
-        if (pairwise) {  // ping-pong buffers of ValueNetwork2.mlp1, all H row tiles: widths d0, d2 -> ks_b; d1, d3 -> ks_c
-            const int* id = c->interaction_dims;
-            net.ks_b = ks_of(max2(id[0], id[2]));
-            net.ks_c = ks_of(max2(id[1], id[3]));
-        }
-        // more than kSarlMaxHumans humans: lstm_mlp_anyh_kernel stages one human's row tile per LSTM step (nothing sized by H)
-        // (... and whenever H row tiles do not fit: ValueNetwork2's ping-pong buffers from 6 humans on)
-        chunked = H > cn::kSarlMaxHumans || cn::lstm_lds_bytes(net, H, hid) > 160 * 1024;
-        s->lds_bytes = cn::lstm_lds_bytes(net, chunked ? 1 : H, hid);
-    } else if (cadrl) {  // ping-pong between A (first / third hidden layer) and B (X staging, second hidden layer)
-        net.ks_a = ks_of(max2(j0, j2));
-        net.ks_b = max2(ks_of(j1), net.ks_x);
-        net.ks_c = 0;
-        chunked = H > cn::kSarlMaxHumans;  // cadrl_mlp_chunked_kernel streams the humans in chunks of 5
-        s->lds_bytes = cn::cadrl_lds_bytes(net, chunked ? cn::kSarlChunk : H, chunked);
-    } else {
-        // one tile's activations + the side chain's pong buffer (sarl_mlp_pipe_kernel) in LDS, or the humans stream through
-        // in chunks (6+ humans at the shipped widths)
-        chunked = H > cn::kSarlMaxHumans || cn::sarl_pipe_lds_bytes(net, H) > 160 * 1024;
-        s->lds_bytes = chunked ? cn::sarl_chunked_lds_bytes(net) : cn::sarl_pipe_lds_bytes(net, H);
-    }
+    sarl_lds_size(s, lds_chunked);
     s->n_groups = (size_t)s->C.B * s->C.n_actions;
     s->n_tiles = (s->n_groups + cn::kSarlGroups - 1) / cn::kSarlGroups;
     const size_t per_tile = (size_t)(cn::kSarlGroups / (H < 1 ? 1 : H));
@@ -264,47 +170,9 @@ SarlRoute sarl_route_f32(const cn_sarl* s, bool lds_chunked) {
     return lds_chunked ? SarlRoute::LdsChunked : SarlRoute::LdsTile;
 }
 
-int sarl_alloc_stream(cn_engine* e, float** stream, int key) {
-    return dev_alloc(e, stream, (size_t)cn::reg_total_quads(key) * 256);
-}
-
-// what the register-resident routes need beside the common buffers: their weight streams
+// what the routes with weight streams of their own need beside the common buffers
 int sarl_alloc_route(cn_engine* e, cn_sarl* s) {
-    const int H = s->C.H, ks_in = s->net.in_dim == 13 ? 4 : 16;
-    int key2 = 0, key3 = 0;  // of reg_stream2, reg_stream3
-    switch (s->route) {
-        case SarlRoute::RegSarl: s->pre = s->net.in_dim != 13, s->stream_key = s->pre ? cn::kRegSarlPre : 4; break;
-        case SarlRoute::RegSarlChunk:
-            s->n_chunks = (H + 3) / 4, s->chunk_nt = (H + s->n_chunks - 1) / s->n_chunks;
-            s->pre = s->net.in_dim != 13, s->stream_key = s->pre ? cn::kRegChunkAPre : cn::kRegChunkA;
-            key2 = cn::kRegChunkG, key3 = cn::kRegChunkB;
-            break;
-        case SarlRoute::RegCadrl:
-            s->stream_key = cn::kRegCadrl;
-            s->cadrl_chunks = (H + cn::kRegHumans - 1) / cn::kRegHumans, s->cadrl_nt = (H + s->cadrl_chunks - 1) / s->cadrl_chunks;
-            break;
-        case SarlRoute::RegLstm: s->stream_key = cn::kRegLstmGates + ks_in, key2 = cn::kRegLstmHead; break;
-        case SarlRoute::RegLstm2: s->stream_key = cn::kRegLstmMlp1 + ks_in, key2 = cn::kRegLstmHead, key3 = cn::kRegLstmGates + cn::kRegLstmKs; break;
-        case SarlRoute::SplitF16: {
-            const int xkb = cn::f16_key(s->net.in_dim == 13 ? 1 : 2, H);
-            int rc;
-            if ((rc = dev_alloc(e, &s->f16_stream, cn::f16_stream_bytes(xkb) / sizeof(_Float16))) ||
-                (rc = dev_alloc(e, &s->f16_bias, (size_t)cn::f16_total_tiles(xkb) * 256)))
-                return rc;
-            return CN_OK;
-        }
-        default: return CN_OK;
-    }
-    int rc;
-    if ((rc = sarl_alloc_stream(e, &s->reg_stream, s->stream_key)) || (key2 && (rc = sarl_alloc_stream(e, &s->reg_stream2, key2))) ||
-        (key3 && (rc = sarl_alloc_stream(e, &s->reg_stream3, key3))))
-        return rc;
-    if (s->route == SarlRoute::RegSarlChunk &&
-        (rc = dev_alloc(e, &s->reg_scratch, (size_t)s->n_cus * cn::kRegWaves * s->n_chunks * s->chunk_nt * 7 * 256)))
-        return rc;
-    if (s->pre && ((rc = dev_alloc(e, &s->om_w, (size_t)160 * 49)) || (rc = dev_alloc(e, &s->om_term, (size_t)s->C.B * H * 160))))
-        return rc;
-    return CN_OK;
+    return s->route == SarlRoute::SplitF16 ? sarl_f16_alloc(e, s) : sarl_reg_alloc(e, s);
 }
 
 // the packing jobs of one cn_sarl_set_weights call are collected and run as ONE launch (sarl_pack_flush)
@@ -337,41 +205,7 @@ int sarl_pack_whole(cn_engine* e, const float* const* p, int sd, int kl) {
     return sarl_pack(e, L, p[2 * sd], p[2 * sd + 1], L.N, L.K, 0);
 }
 
-// a layer of a register-resident kernel's weight stream: state_dict layer sd with the shape of packed layer kl
-void reg_fill(const cn_sarl* s, cn::RegPackLayer& R, const float* const* p, int sd, int kl, int replicate = 0) {
-    const cn::PackedLinear& L = s->net.L[kl];
-    R.W = p[2 * sd], R.b = p[2 * sd + 1], R.N = L.N, R.K = L.K, R.ldw = L.K, R.k_off = 0, R.replicate = replicate;
-}
-void reg_pack(cn_engine* e, const cn::RegPackPlan& plan, float* stream) {
-    const int total = cn::reg_total_quads(plan.xks) * 256;
-    hipLaunchKernelGGL(cn::sarl_reg_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, e->stream, plan, stream);
-}
-
 constexpr int kHeadLayers[4] = {cn::kL_mlp3_0, cn::kL_mlp3_2, cn::kL_mlp3_4, cn::kL_mlp3_6};
-
-// RegLstm / RegLstm2: the gate layer's stream (p: lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0), in front of it
-// mlp1's (RegLstm2; m1: its four layers), then the value head's
-void lstm_reg_pack(cn_engine* e, const float* const* m1p, const float* const* p, const cn::RegPackPlan& head) {
-    const cn_sarl* s = e->sarl;
-    cn::RegPackPlan gates{};
-    gates.xks = s->stream_key;
-    cn::RegPackLayer& G = gates.L[0];
-    G.W = p[0], G.W2 = p[1], G.b = p[2], G.b2 = p[3];
-    G.N = 4 * cn::kRegLstmHid, G.K = s->net.in_dim, G.ldw = s->net.in_dim, G.k_split = s->stream_key - cn::kRegLstmGates;
-    float* gate_stream = s->reg_stream;
-    if (s->route == SarlRoute::RegLstm2) {  // mlp1's stream, the gates on mlp1's 50 outputs
-        const int kl[4] = {cn::kL_mlp2_0, cn::kL_mlp2_2, cn::kL_att_2, cn::kL_att_4};
-        cn::RegPackPlan m1{};
-        m1.xks = s->stream_key;
-        for (int l = 0; l < 4; ++l) reg_fill(s, m1.L[l], m1p, l, kl[l]);
-        reg_pack(e, m1, s->reg_stream);
-        gates.xks = cn::kRegLstmGates + cn::kRegLstmKs;
-        G.K = cn::kRegLstmHid, G.ldw = cn::kRegLstmHid, G.k_split = cn::kRegLstmKs;
-        gate_stream = s->reg_stream3;
-    }
-    reg_pack(e, gates, gate_stream);
-    reg_pack(e, head, s->reg_stream2);
-}
 
 // CADRL and LSTM-RL.  state_dict order: [ValueNetwork2: mlp1.{0,2,4,6}] the value head's four layers [lstm.*]
 int sarl_set_weights_head(cn_engine* e, const float* const* params) {
@@ -386,41 +220,12 @@ int sarl_set_weights_head(cn_engine* e, const float* const* params) {
     }
     for (int i = 0; i < 4; ++i)
         if ((rc = sarl_pack_whole(e, p, i, kHeadLayers[i]))) return rc;
-    cn::RegPackPlan head{};  // the same parameters as a weight stream of cadrl_reg_kernel / lstm_reg_kernel / lstm2_reg_kernel
-    head.xks = s->route == SarlRoute::RegCadrl ? s->stream_key : cn::kRegLstmHead;
-    for (int l = 0; l < 4; ++l) reg_fill(s, head.L[l], p, l, kHeadLayers[l], l == 3 ? 1 : 0);
-    if (s->route == SarlRoute::RegCadrl) reg_pack(e, head, s->reg_stream);
     if (is_lstm(s->cfg)) {  // lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0
         cn::PackedLinear& Li = s->net.L[cn::kL_mlp1_0];
         cn::PackedLinear& Lh = s->net.L[cn::kL_mlp1_2];
         if ((rc = sarl_pack(e, Li, p[8], p[10], Li.N, Li.K, 0)) || (rc = sarl_pack(e, Lh, p[9], p[11], Lh.N, Lh.K, 0))) return rc;
     }
-    if (s->route == SarlRoute::RegLstm || s->route == SarlRoute::RegLstm2) lstm_reg_pack(e, params, p + 8, head);
-    CN_HIP(hipGetLastError());
     return CN_OK;
-}
-
-// RegSarl: the same parameters as the weight stream of sarl_reg_kernel; RegSarlChunk: the same 12 layers dealt over the three
-// streams A, B, G of sarl_reg_chunk_kernel
-void sarl_reg_pack(cn_engine* e, const float* const* p) {
-    const cn_sarl* s = e->sarl;
-    const int sd[cn::kRegLayers] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 9, 10};  // state_dict layer of each stream layer
-    const int kl[cn::kRegLayers] = {cn::kL_mlp1_0, cn::kL_mlp1_2, cn::kL_mlp2_0, cn::kL_mlp2_2, cn::kL_att0_global, cn::kL_att0_local,
-                                    cn::kL_att_2,  cn::kL_att_4,  cn::kL_mlp3_0, cn::kL_mlp3_2, cn::kL_mlp3_4,      cn::kL_mlp3_6};
-    const int at[cn::kRegLayers][2] = {{0, 0}, {0, 1}, {1, 0}, {1, 1}, {2, 0}, {1, 2}, {1, 3}, {1, 4}, {2, 1}, {2, 2}, {2, 3}, {2, 4}};  // chunk: {A B G, slot}
-    const bool chunk = s->route == SarlRoute::RegSarlChunk;
-    cn::RegPackPlan plan[3] = {};
-    plan[0].xks = s->stream_key, plan[1].xks = cn::kRegChunkB, plan[2].xks = cn::kRegChunkG;
-    for (int l = 0; l < cn::kRegLayers; ++l) {
-        cn::RegPackLayer& R = chunk ? plan[at[l][0]].L[at[l][1]] : plan[0].L[l];
-        reg_fill(s, R, p, sd[l], kl[l], l == cn::kR_att_4 || (chunk && l == cn::kR_mlp3_6) ? 1 : 0);
-        if (l == cn::kR_mlp1_0 && s->pre) R.K = 13;  // the map columns live in om_w
-        if (l == cn::kR_att0_local || l == cn::kR_att0_global) R.ldw = 2 * R.K;  // attention.0 sees [h2 | mean]
-        if (l == cn::kR_att0_local) R.b = nullptr;
-        if (l == cn::kR_att0_global) R.k_off = R.K;
-    }
-    reg_pack(e, plan[0], s->reg_stream);
-    if (chunk) reg_pack(e, plan[2], s->reg_stream2), reg_pack(e, plan[1], s->reg_stream3);
 }
 
 // SARL.  state_dict layer i -> packed layer(s)
@@ -441,19 +246,6 @@ int sarl_set_weights_sarl(cn_engine* e, const float* const* p) {
         if ((rc = sarl_pack(e, L, p[2 * i], p[2 * i + 1], L.N, Ktot, 0))) return rc;
         if (net.with_global && (rc = sarl_pack(e, net.L[cn::kL_att0_global], p[2 * i], nullptr, L.N, Ktot, half))) return rc;
     }
-    if (s->route == SarlRoute::SplitF16) {  // Wh / Wl in the matrix instruction's operand order, the biases in accumulator order: one launch
-        cn::F16PackPlan plan{};
-        plan.xkb = cn::f16_key(net.in_dim == 13 ? 1 : 2, s->C.H);
-        for (int l = 0; l < 11; ++l) plan.W[l] = p[2 * l], plan.b[l] = p[2 * l + 1];
-        const int total = cn::f16_total_items(plan.xkb) * 512 + cn::f16_total_tiles(plan.xkb) * 256;
-        hipLaunchKernelGGL(cn::sarl_f16_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, e->stream, plan, s->f16_stream, s->f16_bias);
-        CN_HIP(hipGetLastError());
-    }
-    if (s->route != SarlRoute::RegSarl && s->route != SarlRoute::RegSarlChunk) return CN_OK;
-    sarl_reg_pack(e, p);
-    if (s->pre)  // mlp1.0's map columns and bias
-        hipLaunchKernelGGL(cn::sarl_om_weights_kernel, dim3((160 * 49 + 255) / 256), dim3(256), 0, e->stream, p[0], p[1], s->om_w);
-    CN_HIP(hipGetLastError());
     return CN_OK;
 }
 
@@ -484,154 +276,8 @@ void launch_narrow(cn_engine* e, unsigned tiles, const cn::SarlDecide& D, float*
     e->launch_counts[CN_COUNT_SARL_NARROW] += 1;
 }
 
-// What one launch of the network kernels evaluates: the first n_groups groups of X / hcount / V, on n_tiles tiles of kSarlGroups.
-// A decision is the whole of the engine's buffers (whole_pass); cn_sarl_state_values fills them pass by pass, the last one shorter.
-struct SarlPass {
-    size_t n_groups, n_tiles;
-};
 SarlPass whole_pass(const cn_sarl* s) { return SarlPass{s->n_groups, s->n_tiles}; }
 SarlPass pass_of(size_t groups) { return SarlPass{groups, (groups + cn::kSarlGroups - 1) / cn::kSarlGroups}; }
-
-// the persistent grid of a register-resident kernel: a wave per tile, at most per_cu workgroups (= waves per SIMD) per CU
-dim3 reg_grid(const cn_sarl* s, const SarlPass& pass, unsigned per_cu) {
-    const unsigned wgs = (unsigned)((pass.n_tiles + cn::kRegWaves - 1) / cn::kRegWaves), resident = (unsigned)s->n_cus * per_cu;
-    return dim3(wgs < resident ? wgs : resident);
-}
-const dim3 kRegBlock(cn::kRegWaves * 64);
-
-int bad_humans(int H) { return fail(CN_ERR_UNSUPPORTED, "value network on device: %d humans", H); }
-
-void launch_om_term(cn_engine* e) {  // PRE: the occupancy-map half of mlp1.0, once per (env, human)
-    const cn_sarl* s = e->sarl;
-    const int rows = s->C.B * s->C.H;
-    hipLaunchKernelGGL(cn::sarl_om_term_kernel, dim3((rows + cn::kOmTermRows - 1) / cn::kOmTermRows), dim3(cn::kOmTermThreads), 0,
-                       e->stream, s->om_w, s->om, s->om_term, rows);
-}
-
-int launch_reg_sarl(cn_engine* e, const SarlPass& pass, float* att) {
-    const cn_sarl* s = e->sarl;
-    const int H = s->C.H;
-    if (s->pre) launch_om_term(e);
-    // waves per SIMD by the kernels' register counts (of 512; scripts/kernel_resources.py): 1 / 2 humans 153 / 215 -> 3 / 2, which
-    // also covers the dependent MFMA chain of the 1-human kernel
-    const dim3 grid = reg_grid(s, pass, H == 1 ? 3u : H == 2 ? 2u : 1u);
-    const bool ok = pick_int<1, 2, 3, 4, 5>(H, [&](auto nt) {
-        pick_bool(s->pre, [&](auto pre) {
-            pick_bool(att != nullptr, [&](auto a) {
-                hipLaunchKernelGGL((cn::sarl_reg_kernel<4, decltype(nt)::value, decltype(pre)::value, decltype(a)::value>), grid,
-                                   kRegBlock, 0, e->stream, s->reg_stream, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x,
-                                   s->hcount, (const float*)s->om_term, s->C.n_actions, att);
-            });
-        });
-    });
-    return ok ? CN_OK : bad_humans(H);
-}
-
-int launch_split_f16(cn_engine* e, const SarlPass& pass, float* att) {
-    const cn_sarl* s = e->sarl;
-    const int H = s->C.H;
-    const dim3 grid = reg_grid(s, pass, 1);  // one wave per SIMD at every crowd size (more than 256 registers; scripts/kernel_resources.py)
-    const bool ok = pick_int<1, 2, 3, 4, 5>(H, [&](auto nt) {
-        pick_bool(s->net.in_dim != 13, [&](auto wide) {
-            pick_bool(att != nullptr, [&](auto a) {
-                hipLaunchKernelGGL((cn::sarl_f16_kernel<cn::f16_key(decltype(wide)::value ? 2 : 1, decltype(nt)::value), decltype(nt)::value, decltype(a)::value>), grid,
-                                   kRegBlock, 0, e->stream, (const _Float16*)s->f16_stream, (const float*)s->f16_bias, (const float*)s->X,
-                                   s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x, (const int*)s->hcount, att);
-            });
-        });
-    });
-    return ok ? CN_OK : bad_humans(H);
-}
-
-int launch_reg_sarl_chunk(cn_engine* e, const SarlPass& pass, float* att) {
-    const cn_sarl* s = e->sarl;
-    if (s->pre) launch_om_term(e);
-    const bool ok = pick_int<3, 4>(s->chunk_nt, [&](auto nt) {
-        pick_bool(s->pre, [&](auto pre) {
-            pick_bool(att != nullptr, [&](auto a) {
-                hipLaunchKernelGGL((cn::sarl_reg_chunk_kernel<decltype(nt)::value, decltype(pre)::value, decltype(a)::value>),
-                                   reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3, s->reg_stream2, s->X, s->V,
-                                   s->reg_scratch, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->n_chunks, s->net.ks_x, s->hcount,
-                                   (const float*)s->om_term, s->C.n_actions, att);
-            });
-        });
-    });
-    return ok ? CN_OK : bad_humans(s->C.H);
-}
-
-int launch_reg_cadrl(cn_engine* e, const SarlPass& pass) {
-    const cn_sarl* s = e->sarl;
-    const int NT = s->cadrl_nt;  // (CADRL keeps fewer activations alive than SARL: 4 / 2 waves per SIMD at 1 / 2 humans per chunk)
-    const bool ok = pick_int<1, 2, 3, 4, 5>(NT, [&](auto nt) {
-        hipLaunchKernelGGL(cn::cadrl_reg_kernel<decltype(nt)::value>, reg_grid(s, pass, NT == 1 ? 4u : NT == 2 ? 2u : 1u), kRegBlock, 0,
-                           e->stream, s->reg_stream, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->net.ks_x, s->hcount, s->C.H,
-                           s->cadrl_chunks);
-    });
-    return ok ? CN_OK : bad_humans(s->C.H);
-}
-
-void launch_reg_lstm(cn_engine* e, const SarlPass& pass) {  // RegLstm, RegLstm2: 4 or 16 input k-steps
-    const cn_sarl* s = e->sarl;
-    pick_bool(s->net.in_dim != 13, [&](auto wide) {
-        constexpr int KS = decltype(wide)::value ? 16 : 4;
-        if (s->route == SarlRoute::RegLstm2)
-            hipLaunchKernelGGL(cn::lstm2_reg_kernel<KS>, reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream3,
-                               s->reg_stream2, s->X, s->V, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->net.ks_x, s->hcount);
-        else
-            hipLaunchKernelGGL(cn::lstm_reg_kernel<KS>, reg_grid(s, pass, 1), kRegBlock, 0, e->stream, s->reg_stream, s->reg_stream2, s->X,
-                               s->V, (int)pass.n_groups, (int)pass.n_tiles, s->C.H, s->net.ks_x, s->hcount);
-    });
-}
-
-// LdsTile, LdsChunked — and the one-tile kernel of a configuration whose decisions take the narrow tiles (sarl_state_values)
-int launch_lds(cn_engine* e, const SarlPass& pass, float* att) {
-    const cn_sarl* s = e->sarl;
-    const dim3 grid((unsigned)pass.n_tiles), block(cn::kSarlThreads);
-    const dim3 pgrid((unsigned)(pass.n_tiles < (size_t)s->n_cus ? pass.n_tiles : (size_t)s->n_cus));  // persistent: one workgroup per CU
-    const int ng = (int)pass.n_groups;
-    const bool cadrl = is_cadrl(s->cfg), lstm = is_lstm(s->cfg), chunked = s->route == SarlRoute::LdsChunked;
-    if (chunked && cadrl)
-        hipLaunchKernelGGL(cn::cadrl_mlp_chunked_kernel<cn::kSarlChunk>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
-    else if (chunked && lstm)
-        hipLaunchKernelGGL(cn::lstm_mlp_anyh_kernel, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng);
-    else if (chunked)
-        pick_bool(att != nullptr, [&](auto a) {
-            hipLaunchKernelGGL((cn::sarl_mlp_chunked_kernel<cn::kSarlChunk, decltype(a)::value>), grid, block, s->lds_bytes, e->stream,
-                               s->net, s->X, s->V, ng, att);
-        });
-    if (chunked) return CN_OK;
-    const bool ok = pick_int<1, 2, 3, 4, 5, 6, 7, 8>(s->C.H, [&](auto h) {
-        constexpr int H = decltype(h)::value;
-        if (cadrl)
-            hipLaunchKernelGGL(cn::cadrl_mlp_kernel<H>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng, s->hcount);
-        else if (lstm)
-            hipLaunchKernelGGL(cn::lstm_mlp_kernel<H>, grid, block, s->lds_bytes, e->stream, s->net, s->X, s->V, ng, s->hcount);
-        else
-            pick_bool(att != nullptr, [&](auto a) {
-                hipLaunchKernelGGL((cn::sarl_mlp_pipe_kernel<H, decltype(a)::value>), pgrid, block, s->lds_bytes, e->stream, s->ref,
-                                   s->X, s->V, ng, (int)pass.n_tiles, s->hcount, att);
-            });
-    });
-    return ok ? CN_OK : bad_humans(s->C.H);
-}
-
-// The network on the groups of `pass` as X / hcount hold them, V into s->V: the route's kernel; on a narrow-route engine (whose
-// decisions never put X in HBM) the configuration's LDS one-tile kernel, whose packed layers every configuration uploads.
-int launch_network(cn_engine* e, const SarlPass& pass, float* att) {
-    const cn_sarl* s = e->sarl;
-    switch (s->route) {
-        case SarlRoute::RegSarl: return launch_reg_sarl(e, pass, att);
-        case SarlRoute::RegSarlChunk: return launch_reg_sarl_chunk(e, pass, att);
-        case SarlRoute::SplitF16: return launch_split_f16(e, pass, att);
-        case SarlRoute::RegCadrl: return launch_reg_cadrl(e, pass);
-        case SarlRoute::RegLstm:
-        case SarlRoute::RegLstm2: launch_reg_lstm(e, pass); return CN_OK;
-        case SarlRoute::Narrow:
-        case SarlRoute::LdsChunked:
-        case SarlRoute::LdsTile: return launch_lds(e, pass, att);
-    }
-    return CN_OK;
-}
 
 // cn_sarl_select and cn_sarl_select_attention: att == nullptr launches exactly cn_sarl_select's kernels; otherwise every SARL
 // route takes its ATT instantiation, which also writes the softmax weights it holds, float [B][n_actions][H]
@@ -710,6 +356,24 @@ int state_values_run(cn_engine* e, const double* state8, const double* theta, in
 
 }  // namespace
 
+// The network on the groups of `pass` as X / hcount hold them, V into s->V: the route's kernel; on a narrow-route engine (whose
+// decisions never put X in HBM) the configuration's LDS one-tile kernel, whose packed layers every configuration uploads.
+int launch_network(cn_engine* e, const SarlPass& pass, float* att) {
+    const cn_sarl* s = e->sarl;
+    switch (s->route) {
+        case SarlRoute::RegSarl:
+        case SarlRoute::RegSarlChunk: return launch_reg(e, pass, att);
+        case SarlRoute::SplitF16: return launch_split_f16(e, pass, att);
+        case SarlRoute::RegCadrl:
+        case SarlRoute::RegLstm:
+        case SarlRoute::RegLstm2: return launch_reg_seq(e, pass);
+        case SarlRoute::Narrow:
+        case SarlRoute::LdsChunked:
+        case SarlRoute::LdsTile: return launch_lds(e, pass, att);
+    }
+    return CN_OK;
+}
+
 extern "C" {
 
 int cn_sarl_configure(cn_engine* e, const cn_sarl_config* c, const double* actions_host) {
@@ -776,7 +440,7 @@ int cn_sarl_configure(cn_engine* e, const cn_sarl_config* c, const double* actio
                         "value networks under the mixed rule run the one-tile kernel (it masks an episode's absent humans), whose "
                         "tile — activations %zu B + the pipelined side buffer %zu B — must fit the 160 KiB of LDS; these layer "
                         "widths do not (narrower mlp1 / mlp3 layers do: the shipped 150-wide network needs 150.5 KiB)",
-                        cn::sarl_pipe_lds_bytes(s->net, s->C.H) - sizeof(float) * 64 * (size_t)s->net.ks_a, sizeof(float) * 64 * (size_t)s->net.ks_a);
+                        s->pipe_lds_bytes - sizeof(float) * 64 * (size_t)s->net.ks_a, sizeof(float) * 64 * (size_t)s->net.ks_a);
         return fail(CN_ERR_UNSUPPORTED,
                     "value networks under the mixed rule run the one-tile kernels (they mask an episode's absent humans): "
                     "num_humans must be 5 (the rule never draws more)");
@@ -811,6 +475,8 @@ int cn_sarl_set_weights(cn_engine* e, const float* const* params_host_array) {
     // W0, b0, W1, b1, ... in state_dict order
     if ((rc = cadrl || lstm ? sarl_set_weights_head(e, params_host_array) : sarl_set_weights_sarl(e, params_host_array))) return rc;
     if ((rc = sarl_pack_flush(e))) return rc;
+    // ... and the same parameters as the weight streams of a route that has its own
+    if ((rc = s->route == SarlRoute::SplitF16 ? sarl_f16_pack(e, params_host_array) : sarl_reg_pack(e, params_host_array))) return rc;
     s->weights_set = true;
     return CN_OK;
 }
@@ -1032,13 +698,13 @@ int cn_sarl_export(cn_engine* e, int which, void* dst, uint64_t bytes) {
 }  // extern "C"
 
 #ifdef CN_PHASE_TIMING
-// profiling builds only (scripts/sarl_phase_probe.py)
+// profiling builds only (scripts/sarl_phase_probe.py): cn_sarl_cycles is one copy per unit that holds ticking kernels — this
+// one's (sarl_narrow_kernel) and sarl_reg.hip's (sarl_reg_kernel); the sum of the copies, all of them reset
+int sarl_abi_cycles(unsigned long long* sum16, int reset) { return sarl_cycles_of(HIP_SYMBOL(cn::cn_sarl_cycles), sum16, reset); }
 extern "C" int cn_debug_sarl_cycles(unsigned long long* out16, int reset) {
-    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(cn::cn_sarl_cycles), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long zero[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(cn::cn_sarl_cycles), zero, sizeof(zero)) != hipSuccess) return -1;
-    }
+    unsigned long long sum[16] = {};
+    if (sarl_abi_cycles(out16 ? sum : nullptr, reset) || sarl_reg_cycles(out16 ? sum : nullptr, reset)) return -1;
+    if (out16) memcpy(out16, sum, sizeof(sum));
     return 0;
 }
 #endif

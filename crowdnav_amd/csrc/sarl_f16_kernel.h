@@ -31,6 +31,8 @@
 //     registers that already hold it in those lanes.
 #pragma once
 
+#include "sarl_reg_stream.h"
+
 namespace cn {
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

@@ -1,6 +1,6 @@
-// The six LDS value-network kernels: a workgroup per tile of 16 groups, activations in LDS in fragment order (blocks: sarl_kernels.h)
+// The six LDS value-network kernels: a workgroup per tile of 16 groups, activations in LDS in fragment order (blocks: sarl_net.h)
 #pragma once
-#include "sarl_kernels.h"
+#include "sarl_net.h"
 
 namespace cn {
 

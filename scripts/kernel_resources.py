@@ -1,22 +1,23 @@
 """Per-kernel register / spill / LDS table of libcrowdnav_amd.so's code object, from hipcc's own resource report
 (-Rpass-analysis=kernel-resource-usage; cross-compiles without a GPU).
 
-    python scripts/kernel_resources.py [--tu env|sarl|train|plan] [filter-regex] [-D...]      # extra -D flags go to hipcc
+    python scripts/kernel_resources.py [--tu UNIT|env|sarl|train|plan|all] [filter-regex] [-D...]      # extra -D flags go to hipcc
 
---tu names the translation unit: env (default) = crowdnav_amd.hip, sarl = sarl_abi.hip (the value-network kernels),
-train = sarl_train.hip (the device SGD step), plan = plan.hip (the CEM / MPPI planners' kernels).
+--tu names the translation units — the *.hip files of crowdnav_amd/csrc — by a file's basename or as kernel_asm_diff.py does:
+env (default) = crowdnav_amd.hip, sarl = every sarl_* unit but sarl_train (the value-network kernels), train = sarl_train.hip
+(the device SGD step), plan = plan.hip (the CEM / MPPI planners' kernels), all.  The rows of several units follow each other.
 """
 import os
 import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TUS = {'env': 'crowdnav_amd.hip', 'sarl': 'sarl_abi.hip', 'train': 'sarl_train.hip', 'plan': 'plan.hip'}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_asm_diff import ROOT, units_of  # noqa: E402
 
 
-def report(extra=(), tu='env'):
-    src = os.path.join(ROOT, 'crowdnav_amd', 'csrc', TUS[tu])
+def report(extra=(), unit='crowdnav_amd'):
+    src = os.path.join(ROOT, 'crowdnav_amd', 'csrc', unit + '.hip')
     cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-slp-vectorize',
            '-fno-fast-math', '-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', '/dev/null'] + list(extra)
     err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, cwd=os.path.dirname(src)).stderr
@@ -44,13 +45,14 @@ def main():
     if '--tu' in argv:
         i = argv.index('--tu')
         tu = argv[i + 1]
-        if tu not in TUS:
-            sys.exit('--tu takes one of: ' + ', '.join(TUS))
         del argv[i:i + 2]
+    units = units_of(ROOT, tu)
+    if not units:
+        sys.exit('--tu takes env, sarl, train, plan, all or one of: ' + ', '.join(units_of(ROOT)))
     args = [a for a in argv if not a.startswith('-D')]
     extra = [a for a in argv if a.startswith('-D')]
     pat = re.compile(args[0]) if args else None
-    rows = report(extra, tu)
+    rows = [r for u in units for r in report(extra, u)]
     if not rows:
         sys.exit('no kernel resource remarks: the compile failed (run the hipcc command by hand to see why)')
     names = demangle([r['name'] for r in rows])

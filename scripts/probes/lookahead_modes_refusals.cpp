@@ -4,12 +4,12 @@
 // through one of the dangling pointers below would be reported.  (modes and out are HOST structs the call reads: they are real
 // here, their pointer fields dangle.)
 //
-//   cd crowdnav_amd/csrc && mkdir -p ../../build/asan && for tu in crowdnav_amd sarl_abi sarl_train plan; do
+//   cd crowdnav_amd/csrc && mkdir -p ../../build/asan/units && for tu in $(basename -s .hip *.hip); do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
-//           -Xarch_host -fsanitize=address,undefined -c $tu.hip -o ../../build/asan/$tu.o & done; wait
+//           -Xarch_host -fsanitize=address,undefined -c $tu.hip -o ../../build/asan/units/$tu.o & done; wait     (every *.hip is a unit of the library)
 //   clang++ -std=c++17 -g -I../../include -fsanitize=address,undefined -c ../../scripts/probes/lookahead_modes_refusals.cpp \
 //         -o ../../build/asan/modes_main.o          (hipcc's clang++: /opt/rocm/lib/llvm/bin/clang++)
-//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined ../../build/asan/{crowdnav_amd,sarl_abi,sarl_train,plan,modes_main}.o \
+//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined ../../build/asan/units/*.o ../../build/asan/modes_main.o \
 //         -o ../../build/asan/lookahead_modes_refusals -ldl
 //   ../../build/asan/lookahead_modes_refusals          # prints "ok: N refusals" and exits 0
 //

@@ -3,12 +3,12 @@
 // arguments.  Every call must be refused with the expected status and message WITHOUT reading through a pointer; built with
 // the host sanitizers, a read through one of the dangling pointers below would be reported.
 //
-//   cd crowdnav_amd/csrc && mkdir -p ../../build/asan && for tu in crowdnav_amd sarl_abi sarl_train plan; do
+//   cd crowdnav_amd/csrc && mkdir -p ../../build/asan/units && for tu in $(basename -s .hip *.hip); do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
-//           -Xarch_host -fsanitize=address,undefined -c $tu.hip -o ../../build/asan/$tu.o & done; wait
+//           -Xarch_host -fsanitize=address,undefined -c $tu.hip -o ../../build/asan/units/$tu.o & done; wait     (every *.hip is a unit of the library)
 //   clang++ -std=c++17 -g -I../../include -fsanitize=address,undefined -c ../../scripts/probes/lookahead_paths_refusals.cpp \
 //         -o ../../build/asan/main.o          (hipcc's clang++: /opt/rocm/lib/llvm/bin/clang++)
-//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined ../../build/asan/*.o \
+//   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined ../../build/asan/units/*.o ../../build/asan/main.o \
 //         -o ../../build/asan/lookahead_paths_refusals -ldl
 //   ../../build/asan/lookahead_paths_refusals          # prints "ok: N refusals" and exits 0
 //

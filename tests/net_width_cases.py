@@ -4,7 +4,7 @@ of how cn_sarl_configure sizes a network (packed layers, LDS buffers, bytes per 
 
 Every entry is in the table for a property of its widths, named in `why` and checked by a predicate in test_net_widths_host.py:
 moving a number is fine as long as the predicate still holds.  The sizing functions restate include/crowdnav_amd.h and
-csrc/sarl_kernels.h (sarl_ks, PackedLinear) so that the table can say, without a GPU, which kernel a setting must take."""
+csrc/sarl_net.h (sarl_ks, PackedLinear) so that the table can say, without a GPU, which kernel a setting must take."""
 import collections
 
 import numpy as np
