@@ -33,6 +33,8 @@ MODES_MAX = 8  # cn_path_modes.n_modes
 PREDICT_CONSTANT_VELOCITY, PREDICT_TO_GOAL = 0, 1  # CN_PREDICT_*
 PREDICT_MODELS = ('constant_velocity', 'to_goal')
 PREDICT_ALIASES = {'cv': 'constant_velocity'}
+GOALS_ENGINE, GOALS_HEADING = 0, 1  # CN_GOALS_*
+GOALS_BASES = ('engine', 'heading')
 
 
 class CrowdNavAmdError(RuntimeError):
@@ -259,6 +261,9 @@ SYMBOLS = {
     # the planners on a unicycle engine: the rotation bound and the rotation deviation, which opt the engine in (no version bump)
     'cn_plan_set_unicycle': (C.c_int, [_P, C.c_double, C.c_double]),
     'cn_plan_get_unicycle': (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # the ORCA predictor on M sets of hypothesised human goals [B][M][A - 1][2], and the sampler of such sets (no version bump)
+    'cn_predict_orca_goals': (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    'cn_goal_hypotheses': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32, _P]),
 }
 
 _lib = None

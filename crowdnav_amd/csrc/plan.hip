@@ -10,6 +10,8 @@
 // third predictor beside cn_predict's two, and the *_predict_orca_rollout calls that write it over one slot of cn_predict's table.
 // cn_predict_orca_robot is the same launch with the robot in the humans' sight on a table of actions; the *_nominal_rollout calls
 // give it the plan's clipped mean, candidate 0 of the planning step's first draw.
+// cn_predict_orca_goals is cn_predict_orca's table for M hypotheses about the humans' goals in one launch (the workgroup over B M
+// virtual envs), and cn_goal_hypotheses the streaming kernel that samples such goals from the state.
 // A CN_UNICYCLE engine is served once cn_plan_set_unicycle has named its rotation bound: rows (v, r), the *_uni_kernel forms of
 // the reset, draw, MPPI update and shift; the refit is component-wise and the same kernel.
 #include "engine_host.h"
@@ -276,6 +278,23 @@ int run_predict_orca(cn_engine* e, int n_steps, int n_modes, int mode, double* h
     return CN_OK;
 }
 
+// cn_predict_orca_goals' launch: the same workgroup over B M virtual envs — the copy of Params counts them in B, so the grid,
+// lane_of and build_pairs do; the kernel maps a virtual env back to its real one where it loads the agents
+// (predict_orca_kernel.h).  E, the workgroup size and the LDS per workgroup are the engine's.
+int run_predict_orca_goals(cn_engine* e, int n_steps, int n_modes, const double* goals, double* human_vel) {
+    cn::Params Pk = e->P;
+    Pk.B = e->P.B * n_modes, Pk.robot_visible = 0, Pk.robot_orca = 0;  // (within an int: predict_check_size)
+    pick_maxl(e, [&](auto maxl) {
+        pick_bool(Pk.kd != 0, [&](auto kd) {
+            hipLaunchKernelGGL((cn::predict_orca_goals_kernel<decltype(maxl)::value, decltype(kd)::value>),
+                               dim3(((unsigned)Pk.B + (unsigned)Pk.E - 1u) / (unsigned)Pk.E), dim3(Pk.threads), e->smem, e->stream, Pk, e->S, n_steps, n_modes,
+                               (const double2*)goals, (double2*)human_vel);
+        });
+    });
+    CN_HIP(hipGetLastError());
+    return CN_OK;
+}
+
 // The closed loop of either planner.  pred (the *_predict_rollout calls, whose checks of it precede this): every planning step
 // scores against the table the device predictors make from the state as it then stands; orca_mode >= 0 (the
 // *_predict_orca_rollout calls): slot orca_mode of that table is then overwritten by cn_predict_orca's.  nominal (the
@@ -514,6 +533,48 @@ int cn_plan_mppi_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io*
     const Mppi mppi{temperature, fit_std};
     return predict_rollout(e, io, n_real_steps, cfg, plan, pred, counter, "cn_plan_mppi_predict_orca_nominal_rollout", &mppi, &orca_mode,
                            true);
+}
+
+int cn_predict_orca_goals(cn_engine* e, int n_steps, int n_modes, const double* goals, double* human_vel) {
+    const char* who = "cn_predict_orca_goals";
+    if (!goals) return fail(CN_ERR_INVALID, "%s: goals is NULL", who);
+    if (!human_vel) return fail(CN_ERR_INVALID, "%s: human_vel is NULL", who);
+    if (n_modes < 1) return fail(CN_ERR_INVALID, "%s: n_modes must be >= 1 (got %d)", who, n_modes);
+    if (n_modes > cn::kPredictMaxModes)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_modes = %d exceeds the %d modes of a table", who, n_modes, cn::kPredictMaxModes);
+    if (n_steps < 0) return fail(CN_ERR_INVALID, "%s: n_steps must be >= 0 (got %d)", who, n_steps);
+    if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
+    int rc = predict_check_size(e, n_steps, n_modes, who);  // (B M <= B M (A - 1): the virtual envs are within an int as well)
+    if (rc || n_steps == 0) return rc;
+    if ((rc = bind(e))) return rc;
+    return run_predict_orca_goals(e, n_steps, n_modes, goals, human_vel);
+}
+
+int cn_goal_hypotheses(cn_engine* e, int n_modes, int base, double reach, double std_heading, double std_distance, int nominal_first,
+                       uint64_t seed, uint32_t counter, double* goals) {
+    const char* who = "cn_goal_hypotheses";
+    if (!goals) return fail(CN_ERR_INVALID, "%s: goals is NULL", who);
+    if (n_modes < 1) return fail(CN_ERR_INVALID, "%s: n_modes must be >= 1 (got %d)", who, n_modes);
+    if (n_modes > cn::kPredictMaxModes)
+        return fail(CN_ERR_UNSUPPORTED, "%s: n_modes = %d exceeds the %d modes of a table", who, n_modes, cn::kPredictMaxModes);
+    if (base != CN_GOALS_ENGINE && base != CN_GOALS_HEADING)
+        return fail(CN_ERR_INVALID, "%s: base = %d unknown (CN_GOALS_ENGINE = 0, CN_GOALS_HEADING = 1)", who, base);
+    if (base == CN_GOALS_HEADING && (!std::isfinite(reach) || !(reach > 0.0)))
+        return fail(CN_ERR_INVALID, "%s: reach must be > 0 and finite under CN_GOALS_HEADING (got %g)", who, reach);
+    if (!std::isfinite(std_heading) || !(std_heading >= 0.0))
+        return fail(CN_ERR_INVALID, "%s: std_heading must be >= 0 and finite (got %g)", who, std_heading);
+    if (!std::isfinite(std_distance) || !(std_distance >= 0.0))
+        return fail(CN_ERR_INVALID, "%s: std_distance must be >= 0 and finite (got %g)", who, std_distance);
+    if (!e) return fail(CN_ERR_INVALID, "%s: engine is NULL", who);
+    int rc = predict_check_size(e, 1, n_modes, who);  // (the grid counts workgroups in an unsigned)
+    if (rc || (rc = bind(e))) return rc;
+    const cn::Params& P = e->P;
+    hipLaunchKernelGGL(cn::goal_hypotheses_kernel, dim3(plan_grid((size_t)P.B * n_modes * (P.A - 1))), dim3(cn::kPlanBlock), 0, e->stream,
+                       P.B, P.A, n_modes, base == CN_GOALS_HEADING ? 1 : 0, nominal_first ? 1 : 0, reach, std_heading, std_distance,
+                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), counter, (const double2*)e->S.pos,
+                       (const double2*)e->S.vel, (const double2*)e->S.goal, (double2*)goals);
+    CN_HIP(hipGetLastError());
+    return CN_OK;
 }
 
 }  // extern "C"

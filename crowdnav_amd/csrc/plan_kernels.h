@@ -15,6 +15,7 @@
 //   plan_mppi_kernel   workgroup = env, one wave  the same ranks and best row; weights exp((s - s_max) / T) in LDS; weighted mean / std
 //   plan_shift_kernel  lane = (env, component)    walks t upwards in place: row t <- row t + 1, or the prior at an episode start
 //   predict_kernel     lane = (env, mode, human)  the table of predicted human velocities the *_paths / *_modes planners score against
+//   goal_hypotheses_kernel  lane = (env, mode, human)  the table of hypothesised human goals cn_predict_orca_goals predicts from
 // Unicycle forms: plan_draw_uni_kernel and plan_mppi_uni_kernel are the lane bodies above under UNI = true (the clip alone
 // differs); plan_reset_uni_kernel is lane = env, because the (v, r) prior is a recurrence in t (position and heading), walked as
 // predict_kernel walks to_goal; plan_shift_uni_kernel keeps lane = (env, component) for the shifted envs and hands a re-seeded
@@ -330,6 +331,49 @@ __global__ __launch_bounds__(kPlanBlock) void predict_kernel(int B, int A, int M
         p.x = p.x + v.x * dt;
         p.y = p.y + v.y * dt;
     }
+}
+
+// Hypotheses about where the humans are heading (cn_goal_hypotheses; crowdnav_amd/predict.py's goal_hypotheses restates it):
+// goals[b][m][h] for cn_predict_orca_goals, from the engine's state as it stands.  Lane = (env, mode, human), h fastest: one
+// 16-byte store per lane, consecutive lanes consecutive rows.  No LDS, nothing of the engine written.  The nominal offset d of
+// a human is its goal's (heading = 0: g - p) or `reach` along its velocity (heading = 1; a standing human stays: d = 0); mode 0
+// under nominal_first is p + d (the goal row itself, bit for bit, when heading = 0); every other mode turns d by
+// std_heading z1 and stretches it by 1 + std_distance z2 (not below 0), (z1, z2) the Box-Muller pair of plan_draw_lane from one
+// Philox block on the counter words (h, m, b, counter): a row depends on neither B, M nor H.  Every product, quotient and sum
+// is an operation of its own in the order written.  A parked placeholder of the `mixed` rule is at rest at its goal, so
+// d = 0 under either base and its row is its goal.
+__global__ __launch_bounds__(kPlanBlock) void goal_hypotheses_kernel(int B, int A, int M, int heading, int nominal_first, double reach,
+                                                                     double std_heading, double std_distance, uint32_t seed_lo,
+                                                                     uint32_t seed_hi, uint32_t counter, const double2* pos,
+                                                                     const double2* vel, const double2* goal, double2* goals) {
+    const size_t i = (size_t)blockIdx.x * kPlanBlock + threadIdx.x;
+    const size_t H = (size_t)(A - 1);
+    if (i >= (size_t)B * M * H) return;
+    const size_t h = i % H, bm = i / H, b = bm / M, m = bm % M;
+    const size_t agent = b * A + h + 1;
+    const double2 p = pos[agent], g = goal[agent];
+    double dx = 0.0, dy = 0.0;
+    if (heading) {
+        const double2 v = vel[agent];
+        const double speed = sqrt(v.x * v.x + v.y * v.y);
+        if (speed > 0.0) dx = (v.x / speed) * reach, dy = (v.y / speed) * reach;
+    } else {
+        dx = g.x - p.x, dy = g.y - p.y;
+    }
+    if (m == 0 && nominal_first) {
+        goals[i] = heading ? make_double2(p.x + dx, p.y + dy) : g;
+        return;
+    }
+    const PlanWords r4 = philox4x32_10((uint32_t)h, (uint32_t)m, (uint32_t)b, counter, seed_lo, seed_hi);
+    const double u1 = ((double)(r4.w[0] >> 5) * 67108864.0 + (double)(r4.w[1] >> 6) + 1.0) / 9007199254740992.0;
+    const double u2 = ((double)(r4.w[2] >> 5) * 67108864.0 + (double)(r4.w[3] >> 6)) / 9007199254740992.0;
+    const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
+    const double z1 = r * cos(ang), z2 = r * sin(ang);
+    const double rot = std_heading * z1;
+    double scale = 1.0 + std_distance * z2;
+    if (scale < 0.0) scale = 0.0;
+    const double c = cos(rot), s = sin(rot);
+    goals[i] = make_double2(p.x + scale * (c * dx - s * dy), p.y + scale * (s * dx + c * dy));
 }
 
 }  // namespace cn

@@ -56,4 +56,47 @@ __global__ __launch_bounds__(kMaxBlock) void predict_orca_robot_kernel(Params P,
 #include "predict_orca_body.inc"
 }
 
+// cn_predict_orca_goals: predict_orca_kernel's table for M hypotheses about where the humans are heading, side by side in one
+// launch.  The workgroup is the same one over B M VIRTUAL envs: the host's copy of Params has B = B M (robot_visible = 0 and
+// robot_orca = 0 as above), so lane_of, build_pairs and the grid count virtual envs, and L.env is ve = b M + m.  Two things are
+// indexed by it in global memory: the goal of a human lane, one 16-byte load from goals [B][M][A - 1] (row ve (A - 1) + h),
+// and the output row (ve n_steps + t) (A - 1) + h of human_vel [B][M][n_steps][A - 1].  The agents themselves are the real
+// env's: row (ve / M) A + a of the state — L.gi, which lane_of forms from the virtual env, is NOT a row of the state and is
+// not used.  Nothing else of the body reads global memory by env: orca_phases and what it calls (pair phases, kd trees, the
+// programs) work on registers and LDS only.  A parked placeholder of the `mixed` rule keeps the goal of its state row (its
+// own position), so it gets what predict_orca_kernel gives it.
+// A body of its own, not a flag on predict_orca_body.inc: that text is shared so that the two kernels above keep their
+// instruction streams, and this kernel differs from it where the agent is loaded and where the row is addressed.
+template <int MAXL, bool KD>
+__global__ __launch_bounds__(kMaxBlock) void predict_orca_goals_kernel(Params P, StateView S, int n_steps, int n_modes,
+                                                                       const double2* goals, double2* human_vel) {
+    const Smem s = carve<MAXL>(P);
+    const Lane L = lane_of(P);
+    AgentRegs r = {};
+    if (L.valid) load_agent(S, (size_t)(L.env / n_modes) * P.A + L.a, r);
+    if (L.lane < P.nA) s.rview[L.lane] = (float)(r.rad + 0.01 + P.robot_safety);  // (read by the robot lane's pairs, never solved)
+    build_pairs(P, s);
+    if (KD) kd_fresh(P, s, L);
+    const bool human = L.valid && L.a > 0;
+    if (human && !is_parked(make_double2(r.px, r.py))) {
+        const double2 g = goals[(size_t)L.env * P.NC + (L.a - 1)];
+        r.gx = g.x, r.gy = g.y;
+    }
+    // row (ve, t, h): B M n_steps (A - 1) is within an int (the host checks), the index is formed in size_t
+    double2* row = human_vel + ((size_t)(human ? L.env : 0) * n_steps) * P.NC + (human ? L.a - 1 : 0);
+    for (int t = 0; t < n_steps; ++t) {
+        float vx, vy;
+        orca_phases<MAXL, KD>(P, s, L, r, 0.0f, human, vx, vy);
+        if (human) {
+            const double nvx = vx, nvy = vy;
+            r.px = r.px + nvx * P.dt;
+            r.py = r.py + nvy * P.dt;
+            r.vx = nvx;
+            r.vy = nvy;
+            row[(size_t)t * P.NC] = make_double2(nvx, nvy);
+        }
+        block_sync(P);  // the solve's last LDS reads, before the next step's stage phase writes
+    }
+}
+
 }  // namespace cn

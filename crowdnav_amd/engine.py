@@ -888,6 +888,66 @@ class BatchedCrowdSim(object):
         return self._plan_call('mppi_' + name, plan, C.byref(pred.c), int(orca_mode), float(temperature), int(bool(fit_std)),
                                rollout=True, n_real=n_real, counter=counter)
 
+    # ---------------------------------------------------------------- ... on hypothesised goals, M futures in one launch (cn_predict_orca_goals)
+    def predict_orca_goals(self, n, goals, out=None):
+        """predict_orca's table for M hypotheses about where the humans are heading, in one launch (cn_predict_orca_goals):
+        goals float64 [B, M, H, 2] (M in 1 .. 8) returns float64 [B, M, n, H, 2], lookahead_modes' table — in mode m human h
+        heads for goals[b, m, h] instead of its goal in the engine's state, everything else as predict_orca: the robot unseen,
+        fresh simulators, all n rows written.  goals [B, H, 2] is taken as M = 1 and returns [B, n, H, 2], lookahead_paths'
+        table.  With the engine's own goals (get_state()[0][:, 1:, 4:6]) a mode is predict_orca(n) bit for bit; a parked
+        placeholder of the `mixed` rule ignores its row.  goals: a contiguous float64 tensor on the engine's device is read
+        where it lies, anything else is copied there; goal_hypotheses() makes one from the state.  `out` reuses a contiguous
+        float64 device tensor of the returned shape.  Any engine; nothing of the engine is written and the call is not in
+        launch_counts().  n = 0 is a no-op."""
+        n = int(n)
+        if n < 0:
+            raise ValueError('predict_orca_goals: n must be >= 0')
+        gshape = tuple(getattr(goals, 'shape', np.shape(goals)))
+        single = len(gshape) == 3
+        M = 1 if single else (int(gshape[1]) if len(gshape) == 4 else 0)
+        if not 1 <= M <= _lib.MODES_MAX or gshape != ((self.B, self.H, 2) if single else (self.B, M, self.H, 2)):
+            raise ValueError('predict_orca_goals: goals must be [%d, M in 1..%d, %d, 2] or [%d, %d, 2], got %s'
+                             % (self.B, _lib.MODES_MAX, self.H, self.B, self.H, gshape))
+        shape = (self.B, n, self.H, 2) if single else (self.B, M, n, self.H, 2)
+        if out is None:
+            out = self._new(shape, torch.float64)
+        elif not self._dense(out, torch.float64, shape):
+            raise ValueError('predict_orca_goals: out must be a contiguous %s %s tensor on %s' % (torch.float64, shape, self.device))
+        if n > 0:
+            g, temporary = self._borrow(goals, torch.float64, gshape)
+            check(self._lib.cn_predict_orca_goals(self._h, n, M, _ptr(g), _ptr(out)))
+            self._release(temporary)
+        return out
+
+    def goal_hypotheses(self, M, base='heading', reach=None, std_heading=0.0, std_distance=0.0, nominal_first=True, seed=0,
+                        counter=0, out=None):
+        """M sets of hypothesised human goals, float64 [B, M, H, 2], made on the device from the state as it stands
+        (cn_goal_hypotheses) — predict_orca_goals' table; bit for bit crowdnav_amd.predict.goal_hypotheses on get_state() apart
+        from the device's log, cos and sin.  base 'heading': a human's nominal goal lies `reach` metres along its velocity (a
+        standing human's is where it stands) — positions and velocities only, what a planner outside the simulator observes;
+        reach=None means human_v_pref * time_step * 12, the way a human at its preferred speed makes in twelve steps, the
+        horizon the planners here look ahead.  base 'engine': the nominal goal is the engine's own.  Mode 0 is the nominal goal
+        when nominal_first; every other mode turns the offset from the human to it by std_heading * z1 radians and stretches
+        it by 1 + std_distance * z2 (not below 0), (z1, z2) standard normal from Philox under (seed, counter): the same
+        arguments give the same table, another counter another one.  `out` reuses a contiguous float64 device tensor.  Any
+        engine; nothing of the engine is written."""
+        if base not in _lib.GOALS_BASES:
+            raise ValueError('goal_hypotheses: base must be one of %s, got %r' % (_lib.GOALS_BASES, base))
+        M = int(M)
+        if not 1 <= M <= _lib.MODES_MAX:
+            raise ValueError('goal_hypotheses: M must be in 1..%d, got %d' % (_lib.MODES_MAX, M))
+        if reach is None:
+            reach = self.config['human_v_pref'] * self.config['time_step'] * 12 if base == 'heading' else 0.0
+        shape = (self.B, M, self.H, 2)
+        if out is None:
+            out = self._new(shape, torch.float64)
+        elif not self._dense(out, torch.float64, shape):
+            raise ValueError('goal_hypotheses: out must be a contiguous %s %s tensor on %s' % (torch.float64, shape, self.device))
+        check(self._lib.cn_goal_hypotheses(self._h, M, _lib.GOALS_BASES.index(base), float(reach), float(std_heading),
+                                           float(std_distance), int(bool(nominal_first)), int(seed) & 0xffffffffffffffff,
+                                           int(counter) & 0xffffffff, _ptr(out)))
+        return out
+
     # ---------------------------------------------------------------- shard boundary (explorer.py:74-90)
     def rollout_records(self, max_records=None):
         """The finished episodes of this engine's rollout as ONE self-contained float64 block per env:

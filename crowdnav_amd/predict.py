@@ -17,6 +17,13 @@ full 'orca' lookahead (humans that react to each candidate robot path) — and p
 loop.  It has no host form here: its oracle is the environment itself, stepped with robot_visible = 0.
 BatchedCrowdSim.predict_orca_robot (cn_predict_orca_robot) is the same with the robot in the humans' sight on a sequence of
 actions the caller names — the plan's mean, say: plan_predict_orca_nominal_rollout — one prediction per planning step.
+BatchedCrowdSim.predict_orca_goals (cn_predict_orca_goals) is predict_orca for M hypotheses about where the humans are heading,
+side by side in one launch: the goals are an argument, [B, M, H, 2], not the simulator's.
+
+    goal_hypotheses(state8, M, base, reach, ...)  such a table of goals, sampled around each human's heading (or its goal)
+
+is BatchedCrowdSim.goal_hypotheses (cn_goal_hypotheses) restated in numpy, its oracle, with a small Philox of its own — and the
+table for a caller whose predictor is not the engine's.
 
 torch / numpy only, no device code: a numpy state gives a numpy table, a torch state a torch table on the same device.  Each
 returns [B, n, H, 2] float64, H = A - 1 humans (state8 is get_state()'s [B, A, 8]: px, py, vx, vy, gx, gy, radius, v_pref; row 0 is
@@ -96,6 +103,72 @@ def from_positions(start_xy, positions, dt):
         raise ValueError('dt must be > 0')
     before = torch.cat([start[:, None].to(pos.device), pos[:, :-1]], dim=1)
     return _back((pos - before) / dt, as_numpy)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) on uint64 arrays that hold 32-bit words; returns the four output words."""
+    mask, sh = np.uint64(0xffffffff), np.uint64(32)
+    c0, c1, c2, c3 = (np.asarray(c, np.uint64) for c in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2  # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return c0, c1, c2, c3
+
+
+GOAL_BASES = ('engine', 'heading')
+
+
+def goal_hypotheses(state8, M, base='heading', reach=None, std_heading=0.0, std_distance=0.0, nominal_first=True, seed=0,
+                    counter=0):
+    """M sets of hypothesised human goals, float64 [B, M, H, 2]: BatchedCrowdSim.goal_hypotheses (cn_goal_hypotheses) restated
+    in numpy float64, operation for operation — its oracle, equal to it apart from the device's log, cos and sin — and the
+    table for a caller whose predictor is their own.  With (p, v, g) of human h its nominal offset d is g - p (base 'engine')
+    or `reach` metres along v, (0, 0) for a standing human (base 'heading'; `reach` is required there, g is not read).  Mode 0
+    under nominal_first is the nominal goal: g itself, or p + d.  Every other mode m is p + scale R(rot) d with
+    rot = std_heading z1, scale = max(0, 1 + std_distance z2), (z1, z2) the Box-Muller pair of the Philox4x32-10 block with
+    counter words (h, m, b, counter) and key (seed & 0xffffffff, seed >> 32): a row depends on neither B, M nor H."""
+    humans, as_numpy = _humans(state8)
+    device = humans.device
+    s = humans.detach().cpu().numpy()
+    M = int(M)
+    if base not in GOAL_BASES:
+        raise ValueError('goal_hypotheses: base must be one of %s, got %r' % (GOAL_BASES, base))
+    if not 1 <= M <= 8:
+        raise ValueError('goal_hypotheses: M must be in 1..8, got %d' % M)
+    heading = base == 'heading'
+    if heading and (reach is None or not (np.isfinite(reach) and reach > 0.0)):
+        raise ValueError('goal_hypotheses: base \'heading\' needs reach > 0 (metres along the velocity), got %r' % (reach,))
+    for name, v in (('std_heading', std_heading), ('std_distance', std_distance)):
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError('goal_hypotheses: %s must be >= 0 and finite, got %r' % (name, v))
+    B, H = s.shape[:2]
+    px, py, vx, vy, gx, gy = (s[:, None, :, i] for i in range(6))  # [B, 1, H]
+    if heading:
+        speed = np.sqrt(vx * vx + vy * vy)
+        moving = speed > 0.0
+        safe = np.where(moving, speed, 1.0)
+        dx, dy = np.where(moving, (vx / safe) * float(reach), 0.0), np.where(moving, (vy / safe) * float(reach), 0.0)
+    else:
+        dx, dy = gx - px, gy - py
+    b, m, h = np.arange(B)[:, None, None], np.arange(M)[None, :, None], np.arange(H)[None, None, :]
+    seed = int(seed)
+    w = _philox4x32_10(h, m, b, np.uint64(int(counter) & 0xffffffff), seed & 0xffffffff, (seed >> 32) & 0xffffffff)
+    f = [x.astype(np.float64) for x in (w[0] >> np.uint64(5), w[1] >> np.uint64(6), w[2] >> np.uint64(5), w[3] >> np.uint64(6))]
+    u1 = (f[0] * 67108864.0 + f[1] + 1.0) / 9007199254740992.0
+    u2 = (f[2] * 67108864.0 + f[3]) / 9007199254740992.0
+    r, ang = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586 * u2
+    z1, z2 = r * np.cos(ang), r * np.sin(ang)
+    rot = float(std_heading) * z1
+    scale = 1.0 + float(std_distance) * z2
+    scale = np.where(scale < 0.0, 0.0, scale)
+    c, sn = np.cos(rot), np.sin(rot)
+    out = np.stack([px + scale * (c * dx - sn * dy), py + scale * (sn * dx + c * dy)], axis=-1)
+    if nominal_first:
+        out[:, 0] = np.stack([px + dx, py + dy], axis=-1)[:, 0] if heading else s[:, :, 4:6]
+    out = np.ascontiguousarray(out)
+    return out if as_numpy else torch.from_numpy(out).to(device)
 
 
 def stack_modes(*tables):

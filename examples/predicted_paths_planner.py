@@ -2,9 +2,11 @@
 of the humans is neither ORCA (which reads their goals through the simulator) nor "straight on forever", but a table of
 predicted velocities the CALLER makes from the state after every real step.
 
-    python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--mppi] [--predictor to_goal]
+    python examples/predicted_paths_planner.py [--cases 8] [--candidates 16] [--horizon 8] [--cem | --mppi] [--predictor to_goal]
                                                [--futures cv,to_goal [--reduce min] [--risk-penalty 0.5]]
                                                [--device-loop [--chunk 8]] [--orca-sees-plan] [--goal-weight W]
+                                               [--goal-samples M [--goal-base heading|engine] [--goal-std-heading S]
+                                                [--goal-std-distance S]]
 
 Per real step: read the state, predict (crowdnav_amd.predict.to_goal: every human heads straight for its goal at v_pref and
 stops there; or constant_velocity), one plan_cem_paths / plan_mppi_paths call (draw, score against the table, update,
@@ -28,7 +30,13 @@ real step plan_draw, then BatchedCrowdSim.predict_orca_robot on candidate 0, the
 the sequence) to every candidate's return under every future (set_lookahead_goal_weight); 0 (the default) is the run without it.
 --kinematics unicycle [--max-rotation R] [--rotation-std S] (every mode above): a unicycle robot, the plan a
 Gaussian over (v, r) with r clipped to [-R, R] (set_plan_unicycle; R defaults to pi / 4, the reference's action-space bound)
-and r's deviation starting at S radians."""
+and r's deviation starting at S radians.
+--goal-samples M (1 .. 8) replaces the futures by M ORCA futures on SAMPLED human goals: per real step
+goal_hypotheses(counter = step) makes M sets of goals on the device — --goal-base heading: twelve steps' walk at v_pref along each
+human's velocity, what a planner outside the simulator can observe; engine: the simulator's goals — mode 0 the nominal one, the others
+turned by --goal-std-heading z radians and stretched by 1 + --goal-std-distance z; predict_orca_goals steps the humans towards
+each set in one launch, and plan_cem_modes / plan_mppi_modes plans against the M futures under --reduce and --risk-penalty.
+--goal-weight and --kinematics apply as above.  The per-step loop only: with --device-loop it is refused."""
 import argparse
 import logging
 import math
@@ -44,7 +52,8 @@ from crowdnav_amd.compat.explorer import average, episode_statistics  # noqa: E4
 
 def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, init_std=0.5, temperature=None,
          predictor='to_goal', futures=None, reduce='mean', risk_penalty=0.0, device_loop=False, chunk=8, orca_sees_plan=False,
-         goal_weight=0.0, kinematics='holonomic', max_rotation=math.pi / 4, rotation_std=0.5):
+         goal_weight=0.0, kinematics='holonomic', max_rotation=math.pi / 4, rotation_std=0.5, goal_samples=0, goal_base='heading',
+         goal_std_heading=0.0, goal_std_distance=0.0):
     env_cfg = cn.default_env_config()
     env = cn.CrowdSim()
     env.configure(env_cfg)
@@ -81,8 +90,13 @@ def plan(cases, candidates, horizon, seed=0, gamma=0.9, elites=4, iterations=3, 
                   'constant_velocity': lambda: predict.constant_velocity(state8, horizon),
                   'orca': lambda: (eng.predict_orca_robot(horizon, planner.candidates[:, 0]) if orca_sees_plan
                                    else eng.predict_orca(horizon))}
-        if futures:  # several futures side by side, one call
-            human_vel = predict.stack_modes(*(tables[name]() for name in futures))
+        if futures or goal_samples:  # several futures side by side, one call
+            if goal_samples:  # M ORCA futures on sampled goals, nothing through the host
+                goals = eng.goal_hypotheses(goal_samples, goal_base, std_heading=goal_std_heading, std_distance=goal_std_distance,
+                                            seed=seed, counter=step)
+                human_vel = eng.predict_orca_goals(horizon, goals)
+            else:
+                human_vel = predict.stack_modes(*(tables[name]() for name in futures))
             if temperature is None:
                 eng.plan_cem_modes(planner, human_vel, step * iterations, reduce=reduce, risk_penalty=risk_penalty)
             else:
@@ -114,6 +128,7 @@ def parser():
     ap.add_argument('--horizon', type=int, default=8, help='n: actions per sequence, and steps the humans are predicted for')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--mppi', action='store_true', help='the MPPI update (plan_mppi_paths) instead of the CEM refit (plan_cem_paths)')
+    ap.add_argument('--cem', action='store_true', help='the CEM refit, said aloud: it is the default, and excludes --mppi')
     ap.add_argument('--temperature', type=float, default=1.0, help='--mppi: T of the weights exp((score - best score) / T)')
     ap.add_argument('--elites', type=int, default=4, help='CEM: E, candidates the distribution is refitted to')
     ap.add_argument('--iterations', type=int, default=3, help='I, draw / score / update rounds per real step')
@@ -134,6 +149,12 @@ def parser():
     ap.add_argument('--max-rotation', type=float, default=math.pi / 4, help='--kinematics unicycle: R, r is clipped to [-R, R] radians per step')
     ap.add_argument('--rotation-std', type=float, default=0.5,
                     help="--kinematics unicycle: standard deviation r's steps start from, in radians")
+    ap.add_argument('--goal-samples', type=int, default=0,
+                    help='M in 1..8: plan against M ORCA futures on sampled human goals instead of the futures above (0: off)')
+    ap.add_argument('--goal-base', default='heading', choices=['heading', 'engine'],
+                    help="--goal-samples: the nominal goal, twelve steps' walk along the human's velocity or the simulator's own")
+    ap.add_argument('--goal-std-heading', type=float, default=0.0, help='--goal-samples: deviation of the sampled turn, in radians')
+    ap.add_argument('--goal-std-distance', type=float, default=0.0, help='--goal-samples: deviation of the sampled stretch, relative')
     return ap
 
 
@@ -155,12 +176,21 @@ def main():
         ap.error('--chunk must be >= 1')
     if args.orca_sees_plan and not (futures and 'orca' in futures):
         ap.error('--orca-sees-plan needs --futures with orca in it')
+    if args.cem and args.mppi:
+        ap.error('--cem and --mppi: one update or the other')
+    if args.goal_samples and args.device_loop:
+        ap.error('--goal-samples runs the per-step loop only: there is no one-call rollout on sampled goals, drop --device-loop')
+    if args.goal_samples and (futures or args.orca_sees_plan):
+        ap.error('--goal-samples replaces --futures: give one or the other')
+    if not 0 <= args.goal_samples <= 8:
+        ap.error('--goal-samples must be in 1 .. 8 (0: off)')
     logging.info(plan(args.cases, args.candidates, args.horizon, args.seed, elites=min(args.elites, args.candidates),
                       iterations=args.iterations, init_std=args.init_std, temperature=args.temperature if args.mppi else None,
                       predictor=args.predictor, futures=futures, reduce=args.reduce, risk_penalty=args.risk_penalty,
                       device_loop=args.device_loop, chunk=args.chunk, orca_sees_plan=args.orca_sees_plan,
                       goal_weight=args.goal_weight, kinematics=args.kinematics, max_rotation=args.max_rotation,
-                      rotation_std=args.rotation_std))
+                      rotation_std=args.rotation_std, goal_samples=args.goal_samples, goal_base=args.goal_base,
+                      goal_std_heading=args.goal_std_heading, goal_std_distance=args.goal_std_distance))
     return 0
 
 

@@ -1147,6 +1147,54 @@ int cn_plan_mppi_predict_orca_nominal_rollout(cn_engine* e, const cn_rollout_io*
                                               const cn_plan* plan, const cn_predictors* pred, int orca_mode, double temperature,
                                               int fit_std, uint32_t counter);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The ORCA predictor on hypothesised human goals: M futures in one launch (no version bump: new symbols only; no existing
+ * struct, enum, counter or refusal touched).  cn_predict_orca reads every human's goal from the engine's state — the simulator
+ * knows it, a planner outside one does not.  Here the goals are an argument, M sets of them per env, and a second call samples
+ * such sets from what can be observed.
+ *   cn_predict_orca_goals writes cn_predict_orca's table for every mode m of human_vel [B][n_modes][n_steps][A - 1][2] in one
+ *   launch: in mode m human h + 1 of env b heads for goals[b][m][h] (two doubles) instead of its goal in the engine's state.
+ * Everything else is the engine's as it stands — position, velocity, radius, v_pref, ORCA parameters, max_neighbors, time_step —
+ * and everything cn_predict_orca says of its table holds per mode: the robot unseen, fresh simulators, the kd order carried
+ * inside the kernel, p + v dt in float64, all n_steps rows always written.  With goals[b][m] the engine's own, mode m is
+ * cn_predict_orca's table bit for bit; a mode's rows depend on neither the other modes, M nor B.  A parked placeholder of the
+ * `mixed` rule ignores its row of goals and gets what cn_predict_orca gives it.  ANY engine is served.  ONE launch on the
+ * engine's stream — step_kernel's workgroup per E of the B M virtual envs (b, m), the engine's LDS per workgroup — NOT counted in
+ * cn_launch_counts; nothing of the engine is written (state, cn_rollout_io arrays, ring levels, kd rows, the robot's captured
+ * simulator, settings), `goals` is only read.  Refused, in this order, before anything is enqueued: NULL goals, NULL
+ * human_vel: CN_ERR_INVALID naming it; n_modes < 1: CN_ERR_INVALID, n_modes > 8: CN_ERR_UNSUPPORTED with the number;
+ * n_steps < 0: CN_ERR_INVALID; NULL engine: CN_ERR_INVALID; B n_modes virtual envs or B n_modes n_steps (A - 1) rows beyond an
+ * int: CN_ERR_UNSUPPORTED.  n_steps == 0: CN_OK, nothing launched, nothing written.  Asynchronous: both arrays must stay valid
+ * until the launch has run.  Out of scope: the robot in sight on hypothesised goals, a per-mode v_pref, a one-call rollout form
+ * (the per-step calls are asynchronous already). */
+int cn_predict_orca_goals(cn_engine* e, int n_steps, int n_modes,
+                          const double* goals /* DEVICE [B][n_modes][A-1][2], 16-byte aligned */,
+                          double* human_vel   /* DEVICE [B][n_modes][n_steps][A-1][2], 16-byte aligned */);
+/* cn_goal_hypotheses makes such a table of goals on the device, from the engine's state as it stands: one streaming launch, a
+ * lane and one 16-byte store per (b, m, h), nothing of the engine written, NOT counted in cn_launch_counts.  Float64, every
+ * product, quotient and sum an operation of its own in the order written here.  With (p, v, g) position, velocity and goal of
+ * human h + 1 of env b, its nominal offset d is
+ *   CN_GOALS_ENGINE   d = (gx - px, gy - py)                                    — the simulator's knowledge, perturbed
+ *   CN_GOALS_HEADING  speed = sqrt(vx vx + vy vy); speed > 0: d = ((vx / speed) reach, (vy / speed) reach), else d = (0, 0)
+ *                     — `reach` metres along the way it is walking; a standing human is predicted to stay.  g is not read.
+ * Mode 0 when nominal_first != 0: ENGINE: g, bit for bit; HEADING: (px + dx, py + dy).  Every other mode: the Philox4x32-10 block
+ * of counter words (h, m, b, counter) under key (seed low, seed high) gives u1, u2 and the Box-Muller pair
+ * (z1, z2) = (r cos(a), r sin(a)), r = sqrt(-2 log(u1)), a = 2 pi u2, by cn_plan_draw's expressions; then
+ *   rot = std_heading z1;  scale = 1 + std_distance z2, 0 where that is negative;  c = cos(rot), s = sin(rot)
+ *   goals[b][m][h] = (px + scale (c dx - s dy), py + scale (s dx + c dy)).
+ * So a row depends on neither B, M nor A, the same arguments give the same bits, and with both deviations 0 every mode is
+ * p + d exactly.  The parked placeholders of the `mixed` rule keep their own goals (they are at rest at them: d = 0 under
+ * either base).  crowdnav_amd/predict.py's goal_hypotheses restates it in numpy; the two differ through the device's log, cos
+ * and sin alone.  ANY engine is served.  Refused, in this order, before anything is enqueued: NULL goals: CN_ERR_INVALID;
+ * n_modes as above; a base that is neither value: CN_ERR_INVALID naming it; reach not finite or not > 0 (read, and checked,
+ * under CN_GOALS_HEADING only), std_heading or std_distance not finite or negative: CN_ERR_INVALID naming it; NULL engine:
+ * CN_ERR_INVALID.  Asynchronous: goals must stay valid until the launch has run.  Out of scope: inferring goals from a track's
+ * history. */
+enum { CN_GOALS_ENGINE = 0, CN_GOALS_HEADING = 1 };
+int cn_goal_hypotheses(cn_engine* e, int n_modes, int base, double reach, double std_heading, double std_distance,
+                       int nominal_first, uint64_t seed, uint32_t counter,
+                       double* goals /* DEVICE [B][n_modes][A-1][2], 16-byte aligned */);
+
 #ifdef __cplusplus
 }
 #endif
