@@ -265,6 +265,10 @@ SYMBOLS = {
     'cn_predict_orca_goals': (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     'cn_goal_hypotheses': (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32, _P]),
 }
+# exported for the tests and not declared in the header: the workgroup geometry an engine got (E, threads, LDS bytes, grid)
+DEBUG_SYMBOLS = {
+    'cn_debug_geometry': (C.c_int, [_P, C.POINTER(C.c_int)]),
+}
 
 _lib = None
 
@@ -279,7 +283,7 @@ def load():
             'crowdnav_amd: %s is missing. Build the HIP library first (make -C crowdnav_amd/csrc, or '
             '__graft_entry__.build()); there is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

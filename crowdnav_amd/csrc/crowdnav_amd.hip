@@ -1073,6 +1073,18 @@ int cn_mt_random(cn_engine* e, uint32_t seed, int n, double* out) {
 
 }  // extern "C"
 
+// Which workgroup geometry pick_geometry gave this engine after its clamps: envs per workgroup, threads per workgroup, LDS bytes
+// per workgroup and the grid of the per-env kernels.  For the tests that ask for a geometry through the tuning knobs; host-only,
+// not part of the public header.
+extern "C" int cn_debug_geometry(const cn_engine* e, int out[4]) {
+    if (!e || !out) return fail(CN_ERR_INVALID, "cn_debug_geometry: NULL argument");
+    out[0] = e->P.E;
+    out[1] = e->P.threads;
+    out[2] = (int)e->smem;
+    out[3] = grid_envs(e);
+    return CN_OK;
+}
+
 #ifdef CN_PHASE_TIMING
 // profiling builds only (scripts/phase_probe.py): accumulated shader-clock cycles per rollout phase, [8] = waves
 extern "C" int cn_debug_phase_cycles(unsigned long long* out16, int reset) {

@@ -1037,6 +1037,14 @@ class BatchedCrowdSim(object):
         check(self._lib.cn_sarl_network_route(self._h, C.byref(route)))
         return _lib.SARL_ROUTES[route.value]
 
+    def geometry(self):
+        """The workgroup geometry this engine got when it was created (cn_debug_geometry), after the clamps on the
+        CROWDNAV_AMD_ENVS_PER_WAVE / CROWDNAV_AMD_WAVES_PER_BLOCK knobs: dict of 'E' (envs per workgroup), 'threads' (64 per
+        wave), 'lds_bytes' and 'grid' (workgroups of the per-env kernels).  Read-only, host-side, launches nothing."""
+        out = (C.c_int * 4)()
+        check(self._lib.cn_debug_geometry(self._h, out))
+        return dict(E=int(out[0]), threads=int(out[1]), lds_bytes=int(out[2]), grid=int(out[3]))
+
     def mt_random(self, seed, n):
         out = self._new((n,), torch.float64)
         check(self._lib.cn_mt_random(self._h, int(seed), int(n), _ptr(out)))

@@ -201,6 +201,61 @@ def roll_on(eng, kind, steps):
             eng.rollout_step(torch.tensor([[0.3, 0.2]] * eng.B, dtype=torch.float64, device=eng.device))
 
 
+def rollout_after(eng, bufs):
+    """What a rollout left behind: copies of its bufs, the state, the clock and the heading."""
+    eng.sync()
+    out = {k: v.clone() for k, v in bufs.items()}
+    out['state'], out['global_time'] = eng.get_state()
+    out['theta'] = eng.get_theta()
+    return out
+
+
+def rollout_step_loop(eng, bufs, table, snapshots=None):
+    """T rollout_step calls on table [B, T, 2]; snapshots (a dict of lists): what every env held before each of them."""
+    for t in range(table.shape[1]):
+        if snapshots is not None:
+            snapshots['state8'].append(eng.get_state()[0])
+            for k in ('ep_count', 'cur_steps', 'active'):
+                snapshots[k].append(bufs[k].clone())
+        eng.rollout_step(table[:, t].contiguous())
+
+
+def step_loop(eng, seq, gamma=0.9):
+    """What the engine's envs do under seq [B, n, 2] from where they stand, by cn_step(update=1): per env the discounted
+    return summed left to right on the host, the last info code, the transitions made, global_time, state and heading — all
+    taken at the step the env's episode ended (or after n).  The engine is left wherever the n steps took it.  The discount's
+    exponent takes the engine's own time_step and robot_v_pref."""
+    import math
+    import torch
+    B, n = seq.shape[:2]
+    dt, v_pref = float(eng.config['time_step']), float(eng.config['robot_v_pref'])
+    dev = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
+    got = dict(ret=np.zeros(B), info=np.zeros(B, np.uint8), steps=np.zeros(B, np.int32), time=np.zeros(B),
+               final_state8=np.zeros((B, eng.A, 8)), final_theta=np.zeros(B))
+    running = np.ones(B, bool)
+    for t in range(n):
+        out = eng.step(dev[:, t].contiguous(), update=True, want_obs=False)
+        state, gtime = eng.get_state()
+        reward, done, info, state, gtime, theta = (np_of(x) for x in (out['reward'], out['done'], out['info'], state, gtime,
+                                                                      eng.get_theta()))
+        for b in np.flatnonzero(running):
+            got['ret'][b] = got['ret'][b] + math.pow(gamma, t * dt * v_pref) * reward[b]
+            got['info'][b], got['steps'][b], got['time'][b] = info[b], t + 1, gtime[b]
+            got['final_state8'][b], got['final_theta'][b] = state[b], theta[b]
+            running[b] = not done[b]
+        if not running.any():
+            break
+    return got
+
+
+def assert_branch(look, k, want, what=''):
+    """Branch (., k) of a lookahead dict (numpy) equals a step_loop result, bit for bit."""
+    for key, ref in want.items():
+        if key in look:
+            got = np.ascontiguousarray(look[key][:, k])
+            assert got.dtype == ref.dtype and got.shape == ref.shape and got.tobytes() == ref.tobytes(), (what, key, k, got, ref)
+
+
 def example_line(args):
     """The TEST line of examples/predicted_paths_planner.py on four cases."""
     cmd = [sys.executable, os.path.join(ROOT, 'examples', 'predicted_paths_planner.py'), '--cases', '4', '--candidates', '8', '--horizon', '4'] + args

@@ -29,6 +29,17 @@ def test_library_exports_every_declared_symbol(built):
     assert built.load().cn_abi_version() == built.ABI_VERSION
 
 
+def test_debug_exports_stay_out_of_the_header(built):
+    """cn_debug_geometry: exported and bound (BatchedCrowdSim.geometry), not part of the public header; NULL is refused."""
+    assert sorted(built.DEBUG_SYMBOLS) == ['cn_debug_geometry']
+    assert not set(built.DEBUG_SYMBOLS) & (set(built.SYMBOLS) | set(_declared_symbols()))
+    lib = built.load()
+    out = (C.c_int * 4)(7, 7, 7, 7)
+    assert lib.cn_debug_geometry(None, out) == built.CN_ERR_INVALID and 'cn_debug_geometry' in lib.cn_last_error().decode()
+    assert list(out) == [7, 7, 7, 7]
+    assert lib.cn_abi_version() == built.ABI_VERSION == 12
+
+
 def test_struct_layouts_match_header(built):
     # cn_config: 2 i32, 6 f64, 2 i32, 3 f64, 2 i32, 8 f64, 4 i32 -> 25 x 8 bytes, no padding surprises
     assert C.sizeof(built.CnConfig) == 8 + 48 + 8 + 24 + 8 + 64 + 16

@@ -15,50 +15,16 @@ import pytest
 
 from conftest import ROOT
 from support import (  # noqa: F401  (amd: module fixture)
-    action_space as _space, action_table, amd, external_engine as _engine, np_of as _np, restore as _restore,
-    snapshot as _snapshot)
+    action_space as _space, action_table, amd, assert_branch as _assert_branch, external_engine as _engine, np_of as _np,
+    restore as _restore, snapshot as _snapshot, step_loop as _step_loop)
 
 pytestmark = pytest.mark.gpu
 
 BEGIN = dict(seed_base=1000, seed_mod=500, record_capacity=8)
-DT, V_PREF = 0.25, 1.0  # the engines' defaults (time_step, robot_v_pref)
 
 
 def _table(B, K, n, unicycle=False, seed=11):
     return action_table(B, K, n, unicycle=unicycle, seed=seed)
-
-
-def _step_loop(eng, seq, gamma=0.9):
-    """What the engine's envs do under seq [B, n, 2] from where they stand, by cn_step(update=1): per env the discounted
-    return summed left to right on the host, the last info code, the transitions made, global_time, state and heading — all
-    taken at the step the env's episode ended (or after n).  The engine is left wherever the n steps took it."""
-    import torch
-    B, n = seq.shape[:2]
-    dev = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
-    got = dict(ret=np.zeros(B), info=np.zeros(B, np.uint8), steps=np.zeros(B, np.int32), time=np.zeros(B),
-               final_state8=np.zeros((B, eng.A, 8)), final_theta=np.zeros(B))
-    running = np.ones(B, bool)
-    for t in range(n):
-        out = eng.step(dev[:, t].contiguous(), update=True, want_obs=False)
-        state, gtime = eng.get_state()
-        reward, done, info, state, gtime, theta = (_np(x) for x in (out['reward'], out['done'], out['info'], state, gtime,
-                                                                    eng.get_theta()))
-        for b in np.flatnonzero(running):
-            got['ret'][b] = got['ret'][b] + math.pow(gamma, t * DT * V_PREF) * reward[b]
-            got['info'][b], got['steps'][b], got['time'][b] = info[b], t + 1, gtime[b]
-            got['final_state8'][b], got['final_theta'][b] = state[b], theta[b]
-            running[b] = not done[b]
-        if not running.any():
-            break
-    return got
-
-
-def _assert_branch(look, k, want, what=''):
-    """Branch (., k) of a lookahead dict (numpy) equals a _step_loop result, bit for bit."""
-    for key, ref in want.items():
-        if key in look:
-            got = np.ascontiguousarray(look[key][:, k])
-            assert got.dtype == ref.dtype and got.shape == ref.shape and got.tobytes() == ref.tobytes(), (what, key, k, got, ref)
 
 
 def test_the_predicted_future_is_the_one_that_happens(amd):

@@ -3,8 +3,9 @@ the prior and the shift against the numpy restatement bit for bit, cn_plan_cem a
 against a twin engine driven by the Python loop.  The lookahead that scores the candidates is the existing one and is never the
 code under test here.
 
-Shapes: B = 3 at 5 humans (two envs per workgroup, the last workgroup half full), K = 5 and K = 70 (ranks crossing the 64-lane
-boundary), n = 4 and n = 1, E = 1, 2 and K."""
+Shapes: B = 3 at 5 humans (one env per workgroup on one wave, as every batch up to 2048 envs gets; the lookahead and the real step
+inside the closed loop run packed and on two waves in tests/test_workgroup_geometry.py), K = 5 and K = 70 (ranks crossing the
+64-lane boundary), n = 4 and n = 1, E = 1, 2 and K elites."""
 import ctypes as C
 import os
 import subprocess

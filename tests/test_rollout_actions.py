@@ -9,7 +9,8 @@ import pytest
 
 from conftest import load_golden
 from support import (  # noqa: F401  (amd: module fixture)
-    action_table, amd, external_engine as _engine, np_of as _np, same_tensors as _same)
+    action_table, amd, environ, external_engine as _engine, np_of as _np, rollout_after as _after,
+    rollout_step_loop as _step_loop, same_tensors as _same)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,27 +21,20 @@ def _table(B, T, unicycle=False, seed=7):
     return action_table(B, T, unicycle=unicycle, seed=seed)
 
 
-def _after(eng, bufs):
-    eng.sync()
-    out = {k: v.clone() for k, v in bufs.items()}
-    out['state'], out['global_time'] = eng.get_state()
-    out['theta'] = eng.get_theta()
-    return out
-
-
-def _step_loop(eng, bufs, table, snapshots=None):
-    """T rollout_step calls; snapshots (a dict of lists): what every env held before each of them."""
-    for t in range(table.shape[1]):
-        if snapshots is not None:
-            snapshots['state8'].append(eng.get_state()[0])
-            for k in ('ep_count', 'cur_steps', 'active'):
-                snapshots[k].append(bufs[k].clone())
-        eng.rollout_step(table[:, t].contiguous())
+def _case_engine(amd, c):
+    """The case's engine; under the case's `knobs`, with the geometry they ask for asserted."""
+    with environ(**c.get('knobs', {})):
+        eng = _engine(amd, c['B'], c['H'], **c['cfg'])
+    if 'knobs' in c:
+        assert eng.geometry()['E'] == c['knobs']['CROWDNAV_AMD_ENVS_PER_WAVE'], eng.geometry()
+    return eng
 
 
 CASES = {
-    # T = 70 over 32-step episodes (time_limit 8): every env passes two episode ends; B = 3 half-fills the last workgroup
-    'ragged_two_episode_ends': dict(B=3, H=5, T=70, cfg=dict(robot_visible=1, time_limit=8.0)),
+    # T = 70 over 32-step episodes (time_limit 8): every env passes two episode ends; two envs per workgroup (the geometry of
+    # every engine above 2048 envs, asked for here), so B = 3 half-fills the last workgroup
+    'ragged_two_episode_ends': dict(B=3, H=5, T=70, cfg=dict(robot_visible=1, time_limit=8.0),
+                                    knobs=dict(CROWDNAV_AMD_ENVS_PER_WAVE=2)),
     'one_human': dict(B=2, H=1, T=70, cfg=dict(robot_visible=1, time_limit=8.0)),
     'twelve_humans_ten_half_planes_kd': dict(B=2, H=12, T=40, cfg=dict(robot_visible=1, time_limit=8.0)),
     'unicycle': dict(B=3, H=5, T=70, cfg=dict(robot_visible=1, time_limit=8.0, robot_kinematics=1), unicycle=True),
@@ -56,11 +50,11 @@ def test_one_table_call_equals_the_step_loop(amd, case):
     c = CASES[case]
     B, H, T, cfg, limit = c['B'], c['H'], c['T'], c['cfg'], c.get('limit', -1)
     table = torch.from_numpy(_table(B, T, c.get('unicycle', False))).cuda()
-    x = _engine(amd, B, H, **cfg)
+    x = _case_engine(amd, c)
     xbufs = x.rollout_begin(episode_limit=limit, **BEGIN)
     _step_loop(x, xbufs, table)
     want = _after(x, xbufs)
-    y = _engine(amd, B, H, **cfg)
+    y = _case_engine(amd, c)
     ybufs = y.rollout_begin(episode_limit=limit, **BEGIN)
     before = y.launch_counts()
     calls = c.get('split', (T,))
@@ -119,13 +113,13 @@ def case_one(amd):
     c = CASES['ragged_two_episode_ends']
     B, H, T, cfg = c['B'], c['H'], c['T'], c['cfg']
     table = torch.from_numpy(_table(B, T)).cuda()
-    x = _engine(amd, B, H, **cfg)
+    x = _case_engine(amd, c)
     xbufs = x.rollout_begin(**BEGIN)
     snaps = dict(state8=[], ep_count=[], cur_steps=[], active=[])
     _step_loop(x, xbufs, table, snaps)
     want = _after(x, xbufs)
     snaps = {k: _np(torch.stack(v)).swapaxes(0, 1) for k, v in snaps.items()}  # [B, T, ...]
-    y = _engine(amd, B, H, **cfg)
+    y = _case_engine(amd, c)
     ybufs = y.rollout_begin(**BEGIN)
     before = y.launch_counts()['rollout_kernels']
     rows = y.rollout_actions(table, trace=True, rewards=True)

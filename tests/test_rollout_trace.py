@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import TRAJ_FIXTURES, episodes_of, load_golden
-from support import amd, np_of as _np  # noqa: F401  (amd: module fixture)
+from support import amd, environ, np_of as _np  # noqa: F401  (amd: module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +51,8 @@ def _stepwise(eng, n):
 
 
 CASES = {
-    'two_envs_per_workgroup_ragged': dict(B=3, H=5, n=120),
+    # the geometry of every engine above 2048 envs, asked for here: B = 3 leaves the second workgroup half full
+    'two_envs_per_workgroup_ragged': dict(B=3, H=5, n=120, knobs=dict(CROWDNAV_AMD_ENVS_PER_WAVE=2)),
     'envs_retire': dict(B=5, H=5, n=120, L=7),
     'random_attributes_invisible': dict(B=4, H=5, n=90, cfg=dict(robot_visible=0, randomize_attributes=1)),
     'square_crossing': dict(B=4, H=5, n=90, cfg=dict(scenario_rule=1)),
@@ -67,10 +68,12 @@ def test_trace_equals_the_stepwise_path(amd, case):
     c = CASES[case]
     B, H, n, L, cfg = c['B'], c['H'], c['n'], c.get('L', -1), c.get('cfg', {})
     asynchronous = bool(cfg.get('flags', 0) & amd.FLAG_ASYNC_SCENARIO_FILL)
-    x = _engine(amd, B, H, **cfg)
+    with environ(**c.get('knobs', {})):
+        x, y, z = (_engine(amd, B, H, **cfg) for _ in range(3))
+    if 'knobs' in c:
+        assert [e.geometry()['E'] for e in (x, y, z)] == [c['knobs']['CROWDNAV_AMD_ENVS_PER_WAVE']] * 3
     _begin(x, L)
     want = _stepwise(x, n)
-    y = _engine(amd, B, H, **cfg)
     ybufs = _begin(y, L)
     got = _trace(y, n, rewards=True, out=_filled_out(y, n))
     y.sync()
@@ -107,7 +110,6 @@ def test_trace_equals_the_stepwise_path(amd, case):
     if L >= 0:
         assert idle.any() and live.any()  # some env retired inside the call
     # the engine afterwards: exactly what one rollout(n) leaves
-    z = _engine(amd, B, H, **cfg)
     zbufs = _begin(z, L)
     z.rollout(n)
     z.sync()

@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from support import (  # noqa: F401  (amd: module fixture)
-    action_space as _space, amd, np_of as _np, restore as _restore, same_bits as _same_bits, snapshot as _snapshot)
+    action_space as _space, amd, np_of as _np, restore as _restore, same_bits as _same_bits, snapshot as _snapshot,
+    step_loop as _step_loop)
 
 pytestmark = pytest.mark.gpu
 
@@ -182,30 +183,6 @@ def test_one_step_is_the_decision(amd, H):
     assert _same_bits(look['score'][~ended], values[~ended])
     assert _same_bits(look['score'][ended], look['ret'][ended])
     eng.close()
-
-
-def _step_loop(eng, seq):
-    """What the engine's envs do under seq [B, n, 2] from where they stand, by cn_step(update=1): per env the discounted return
-    summed left to right on the host, the last info code, the transitions made, global_time, state and heading, taken at the
-    step the env's episode ended (or after n).  (tests/test_lookahead.py's helper, restated.)"""
-    B, n = seq.shape[:2]
-    dev = torch.from_numpy(np.ascontiguousarray(seq)).to(eng.device)
-    got = dict(ret=np.zeros(B), info=np.zeros(B, np.uint8), steps=np.zeros(B, np.int32), time=np.zeros(B),
-               final_state8=np.zeros((B, eng.A, 8)), final_theta=np.zeros(B))
-    running = np.ones(B, bool)
-    for t in range(n):
-        out = eng.step(dev[:, t].contiguous(), update=True, want_obs=False)
-        state, gtime = eng.get_state()
-        reward, done, info, state, gtime, theta = (_np(x) for x in (out['reward'], out['done'], out['info'], state, gtime,
-                                                                    eng.get_theta()))
-        for b in np.flatnonzero(running):
-            got['ret'][b] = got['ret'][b] + math.pow(GAMMA, t * DT * V_PREF) * reward[b]
-            got['info'][b], got['steps'][b], got['time'][b] = info[b], t + 1, gtime[b]
-            got['final_state8'][b], got['final_theta'][b] = state[b], theta[b]
-            running[b] = not done[b]
-        if not running.any():
-            break
-    return got
 
 
 def _bootstrap_against_the_step_loop(amd, eng, table, snap, unicycle):
